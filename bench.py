@@ -16,6 +16,10 @@ Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant
 HIP-event timed inside the run), `rotating_h2d` (the same step over rotating host batches with
 the image upload inside the timed region) and `cpu_baseline` (the oracle's restated Chainer CPU
 path timed on the host cores on BASELINE configs[0] in full, reported only).
+
+`--steps K` is the number of timed steps of the headline (`ms_per_step` = one of them);
+`--dump-outputs DIR` writes what the last of them computed as DIR/<name>.npy, so that two builds
+can be compared output for output on identical seeded inputs.
 """
 import argparse
 import ctypes
@@ -398,10 +402,11 @@ def cpu_baseline():
                            phases)))
 
 
-def bench_infer(args, device, rank, steps=None, warmup=None):
+def bench_infer(args, device, rank, steps=None, warmup=None, dump_dir=None):
     """BASELINE configs[4]: ResNet50-C4 inference, batch 8 x 1024 x 1024, 1000 proposals/img,
     per-class NMS + mask head on the <= 100 detections/img (MaskRCNN.predict minus the host
-    cv2 prepare/paste, models/mask_rcnn.py:311-335).  Returns the JSON object (rank 0) or None."""
+    cv2 prepare/paste, models/mask_rcnn.py:311-335).  Returns the JSON object (rank 0) or None.
+    ``dump_dir``: rank 0 writes the last timed step's detections there (write_outputs)."""
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
     import chainer_mask_rcnn_amd as cmr
@@ -439,6 +444,8 @@ def bench_infer(args, device, rank, steps=None, warmup=None):
     elapsed = time.perf_counter() - t0
     prof = profile_summary()
     lib.mrcnn_profile_enable(0)
+    if dump_dir is not None and rank == 0:
+        write_outputs(dump_dir, infer_outputs(out))
     n_det = [len(b) for b in out[0]]
     del model, x
     if rank == 0:
@@ -522,6 +529,59 @@ def free_port():
     return port
 
 
+DUMP_MAX_BYTES = 64 << 20        # --dump-outputs: every file together
+DUMP_SAMPLE = 1 << 22            # elements kept of a larger output (a fixed, seeded sample)
+
+
+def write_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: {name: array} -> out_dir/<name>.npy, float64 for scalars and float64
+    arrays, float32 otherwise.  An output of more than DUMP_SAMPLE elements is flattened and
+    replaced by DUMP_SAMPLE of its elements at positions drawn from a private RandomState(seed):
+    the same positions for every output of that size, in every run.  Returns the bytes written."""
+    ready = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.ndim == 0 or a.dtype == np.float64 else np.float32)
+        if a.size > DUMP_SAMPLE:
+            idx = np.random.RandomState(seed).choice(a.size, DUMP_SAMPLE, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        ready[name] = a
+    total = sum(a.nbytes for a in ready.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError('--dump-outputs: %d bytes exceed the %d-byte limit' % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in ready.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return total
+
+
+def train_step_outputs(chain, opt):
+    """What a caller of the timed train step holds after its last step: the six losses the chain
+    reports, and the trainable parameters after the update with the optimizer's momentum buffers,
+    each flattened and concatenated in parameter-name order (call after the deferred updates are
+    flushed)."""
+    out = {k: np.float64(v.item()) for k, v in sorted(chain.report.items())}
+    a = opt.arena
+    names = {id(p): n for n, p in chain.named_parameters()}
+    order = sorted(range(len(a.params)), key=lambda i: names[id(a.params[i])])
+    with torch.no_grad():
+        vals = [a.params[i].detach().reshape(-1) for i in order]
+        moms = [torch.as_strided(a.momenta, tuple(a.params[i].shape), a.params[i].stride(),
+                                 a.offsets[i]).reshape(-1) for i in order]
+        out['params'] = torch.cat(vals).cpu().numpy()
+        out['momenta'] = torch.cat(moms).cpu().numpy()
+    return out
+
+
+def infer_outputs(out):
+    """model.predict_prepared's result (per-image bboxes, mask logits, labels, scores), each
+    concatenated over the images, with the detection count of every image."""
+    bboxes, masks, labels, scores = out[:4]
+    return dict(bboxes=np.concatenate(bboxes), labels=np.concatenate(labels),
+                scores=np.concatenate(scores), mask_logits=np.concatenate(masks),
+                detections_per_image=np.array([len(b) for b in bboxes]))
+
+
 _REAL_STDOUT = None
 
 
@@ -558,9 +618,10 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=3,
+    ap.add_argument('--repeats', type=int, default=1,
                     help='how many times the timed region of --steps steps is run back to back; `value` '
-                         'is the median region, `repeats` reports all of them')
+                         'is the median region, `repeats` reports all of them (default 1: the headline '
+                         'times exactly --steps steps)')
     ap.add_argument('--layers', type=int, default=50, choices=[50, 101])
     ap.add_argument('--batch', type=int, default=2, help='images per GPU')
     ap.add_argument('--height', type=int, default=800)
@@ -619,7 +680,14 @@ def main():
                     help='multi-GPU runs: also run the auxiliary single-GPU measurements (rotating_h2d, '
                          'fg_capped, device_targets, direct_head_forward, fp32_mfma, pipeline_h2d); by default '
                          'a run with --gpus > 1 times the headline region only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the headline's timed steps, write what its last step computed as "
+                         'DIR/<name>.npy (train: the reported losses, and the parameters and momentum '
+                         'buffers after the update; infer: the detections), at most 64 MB in all, '
+                         'larger outputs as a fixed, seeded sample')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.repeats < 1:
+        ap.error('--steps and --repeats must be >= 1 and --warmup >= 0')
     if args.gpus > 1 and not args.all_legs:
         # the scaling runs need `value` per N; every auxiliary leg is one more place where eight
         # ranks must stay in step, and none of them says anything about scaling
@@ -662,7 +730,7 @@ def main():
     device = torch.device('cuda', local)
 
     if args.workload == 'infer':
-        line = bench_infer(args, device, rank)
+        line = bench_infer(args, device, rank, dump_dir=args.dump_outputs)
         if line is not None:
             emit_json(line)
         return
@@ -717,10 +785,10 @@ def main():
     if sync is not None:
         sync.exchange.timing(True)
     # The headline region, `--repeats` times back to back (each: EXACTLY args.steps steps between
-    # two fences = barrier + device synchronise): the package runs these kernels at its power cap,
-    # so one 0.5 s sample moves with the box and its thermal state — `value` is the MEDIAN region,
-    # `repeats` keeps every region's time, and the power / shader clock sampled meanwhile go into
-    # `roofline`.
+    # two fences = barrier + device synchronise; one region by default): the package runs these
+    # kernels at its power cap, so one 0.5 s sample moves with the box and its thermal state — with
+    # --repeats R `value` is the MEDIAN region, `repeats` keeps every region's time, and the power /
+    # shader clock sampled meanwhile go into `roofline`.
     R = max(1, args.repeats)
     region_s = []
     smi = SmiSampler(local, enabled=args.smi)
@@ -746,6 +814,9 @@ def main():
     n_rois = chain.last_targets['n_rois']
     loss_val = float(loss.item())
     elapsed = float(np.median(region_s))
+    if args.dump_outputs is not None and rank == 0:
+        # the last timed step's results, before any later measurement steps the model again
+        write_outputs(args.dump_outputs, train_step_outputs(chain, opt))
     roi_iso = None
     if not args.no_profile and 'sample_roi_indices' in chain.last_targets:
         roi_iso = roi_align_isolated(chain, device)

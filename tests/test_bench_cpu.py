@@ -52,3 +52,51 @@ def test_multi_gpu_request_without_devices_is_refused():
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '1'],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and 'one process per GPU' in (r.stderr + r.stdout)
+
+
+def test_write_outputs_dtypes_seeded_sample_and_size_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import pytest
+    monkeypatch.setattr(bench, 'DUMP_SAMPLE', 100)
+    big = np.arange(1000, dtype=np.float32)
+    arrays = dict(loss=np.float64(1.25), labels=np.array([3, 1], np.int32), big=big)
+    n = bench.write_outputs(str(tmp_path / 'a'), arrays)
+    bench.write_outputs(str(tmp_path / 'b'), dict(big=big[::-1].copy()))
+    got = {k: np.load(str(tmp_path / 'a' / (k + '.npy'))) for k in arrays}
+    assert got['loss'].dtype == np.float64 and got['loss'] == 1.25
+    assert got['labels'].dtype == np.float32 and got['labels'].tolist() == [3., 1.]
+    # a fixed sample: distinct sorted positions, the same ones for every output of that size
+    s = got['big']
+    assert s.dtype == np.float32 and s.shape == (100,) and np.all(np.diff(s) > 0)
+    assert np.array_equal(np.load(str(tmp_path / 'b' / 'big.npy')), 999 - s)
+    assert n == 8 + 2 * 4 + 100 * 4
+    monkeypatch.setattr(bench, 'DUMP_MAX_BYTES', 64)
+    with pytest.raises(ValueError):
+        bench.write_outputs(str(tmp_path / 'c'), dict(big=big))
+    assert not (tmp_path / 'c').exists()                  # nothing written past the limit
+
+
+def test_train_step_outputs_concatenate_in_parameter_name_order():
+    import torch
+    from chainer_mask_rcnn_amd import optimizers
+
+    class Chain(torch.nn.Module):
+        def __init__(self):
+            super(Chain, self).__init__()
+            self.b = torch.nn.Parameter(torch.arange(6, dtype=torch.float32).reshape(2, 3))
+            # dense but transposed: the arena keeps its memory order, the dump its logical order
+            self.a = torch.nn.Parameter(torch.arange(100, 104, dtype=torch.float32).reshape(2, 2).t())
+            self.frozen = torch.nn.Parameter(torch.zeros(5), requires_grad=False)
+            self.report = {'loss': torch.tensor(2.5), 'roi_cls_loss': torch.tensor(0.5)}
+
+    chain = Chain()
+    opt = optimizers.MomentumSGD(lr=0.1).setup(chain)
+    opt._build()
+    a = opt.arena
+    a.momenta.copy_(-torch.arange(a.size, dtype=torch.float32))
+    out = bench.train_step_outputs(chain, opt)
+    assert out['loss'] == 2.5 and out['roi_cls_loss'] == 0.5
+    assert out['params'].tolist() == [100., 102., 101., 103., 0., 1., 2., 3., 4., 5.]
+    off = {n: a.offsets[[id(p) for p in a.params].index(id(getattr(chain, n)))] for n in 'ab'}
+    want = [off['a'] + k for k in (0, 2, 1, 3)] + [off['b'] + k for k in range(6)]
+    assert out['momenta'].tolist() == [-float(v) for v in want]
