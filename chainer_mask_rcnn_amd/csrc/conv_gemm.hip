@@ -36,83 +36,29 @@
 
 #include "common.h"
 
-// Ablation / instrumentation switches (MRCNN_DBG_*, MRCNN_GEMM_TRACE, MRCNN_GEMM_CLOCKPROBE: several
-// of them produce garbage results by design) compile only in an experiment build
-// (tools/build_variant.sh passes -DMRCNN_EXPERIMENT_BUILD and writes the library under
-// csrc/variants/): a stray EXTRA= on the product build must not ship a silently wrong library.
-#if !defined(MRCNN_EXPERIMENT_BUILD) &&                                                              \
-    (defined(MRCNN_DBG_NOLOAD) || defined(MRCNN_DBG_NOLOAD_A) || defined(MRCNN_DBG_NOLOAD_B) ||      \
-     defined(MRCNN_DBG_NOSTORE) || defined(MRCNN_DBG_NOSPLITVALU) || defined(MRCNN_DBG_NOSPLIT_B) || \
-     defined(MRCNN_DBG_NOSTAGE) || defined(MRCNN_DBG_NOGLOBAL) || defined(MRCNN_DBG_PLAIN_EPI) ||    \
-     defined(MRCNN_DBG_AMOD) || defined(MRCNN_DBG_PITCH) || defined(MRCNN_GEMM_TRACE) ||             \
-     defined(MRCNN_GEMM_CLOCKPROBE) || defined(MRCNN_GEMM_BIGBLOCKS) || defined(MRCNN_SPLIT_PK_SUB))
-#error "MRCNN_DBG_* / trace / probe switches need -DMRCNN_EXPERIMENT_BUILD (tools/build_variant.sh): such a library must never be the product build"
-#endif
-
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-#ifndef MRCNN_GEMM_BK
-#define MRCNN_GEMM_BK 32
-#endif
-constexpr int BK = MRCNN_GEMM_BK;
-#ifndef MRCNN_GEMM_LOAD_AUX       // cache policy bits of the staged operand loads (experiment)
-#define MRCNN_GEMM_LOAD_AUX 0
-#endif
-#ifndef MRCNN_GEMM_SETPRIO
-#define MRCNN_GEMM_SETPRIO 0
-#endif
+constexpr int BK = 32;
 // The forward-form kernel without mask staging fits 168 registers, so it runs with ONE LDS stage
 // (37 KB) and three workgroups per CU: a wave spends ~40 % of a K slice issuing MFMAs and
 // ~60 % staging (measured with s_memtime), so three interleaved waves per SIMD keep the pipe
 // fuller than two (res5 3x3: 129 vs 122 TFLOP/s).  The variants that stage a mask (16 more
 // registers) and the K-strided DGRAD gather would spill at 168 and keep two stages / two
 // workgroups per CU.
-#ifndef MRCNN_GEMM_SINGLEBUF
-#define MRCNN_GEMM_SINGLEBUF 1
-#endif
-#ifndef MRCNN_GEMM_SINGLEBUF_WGRAD
-#define MRCNN_GEMM_SINGLEBUF_WGRAD 1
-#endif
-#ifndef MRCNN_GEMM_MINWAVES
-#define MRCNN_GEMM_MINWAVES 1
-#endif
-#ifndef MRCNN_GEMM_SINGLEBUF_SMALL
-#define MRCNN_GEMM_SINGLEBUF_SMALL 1
-#endif
 constexpr bool single_buffered(int tm, int mode, bool masked)
 {
-    if (tm == 1) return MRCNN_GEMM_SINGLEBUF_SMALL != 0 && !masked && mode == 0;
-    return MRCNN_GEMM_SINGLEBUF != 0 && tm >= 2 && !masked &&
-           (mode == 0 || (mode == 2 && MRCNN_GEMM_SINGLEBUF_WGRAD != 0));
+    if (tm == 1) return !masked && mode == 0;
+    return tm >= 2 && !masked && (mode == 0 || mode == 2);
 }
 // minimum workgroups per CU the register allocation must allow (256-thread workgroups: one
 // wave per SIMD each)
 constexpr int min_blocks(int tm, int mode, bool masked)
 {
-    if (!single_buffered(tm, mode, masked)) return MRCNN_GEMM_MINWAVES;
-#ifdef MRCNN_GEMM_BIGBLOCKS     // experiment: resident workgroups per CU of the 128x128 kernels
-    return tm == 2 ? MRCNN_GEMM_BIGBLOCKS : 6;
-#else
+    if (!single_buffered(tm, mode, masked)) return 1;
     return tm == 4 ? 2 : (tm == 2 ? 3 : 6);
-#endif
 }
-// Experiment, off by default: the last workgroup of a wgrad tile to arrive sums the split-K
-// slabs inside the GEMM kernel instead of a separate reduce launch.  Correct (tools/
-// check_wgrad_reduce.py: no stale slab under load, bit-repeatable), but the agent-scope release
-// every workgroup needs before it signals writes back its XCD's whole dirty L2 — measured
-// 55.6 vs 51.6 ms per train step, i.e. 4 ms SLOWER than the 0.67 ms reduce launches it removes.
-#ifndef MRCNN_WGRAD_INKERNEL_REDUCE
-#define MRCNN_WGRAD_INKERNEL_REDUCE 0
-#endif
-constexpr int64_t kWgradCounterBytes = 1 << 20;   // >= 4 B x tiles for any supported filter
-#ifndef MRCNN_SPLIT_ILV          // SPLIT forward form: next slice's loads between the MFMAs (see ILV)
-#define MRCNN_SPLIT_ILV 1
-#endif
-#ifndef MRCNN_GEMM_WIDE_EPILOGUE
-#define MRCNN_GEMM_WIDE_EPILOGUE 1
-#endif
 constexpr int KPAD = 4;  // K-contiguous LDS rows are 36 floats (conflict-free b128)
 
 // The stride-1 dgrad is also run in FWD mode: a forward convolution of gy with the flipped,
@@ -155,10 +101,6 @@ struct GemmParams {
     // the same image block, whose pixels therefore stay in the XCD's L2.  perm_n = number of
     // images (M is padded to whole blocks), 0 = natural (image, y, x) order.
     int perm_n;
-    // WGRAD in-kernel slab reduction: per-tile arrival counters (zeroed by the host) and the
-    // final gradient; the last workgroup of a tile to arrive sums the slabs in slab order
-    int *tile_counters;
-    float *reduce_out;
     // Fused backward of the producing conv's epilogue, applied while gy is staged
     // (DGRAD A operand / WGRAD A' operand):  g = gy * (mask_y > 0) * in_scale[k]
     const float *mask_y;   // output of the ReLU that followed the conv (same shape as gy) or NULL
@@ -186,25 +128,7 @@ struct GemmParams {
     // winograd.hip): floats between consecutive problems of A, B and C.  The extents above
     // are then per problem.
     int64_t batch_a, batch_b, batch_c;
-    // Start-up stagger (launch_kernel_m): the dispatcher places workgroup b, b + 256, b + 512 on
-    // the same CU, and co-resident workgroups that start together stay in lockstep for hundreds
-    // of microseconds — they stage, hit their barriers and run their epilogues at the same time,
-    // and the matrix pipe idles meanwhile.  Workgroup b of the first stagger_slots x 256 sleeps
-    // (b / 256) x stagger_cycles shader cycles before its first load, so the phases interleave.
-    // Placement only decides how well this works, never the result.
-    int stagger_slots, stagger_cycles;
 };
-
-#ifdef MRCNN_GEMM_TRACE
-__device__ unsigned long long g_trace[64 * 4 * 64 * 5];
-#endif
-#ifdef MRCNN_GEMM_CLOCKPROBE
-// developer instrumentation: per workgroup (shader-clock, 100 MHz reference clock) stamps at the
-// start and the end of the kernel body + the XCC / CU it ran on (tools/exp/clock_probe.py)
-constexpr int kProbeSlots = 16384;
-__device__ unsigned long long g_probe[kProbeSlots * 5];
-__device__ unsigned long long g_probe2[kProbeSlots * 8];   // main loop entry / exit (s_memrealtime)
-#endif
 
 // GEMM row -> (image, position) under the block-position-major order of GemmParams::perm_n
 constexpr int kPermBlock = 128;
@@ -245,10 +169,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *p, unsig
 }
 __device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t r, unsigned off)
 {
-#ifdef MRCNN_DBG_NOLOAD   // experiment: every staged load hits the out-of-range path
-    off = kOOB;
-#endif
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, MRCNN_GEMM_LOAD_AUX);
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z),
                        __uint_as_float(v.w));
 }
@@ -260,18 +181,12 @@ __device__ __forceinline__ void bstore1(__amdgpu_buffer_rsrc_t r, unsigned off, 
 {
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, off, 0, 0);
 }
-#ifndef MRCNN_GEMM_STORE_AUX
-#define MRCNN_GEMM_STORE_AUX 0
-#endif
 __device__ __forceinline__ void bstore4(__amdgpu_buffer_rsrc_t r, unsigned off, float4 v)
 {
     u32x4 u;
     u.x = __float_as_uint(v.x); u.y = __float_as_uint(v.y);
     u.z = __float_as_uint(v.z); u.w = __float_as_uint(v.w);
-#ifdef MRCNN_DBG_NOSTORE      // ablation: every wide store takes the dropped (out-of-range) path
-    off = kOOB;
-#endif
-    __builtin_amdgcn_raw_buffer_store_b128(u, r, off, 0, MRCNN_GEMM_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(u, r, off, 0, 0);
 }
 __device__ __forceinline__ void bstore8(__amdgpu_buffer_rsrc_t r, unsigned off, unsigned a, unsigned b)
 {
@@ -304,20 +219,12 @@ __device__ __forceinline__ unsigned pack_bf16(float a, float b)
 // which costs far more than its issue slot beside MFMAs (MI355X_MICROARCH.md, filler prices)
 __device__ __forceinline__ float sub_f32(float a, float b)
 {
-#ifdef MRCNN_SPLIT_PK_SUB
-    return a - b;
-#else
     float r;
     asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
-#endif
 }
 __device__ __forceinline__ void split3(float a, float b, unsigned &h, unsigned &m, unsigned &l)
 {
-#ifdef MRCNN_DBG_NOSPLITVALU   // ablation: no conversion arithmetic (results are garbage)
-    h = __float_as_uint(a); m = __float_as_uint(b); l = h ^ m;
-    return;
-#endif
     h = pack_bf16(a, b);
     a = sub_f32(a, __uint_as_float(h << 16));
     b = sub_f32(b, __uint_as_float(h & 0xffff0000u));
@@ -399,7 +306,7 @@ conv_gemm_kernel(const GemmParams p)
     const int gStride = GEO ? 1 : p.stride, gPad = PWC ? 0 : K3 ? 1 : p.pad;
     const int gPermN = GEO ? 0 : p.perm_n;
     const bool gStem = !GEO && p.stem;
-    constexpr bool ILV = MRCNN_SPLIT_ILV != 0 && SPLIT && MODE == FWD && !MASKED;
+    constexpr bool ILV = SPLIT && MODE == FWD && !MASKED;
     static_assert(!SPLIT || (BK == 32 && TM == TN &&
                              ((MODE == FWD && (TM == 1 || TM == 2)) || (MODE == WGRAD && !WPERM && TM == 2))),
                   "SPLIT: forward form (128x128, 64x64) / weight gradient (128x128) only");
@@ -431,30 +338,8 @@ conv_gemm_kernel(const GemmParams p)
     // register transfer) and a fragment read 16 rows with 16 different bank slots; the
     // permutation is undone where the tile is written (gw row 4 rr + .., column 4 li + ..).
     constexpr bool WROWPERM = SPLIT && MODE == WGRAD;
-    static_assert(!(WROWPERM && MRCNN_WGRAD_INKERNEL_REDUCE),
-                  "the WROWPERM epilogue returns before the in-kernel slab reduction: gw would stay unwritten");
     auto swz = [](int row) { return !SPLIT || MODE == WGRAD ? 0 : ((row >> 2) & 3) << 1; };
     const int tid = threadIdx.x;
-#ifdef MRCNN_GEMM_CLOCKPROBE
-    const unsigned long long probe_c0 = __builtin_amdgcn_s_memtime();
-    const unsigned long long probe_r0 = __builtin_amdgcn_s_memrealtime();
-    struct ProbeEnd {
-        unsigned long long c0, r0; int tid;
-        __device__ ~ProbeEnd() {
-            if (tid != 0) return;
-            const unsigned slot = blockIdx.x + blockIdx.y * gridDim.x + blockIdx.z * gridDim.x * gridDim.y;
-            if (slot >= (unsigned)kProbeSlots) return;
-            unsigned hw;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-            unsigned xcc;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            unsigned long long *q = g_probe + (size_t)slot * 5;
-            q[0] = c0; q[1] = r0;
-            q[2] = __builtin_amdgcn_s_memtime(); q[3] = __builtin_amdgcn_s_memrealtime();
-            q[4] = ((unsigned long long)xcc << 32) | hw;
-        }
-    } probe_end = {probe_c0, probe_r0, tid};
-#endif
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
 
@@ -510,9 +395,6 @@ conv_gemm_kernel(const GemmParams p)
         for (int i = 0; i < NA; ++i) {
             const int m = m0 + a_row(i);
             a_n[i] = m < p.M ? m : 0;          // (pixel index; folded into a_base below)
-#ifdef MRCNN_DBG_AMOD      // experiment: every tile reads the same few A rows (L2-resident operand)
-            a_n[i] &= MRCNN_DBG_AMOD - 1;
-#endif
             a_x[i] = 0;
             a_y[i] = m < p.M ? 0 : -(1 << 28);
         }
@@ -626,16 +508,6 @@ conv_gemm_kernel(const GemmParams p)
         nslices = max(0, min(nslices - kt0, split_len));
     }
 
-    if (p.stagger_cycles > 0) {
-        const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-        const unsigned slot = lin >> 8;
-        if (slot > 0 && slot < (unsigned)p.stagger_slots) {          // workgroup-uniform
-            const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-            const unsigned long long wait = (unsigned long long)slot * (unsigned)p.stagger_cycles;
-            while (__builtin_amdgcn_s_memtime() - t0 < wait) __builtin_amdgcn_s_sleep(8);
-        }
-    }
-
     float4 ra[AV], rb[BV];
     float4 rm[HAS_MASK ? AV : 1];
     float4 rscale = make_float4(1.f, 1.f, 1.f, 1.f);
@@ -692,9 +564,6 @@ conv_gemm_kernel(const GemmParams p)
     // (s_memtime stamps) before its first MFMA.
     unsigned oa[ILV ? NA : 1], ob[ILV ? NB : 1];
     auto ldA = [&](int i, unsigned off) {
-#ifdef MRCNN_DBG_NOLOAD_A     // ablation: the A operand's loads take the out-of-range path
-        off = kOOB;
-#endif
         if constexpr (ILV) {
             oa[i] = off;
         } else {
@@ -703,9 +572,6 @@ conv_gemm_kernel(const GemmParams p)
         }
     };
     auto ldB = [&](int i, unsigned off) {
-#ifdef MRCNN_DBG_NOLOAD_B
-        off = kOOB;
-#endif
         if constexpr (ILV) ob[i] = off;
         else rb[i] = bload4(rB, off);
     };
@@ -896,16 +762,7 @@ conv_gemm_kernel(const GemmParams p)
             }
 #pragma unroll
             for (int i = 0; i < BV; ++i) {
-#ifdef MRCNN_DBG_NOSPLIT_B    // ablation: the B operand costs no conversion (results are garbage)
-                const int row = kc_row + KC_RPP * i;
-                unsigned short *q = pb + row * SROW + ((kc_c4 ^ swz(row)) << 2);
-                const uint2 u = make_uint2(__float_as_uint(rb[i].x), __float_as_uint(rb[i].y));
-                *reinterpret_cast<uint2 *>(q) = u;
-                *reinterpret_cast<uint2 *>(q + PLB) = make_uint2(__float_as_uint(rb[i].z), __float_as_uint(rb[i].w));
-                *reinterpret_cast<uint2 *>(q + 2 * PLB) = u;
-#else
                 put(pb, PLB, kc_row + KC_RPP * i, rb[i]);
-#endif
             }
             return;
         }
@@ -995,9 +852,7 @@ conv_gemm_kernel(const GemmParams p)
                             (((ks * 4 + lk * 2) ^ swz(wn * (32 * TN) + j * 32 + li)) << 2));
             };
             frag(0, fa[0], fb[0]);
-#ifndef MRCNN_DBG_NOGLOBAL
             if constexpr (ISSUE) issue_loads();
-#endif
 #pragma unroll
             for (int ks = 0; ks < BK / 16; ++ks) {
                 if (ks + 1 < BK / 16) frag(ks + 1, fa[(ks + 1) & 1], fb[(ks + 1) & 1]);
@@ -1028,16 +883,11 @@ conv_gemm_kernel(const GemmParams p)
                 // and the second K step's fragment reads dealt out between them, then the rest
                 constexpr int NFR = 3 * (TM + TN), NMH = 6 * TM * TN;
                 __builtin_amdgcn_sched_group_barrier(0x100, NFR, 0);
-#if MRCNN_SPLIT_ILV == 2      // (A/B: loads bunched into the first K step's MFMAs)
-                sgb_interleave<NA + NB, NMH, NMH, NFR>();
-                __builtin_amdgcn_sched_group_barrier(0x008, NMH * (BK / 16 - 1), 0);
-#else
                 // the CU's texture path takes ~64 cycles per 16-byte-per-lane wave load whoever
                 // issues it (tools/exp/planes_probe.py ablations: kernel time = compute + 64 cycles
                 // x loads): a wave whose load waits for its slot issues no MFMA either, so the
                 // loads sit as far apart as the slice allows — one per NM / (NA + NB) MFMAs
                 sgb_interleave<NA + NB, NMH * (BK / 16), NMH * (BK / 16 - 1) - 2 * TM * TN, NFR>();
-#endif
             }
             return;
         }
@@ -1045,8 +895,6 @@ conv_gemm_kernel(const GemmParams p)
         const float *sb = smem[buf] + C_::A_FLOATS;
         float af[2][TM][4], bf[2][TN][4];
         load_frag(sa, sb, 0, af[0], bf[0]);
-        if (MRCNN_GEMM_SETPRIO == 1) __builtin_amdgcn_s_setprio(1);
-        if (MRCNN_GEMM_SETPRIO == 2) __builtin_amdgcn_s_setprio(0);   // staging phases run at 2
         // DS read instructions per K block (b32 pairs are merged into ds_read2_b32)
         constexpr int NR = (C_::A_KC ? TM : 2 * TM) + (C_::B_KC ? TN : 2 * TN);
         constexpr int NMFMA = 4 * TM * TN;
@@ -1076,16 +924,9 @@ conv_gemm_kernel(const GemmParams p)
                 __builtin_amdgcn_sched_group_barrier(0x008, NMFMA, 0);
             }
         }
-        if (MRCNN_GEMM_SETPRIO == 1) __builtin_amdgcn_s_setprio(0);
-        if (MRCNN_GEMM_SETPRIO == 2) __builtin_amdgcn_s_setprio(2);
     };
     auto compute = [&](int buf) { compute_(buf, std::true_type()); };
 
-#ifdef MRCNN_GEMM_CLOCKPROBE
-    const unsigned probe_slot = blockIdx.x + blockIdx.y * gridDim.x + blockIdx.z * gridDim.x * gridDim.y;
-    if (tid == 0 && probe_slot < (unsigned)kProbeSlots) g_probe2[probe_slot * 8] = __builtin_amdgcn_s_memrealtime();
-#endif
-    if (MRCNN_GEMM_SETPRIO == 2) __builtin_amdgcn_s_setprio(2);
     if (nslices > 0) {
         load_slice(0);
         issue_loads();
@@ -1127,34 +968,12 @@ conv_gemm_kernel(const GemmParams p)
         // one LDS stage (37 KB -> three workgroups per CU, three waves per SIMD): a wave spends
         // ~40 % of a slice issuing MFMAs and ~60 % staging, so three interleaved waves are
         // needed to keep the pipe full; two barriers per slice instead of one.
-#ifdef MRCNN_GEMM_TRACE
-        // developer instrumentation: per-phase s_memtime stamps of every wave of 64 workgroups
-        const unsigned tr_lin = blockIdx.x + blockIdx.y * gridDim.x;
-        unsigned long long *tr1 = g_trace + ((size_t)(tr_lin & 63) * 4 + wave) * 64 * 5;
-        const bool tr1_on = tr_lin >= 256 && tr_lin < 256 + 64 && lane == 0 && blockIdx.z == 0;
-#define TRACE1(slot)                                                             \
-    if (tr1_on && kt >= 4 && kt < 68) {                                          \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                       \
-        tr1[(kt - 4) * 5 + slot] = __builtin_amdgcn_s_memtime();                 \
-    }
-#else
-#define TRACE1(slot)
-#endif
         for (int kt = 0; kt < nslices; ++kt) {
-            TRACE1(0)
-#ifndef MRCNN_DBG_NOSTAGE     // ablation: MFMA + fragment reads only (results are garbage)
             if (kt > 0) {
                 __syncthreads();          // every wave is done reading the stage
-#ifdef MRCNN_GEMM_TRACE
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-                TRACE1(1)
                 store_slice(0);
             }
             __syncthreads();
-#endif
-            TRACE1(2)
-#ifndef MRCNN_DBG_NOGLOBAL    // ablation: no global loads in the loop (results are garbage)
             if (kt + 1 < nslices) {
                 load_slice(kt + 1);
             } else if constexpr (ILV) {      // (compute() issues the loads: none left)
@@ -1163,47 +982,19 @@ conv_gemm_kernel(const GemmParams p)
 #pragma unroll
                 for (int i = 0; i < NB; ++i) ob[i] = kOOB;
             }
-#endif
-            TRACE1(3)
             compute(0);
-            TRACE1(4)
         }
-#undef TRACE1
     } else {
         __syncthreads();
-#ifdef MRCNN_GEMM_TRACE
-        // developer instrumentation: per-phase s_memtime stamps of one wave per block
-        unsigned long long *tr = g_trace + ((size_t)blockIdx.x * 4 + wave) * 64 * 5;
-        const bool tr_on = blockIdx.x < 64 && lane == 0 && blockIdx.y == 0;
-#define TRACE_STAMP(slot)                                                        \
-    if (tr_on && kt >= 8 && kt < 72) {                                           \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                       \
-        tr[(kt - 8) * 5 + slot] = __builtin_amdgcn_s_memtime();                  \
-    }
-#else
-#define TRACE_STAMP(slot)
-#endif
         for (int kt = 0; kt < nslices; ++kt) {
             const bool more = kt + 1 < nslices;
-            TRACE_STAMP(0)
             if (more) load_slice(kt + 1);
-            TRACE_STAMP(1)
             compute(kt & 1);
-            TRACE_STAMP(2)
-#ifdef MRCNN_GEMM_TRACE
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-            TRACE_STAMP(3)
             if (more) store_slice((kt + 1) & 1);
             __syncthreads();
-            TRACE_STAMP(4)
         }
-#undef TRACE_STAMP
     }
 
-#ifdef MRCNN_GEMM_CLOCKPROBE
-    if (tid == 0 && probe_slot < (unsigned)kProbeSlots) g_probe2[probe_slot * 8 + 1] = __builtin_amdgcn_s_memrealtime();
-#endif
     // ---------------- epilogue ------------------------------------------------------
     // Per 32x32 MFMA tile: compute the 16 element offsets, issue every auxiliary load
     // (residual / accumulate / shortcut gradient) back to back, then combine and store.
@@ -1218,22 +1009,17 @@ conv_gemm_kernel(const GemmParams p)
     const __amdgpu_buffer_rsrc_t rResG = make_rsrc(p.res_g, p.c_bytes);
     const __amdgpu_buffer_rsrc_t rResY = make_rsrc(p.res_y, p.c_bytes);
     const __amdgpu_buffer_rsrc_t rOutM = make_rsrc(p.out_mask_y, p.c_bytes);
-#ifdef MRCNN_DBG_PLAIN_EPI     // ablation: no fused epilogue arithmetic at all (plain stores)
-    constexpr bool f_bias = false, f_aff = false, f_res = false, f_relu = false, f_acc = false;
-    constexpr bool f_resg = false, f_resy = false, f_outm = false;
-#else
     const bool f_bias = (e_flags & MRCNN_EPI_BIAS) != 0, f_aff = (e_flags & MRCNN_EPI_AFFINE) != 0;
     const bool f_res = (e_flags & MRCNN_EPI_RESIDUAL) != 0, f_relu = (e_flags & MRCNN_EPI_RELU) != 0;
     const bool f_acc = (e_flags & MRCNN_EPI_ACCUM) != 0;
     const bool f_resg = MODE != WGRAD && !tail && p.res_g != nullptr;
     const bool f_resy = f_resg && p.res_y != nullptr;
     const bool f_outm = MODE != WGRAD && !tail && p.out_mask_y != nullptr;
-#endif
     constexpr int EG = 8;       // accumulator rows handled per batch of auxiliary loads
 
     // (PW / W8 launches write plain rows in natural order by the host's rule)
-    if (MODE == FWD && TM >= 2 && MRCNN_GEMM_WIDE_EPILOGUE != 0 && (GEO || p.out_mode == OUT_PLAIN)) {   // (uniform)
-      if constexpr (MODE == FWD && TM >= 2 && MRCNN_GEMM_WIDE_EPILOGUE != 0) {
+    if (MODE == FWD && TM >= 2 && (GEO || p.out_mode == OUT_PLAIN)) {   // (uniform)
+      if constexpr (MODE == FWD && TM >= 2) {
         // Forward-form launches: the accumulators (one column x 16 rows per lane) are turned
         // into row-major float4s through the wave's corner of the LDS stages, so the residual
         // / mask reads and the output stores are 16 B per lane — a quarter of the memory
@@ -1245,12 +1031,6 @@ conv_gemm_kernel(const GemmParams p)
         constexpr int NK = 32 / RPI;                // passes per 32-row half
         constexpr int QG = TM >= 2 ? 4 : 2;         // passes whose loads are in flight together
         __syncthreads();                            // every wave is done with the K loop's LDS
-#ifdef MRCNN_GEMM_CLOCKPROBE
-#define PROBE2(k) if (tid == 0 && probe_slot < (unsigned)kProbeSlots) g_probe2[probe_slot * 8 + (k)] = __builtin_amdgcn_s_memrealtime();
-#else
-#define PROBE2(k)
-#endif
-        PROBE2(2)
         float *ep = &smem_all[0][0][0] + wave * (32 * LDW);
         const int c4 = lane % F4, r_in = lane / F4;
         const int col = n0 + wn * CW + c4 * 4;
@@ -1292,7 +1072,6 @@ conv_gemm_kernel(const GemmParams p)
                         ep[((e & 3) + 8 * (e >> 2) + 4 * lk) * LDW + j * 32 + li] = acc[i][j][e];
                 // same wave writes and reads: LDS operations of a wave execute in order
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                if (i == 0) { PROBE2(3) } else { PROBE2(5) }
 #pragma unroll
                 for (int kg = 0; kg < NK; kg += QG) {
                     unsigned off[QG];
@@ -1358,7 +1137,6 @@ conv_gemm_kernel(const GemmParams p)
                         bstore4(rC, off[q], make_float4(x[0], x[1], x[2], x[3]));
                     }
                 }
-                if (i == 0) { PROBE2(4) } else { PROBE2(6) }
             }
         };
         const int combo = (f_bias ? C_BIAS : 0) | (f_aff ? C_AFF : 0) | (f_res ? C_RES : 0) |
@@ -1511,65 +1289,6 @@ conv_gemm_kernel(const GemmParams p)
             }
         }
     }
-
-#if MRCNN_WGRAD_INKERNEL_REDUCE
-    if (MODE == WGRAD && p.tile_counters != nullptr) {
-        // Hand-off (MI355X_MICROARCH.md, inter-workgroup visibility): plain stores ->
-        // barrier -> lane 0: agent-scope release, explicit vmcnt(0), relaxed agent atomic on
-        // the tile's counter; the workgroup that observes splits-1 earlier arrivals performs
-        // ONE agent-scope acquire, then everybody reads the slabs with plain loads.
-        const int nsplits = (int)gridDim.y;
-        __syncthreads();                 // every wave is done with the LDS stages: reuse a word
-        int &s_last = *reinterpret_cast<int *>(&smem_all[0][0][0]);
-        if (threadIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const int old = __hip_atomic_fetch_add(&p.tile_counters[tile], 1, __ATOMIC_RELAXED,
-                                                   __HIP_MEMORY_SCOPE_AGENT);
-            const int last = old == nsplits - 1;
-            if (last) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                p.tile_counters[tile] = 0;       // ready for the next launch
-            }
-            s_last = last;
-        }
-        __syncthreads();
-        if (!s_last) return;
-        const __amdgpu_buffer_rsrc_t rOut = make_rsrc(p.reduce_out, p.c_bytes);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int col = n0 + wn * (32 * TN) + j * 32 + li;
-            const bool col_ok = col < p.N;
-            const int colc = col_ok ? col : 0;
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-#pragma unroll
-                for (int g = 0; g < 2; ++g) {
-                    unsigned off[8];
-                    float sum[8];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const int e = g * 8 + q;
-                        const int row = m0 + wm * (32 * TM) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * lk;
-                        off[q] = (col_ok && row < p.M) ? 4u * (unsigned)(row * p.ldc + colc) : kOOB;
-                        sum[q] = 0.f;
-                    }
-                    for (int sp = 0; sp < nsplits; ++sp) {       // fixed order: deterministic
-                        const __amdgpu_buffer_rsrc_t rS =
-                            make_rsrc(p.C + (int64_t)sp * p.split_stride, p.c_bytes);
-                        float v[8];
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) v[q] = bload1(rS, off[q]);
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) sum[q] += v[q];
-                    }
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) bstore1(rOut, off[q], sum[q]);
-                }
-            }
-        }
-    }
-#endif
 }
 
 __global__ void splitk_reduce_kernel(const float *__restrict__ ws, int splits, int64_t n,
@@ -1602,16 +1321,11 @@ __global__ void splitk_reduce_kernel(const float *__restrict__ ws, int splits, i
 // Workgroups resident at once: 128x128 tiles run 2 per CU (73 KB LDS), 64x64 tiles 4 per CU.
 constexpr int64_t kSlotsBig = 512, kSlotsSmall = 1024;
 
-int g_extra_lds = 0;   // developer knob: dynamic LDS bytes added to every GEMM launch (lowers
-                       // the resident workgroups per CU for co-residency experiments)
-
 int g_split_bf16 = 3;  // mrcnn_set_tuning("split_bf16"): bit 0 = 128x128 kernels, bit 1 = 64x64 forward form on the
                        // split-operand arithmetic (see SPLIT; the default since round 4), 0 = fp32 MFMA everywhere
-int g_stagger = 0;    // mrcnn_set_tuning("stagger", percent of the nominal start-up stagger; 0 = off)
 int g_big_split_k = -1; // mrcnn_set_tuning("big_split_k"): small-M problems as 128x128 tiles cut along K.
                       // -1 (default since round 6) = the one-round rule in launch(), 0 = off (64x64 tiles),
                       // k > 0 = aim at k workgroups
-int g_stagger_min_rounds = 2;
 int g_big_split_min_slices = 16;   // mrcnn_set_tuning("big_split_min_slices"): fewest K slices per slab of the one-round rule
 int g_w8_min_k = 256; // mrcnn_set_tuning("w8_min_k"): shallowest K (input channels) a W8 launch takes
 int g_w8 = 1;         // mrcnn_set_tuning("w8", 0/1): 256x128 tiles on 512-thread workgroups (W8) for the large
@@ -1635,68 +1349,28 @@ inline bool k3_plain(const GemmParams &p)
 }
 
 template <int TM, int TN, int MODE, bool MASKED>
-void launch_kernel_m(const GemmParams &p0, int64_t tiles, int splits, hipStream_t s, int batch = 1)
+void launch_kernel_m(const GemmParams &p, int64_t tiles, int splits, hipStream_t s, int batch = 1)
 {
-    GemmParams p = p0;
-    {
-        // resident workgroups per CU of this instantiation (registers / LDS, see min_blocks)
-        const int slots = TM == 4 ? 2 : single_buffered(TM, MODE, MASKED) ? (TM == 2 ? 3 : 6) : (TM == 2 ? 2 : 4);
-        const int64_t wgs = tiles * splits * batch;
-        // K slices one workgroup walks and the matrix-pipe cycles of one of its waves per slice
-        const int64_t slices = MODE == WGRAD ? mrcnn::ceil_div(p.split_len, BK)
-                               : (p.split_len > 0 ? p.split_len
-                                                  : (int64_t)p.R * p.S * mrcnn::ceil_div(p.stem ? 32 : p.Kc, BK));
-        const int64_t slice_cycles = 4 * TM * TN * (BK / 8) * 64;
-        p.stagger_slots = 0; p.stagger_cycles = 0;
-        if (g_stagger > 0 && wgs >= 256ll * slots) {
-            int64_t cyc;
-            if (wgs >= (int64_t)g_stagger_min_rounds * 256 * slots)
-                cyc = slices * slice_cycles;       // a third (1 / slots) of a tile's lifetime
-            else
-                cyc = slice_cycles + 512;          // one round only: interleave the slice phases
-            cyc = cyc * g_stagger / 100;
-            p.stagger_slots = slots;
-            p.stagger_cycles = (int)std::min<int64_t>(cyc, 1 << 20);
-        }
-    }
     hipEvent_t ev0, ev1;          // kernel-only timing (ProfKernelScope of the caller), usually null
     mrcnn::prof_take(&ev0, &ev1);
+    auto go = [&](auto kernel) {
+        hipExtLaunchKernelGGL(kernel, dim3((unsigned)tiles, splits, batch), dim3(256), 0, s, ev0, ev1, 0, p);
+    };
     if constexpr (MODE == WGRAD && TM == 2 && TN == 2) {
-        if ((g_split_bf16 & 1) && p.perm_n == 0) {
-            hipExtLaunchKernelGGL((conv_gemm_kernel<TM, TN, MODE, MASKED, false, true>),
-                               dim3((unsigned)tiles, splits, batch), dim3(256), g_extra_lds, s, ev0, ev1, 0,
-                                  p);
-            return;
-        }
+        if ((g_split_bf16 & 1) && p.perm_n == 0) return go(conv_gemm_kernel<TM, TN, MODE, MASKED, false, true>);
     }
     if constexpr (MODE == WGRAD && !MASKED) {
-        if (p.perm_n > 0) {
-            hipExtLaunchKernelGGL((conv_gemm_kernel<TM, TN, MODE, MASKED, true>),
-                               dim3((unsigned)tiles, splits, batch), dim3(256), g_extra_lds, s, ev0, ev1, 0,
-                                  p);
-            return;
-        }
+        if (p.perm_n > 0) return go(conv_gemm_kernel<TM, TN, MODE, MASKED, true>);
     }
     if constexpr (MODE == FWD && TM == TN && (TM == 1 || TM == 2)) {
         if (g_split_bf16 & (TM == 2 ? 1 : 2)) {
-            if ((g_pw & 1) && pw_plain(p))
-                hipExtLaunchKernelGGL((conv_gemm_kernel<TM, TN, MODE, MASKED, false, true, false, true>),
-                                      dim3((unsigned)tiles, splits, batch), dim3(256), g_extra_lds, s, ev0, ev1,
-                                      0, p);
-            else if ((g_pw & 2) && k3_plain(p))
-                hipExtLaunchKernelGGL((conv_gemm_kernel<TM, TN, MODE, MASKED, false, true, false, false, true>),
-                                      dim3((unsigned)tiles, splits, batch), dim3(256), g_extra_lds, s, ev0, ev1,
-                                      0, p);
-            else
-                hipExtLaunchKernelGGL((conv_gemm_kernel<TM, TN, MODE, MASKED, false, true>),
-                                      dim3((unsigned)tiles, splits, batch), dim3(256), g_extra_lds, s, ev0, ev1,
-                                      0, p);
-            return;
+            if ((g_pw & 1) && pw_plain(p)) return go(conv_gemm_kernel<TM, TN, MODE, MASKED, false, true, false, true>);
+            if ((g_pw & 2) && k3_plain(p))
+                return go(conv_gemm_kernel<TM, TN, MODE, MASKED, false, true, false, false, true>);
+            return go(conv_gemm_kernel<TM, TN, MODE, MASKED, false, true>);
         }
     }
-    hipExtLaunchKernelGGL((conv_gemm_kernel<TM, TN, MODE, MASKED>),
-                       dim3((unsigned)tiles, splits, batch), dim3(256), g_extra_lds, s, ev0, ev1, 0,
-                                  p);
+    go(conv_gemm_kernel<TM, TN, MODE, MASKED>);
 }
 
 inline bool is_masked(const GemmParams &p) { return p.mask_y != nullptr || p.in_scale != nullptr; }
@@ -1728,7 +1402,7 @@ void launch_w8_kernel(const GemmParams &p, int64_t wgs, int batch, hipStream_t s
     hipEvent_t ev0, ev1;
     mrcnn::prof_take(&ev0, &ev1);
     hipExtLaunchKernelGGL((conv_gemm_kernel<2, 2, FWD, false, false, true, true>),
-                          dim3((unsigned)wgs, 1, batch), dim3(512), g_extra_lds, s, ev0, ev1, 0, p);
+                          dim3((unsigned)wgs, 1, batch), dim3(512), 0, s, ev0, ev1, 0, p);
 }
 
 template <int TM, int TN, int MODE>
@@ -1736,6 +1410,20 @@ void launch_kernel(const GemmParams &p, int64_t tiles, int splits, hipStream_t s
 {
     if (is_masked(p)) launch_kernel_m<TM, TN, MODE, true>(p, tiles, splits, s, batch);
     else launch_kernel_m<TM, TN, MODE, false>(p, tiles, splits, s, batch);
+}
+
+// Profiler record of a forward-form / DGRAD launch over `rows` GEMM rows: the operation and byte
+// estimate of the problem, and the bucket of the kernel SYMBOL (what rocprofv3 reports): the
+// forward-form instantiation runs forward convolutions and the transposed-filter dgrads alike
+template <int TM, int MODE>
+mrcnn::ProfKernelScope gemm_prof(const GemmParams &p, int64_t rows, bool w8 = false)
+{
+    const double kdepth = (double)p.R * p.S * (p.stem ? 21.0 : (double)p.Kc);
+    const double flops = 2.0 * rows * p.N * kdepth;
+    const double bytes = 4.0 * ((double)rows * p.N + (double)rows * p.Kc + (double)p.N * kdepth);
+    const int kind = w8 ? mrcnn::PROF_CONV_FWD_W8
+                        : (MODE == FWD ? mrcnn::PROF_CONV_FWD_128 : mrcnn::PROF_CONV_DGRAD_128) + (TM >= 2 ? 0 : 1);
+    return mrcnn::ProfKernelScope(kind, flops, bytes);
 }
 
 template <int TM, int TN, int MODE>
@@ -1746,18 +1434,8 @@ void launch_tiles(GemmParams p, int m_lo, int m_hi, int splits, hipStream_t s)
     p.M = m_hi;
     const int64_t blocks = mrcnn::ceil_div(m_hi - m_lo, BM) * mrcnn::ceil_div(p.N, BN);
     if (blocks <= 0) return;
-    const int64_t rows = m_hi - m_lo;
-    const double kdepth = (double)p.R * p.S * (p.stem ? 21.0 : (double)p.Kc);
-    const double flops = 2.0 * rows * p.N * kdepth;
-    const double bytes = 4.0 * ((double)rows * p.N + (double)rows * p.Kc + (double)p.N * kdepth);
-    // profiler buckets follow the kernel SYMBOL (what rocprofv3 reports): the forward-form
-    // instantiation runs forward convolutions and the transposed-filter dgrads alike
-    {
-        mrcnn::ProfKernelScope prof((MODE == FWD ? mrcnn::PROF_CONV_FWD_128 : mrcnn::PROF_CONV_DGRAD_128) +
-                                        (TM >= 2 ? 0 : 1),
-                                    flops, bytes);
-        launch_kernel<TM, TN, MODE>(p, blocks, splits, s);
-    }
+    const auto prof = gemm_prof<TM, MODE>(p, m_hi - m_lo);
+    launch_kernel<TM, TN, MODE>(p, blocks, splits, s);
 }
 
 // ---- split-K for the leftover rows of a small-M forward / dgrad ----------------------------
@@ -1818,31 +1496,70 @@ bool can_split_rows(const GemmParams &p)
            p.ldc == p.N;
 }
 
+// fewer slabs while `splits` slabs of a rows x N output overflow the split-K workspace
+int64_t fit_ws(int64_t splits, int64_t rows, int N)
+{
+    while (splits > 1 && rows * N * splits * 4 > kSplitWsBytes) --splits;
+    return splits;
+}
+
+// K-split count of a split launch over `tiles` tiles of a rows x N output: about target_wgs
+// workgroups, at most `cap` slabs, each at least depth_div K slices deep, within the workspace
+int64_t k_splits(int total_slices, int depth_div, int64_t target_wgs, int64_t tiles, int64_t rows, int N,
+                 int64_t cap)
+{
+    return fit_ws(std::min<int64_t>(std::min<int64_t>(cap, total_slices / depth_div),
+                                    mrcnn::ceil_div(target_wgs, tiles)),
+                  rows, N);
+}
+
+// The ordered sum of the `splits` slabs of p.split_ws that hold rows [rows_lo, p.M), with p's
+// epilogue, into p.C
+template <int MODE>
+void slab_sum(const GemmParams &p, int rows_lo, int splits, hipStream_t s)
+{
+    const int rows = p.M - rows_lo;
+    FixParams f = {};
+    f.ws = p.split_ws; f.C = p.C;
+    f.bias = p.bias; f.scale = p.scale; f.shift = p.shift; f.residual = p.residual;
+    f.res_g = p.res_g; f.res_y = p.res_y; f.out_mask_y = p.out_mask_y;
+    f.splits = splits; f.rows = rows; f.N = p.N; f.row0 = rows_lo; f.ldc = p.ldc;
+    f.flags = p.flags; f.stride = (int64_t)rows * p.N;
+    f.perm_n = MODE == FWD ? p.perm_n : 0; f.pq = p.gp * p.gq;
+    const int64_t n = (int64_t)rows * (p.N / 4);
+    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)mrcnn::ceil_div(n, 256)), dim3(256), 0, s, f);
+}
+
 // rows [rows_lo, p.M) as 64 TM x 64 TM tiles cut along K into `splits` slabs + the ordered slab sum
 template <int MODE, int TM = 1>
 void launch_split_rows(const GemmParams &p, int rows_lo, int splits, int total_slices, hipStream_t s)
 {
-    const int rows_left = p.M - rows_lo;
     GemmParams q = p;
     q.C = p.split_ws;
     q.flags = 0;
     q.bias = q.scale = q.shift = q.residual = q.res_g = q.res_y = q.out_mask_y = nullptr;
     q.split_len = (int)mrcnn::ceil_div(total_slices, splits);
     splits = (int)mrcnn::ceil_div(total_slices, q.split_len);
-    q.split_stride = (int64_t)rows_left * p.N;
+    q.split_stride = (int64_t)(p.M - rows_lo) * p.N;
     q.out_row0 = rows_lo;
     q.c_bytes = (unsigned)(q.split_stride * 4);
     launch_tiles<TM, TM, MODE>(q, rows_lo, p.M, splits, s);
-    FixParams f = {};
-    f.ws = p.split_ws; f.C = p.C;
-    f.bias = p.bias; f.scale = p.scale; f.shift = p.shift; f.residual = p.residual;
-    f.res_g = p.res_g; f.res_y = p.res_y; f.out_mask_y = p.out_mask_y;
-    f.splits = splits; f.rows = rows_left; f.N = p.N; f.row0 = rows_lo; f.ldc = p.ldc;
-    f.flags = p.flags; f.stride = q.split_stride;
-    f.perm_n = MODE == FWD ? p.perm_n : 0; f.pq = p.gp * p.gq;
-    const int64_t n = (int64_t)rows_left * (p.N / 4);
-    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)mrcnn::ceil_div(n, 256)), dim3(256), 0,
-                       s, f);
+    slab_sum<MODE>(p, rows_lo, splits, s);
+}
+
+// Rows [rows_main, p.M) as the K-split pieces of a fused launch (GemmParams::tail_*) behind its
+// first tail_first workgroups; returns the pieces per tile, re-derived from the slab depth.
+int set_tail(GemmParams &p, int rows_main, int64_t tail_first, int total_slices, int64_t splits)
+{
+    p.tail_split_len = (int)mrcnn::ceil_div(total_slices, splits);
+    p.tail_splits = (int)mrcnn::ceil_div(total_slices, p.tail_split_len);
+    p.tail_first = (int)tail_first;
+    p.tail_row0 = rows_main;
+    p.tail_ws = p.split_ws;
+    p.tail_stride = (int64_t)(p.M - rows_main) * p.N;
+    p.tail_bytes = (unsigned)(p.tail_stride * 4);
+    p.m_lo = 0;
+    return p.tail_splits;
 }
 
 int g_fused_tail = 512;            // mrcnn_set_tuning("fused_tail", 0 = off, else target number of tail pieces)
@@ -1859,41 +1576,16 @@ bool launch_fused_tail(GemmParams p, int rows_main, hipStream_t s)
         return false;
     const int64_t ntn = mrcnn::ceil_div(p.N, BN);
     const int64_t main_tiles = (rows_main / BM) * ntn;
-    const int rows_left = p.M - rows_main;
-    const int64_t tail_tiles = mrcnn::ceil_div(rows_left, BM) * ntn;
+    const int64_t tail_tiles = mrcnn::ceil_div(p.M - rows_main, BM) * ntn;
     const int total_slices = p.R * p.S * (int)mrcnn::ceil_div(p.Kc, BK);
-    int64_t splits = std::min<int64_t>(std::min<int64_t>(16, total_slices / 4),
-                                       mrcnn::ceil_div(g_fused_tail, tail_tiles));
-    while (splits > 1 && (int64_t)rows_left * p.N * splits * 4 > kSplitWsBytes) --splits;
+    const int64_t splits = k_splits(total_slices, 4, g_fused_tail, tail_tiles, p.M - rows_main, p.N, 16);
     if (splits < 2) return false;
-    p.tail_split_len = (int)mrcnn::ceil_div(total_slices, splits);
-    splits = mrcnn::ceil_div(total_slices, p.tail_split_len);
-    p.tail_first = (int)main_tiles;
-    p.tail_splits = (int)splits;
-    p.tail_row0 = rows_main;
-    p.tail_ws = p.split_ws;
-    p.tail_stride = (int64_t)rows_left * p.N;
-    p.tail_bytes = (unsigned)(p.tail_stride * 4);
-    p.m_lo = 0;
+    const int pieces = set_tail(p, rows_main, main_tiles, total_slices, splits);
     {
-        const double kdepth = (double)p.R * p.S * (double)p.Kc;
-        const double flops = 2.0 * p.M * p.N * kdepth;
-        const double bytes = 4.0 * ((double)p.M * p.N + (double)p.M * p.Kc + (double)p.N * kdepth);
-        mrcnn::ProfKernelScope prof((MODE == FWD ? mrcnn::PROF_CONV_FWD_128 : mrcnn::PROF_CONV_DGRAD_128) +
-                                        (TM >= 2 ? 0 : 1),
-                                    flops, bytes);
-        launch_kernel<TM, TN, MODE>(p, main_tiles + tail_tiles * splits, 1, s);
+        const auto prof = gemm_prof<TM, MODE>(p, p.M);
+        launch_kernel<TM, TN, MODE>(p, main_tiles + tail_tiles * pieces, 1, s);
     }
-    FixParams f = {};
-    f.ws = p.split_ws; f.C = p.C;
-    f.bias = p.bias; f.scale = p.scale; f.shift = p.shift; f.residual = p.residual;
-    f.res_g = p.res_g; f.res_y = p.res_y; f.out_mask_y = p.out_mask_y;
-    f.splits = (int)splits; f.rows = rows_left; f.N = p.N; f.row0 = rows_main; f.ldc = p.ldc;
-    f.flags = p.flags; f.stride = p.tail_stride;
-    f.perm_n = MODE == FWD ? p.perm_n : 0; f.pq = p.gp * p.gq;
-    const int64_t n = (int64_t)rows_left * (p.N / 4);
-    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)mrcnn::ceil_div(n, 256)), dim3(256), 0,
-                       s, f);
+    slab_sum<MODE>(p, rows_main, pieces, s);
     return true;
 }
 
@@ -1905,9 +1597,7 @@ void launch_remainder(const GemmParams &p, int rows_lo, hipStream_t s)
 {
     const int64_t left_tiles = mrcnn::ceil_div(p.M - rows_lo, 64) * mrcnn::ceil_div(p.N, 64);
     const int total_slices = p.R * p.S * (int)mrcnn::ceil_div(p.Kc, BK);
-    int64_t splits = std::min<int64_t>(std::min<int64_t>(16, total_slices / 8),
-                                       mrcnn::ceil_div(512, left_tiles));
-    while (splits > 1 && (int64_t)(p.M - rows_lo) * p.N * splits * 4 > kSplitWsBytes) --splits;
+    const int64_t splits = k_splits(total_slices, 8, 512, left_tiles, p.M - rows_lo, p.N, 16);
     if (!can_split_rows<MODE>(p) || splits < 2) {
         launch_tiles<1, 1, MODE>(p, rows_lo, p.M, 1, s);
         return;
@@ -1917,56 +1607,32 @@ void launch_remainder(const GemmParams &p, int rows_lo, hipStream_t s)
 
 // One W8 launch for the whole problem: whole rounds of 256 tiles (one 512-thread workgroup per CU)
 // and, when the last round would be less than ~60 % full, its rows as K-split pieces appended to
-// the same grid + the ordered slab sum (the fused-tail scheme of launch_fused_tail).
+// the same grid + the ordered slab sum (the fused-tail scheme of launch_fused_tail, with its own
+// K partition: the W8 and the 128x128 tail pieces of a problem are not bit-identical).
 void launch_w8(GemmParams p, hipStream_t s)
 {
     const int64_t tm = mrcnn::ceil_div(p.M, kW8BM), tn = mrcnn::ceil_div(p.N, kW8BN);
     const int64_t T = tm * tn, full = T / 256, rem = T - full * 256;
-    const double kdepth = (double)p.Kc;
-    const double flops = 2.0 * p.M * p.N * kdepth;
-    const double bytes = 4.0 * ((double)p.M * p.N + (double)p.M * p.Kc + (double)p.N * kdepth);
     const int total_slices = (int)mrcnn::ceil_div(p.Kc, BK);
     int64_t main_rows_tiles = tm;
     if (rem > 0 && rem < 154 && full >= 1 && g_fused_tail && p.split_ws && p.N % 4 == 0 && p.ldc == p.N)
         main_rows_tiles = (full * 256) / tn;
     const int rows_main = (int)std::min<int64_t>(p.M, main_rows_tiles * kW8BM);
-    int64_t splits = 1, tail_tiles = 0;
-    if (rows_main < p.M) {
-        const int rows_left = p.M - rows_main;
-        tail_tiles = mrcnn::ceil_div(rows_left, kW8BM) * tn;
-        splits = std::min<int64_t>(std::min<int64_t>(16, total_slices / 4), mrcnn::ceil_div(256, tail_tiles));
-        while (splits > 1 && (int64_t)rows_left * p.N * splits * 4 > kSplitWsBytes) --splits;
-    }
-    mrcnn::ProfKernelScope prof(mrcnn::PROF_CONV_FWD_W8, flops, bytes);
+    const int64_t tail_tiles = mrcnn::ceil_div(p.M - rows_main, kW8BM) * tn;
+    const int64_t splits =
+        rows_main < p.M ? k_splits(total_slices, 4, 256, tail_tiles, p.M - rows_main, p.N, 16) : 1;
+    const auto prof = gemm_prof<2, FWD>(p, p.M, true);
     if (splits < 2) {
         p.m_lo = 0;
         launch_w8_kernel(p, T, 1, s);
         return;
     }
-    const int rows_left = p.M - rows_main;
-    p.tail_split_len = (int)mrcnn::ceil_div(total_slices, splits);
-    splits = mrcnn::ceil_div(total_slices, p.tail_split_len);
-    p.tail_first = (int)(main_rows_tiles * tn);
-    p.tail_splits = (int)splits;
-    p.tail_row0 = rows_main;
-    p.tail_ws = p.split_ws;
-    p.tail_stride = (int64_t)rows_left * p.N;
-    p.tail_bytes = (unsigned)(p.tail_stride * 4);
-    p.m_lo = 0;
-    launch_w8_kernel(p, p.tail_first + tail_tiles * splits, 1, s);
-    FixParams f = {};
-    f.ws = p.split_ws; f.C = p.C;
-    f.bias = p.bias; f.scale = p.scale; f.shift = p.shift; f.residual = p.residual;
-    f.res_g = p.res_g; f.res_y = p.res_y; f.out_mask_y = p.out_mask_y;
-    f.splits = (int)splits; f.rows = rows_left; f.N = p.N; f.row0 = rows_main; f.ldc = p.ldc;
-    f.flags = p.flags; f.stride = p.tail_stride;
-    f.perm_n = 0; f.pq = p.gp * p.gq;
-    const int64_t n = (int64_t)rows_left * (p.N / 4);
-    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)mrcnn::ceil_div(n, 256)), dim3(256), 0, s, f);
+    const int pieces = set_tail(p, rows_main, main_rows_tiles * tn, total_slices, splits);
+    launch_w8_kernel(p, p.tail_first + tail_tiles * pieces, 1, s);
+    slab_sum<FWD>(p, rows_main, pieces, s);
 }
 
 extern float g_wino_ambiguity;
-int g_small_whole_max = 1024, g_small_rem_max = 154;   // developer knobs (A/B)
 int g_big_min_tiles = 384;        // mrcnn_set_tuning("big_min_tiles"): fewest 128x128 tiles that get 128x128 tiles
 int g_small_m_split = 0;          // mrcnn_set_tuning("small_m_split", target workgroups per CU)
 int g_tiny_split = 1;             // mrcnn_set_tuning("tiny_split", 0/1): K-split of launches with <= 128 tiles and >= 32 slices
@@ -1986,8 +1652,7 @@ void launch_small(const GemmParams &p, hipStream_t s)
     // tiles of 64 slices each on 112 of 256 CUs, 80 us of pure K-loop latency): cut along K so that
     // ~512 workgroups share the walk, ordered slab sum as for the leftover rows.
     if (g_tiny_split && can_split_rows<MODE>(p) && T <= 128 && total_slices >= 32) {
-        int64_t splits = std::min<int64_t>(std::min<int64_t>(16, total_slices / 8), mrcnn::ceil_div(512, T));
-        while (splits > 1 && (int64_t)p.M * p.N * splits * 4 > kSplitWsBytes) --splits;
+        const int64_t splits = k_splits(total_slices, 8, 512, T, p.M, p.N, 16);
         if (splits >= 2) {
             launch_split_rows<MODE>(p, 0, (int)splits, total_slices, s);
             return;
@@ -1995,24 +1660,23 @@ void launch_small(const GemmParams &p, hipStream_t s)
     }
     if (g_small_m_split > 0 && can_split_rows<MODE>(p) && T < 256ll * g_small_m_split &&
         total_slices >= 16) {
-        int64_t splits = std::min<int64_t>(std::min<int64_t>(16, total_slices / 8),
-                                           mrcnn::ceil_div(256ll * g_small_m_split, T));
-        while (splits > 1 && (int64_t)p.M * p.N * splits * 4 > kSplitWsBytes) --splits;
+        const int64_t splits = k_splits(total_slices, 8, 256ll * g_small_m_split, T, p.M, p.N, 16);
         if (splits >= 2) {
             launch_split_rows<MODE>(p, 0, (int)splits, total_slices, s);
             return;
         }
     }
-    const bool can_split = can_split_rows<MODE>(p) && whole > 0 && whole <= g_small_whole_max && rem > 0 &&
-                           rem < g_small_rem_max && total_slices >= 8;   // beyond 4 tile-times per CU the
+    const bool can_split = can_split_rows<MODE>(p) && whole > 0 && whole <= 1024 && rem > 0 &&
+                           rem < 154 && total_slices >= 8;   // beyond 4 tile-times per CU the
                                                              // two extra launches cost more than
                                                              // the imbalance
     const int rows_main = can_split ? (int)std::min<int64_t>(p.M, (whole / tn) * 64) : p.M;
     const int64_t left_tiles = mrcnn::ceil_div(p.M - rows_main, 64) * tn;
     int splits = 1;
+    // (two or more slabs need left_tiles < 256, so splits x left_tiles < 512 tiles of 16 KB: the
+    // workspace clamp of k_splits never applies here)
     if (can_split && rows_main < p.M)
-        splits = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(16, total_slices / 4),
-                                                               mrcnn::ceil_div(256, left_tiles)));
+        splits = (int)k_splits(total_slices, 4, 256, left_tiles, p.M - rows_main, p.N, 16);
     if (splits < 2) {
         launch_tiles<1, 1, MODE>(p, 0, p.M, 1, s);
         return;
@@ -2047,12 +1711,12 @@ int launch(const GemmParams &p0, int splits, hipStream_t s)
     int64_t ksplits = 1;
     if (g_big_split_k != 0 && big_ok && T < g_big_min_tiles && splits == 1 && can_split_rows<MODE>(p)) {
         if (g_big_split_k > 0) {
-            ksplits = std::min<int64_t>(std::min<int64_t>(8, total_slices_ / 8), mrcnn::ceil_div(g_big_split_k, T));
+            ksplits = k_splits(total_slices_, 8, g_big_split_k, T, p.M, p.N, 8);
         } else {
             const int64_t fit = kSlotsBig / T;                 // splits that still make one round
-            if (fit >= 2 && fit <= 8 && T * fit >= kSlotsBig * 3 / 4 && total_slices_ / fit >= g_big_split_min_slices) ksplits = fit;
+            if (fit >= 2 && fit <= 8 && T * fit >= kSlotsBig * 3 / 4 && total_slices_ / fit >= g_big_split_min_slices)
+                ksplits = fit_ws(fit, p.M, p.N);
         }
-        while (ksplits > 1 && (int64_t)p.M * p.N * ksplits * 4 > kSplitWsBytes) --ksplits;
     }
     if (MODE == FWD && splits == 1 && w8_ok(p)) {
         launch_w8(p, s);
@@ -2146,30 +1810,6 @@ int wgrad_splits(int64_t tiles, int64_t pixels, int64_t slots)
 
 }  // namespace
 
-#ifdef MRCNN_GEMM_CLOCKPROBE
-extern "C" int mrcnn_gemm_probe_read(unsigned long long *host, int n)
-{
-    MRCNN_HIP_TRY(hipMemcpyFromSymbol(host, HIP_SYMBOL(g_probe), sizeof(unsigned long long) * n));
-    void *dptr = nullptr;
-    MRCNN_HIP_TRY(hipGetSymbolAddress(&dptr, HIP_SYMBOL(g_probe)));
-    MRCNN_HIP_TRY(hipMemset(dptr, 0, sizeof(g_probe)));      // ready for the next pass
-    return 0;
-}
-extern "C" int mrcnn_gemm_probe2_read(unsigned long long *host, int n)
-{
-    MRCNN_HIP_TRY(hipMemcpyFromSymbol(host, HIP_SYMBOL(g_probe2), sizeof(unsigned long long) * n));
-    return 0;
-}
-#endif
-
-#ifdef MRCNN_GEMM_TRACE
-extern "C" int mrcnn_gemm_trace_read(unsigned long long *host, int n)
-{
-    MRCNN_HIP_TRY(hipMemcpyFromSymbol(host, HIP_SYMBOL(g_trace), sizeof(unsigned long long) * n));
-    return 0;
-}
-#endif
-
 extern "C" int64_t mrcnn_conv2d_split_workspace_bytes(void) { return kSplitWsBytes; }
 
 extern "C" int mrcnn_set_tuning(const char *name, int value)
@@ -2177,10 +1817,6 @@ extern "C" int mrcnn_set_tuning(const char *name, int value)
     MRCNN_REQUIRE(name != nullptr, "set_tuning: null name");
     if (strcmp(name, "position_major_rows") == 0) {
         g_position_major_rows = value != 0;
-        return 0;
-    }
-    if (strcmp(name, "gemm_extra_lds") == 0) {
-        g_extra_lds = value;
         return 0;
     }
     if (strcmp(name, "fused_tail") == 0) {
@@ -2195,24 +1831,12 @@ extern "C" int mrcnn_set_tuning(const char *name, int value)
         g_big_min_tiles = value;
         return 0;
     }
-    if (strcmp(name, "small_whole_max") == 0) {
-        g_small_whole_max = value;
-        return 0;
-    }
-    if (strcmp(name, "small_rem_max") == 0) {
-        g_small_rem_max = value;
-        return 0;
-    }
     if (strcmp(name, "small_m_split") == 0) {
         g_small_m_split = value;
         return 0;
     }
     if (strcmp(name, "split_bf16") == 0) {
         g_split_bf16 = value;          // bit 0: 128x128 kernels, bit 1: 64x64 forward form
-        return 0;
-    }
-    if (strcmp(name, "stagger") == 0) {
-        g_stagger = value;
         return 0;
     }
     if (strcmp(name, "big_split_k") == 0) {
@@ -2237,10 +1861,6 @@ extern "C" int mrcnn_set_tuning(const char *name, int value)
     }
     if (strcmp(name, "tiny_split") == 0) {
         g_tiny_split = value;
-        return 0;
-    }
-    if (strcmp(name, "stagger_min_rounds") == 0) {
-        g_stagger_min_rounds = value;
         return 0;
     }
     if (mrcnn::roi_align_set_tuning(name, value) == 0) return 0;     // roi_fwd_lanes / roi_bwd_lanes
@@ -2273,13 +1893,6 @@ extern "C" int mrcnn_conv2d_fwd(const mrcnn_conv_desc *d, const float *x, const 
     if (int rc = set_extents(p, (int64_t)d->N * d->H * d->W * d->C, (int64_t)d->K * d->R * d->S * d->C,
                              (int64_t)d->N * d->P * d->Q * d->K))
         return rc;
-#ifdef MRCNN_DBG_PITCH      // experiment: rows of x and w MRCNN_DBG_PITCH floats apart (caller over-allocates)
-    if (d->R == 1 && d->stride == 1) {
-        p.lda = d->C + MRCNN_DBG_PITCH; p.ldb = d->C + MRCNN_DBG_PITCH;
-        p.a_bytes = (unsigned)((int64_t)d->N * d->H * d->W * p.lda * 4);
-        p.b_bytes = (unsigned)((int64_t)d->K * p.ldb * 4);
-    }
-#endif
     return launch<FWD>(p, 1, mrcnn::as_stream(stream));
 }
 
@@ -2530,7 +2143,7 @@ extern "C" int64_t mrcnn_conv2d_wgrad_workspace_bytes(const mrcnn_conv_desc *d)
 {
     if (!d) return 0;
     const int64_t gwsz = (int64_t)d->K * d->R * d->S * d->C;
-    return 64 * gwsz * 4 + kWgradCounterBytes;  // 64 split slabs + per-tile arrival counters
+    return 64 * gwsz * 4;  // 64 split slabs
 }
 
 static int wgrad_impl(const float *gy, int ldg, const float *x, float *gw, int Kout, int64_t pixels,
@@ -2569,13 +2182,6 @@ static int wgrad_impl(const float *gy, int ldg, const float *x, float *gw, int K
     p.split_stride = gwsz;
     if (int rc = set_extents(p, pixels * ldg, (int64_t)N_ * H * W * C, gwsz)) return rc;
     p.C = splits > 1 ? (float *)ws : gw;
-    const bool in_kernel = MRCNN_WGRAD_INKERNEL_REDUCE != 0 && splits > 1;
-    if (in_kernel) {
-        // counters live behind the 64 slabs of the workspace
-        p.tile_counters = (int *)((char *)ws + 64 * gwsz * 4);
-        p.reduce_out = gw;
-        MRCNN_HIP_TRY(hipMemsetAsync(p.tile_counters, 0, sizeof(int) * (size_t)tiles, s));
-    }
     {
         mrcnn::ProfKernelScope prof(use_big ? mrcnn::PROF_CONV_WGRAD_128 : mrcnn::PROF_CONV_WGRAD_64,
                                     2.0 * p.M * p.N * (double)pixels,
@@ -2585,7 +2191,10 @@ static int wgrad_impl(const float *gy, int ldg, const float *x, float *gw, int K
         else
             launch_kernel<1, 1, WGRAD>(p, tiles, splits, s);
     }
-    if (splits > 1 && !in_kernel) {
+    // (Summing the slabs in the last-arriving workgroup of each tile instead was measured 4 ms per
+    // train step slower: the agent-scope release every workgroup needs before it signals writes
+    // back its XCD's whole dirty L2.)
+    if (splits > 1) {
         const int64_t blocks = mrcnn::ceil_div(gwsz / 4, 256);   // one float4 per thread
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
                            (const float *)ws, splits, gwsz, gwsz, gw);
@@ -2673,7 +2282,7 @@ extern "C" int mrcnn_deconv2x2s2_dgrad(const float *gy, const float *w, float *g
 
 extern "C" int64_t mrcnn_deconv2x2s2_wgrad_workspace_bytes(int N, int H, int W, int C, int K)
 {
-    return 64ll * C * 4 * K * 4 + kWgradCounterBytes;
+    return 64ll * C * 4 * K * 4;
 }
 
 extern "C" int mrcnn_deconv2x2s2_wgrad(const float *x, const float *gy, float *gw, int N, int H,

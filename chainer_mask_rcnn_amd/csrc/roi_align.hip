@@ -555,10 +555,8 @@ __device__ __forceinline__ RoiExtent roi_extent(const RoiGeom &g, int H, int W, 
 constexpr int kOwnXT = 8;        // pixels of a row per workgroup
 constexpr int kOwnThreads = 256; // upper bound of the workgroup size (LDS list capacities)
 constexpr int kOwnScan = 4;      // RoIs tested per thread and chunk
-#ifndef MRCNN_ROI_DEPTH
-#define MRCNN_ROI_DEPTH 4    // measured: 4 at five waves per SIMD = 8 at four; 16 spills
-#endif
-constexpr int kOwnDepth = MRCNN_ROI_DEPTH;     // gy loads in flight per lane
+// gy loads in flight per lane; measured: 4 at five waves per SIMD = 8 at four; 16 spills
+constexpr int kOwnDepth = 4;
 
 // ext[r] = (ylo | yhi << 16, xlo | xhi << 16, batch, 0);  Ay[r][y][oh];  Bx[r][ow][x] (row
 // stride Wp, a multiple of 8, zero beyond the patch)
@@ -614,14 +612,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float fma_vec(float acc, float w, float v) { return __builtin_fmaf(w, v, acc); }
 __device__ __forceinline__ float4 fma_vec(float4 acc, float w, float4 v)
 {
-#if defined(MRCNN_ROI_BWD_SCALAR_FMA) && defined(MRCNN_EXPERIMENT_BUILD)   // experiment build (tools/build_variant.sh): four v_fma_f32
-    float4 r;
-    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r.x) : "v"(v.x), "v"(w), "v"(acc.x));
-    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r.y) : "v"(v.y), "v"(w), "v"(acc.y));
-    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r.z) : "v"(v.z), "v"(w), "v"(acc.z));
-    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r.w) : "v"(v.w), "v"(w), "v"(acc.w));
-    return r;
-#endif
     // two v_pk_fma_f32
     const f32x2 ww = {w, w};
     const f32x2 lo = __builtin_elementwise_fma((f32x2){v.x, v.y}, ww, (f32x2){acc.x, acc.y});
@@ -642,11 +632,9 @@ __device__ __forceinline__ void owner_consume(V (&acc)[kOwnXT], const V v, const
     for (int x = 0; x < kOwnXT; ++x) acc[x] = fma_vec(acc[x], ww[x], v);
 }
 
-#ifndef MRCNN_ROI_WAVES
-#define MRCNN_ROI_WAVES 5
-#endif
+constexpr int kOwnWaves = 5;     // waves per SIMD the owner kernel's register allocation must allow
 template <typename V>
-__global__ void __launch_bounds__(kOwnThreads) __attribute__((amdgpu_waves_per_eu(MRCNN_ROI_WAVES, 8)))
+__global__ void __launch_bounds__(kOwnThreads) __attribute__((amdgpu_waves_per_eu(kOwnWaves, 8)))
 roi_align_bwd_owner_kernel(const V *__restrict__ gy, const int4 *__restrict__ ext,
                            const float *__restrict__ Ay, const float *__restrict__ Bx,
                            V *__restrict__ gx, int R, int N, int H, int W, int Wp, int CV, int OH,

@@ -215,7 +215,8 @@ typedef struct {
  * average 2.09) runs its leftover rows split along K into many short workgroups whose partial
  * sums are combined, in a fixed order, by a small epilogue kernel. */
 int64_t mrcnn_conv2d_split_workspace_bytes(void);
-/* Developer switches for A/B measurements (results are identical either way):
+/* Run-time tuning switches; an unknown name is an error.
+ * Developer switches for A/B measurements (results are identical either way):
  *   "position_major_rows" (default 1): forward-form convolutions over many small maps (RoI
  *   features, 3x3 / pad 1 on 7x7) order their GEMM rows position-major so that the K slices of
  *   filter taps that fall into the zero padding for every row of a tile are skipped.
@@ -236,13 +237,19 @@ int64_t mrcnn_conv2d_split_workspace_bytes(void);
  *   runs that way, slabs summed in order by the epilogue kernel, instead of as 64x64 tiles; 0 = off;
  *   k > 0 = aim at k workgroups (probe); "big_split_min_slices" (default 16): fewest K slices per slab.
  *   "tiny_split" (default 1): launches of <= 128 tiles and >= 32 K slices are cut along K.
+ *   "small_m_split" (default 0 = off; k > 0): 64x64-tile problems of fewer than 256 k tiles and
+ *   >= 16 K slices are cut along K to about 256 k workgroups.
  *   Summation order differs between these settings (each deterministic).
- * Kernel selection, results bit-identical either way (round 6):
+ *   "wino_ambiguity_ppb" (default 4000, parts per 1e9): rounding bound below which a Winograd
+ *   forward output's sign counts as ambiguous and is recomputed directly.
+ * Kernel selection (round 6):
  *   "w8" (default 1): large pointwise forward-form launches of the split arithmetic (K >= "w8_min_k",
- *   default 256, and at least 768 tiles) on 256x128 tiles / 512-thread workgroups.
+ *   default 256, and at least 768 tiles) on 256x128 tiles / 512-thread workgroups.  Bit-identical
+ *   either way unless the launch's last round runs as K-split tail pieces: W8 cuts that tail along K
+ *   differently from the 128x128 kernels, so those rows are summed in another order.
  *   "pw" (default 3): bit 0 = pointwise (1x1 / stride 1) forward-form launches, bit 1 = 3x3 / stride 1 /
- *   pad 1 ones run instantiations with that geometry as compile-time constants.
- *   "roi_fwd_lanes" / "roi_bwd_lanes" (default 256): lanes per ROIAlign workgroup. */
+ *   pad 1 ones run instantiations with that geometry as compile-time constants; bit-identical.
+ *   "roi_fwd_lanes" / "roi_bwd_lanes" (default 0 = 256): cap of the lanes per ROIAlign workgroup. */
 int mrcnn_set_tuning(const char *name, int value);
 int mrcnn_conv2d_fwd(const mrcnn_conv_desc *d, const float *x, const float *w,
                      const float *bias, const float *scale, const float *shift,

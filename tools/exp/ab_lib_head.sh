@@ -1,3 +1,5 @@
+# A/B of the shipped library ("base") against chainer_mask_rcnn_amd/csrc/variants/libhead.so, built with
+#   make -C chainer_mask_rcnn_amd/csrc OBJDIR=chainer_mask_rcnn_amd/csrc/build_head OUT=chainer_mask_rcnn_amd/csrc/variants/libhead.so
 R=$GRAFT_REPO_ROOT
 Q="--no-cpu-baseline --rotate-batches 0 --no-fg-capped --no-direct-head-forward --no-device-targets --pipeline-examples 0 --no-extra-workloads --no-fp32-mfma --repeats 3"
 python -m pytest tests/test_gpu_conv.py -q -k "w8" -x 2>&1 | tail -2

@@ -1,5 +1,6 @@
 # usage (GPU box): bash tools/exp/run_variants.sh "<bench_conv filter>" <variant> [<variant> ...]
-#   variant "base" = the shipped library; others = chainer_mask_rcnn_amd/csrc/variants/lib<name>.so
+#   variant "base" = the shipped library; others = chainer_mask_rcnn_amd/csrc/variants/lib<name>.so, built with
+#   make -C chainer_mask_rcnn_amd/csrc OBJDIR=chainer_mask_rcnn_amd/csrc/build_<name> OUT=chainer_mask_rcnn_amd/csrc/variants/lib<name>.so
 # Per variant: conv parity tests (tests/test_gpu_conv.py), then tools/bench_conv.py on the filter.
 R=$GRAFT_REPO_ROOT
 F="$1"; shift
