@@ -8,6 +8,12 @@ from .roi_align_2d import roi_align_2d
 from .roi_align_2d import ROIAlign2D
 from .roi_align_2d import spatial_order as roi_spatial_order
 
+from .roi_pooling_2d import roi_pooling_2d
+from .roi_pooling_2d import ROIPooling2D
+
+from .crop_and_resize import crop_and_resize
+from .crop_and_resize import CropAndResize
+
 from .conv import conv2d, deconv2x2s2, linear, stem_conv, bottleneck, building_block
 from .pooling import max_pooling_2d, average_pooling_2d
 from .rows import fanout_rows

@@ -40,6 +40,12 @@ class _Deconvolution2D(torch.nn.Module):
         self.b = torch.nn.Parameter(torch.zeros((out_ch,), dtype=torch.float32))
 
 
+# RoI feature extractors that take ``bin_stride`` / ``order`` (f(...)[:, :, ::s, ::s] exactly):
+# the head pools only the bins res5.a reads through them.  Any other pooling_func (a user's own)
+# runs the reference-shaped branch.
+_BIN_STRIDE_POOLING = (functions.roi_align_2d, functions.roi_pooling_2d, functions.crop_and_resize)
+
+
 class ResNetRoIHead(torch.nn.Module):
 
     mask_size = 14  # Size of the predicted mask.
@@ -119,7 +125,7 @@ class ResNetRoIHead(torch.nn.Module):
                                  self.roi_size, self.roi_size,
                                  self.spatial_scale, bin_stride=res5_stride, order=order, proj=pre)
             res5 = self.res5(x, first_stride=1, roi=spec, **kw)
-        elif res5_stride > 1 and self.pooling_func is functions.roi_align_2d:
+        elif res5_stride > 1 and self.pooling_func in _BIN_STRIDE_POOLING:
             # res5.a reads the pooled map only through 1x1 stride-s convolutions (conv1 and
             # the shortcut conv4), i.e. only the bins (s*i, s*j): pool just those and run the
             # block with stride 1 — same values, a quarter of the ROIAlign work and traffic.

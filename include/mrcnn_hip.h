@@ -119,6 +119,56 @@ int mrcnn_roi_align_bwd_ws(const float *gy, const float *rois, float *gx,
                            float spatial_scale, int sampling_ratio, void *ws, int64_t ws_bytes,
                            void *stream);
 
+/* ---- RoI max pooling and crop-and-resize --------------------------------------------------
+ * The two other RoI feature extractors the reference's head accepts as pooling_func
+ * (examples/train_common.py:138-147: --pooling-func pooling / resize).  Same conventions as the
+ * ROIAlign calls above: x (N,H,W,C), rois (R,5) = (batch, x1, y1, x2, y2), y (R,OH,OW,C) with
+ * OH = ceil(PH / bin_stride), OW = ceil(PW / bin_stride) — only the bins (oh*bin_stride,
+ * ow*bin_stride) of the PH x PW grid, whose geometry is that of the full grid; order (may be
+ * NULL) is a processing permutation of the RoIs that does not change the result.  Validation
+ * errors (outh / outw / C < 1, bin_stride < 1, a NULL pointer with R > 0) return non-zero with
+ * mrcnn_last_error(); R == 0 is a successful no-op (the backwards zero-fill gx).  Backwards are
+ * pixel-owner only: ws (16-byte aligned, at least the size query's bytes) is required, no
+ * atomics, every gx element written once, bit-reproducible.  RoIs whose batch index is not in
+ * [0, N) produce zeros (argmax -1) and receive no gradient. */
+/* Replaces chainer's F.roi_pooling_2d forward GPU kernel (Caffe's Fast R-CNN ROIPooling), which
+ * the reference selects as cmr.functions.roi_pooling_2d (examples/train_common.py:141-142).
+ * Per bin, all in fp32: start = roundf(x1 * s) (half away from zero), roi size
+ * max(end - start + 1, 1), window [floor(p * bin), ceil((p + 1) * bin)) + start clamped to
+ * [0, size]; the first maximum in (h, w) ascending order, initial value -1e37 (a NaN never wins);
+ * an empty window gives 0 and argmax -1.  argmax (R,OH,OW,C) int32 holds h * W + w. */
+int mrcnn_roi_pool_fwd(const float *x, const float *rois, float *y, int *argmax,
+                       int N, int H, int W, int C, int R, int PH, int PW, int bin_stride,
+                       float spatial_scale, const int *order, void *stream);
+/* Replaces chainer's F.roi_pooling_2d backward GPU kernel: gx[n,h,w,c] = the sum of gy[r,oh,ow,c]
+ * over the bins whose argmax for channel c is h * W + w, in ascending (r, oh, ow) order — the
+ * order of chainer's kernel.  gy / argmax as written by mrcnn_roi_pool_fwd. */
+int64_t mrcnn_roi_pool_bwd_workspace_bytes(int N, int H, int W, int R, int PH, int PW,
+                                           int bin_stride);
+int mrcnn_roi_pool_bwd_ws(const float *gy, const int *argmax, const float *rois, float *gx,
+                          int N, int H, int W, int C, int R, int PH, int PW, int bin_stride,
+                          float spatial_scale, void *ws, int64_t ws_bytes, void *stream);
+/* Replaces chainer_mask_rcnn.functions.crop_and_resize (functions/crop_and_resize.py:7-41): an
+ * integer crop followed by F.resize_images (bilinear, aligned corners).  Crop start
+ * rint(double(x1) * spatial_scale) (half to even, as Python's round), clamped into [0, W-1]
+ * (extension: the reference wraps a negative start and fails on a start past the map); crop end
+ * max(rint(double(x2) * spatial_scale), start + 1) truncated at W; the same along y.  Sample p of
+ * linspace(0, crop - 1, PH) in float64 (0 when PH == 1), taps clip(floor(v), 0, crop - 2) and + 1
+ * (one row when the crop is one row), per-axis weights in float64 rounded once to fp32, value
+ * ((w00 v00 + w01 v01) + w10 v10) + w11 v11 in fp32 with w_ij = wy_i * wx_j.
+ * out_rows (may be NULL = identity): the output row of each RoI — functions.crop_and_resize passes
+ * the stable sort by batch index, the reference's output order (its per-image concat). */
+int mrcnn_crop_resize_fwd(const float *x, const float *rois, const int *out_rows, float *y,
+                          int N, int H, int W, int C, int R, int PH, int PW, int bin_stride,
+                          double spatial_scale, const int *order, void *stream);
+/* Adjoint of the four bilinear taps of mrcnn_crop_resize_fwd (the backward chainer derives for
+ * F.resize_images), summed per gx pixel in (r, oh, ow) order. */
+int64_t mrcnn_crop_resize_bwd_workspace_bytes(int N, int H, int W, int R, int PH, int PW,
+                                              int bin_stride);
+int mrcnn_crop_resize_bwd_ws(const float *gy, const float *rois, const int *out_rows, float *gx,
+                             int N, int H, int W, int C, int R, int PH, int PW, int bin_stride,
+                             double spatial_scale, void *ws, int64_t ws_bytes, void *stream);
+
 /* ---- row-sparse backward of a 3x3 / stride 1 / pad 1 convolution --------------------------
  * The reference back-propagates the RPN losses through conv1 of
  * models/region_proposal_network.py:75-80 densely, although the losses ignore every anchor but

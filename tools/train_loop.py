@@ -247,17 +247,24 @@ class SyntheticInstances(object):
         return self.examples[i % len(self.examples)]
 
 
+# --pooling-func -> the head's RoI feature extractor (examples/train_common.py:138-147)
+POOLING_FUNCS = {'align': 'roi_align_2d', 'pooling': 'roi_pooling_2d', 'resize': 'crop_and_resize'}
+
+
 def build(dataset, n_layers=50, device='cuda:0', batch_size=2, seed=0, defer=5, prefetch=True,
-          world=1):
+          world=1, pooling_func='align'):
     """Model, optimizer and loop as examples/train_common.py:135-231 builds them (COCO settings of
-    examples/coco/train.py:36-38)."""
+    examples/coco/train.py:36-38); ``pooling_func`` one of POOLING_FUNCS."""
     import bench
     import chainer_mask_rcnn_amd as cmr
     random.seed(seed)                                   # :135-136
     np.random.seed(seed)
     torch.manual_seed(seed)
     device = torch.device(device)
+    if pooling_func not in POOLING_FUNCS:
+        raise ValueError('Unsupported pooling_func: {}'.format(pooling_func))
     model, chain, opt, sync = bench.build_trainer(n_layers, device, world, batch_size * world, defer=defer)
+    model.head.pooling_func = getattr(cmr.functions, POOLING_FUNCS[pooling_func])
     train_data = TransformDataset(dataset, cmr.datasets.MaskRCNNTransform(model))
     it = SerialIterator(train_data, batch_size)
     return TrainLoop(it, chain, opt, device, prefetch=prefetch), model, chain, opt
@@ -274,6 +281,9 @@ def main():
     ap.add_argument('--batch', type=int, default=2)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--no-prefetch', action='store_true')
+    ap.add_argument('--pooling-func', default='align', choices=sorted(POOLING_FUNCS),
+                    help='RoI feature extractor of the head: align (roi_align_2d), pooling '
+                         '(roi_pooling_2d) or resize (crop_and_resize)')
     args = ap.parse_args()
     import chainer_mask_rcnn_amd as cmr
     if os.environ.get('TORCH_THREADS'):
@@ -283,7 +293,7 @@ def main():
     else:
         data = cmr.datasets.COCOInstanceSegmentationDataset(args.split, root_dir=args.coco_root)
     loop, model, chain, opt = build(data, args.layers, 'cuda:0', args.batch, args.seed,
-                                    prefetch=not args.no_prefetch)
+                                    prefetch=not args.no_prefetch, pooling_func=args.pooling_func)
     for _ in range(int(os.environ.get('WARMUP', 3))):
         loop.step()
     opt.flush()
