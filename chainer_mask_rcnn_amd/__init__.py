@@ -8,6 +8,7 @@ HIP kernels behind the C ABI of ``include/mrcnn_hip.h``.
 __version__ = '0.1.0'
 
 from . import datasets
+from . import extensions
 from . import functions
 from . import links
 from . import models

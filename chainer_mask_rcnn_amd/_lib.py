@@ -137,6 +137,9 @@ SIGNATURES = {
                                     ctypes.POINTER(c_f32), c_vp, c_int, c_int, c_int, c_int, c_int,
                                     c_int, c_vp]),
     'mrcnn_paste_masks': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    'mrcnn_mask_pack': (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'mrcnn_paste_masks_packed': (c_int, [c_vp, c_vp, c_vp] + [c_int] * 5 + [c_vp] * 4),
+    'mrcnn_mask_intersect': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp] + [c_int] * 3 + [c_vp, c_vp]),
     'mrcnn_decode_cls_boxes': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_f32,
                                        ctypes.POINTER(ctypes.c_double),
                                        ctypes.POINTER(ctypes.c_double), c_f32, c_f32, c_vp]),

@@ -1,0 +1,158 @@
+"""InstanceSegmentationVOCEvaluator / InstanceSegmentationCOCOEvaluator — the reference's
+chainer_mask_rcnn/extensions/instance_segmentation_{voc,coco}_evaluator.py.
+
+``evaluate()`` returns the observation dict chainer's reporter builds for ``name='validation'``
+(``validation/main/map``, ...).  Predicted masks never leave the device: per batch,
+``prepare`` -> ``predict_prepared(masks_to_host=False)`` -> packed paste -> intersections
+against the uploaded and packed ground truth, all queued before one read-back of the counts
+and areas.  Boxes, labels and scores come back as ``predict_prepared`` returns them.  Matching
+and accumulation run on the host from those counts (utils/evaluations/matching.py).
+"""
+import copy
+
+import numpy as np
+import torch
+
+from ..utils.evaluations import masks as M
+from ..utils.evaluations import matching
+
+
+def _batches(iterator):
+    """Batches of examples from a chainer-style iterator (``reset()``: iterated once after a
+    reset), an iterator exposing ``dataset`` and ``batch_size`` (the dataset in order, once), or
+    any iterable of batches."""
+    if hasattr(iterator, 'reset'):
+        iterator.reset()
+        for batch in iterator:
+            yield batch
+    elif hasattr(iterator, 'dataset') and hasattr(iterator, 'batch_size'):
+        data, bs = iterator.dataset, int(iterator.batch_size)
+        for i in range(0, len(data), bs):
+            yield [data[j] for j in range(i, min(i + bs, len(data)))]
+    else:
+        # a one-shot iterator (e.g. a generator) is consumed as it is; a container is copied
+        for batch in (iterator if iter(iterator) is iterator else copy.copy(iterator)):
+            yield batch
+
+
+class _InstanceSegmentationEvaluator(object):
+
+    name = 'validation'
+
+    def __init__(self, iterator, target, label_names=None):
+        self.iterator = iterator
+        self.target = target
+        self.label_names = label_names
+
+    def __call__(self, trainer=None):
+        return self.evaluate()
+
+    def _observation(self, report):
+        return {'%s/main/%s' % (self.name, k): v for k, v in report.items()}
+
+    def collect(self):
+        """Run the model over the iterator.  Returns (counts, pred_labels, pred_scores,
+        ground-truth tuples): counts[i] = (inter (P,G), pred_area (P,), gt_area (G,)) host int64
+        arrays; gt tuple = the example's entries after the image (bbox, label, mask, ...)."""
+        target = self.target
+        counts, pred_labels, pred_scores, gts = [], [], [], []
+        for batch in _batches(self.iterator):
+            batch = list(batch)
+            if not batch:
+                continue
+            for ex in batch:
+                if len(ex) not in (4, 5, 6):
+                    raise ValueError('expected (img, bbox, label, mask[, difficult | crowd, area]) '
+                                     'examples, got a %d-tuple' % len(ex))
+            x, sizes, scales = target.prepare([ex[0] for ex in batch])
+            bboxes, roi_masks, labels, scores = target.predict_prepared(
+                x, scales, sizes, masks_to_host=False)
+            dev = x.device
+            queued = []
+            for j, ex in enumerate(batch):
+                gt_mask = ex[3]
+                H, W = sizes[j]
+                if tuple(gt_mask.shape[1:]) != (H, W):
+                    raise ValueError('ground-truth masks of shape %s for an image of size %s'
+                                     % (tuple(gt_mask.shape), (H, W)))
+                pred = M.paste_packed(roi_masks[j], labels[j], bboxes[j], (H, W))
+                gt = M.pack_masks(gt_mask, device=dev)
+                inter = M.queue_intersections(pred, gt, W)
+                queued.append((inter, pred[1], gt[1]))
+            # one read-back for the whole batch
+            flat = torch.cat([t.reshape(-1).to(torch.int64) for q in queued for t in q])
+            host = flat.cpu().numpy()
+            o = 0
+            for (inter, pa, ga), l, s, ex in zip(queued, labels, scores, batch):
+                P, G = inter.shape
+                c_inter = host[o:o + P * G].reshape(P, G)
+                o += P * G
+                c_pa = host[o:o + P]
+                o += P
+                c_ga = host[o:o + G]
+                o += G
+                counts.append((c_inter, c_pa, c_ga))
+                pred_labels.append(l)
+                pred_scores.append(s)
+                gts.append(tuple(ex[1:]))
+        return counts, pred_labels, pred_scores, gts
+
+
+class InstanceSegmentationVOCEvaluator(_InstanceSegmentationEvaluator):
+    """``validation/main/map`` and, with ``label_names``, ``validation/main/ap/<name>``
+    (class l's AP is ``ap[l]``; NaN for a class that never occurs)."""
+
+    def __init__(self, iterator, target, use_07_metric=False, label_names=None):
+        super(InstanceSegmentationVOCEvaluator, self).__init__(iterator, target, label_names)
+        self.use_07_metric = use_07_metric
+
+    def evaluate(self):
+        counts, pred_labels, pred_scores, gts = self.collect()
+        gt_labels = [g[1] for g in gts]
+        gt_difficults = None
+        if gts and len(gts[0]) == 4:
+            gt_difficults = [g[3] for g in gts]
+        prec, rec = matching.voc_prec_rec_from_counts(counts, pred_labels, pred_scores, gt_labels,
+                                                      gt_difficults)
+        ap = matching.calc_detection_voc_ap(prec, rec, use_07_metric=self.use_07_metric)
+        return self._observation(voc_report(ap, self.label_names))
+
+
+class InstanceSegmentationCOCOEvaluator(_InstanceSegmentationEvaluator):
+    """``validation/main/map`` (IoU .50:.95), ``map@0.5``, ``map@0.75`` and, with
+    ``label_names``, ``ap/<name>`` keyed by the real label (the reference indexes the K axis,
+    the sorted labels present, by label: DESIGN.md section 9)."""
+
+    def evaluate(self):
+        counts, pred_labels, pred_scores, gts = self.collect()
+        gt_labels = [g[1] for g in gts]
+        gt_crowdeds = gt_areas = None
+        if gts and len(gts[0]) == 5:
+            gt_crowdeds = [g[3] for g in gts]
+            gt_areas = [g[4] for g in gts]
+        result = matching.coco_results(matching.coco_evaluate_from_counts(
+            counts, pred_labels, pred_scores, gt_labels, gt_crowdeds, gt_areas))
+        return self._observation(coco_report(result, self.label_names))
+
+
+def voc_report(ap, label_names=None):
+    report = {'map': np.nanmean(ap)}
+    if label_names is not None:
+        for l, label_name in enumerate(label_names):
+            report['ap/{:s}'.format(label_name)] = ap[l] if l < len(ap) else np.nan
+    return report
+
+
+def coco_report(result, label_names=None):
+    report = {
+        'map': result['map/iou=0.50:0.95/area=all/maxDets=100'],
+        'map@0.5': result['map/iou=0.50/area=all/maxDets=100'],
+        'map@0.75': result['map/iou=0.75/area=all/maxDets=100'],
+    }
+    if label_names is not None:
+        per_class = result['ap/iou=0.50:0.95/area=all/maxDets=100']
+        k_of = {int(c): k for k, c in enumerate(result['coco_eval']['params']['catIds'])}
+        for l, label_name in enumerate(label_names):
+            k = k_of.get(l)
+            report['ap/{:s}'.format(label_name)] = per_class[k] if k is not None else np.nan
+    return report

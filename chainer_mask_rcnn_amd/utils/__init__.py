@@ -1,3 +1,5 @@
 # flake8: noqa
 from .bbox import (generate_anchor_base, enumerate_shifted_anchor, bbox_iou, bbox2loc,
                    resize_bilinear)
+from .evaluations import (eval_instseg_voc, eval_instseg_coco, calc_instseg_voc_prec_rec,
+                          calc_detection_voc_ap, mask_iou)

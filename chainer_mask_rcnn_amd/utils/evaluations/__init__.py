@@ -1,0 +1,5 @@
+# flake8: noqa
+from .eval_instance_segmentation_voc import eval_instseg_voc, calc_instseg_voc_prec_rec
+from .eval_instance_segmentation_coco import eval_instseg_coco
+from .masks import mask_iou
+from .matching import calc_detection_voc_ap

@@ -1,0 +1,133 @@
+"""Packed instance masks on the device (format: include/mrcnn_hip.h, "Packed masks").
+
+``pack_masks`` / ``paste_packed`` produce (packed, area, extent) device tensors and
+``queue_intersections`` the (P, G) int32 intersection counts of two packed sets; nothing here
+synchronises.  ``mask_iou`` is the reference's ``mask_iou`` (utils/evaluations/
+eval_instance_segmentation_voc.py) on top of them: the counts come from the device, the float64
+IoU is formed on the host.  There is no host fallback: a device is required.
+"""
+import numpy as np
+import torch
+
+from ... import _lib
+
+
+def _device():
+    return torch.device('cuda', torch.cuda.current_device())
+
+
+def _as_device_masks(masks, dev):
+    """(N, H, W) host array or device tensor -> contiguous device uint8 or int32 tensor whose
+    nonzero elements are foreground."""
+    if isinstance(masks, torch.Tensor):
+        t = masks.to(dev) if masks.device != dev else masks
+        if t.dtype == torch.bool:
+            t = t.view(torch.uint8)
+        elif t.dtype not in (torch.uint8, torch.int32):
+            t = (t != 0).to(torch.uint8)
+        return t.contiguous()
+    a = np.asarray(masks)
+    if a.dtype == np.bool_:
+        a = a.view(np.uint8)
+    elif a.dtype not in (np.uint8, np.int32):
+        a = (a != 0).view(np.uint8)
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=False)
+
+
+def packed_words(W):
+    return (int(W) + 63) // 64
+
+
+def pack_masks(masks, device=None):
+    """(N, H, W) uint8 / bool / int32 masks (host array or device tensor) -> (packed (N,H,Wq)
+    int64 bit pattern, area (N,) int32, extent (N,4) int32) device tensors."""
+    dev = torch.device(device) if device is not None else (
+        masks.device if isinstance(masks, torch.Tensor) and masks.is_cuda else _device())
+    m = _as_device_masks(masks, dev)
+    _lib.require_device(m)
+    if m.dim() != 3:
+        raise ValueError('pack_masks expects (N, H, W) masks, got shape %s' % (tuple(m.shape),))
+    N, H, W = m.shape
+    packed = torch.empty((N, H, packed_words(W)), dtype=torch.int64, device=dev)
+    area = torch.empty((N,), dtype=torch.int32, device=dev)
+    extent = torch.empty((N, 4), dtype=torch.int32, device=dev)
+    if N == 0 or H == 0 or W == 0:
+        area.zero_()
+        extent.zero_()
+    else:
+        _lib.call('mrcnn_mask_pack', _lib.ptr(m), m.element_size(), N, H, W, _lib.ptr(packed),
+                  _lib.ptr(area), _lib.ptr(extent), _lib.stream_ptr())
+    return packed, area, extent
+
+
+def paste_packed(roi_mask_logits, label, bbox, size):
+    """``MaskRCNN._to_masks`` for one image in the packed format: roi_mask_logits is the
+    (D, n_fg, M, M) device tensor of ``predict_prepared(masks_to_host=False)``, label (D,) and
+    bbox (D, 4) the host detections, size (H, W).  Returns (packed, area, extent)."""
+    from ...functions._layout import nhwc
+    H, W = int(size[0]), int(size[1])
+    D = len(bbox)
+    dev = roi_mask_logits.device
+    packed = torch.empty((D, H, packed_words(W)), dtype=torch.int64, device=dev)
+    area = torch.empty((D,), dtype=torch.int32, device=dev)
+    extent = torch.empty((D, 4), dtype=torch.int32, device=dev)
+    if D == 0:
+        return packed, area, extent
+    logits = nhwc(roi_mask_logits)
+    label_d = torch.tensor(np.asarray(label, np.int32), device=dev)
+    bbox_d = torch.tensor(np.asarray(bbox, np.float32), device=dev)
+    _lib.call('mrcnn_paste_masks_packed', _lib.ptr(logits), _lib.ptr(label_d), _lib.ptr(bbox_d),
+              D, logits.shape[2], logits.shape[1], H, W, _lib.ptr(packed), _lib.ptr(area),
+              _lib.ptr(extent), _lib.stream_ptr())
+    # label_d / bbox_d: the caching allocator keeps their blocks for the queued kernel (same
+    # stream), as in MaskRCNN._to_masks
+    return packed, area, extent
+
+
+def queue_intersections(a, b, W):
+    """inter (P, G) int32 device tensor = |A_p & B_g| for packed sets a = (packed, area, extent)
+    and b of an image of width W (queued, not synchronised)."""
+    pa, _, ea = a
+    pb, _, eb = b
+    P, H = pa.shape[0], pa.shape[1]
+    G = pb.shape[0]
+    if pb.shape[1:] != pa.shape[1:] or pa.shape[2] != packed_words(W):
+        raise ValueError('packed mask sets of different image sizes: %s vs %s'
+                         % (tuple(pa.shape[1:]), tuple(pb.shape[1:])))
+    inter = torch.zeros((P, G), dtype=torch.int32, device=pa.device)
+    if P and G and H:
+        _lib.call('mrcnn_mask_intersect', _lib.ptr(pa), _lib.ptr(ea), P, _lib.ptr(pb),
+                  _lib.ptr(eb), G, H, int(W), _lib.ptr(inter), _lib.stream_ptr())
+    return inter
+
+
+def mask_counts(mask_a, mask_b):
+    """(inter (P,G), area_a (P,), area_b (G,)) as host int64 arrays for two mask sets of the
+    same image size (host arrays or device tensors)."""
+    if tuple(mask_a.shape[1:]) != tuple(mask_b.shape[1:]):
+        raise ValueError('mask sets of different image sizes: %s vs %s'
+                         % (tuple(mask_a.shape[1:]), tuple(mask_b.shape[1:])))
+    W = mask_a.shape[2]
+    a = pack_masks(mask_a)
+    b = pack_masks(mask_b, device=a[0].device)
+    inter = queue_intersections(a, b, W)
+    return (inter.cpu().numpy().astype(np.int64), a[1].cpu().numpy().astype(np.int64),
+            b[1].cpu().numpy().astype(np.int64))
+
+
+def iou_from_counts(inter, area_a, area_b):
+    """float64 (P, G): inter / (a + b - inter), 0 where the union is 0 — the reference's
+    ``1.0 * intersect / union`` of get_mask_overlap, value for value."""
+    inter = np.asarray(inter, dtype=np.int64)
+    union = np.asarray(area_a, np.int64)[:, None] + np.asarray(area_b, np.int64)[None, :] - inter
+    iou = np.zeros(inter.shape, dtype=np.float64)
+    nz = union != 0
+    iou[nz] = inter[nz] / union[nz]
+    return iou
+
+
+def mask_iou(mask_a, mask_b):
+    """utils.mask_iou: float64 (P, G) IoU of two (N, H, W) mask sets."""
+    if tuple(mask_a.shape[1:]) != tuple(mask_b.shape[1:]):
+        raise ValueError
+    return iou_from_counts(*mask_counts(mask_a, mask_b))

@@ -525,6 +525,33 @@ int mrcnn_prepare_image(const void *src_chw, int src_is_u8, int C, int H, int W,
 int mrcnn_paste_masks(const float *mask_logits, const int32_t *label, const float *bbox,
                       int D, int M, int Kc, int im_h, int im_w, uint8_t *out, void *stream);
 
+/* ---- Packed masks for instance-segmentation evaluation (csrc/mask_eval.hip, image.hip) ---
+ * Format: a set of N masks over an H x W image is uint64 (N, H, Wq), Wq = ceil(W / 64); bit
+ * (x & 63) of word [n, y, x >> 6] is pixel (n, y, x), pad bits are zero — byte for byte
+ * np.packbits(m, axis=-1, bitorder='little') of rows zero-padded to a multiple of 64.  Any
+ * nonzero input value is foreground.  Each mask carries its exact area (int32 pixel count) and
+ * an extent int32 (y_lo, y_hi, wq_lo, wq_hi): half-open row and word ranges that contain every
+ * set bit (empty, lo >= hi, for a mask with none).  H * W < 2^31. */
+/* Pack (N,H,W) masks of elem_bytes 1 (uint8 / bool) or 4 (int32): packed (N,H,Wq), area (N),
+ * tight extent (N,4).  Replaces the per-mask work of get_mask_overlap
+ * (chainer_mask_rcnn/utils/geometry.py) and pycocotools.mask.encode / area. */
+int mrcnn_mask_pack(const void *masks, int elem_bytes, int N, int H, int W, uint64_t *packed,
+                    int32_t *area, int32_t *extent, void *stream);
+/* mrcnn_paste_masks written in the packed format: the bits equal pack(mrcnn_paste_masks(...))
+ * exactly (one shared per-pixel function), area (D) exact, extent (D,4) = the clipped expanded
+ * box widened to whole words.  Replaces segm_results (models/mask_rcnn.py:63-107) followed by
+ * the host-side mask handling of the evaluators. */
+int mrcnn_paste_masks_packed(const float *mask_logits, const int32_t *label, const float *bbox,
+                             int D, int M, int Kc, int im_h, int im_w, uint64_t *packed,
+                             int32_t *area, int32_t *extent, void *stream);
+/* inter (P,G) int32 = |A_p & B_g| for packed A (P,H,Wq) and B (G,H,Wq) of an H x W image; only
+ * the overlap of the two extents (clamped to the image) is read, a pair whose extents do not
+ * overlap gives 0.  Replaces np.bitwise_and(...).sum() of get_mask_overlap and the RLE
+ * intersection of pycocotools' rleIou; union = area_a + area_b - inter. */
+int mrcnn_mask_intersect(const uint64_t *a, const int32_t *ext_a, int P, const uint64_t *b,
+                         const int32_t *ext_b, int G, int H, int W, int32_t *inter,
+                         void *stream);
+
 /* Second half of MaskRCNN._suppress (models/mask_rcnn.py:195-202): the rows kept by
  * mrcnn_nms_sorted_batched (keep (G,R), n_keep (G)) of every class packed densely, class after
  * class and in keep order: bbox (<= G*R, 4), label, score, *total = number of rows. */

@@ -1,0 +1,132 @@
+"""Instance-segmentation evaluation of a model: the counterpart of the reference's
+examples/evaluate_common.py + examples/coco/evaluate.py.
+
+    python tools/evaluate.py --coco-root DIR --split minival --detectron model.pkl
+    python tools/evaluate.py --coco-root DIR --snapshot snapshot_model.npz --evaluator voc
+    python tools/evaluate.py --synthetic 16            # no dataset: random weights, synthetic images
+
+Runs the evaluator (predicted masks stay on the device; extensions/), prints the report and
+the seconds per image spent in prediction and in evaluation, and writes the result as YAML (or
+JSON when PyYAML is missing) next to the snapshot as ``<snapshot>.eval_result.yaml``.
+"""
+import argparse
+import json
+import os
+import pprint
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+
+POOLING_FUNCS = {'align': 'roi_align_2d', 'pooling': 'roi_pooling_2d', 'resize': 'crop_and_resize'}
+
+
+class _TimedTarget(object):
+    """The model, with the seconds spent in prepare + predict_prepared counted."""
+
+    def __init__(self, model):
+        self.model, self.seconds = model, 0.
+
+    def prepare(self, imgs):
+        t0 = time.perf_counter()
+        out = self.model.prepare(imgs)
+        self.seconds += time.perf_counter() - t0
+        return out
+
+    def predict_prepared(self, *a, **k):
+        t0 = time.perf_counter()
+        out = self.model.predict_prepared(*a, **k)
+        torch.cuda.synchronize()
+        self.seconds += time.perf_counter() - t0
+        return out
+
+
+def main():
+    ap = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    ap.add_argument('--coco-root', default=None, help='COCO-layout directory')
+    ap.add_argument('--split', default='minival')
+    ap.add_argument('--snapshot', default=None, help='snapshot_model.npz of this package / the reference')
+    ap.add_argument('--detectron', default=None, help='Detectron R-50-C4 / R-101-C4 .pkl')
+    ap.add_argument('--layers', type=int, default=50, choices=[50, 101])
+    ap.add_argument('--pooling-func', default='align', choices=sorted(POOLING_FUNCS))
+    ap.add_argument('--evaluator', default='coco', choices=['voc', 'coco'])
+    ap.add_argument('--limit', type=int, default=0, help='evaluate the first N images only')
+    ap.add_argument('--synthetic', type=int, default=0, help='N synthetic images, no dataset')
+    ap.add_argument('--batch', type=int, default=1)
+    ap.add_argument('--out', default=None, help='result file (default: next to the weights)')
+    args = ap.parse_args()
+
+    import chainer_mask_rcnn_amd as cmr
+    from chainer_mask_rcnn_amd import serializers
+    dev = torch.device('cuda:0')
+
+    if args.synthetic:
+        import train_loop
+        data = train_loop.SyntheticInstances(args.synthetic, seed=1)
+        class_names = ['class%d' % i for i in range(80)]
+    else:
+        if args.coco_root is None:
+            ap.error('--coco-root or --synthetic is required')
+        data = cmr.datasets.COCOInstanceSegmentationDataset(
+            args.split, root_dir=args.coco_root, use_crowd=True, return_crowd=True,
+            return_area=True)
+        class_names = [str(n) for n in data.class_names]
+
+    torch.manual_seed(0)
+    model = cmr.models.MaskRCNNResNet(
+        n_layers=args.layers, n_fg_class=len(class_names), min_size=800, max_size=1333,
+        anchor_scales=(2, 4, 8, 16, 32), roi_size=14,
+        pooling_func=getattr(cmr.functions, POOLING_FUNCS[args.pooling_func])).to(dev)
+    weights = args.snapshot or args.detectron
+    if args.snapshot:
+        serializers.load_npz(args.snapshot, model)
+    elif args.detectron:
+        serializers.load_detectron(args.detectron, model, n_layers=args.layers)
+    else:
+        import bench
+        bench.stabilise_synthetic_weights(model)
+        with torch.no_grad():                 # random weights: sharpen scores to get detections
+            model.head.cls_loc_score.W[4 * 81:5 * 81] *= 60.
+    model.eval()
+
+    transform = cmr.datasets.MaskRCNNTransform(model, train=False)
+    n = len(data) if not args.limit else min(args.limit, len(data))
+    batches = ([transform(data[j]) for j in range(i, min(i + args.batch, n))]
+               for i in range(0, n, args.batch))
+
+    target = _TimedTarget(model)
+    cls = (cmr.extensions.InstanceSegmentationVOCEvaluator if args.evaluator == 'voc'
+           else cmr.extensions.InstanceSegmentationCOCOEvaluator)
+    kw = {'use_07_metric': True} if args.evaluator == 'voc' else {}
+    evaluator = cls(batches, target, label_names=class_names, **kw)
+    t0 = time.perf_counter()
+    result = evaluator.evaluate()
+    total = time.perf_counter() - t0
+    result = {k: float(v) for k, v in result.items()}
+    timing = {'images': n, 'predict_s_per_image': target.seconds / n,
+              'eval_s_per_image': (total - target.seconds) / n}
+    pprint.pprint(result)
+    print('timing:', json.dumps(timing))
+
+    out = args.out or ((weights + '.eval_result.yaml') if weights else
+                       'synthetic.eval_result.yaml')
+    payload = {'result': result, 'timing': timing, 'evaluator': args.evaluator,
+               'weights': weights, 'split': None if args.synthetic else args.split}
+    try:
+        import yaml
+        with open(out, 'w') as f:
+            yaml.safe_dump(payload, f, default_flow_style=False)
+    except ImportError:
+        out = os.path.splitext(out)[0] + '.json'
+        with open(out, 'w') as f:
+            json.dump(payload, f, indent=1)
+    print('Saved evaluation:', out)
+
+
+if __name__ == '__main__':
+    main()
