@@ -140,6 +140,10 @@ SIGNATURES = {
     'mrcnn_mask_pack': (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mrcnn_paste_masks_packed': (c_int, [c_vp, c_vp, c_vp] + [c_int] * 5 + [c_vp] * 4),
     'mrcnn_mask_intersect': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp] + [c_int] * 3 + [c_vp, c_vp]),
+    'mrcnn_label_scan': (c_int, [c_vp, c_int, c_vp] + [c_int] * 4 + [c_vp] * 4),
+    'mrcnn_label_instances': (c_int, [c_vp, c_int, c_vp] + [c_int] * 4 + [c_vp] * 3
+                              + [c_int] * 4 + [c_vp] * 6),
+    'mrcnn_instances_to_label': (c_int, [c_vp] * 3 + [c_int] * 3 + [c_vp] * 3),
     'mrcnn_decode_cls_boxes': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_f32,
                                        ctypes.POINTER(ctypes.c_double),
                                        ctypes.POINTER(ctypes.c_double), c_f32, c_f32, c_vp]),

@@ -5,3 +5,6 @@ from .transforms import MaskRCNNTransform  # NOQA
 from .transforms import resize_bbox, flip_bbox, resize_nearest, flip  # NOQA
 from .concat_examples import concat_examples  # NOQA
 from .coco import COCOInstanceSegmentationDataset  # NOQA
+from .voc import VOC2012InstanceSegmentationDataset, SBDInstanceSegmentationDataset  # NOQA
+from .voc import VOC2012InstanceSeg, SBDInstanceSeg  # NOQA
+from .mask_rcnn import MaskRcnnDataset  # NOQA

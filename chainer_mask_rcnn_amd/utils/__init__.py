@@ -3,3 +3,5 @@ from .bbox import (generate_anchor_base, enumerate_shifted_anchor, bbox_iou, bbo
                    resize_bilinear)
 from .evaluations import (eval_instseg_voc, eval_instseg_coco, calc_instseg_voc_prec_rec,
                           calc_detection_voc_ap, mask_iou)
+from .geometry import (label2instance_boxes, instance_boxes2label, mask_to_bbox, get_bbox_overlap,
+                       get_mask_overlap)

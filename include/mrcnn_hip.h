@@ -552,6 +552,43 @@ int mrcnn_mask_intersect(const uint64_t *a, const int32_t *ext_a, int P, const u
                          const int32_t *ext_b, int G, int H, int W, int32_t *inter,
                          void *stream);
 
+/* ---- Instance label images (csrc/instance_labels.hip) --------------------------------------
+ * Replaces label2instance_boxes and instance_boxes2label (chainer_mask_rcnn/utils/
+ * geometry.py:94-147).  ins and cls are (H, W) label images of elem_bytes 4 (int32) or 1
+ * (uint8, where 255 reads as -1: the VOC PNG "void" index); H * W < 2^31.  With
+ * mask_by_class, pixels whose class is -1 or 0 have instance -1 (the datasets'
+ * lbl_ins[np.isin(lbl_cls, [-1, 0])] = -1).  Instances are the distinct instance values other
+ * than -1 (0 and other negatives included), ranked ascending.
+ * Limits: the instance values and the class values under instances each span at most
+ * MRCNN_LABEL_WINDOW (max - min + 1), and n_instances * n_classes <= MRCNN_LABEL_WINDOW. */
+#define MRCNN_LABEL_WINDOW (1 << 24)
+/* First half (queued, the caller then reads meta): meta int32[6] = (ins_min, ins_max,
+ * cls_min, cls_max, n_instances, n_classes), ranges empty (min > max) without an instance
+ * pixel; bitmaps uint32[2 * MRCNN_LABEL_WINDOW / 32] (instances, then classes) and prefix
+ * int32[2 * MRCNN_LABEL_WINDOW / 32] are caller-owned scratch for mrcnn_label_instances.
+ * A span over the window leaves counts for the in-window values only: the caller rejects it. */
+int mrcnn_label_scan(const void *ins, int ins_bytes, const void *cls, int cls_bytes, int H, int W,
+                     int mask_by_class, int32_t *meta, uint32_t *bitmaps, int32_t *prefix,
+                     void *stream);
+/* Second half, with n = meta[4], ncls = meta[5], span_ins = meta[1] - meta[0] + 1 and
+ * span_cls = meta[3] - meta[2] + 1 read by the caller.  table int32[2 * n * ncls + ncls] is
+ * scratch (pixel count and first row-major position per (instance, class), class values).
+ * Outputs: ids (n) ascending instance values; classes (n) the majority class of each
+ * instance, ties to the class whose first pixel in row-major order comes first (the
+ * reference's Counter insertion order), -1 / 0 reported as they are; boxes (n, 4)
+ * (y1, x1, y2, x2) half-open; masks (n, H, W) uint8 0/1 unless masks is NULL. */
+int mrcnn_label_instances(const void *ins, int ins_bytes, const void *cls, int cls_bytes, int H,
+                          int W, int mask_by_class, const int32_t *meta, const uint32_t *bitmaps,
+                          const int32_t *prefix, int span_ins, int span_cls, int n, int ncls,
+                          int32_t *table, int32_t *ids, int32_t *classes, int32_t *boxes,
+                          uint8_t *masks, void *stream);
+/* lbl_ins / lbl_cls (H, W) int32 from masks (N, H, W) uint8 painted in the order
+ * order[0..N) (NULL: 0..N-1); the last mask covering a pixel wins: lbl_ins = its position j in
+ * the painting order, lbl_cls = labels[order[j]]; -1 and 0 where no mask covers. */
+int mrcnn_instances_to_label(const uint8_t *masks, const int32_t *order, const int32_t *labels,
+                             int N, int H, int W, int32_t *lbl_ins, int32_t *lbl_cls,
+                             void *stream);
+
 /* Second half of MaskRCNN._suppress (models/mask_rcnn.py:195-202): the rows kept by
  * mrcnn_nms_sorted_batched (keep (G,R), n_keep (G)) of every class packed densely, class after
  * class and in keep order: bbox (<= G*R, 4), label, score, *total = number of rows. */

@@ -4,6 +4,7 @@ examples/evaluate_common.py + examples/coco/evaluate.py.
     python tools/evaluate.py --coco-root DIR --split minival --detectron model.pkl
     python tools/evaluate.py --coco-root DIR --snapshot snapshot_model.npz --evaluator voc
     python tools/evaluate.py --synthetic 16            # no dataset: random weights, synthetic images
+    python tools/evaluate.py --dataset sbd --sbd-root DIR --snapshot snapshot_model.npz
 
 Runs the evaluator (predicted masks stay on the device; extensions/), prints the report and
 the seconds per image spent in prediction and in evaluation, and writes the result as YAML (or
@@ -48,18 +49,28 @@ class _TimedTarget(object):
 
 def main():
     ap = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    ap.add_argument('--dataset', default='coco', choices=['coco', 'voc', 'sbd'],
+                    help='voc (VOC2012) and sbd evaluate the 20-class model of examples/voc/train.py')
     ap.add_argument('--coco-root', default=None, help='COCO-layout directory')
-    ap.add_argument('--split', default='minival')
+    ap.add_argument('--voc-root', default=None, help='VOCdevkit/VOC2012 directory')
+    ap.add_argument('--sbd-root', default=None, help='benchmark_RELEASE/dataset directory of SBD')
+    ap.add_argument('--split', default=None, help='default: minival (coco), val (voc, sbd)')
     ap.add_argument('--snapshot', default=None, help='snapshot_model.npz of this package / the reference')
     ap.add_argument('--detectron', default=None, help='Detectron R-50-C4 / R-101-C4 .pkl')
     ap.add_argument('--layers', type=int, default=50, choices=[50, 101])
     ap.add_argument('--pooling-func', default='align', choices=sorted(POOLING_FUNCS))
-    ap.add_argument('--evaluator', default='coco', choices=['voc', 'coco'])
+    ap.add_argument('--evaluator', default=None, choices=['voc', 'coco'],
+                    help='default: voc for --dataset voc / sbd, else coco')
     ap.add_argument('--limit', type=int, default=0, help='evaluate the first N images only')
     ap.add_argument('--synthetic', type=int, default=0, help='N synthetic images, no dataset')
     ap.add_argument('--batch', type=int, default=1)
     ap.add_argument('--out', default=None, help='result file (default: next to the weights)')
     args = ap.parse_args()
+    voc = args.dataset in ('voc', 'sbd') and not args.synthetic
+    if args.evaluator is None:
+        args.evaluator = 'voc' if voc else 'coco'
+    if args.split is None:
+        args.split = 'val' if voc else 'minival'
 
     import chainer_mask_rcnn_amd as cmr
     from chainer_mask_rcnn_amd import serializers
@@ -69,6 +80,12 @@ def main():
         import train_loop
         data = train_loop.SyntheticInstances(args.synthetic, seed=1)
         class_names = ['class%d' % i for i in range(80)]
+    elif voc:
+        if args.dataset == 'voc':
+            data = cmr.datasets.VOC2012InstanceSegmentationDataset(args.split, root_dir=args.voc_root)
+        else:
+            data = cmr.datasets.SBDInstanceSegmentationDataset(args.split, root_dir=args.sbd_root)
+        class_names = [str(n) for n in data.class_names]
     else:
         if args.coco_root is None:
             ap.error('--coco-root or --synthetic is required')
@@ -78,10 +95,12 @@ def main():
         class_names = [str(n) for n in data.class_names]
 
     torch.manual_seed(0)
+    # examples/voc/train.py: 600 / 1000 and anchor scales (4, 8, 16, 32); COCO: 800 / 1333
+    size = dict(min_size=600, max_size=1000, anchor_scales=(4, 8, 16, 32)) if voc else dict(
+        min_size=800, max_size=1333, anchor_scales=(2, 4, 8, 16, 32))
     model = cmr.models.MaskRCNNResNet(
-        n_layers=args.layers, n_fg_class=len(class_names), min_size=800, max_size=1333,
-        anchor_scales=(2, 4, 8, 16, 32), roi_size=14,
-        pooling_func=getattr(cmr.functions, POOLING_FUNCS[args.pooling_func])).to(dev)
+        n_layers=args.layers, n_fg_class=len(class_names), roi_size=14,
+        pooling_func=getattr(cmr.functions, POOLING_FUNCS[args.pooling_func]), **size).to(dev)
     weights = args.snapshot or args.detectron
     if args.snapshot:
         serializers.load_npz(args.snapshot, model)
@@ -91,7 +110,8 @@ def main():
         import bench
         bench.stabilise_synthetic_weights(model)
         with torch.no_grad():                 # random weights: sharpen scores to get detections
-            model.head.cls_loc_score.W[4 * 81:5 * 81] *= 60.
+            n_class = len(class_names) + 1
+            model.head.cls_loc_score.W[4 * n_class:5 * n_class] *= 60.
     model.eval()
 
     transform = cmr.datasets.MaskRCNNTransform(model, train=False)

@@ -24,6 +24,7 @@ gives bit-identical losses (tests/test_gpu_train_loop.py).
 
     python tools/train_loop.py --coco-root DIR --iterations 100      # a COCO-layout directory
     python tools/train_loop.py --synthetic 64 --iterations 20        # in-memory synthetic examples
+    python tools/train_loop.py --dataset sbd --sbd-root DIR --split train   # VOC settings (20 classes)
 """
 import functools
 import os
@@ -249,12 +250,43 @@ class SyntheticInstances(object):
 
 # --pooling-func -> the head's RoI feature extractor (examples/train_common.py:138-147)
 POOLING_FUNCS = {'align': 'roi_align_2d', 'pooling': 'roi_pooling_2d', 'resize': 'crop_and_resize'}
+# model settings of examples/voc/train.py (SBD / VOC2012: 20 foreground classes)
+VOC_MODEL = dict(n_fg_class=20, min_size=600, max_size=1000, anchor_scales=(4, 8, 16, 32))
+
+
+def build_voc_trainer(n_layers, device, lr_batch, defer=5):
+    """``bench.build_trainer`` (which is fixed to the COCO settings) with examples/voc/train.py's
+    model: the same optimizer, frozen layers, synthetic-weight scaling and deferred gradients."""
+    import bench
+    import chainer_mask_rcnn_amd as cmr
+    from chainer_mask_rcnn_amd import optimizers
+    from chainer_mask_rcnn_amd.links import AffineChannel2D
+    model = cmr.models.MaskRCNNResNet(n_layers=n_layers, pretrained_model=None, roi_size=14,
+                                      pooling_func=cmr.functions.roi_align_2d, **VOC_MODEL)
+    chain = cmr.models.MaskRCNNTrainChain(model).to(device)
+    chain.train()
+    opt = optimizers.MomentumSGD(lr=0.00125 * lr_batch, momentum=0.9)
+    opt.setup(chain)
+    opt.add_hook(optimizers.WeightDecay(rate=0.0001))
+    for link in (model.extractor.conv1, model.extractor.bn1, model.extractor.res2):
+        optimizers.disable_update(link)
+    for m in chain.modules():
+        if isinstance(m, AffineChannel2D):
+            optimizers.disable_update(m)
+    bench.stabilise_synthetic_weights(model)
+    if defer > 0:
+        a, b1, b2 = model.head.res5.a, model.head.res5.b1, model.head.res5.b2
+        opt.defer_weight_gradients([a.conv2.W, a.conv3.W, b1.conv2.W, b1.conv1.W, b1.conv3.W,
+                                    b2.conv2.W, b2.conv1.W, b2.conv3.W, a.conv1.W,
+                                    a.conv4.W][:defer])
+    return model, chain, opt, None
 
 
 def build(dataset, n_layers=50, device='cuda:0', batch_size=2, seed=0, defer=5, prefetch=True,
-          world=1, pooling_func='align'):
+          world=1, pooling_func='align', model_settings='coco'):
     """Model, optimizer and loop as examples/train_common.py:135-231 builds them (COCO settings of
-    examples/coco/train.py:36-38); ``pooling_func`` one of POOLING_FUNCS."""
+    examples/coco/train.py:36-38, or with ``model_settings='voc'`` those of
+    examples/voc/train.py); ``pooling_func`` one of POOLING_FUNCS."""
     import bench
     import chainer_mask_rcnn_amd as cmr
     random.seed(seed)                                   # :135-136
@@ -263,7 +295,15 @@ def build(dataset, n_layers=50, device='cuda:0', batch_size=2, seed=0, defer=5, 
     device = torch.device(device)
     if pooling_func not in POOLING_FUNCS:
         raise ValueError('Unsupported pooling_func: {}'.format(pooling_func))
-    model, chain, opt, sync = bench.build_trainer(n_layers, device, world, batch_size * world, defer=defer)
+    if model_settings == 'voc':
+        if world != 1:
+            raise ValueError('the VOC settings are built for one device')
+        model, chain, opt, sync = build_voc_trainer(n_layers, device, batch_size, defer=defer)
+    elif model_settings == 'coco':
+        model, chain, opt, sync = bench.build_trainer(n_layers, device, world, batch_size * world,
+                                                      defer=defer)
+    else:
+        raise ValueError('model_settings must be coco or voc, got %r' % (model_settings,))
     model.head.pooling_func = getattr(cmr.functions, POOLING_FUNCS[pooling_func])
     train_data = TransformDataset(dataset, cmr.datasets.MaskRCNNTransform(model))
     it = SerialIterator(train_data, batch_size)
@@ -273,8 +313,13 @@ def build(dataset, n_layers=50, device='cuda:0', batch_size=2, seed=0, defer=5, 
 def main():
     import argparse
     ap = argparse.ArgumentParser()
+    ap.add_argument('--dataset', default=None, choices=['coco', 'voc', 'sbd', 'synthetic'],
+                    help='coco (default; synthetic with --synthetic N), voc (VOC2012) or sbd; voc '
+                         'and sbd train the 20-class model of examples/voc/train.py')
     ap.add_argument('--coco-root', default=None, help='COCO-layout directory (annotations/, train2014/ ...)')
-    ap.add_argument('--split', default='minival')
+    ap.add_argument('--voc-root', default=None, help='VOCdevkit/VOC2012 directory')
+    ap.add_argument('--sbd-root', default=None, help='benchmark_RELEASE/dataset directory of SBD')
+    ap.add_argument('--split', default=None, help='minival (coco) / train (voc, sbd) by default')
     ap.add_argument('--synthetic', type=int, default=0, help='use N in-memory synthetic examples')
     ap.add_argument('--iterations', type=int, default=20)
     ap.add_argument('--layers', type=int, default=50, choices=[50, 101])
@@ -288,12 +333,22 @@ def main():
     import chainer_mask_rcnn_amd as cmr
     if os.environ.get('TORCH_THREADS'):
         torch.set_num_threads(int(os.environ['TORCH_THREADS']))
-    if args.synthetic:
-        data = SyntheticInstances(args.synthetic, seed=args.seed, virtual_len=4096)
+    dataset = args.dataset or ('synthetic' if args.synthetic else 'coco')
+    settings = 'voc' if dataset in ('voc', 'sbd') else 'coco'
+    if dataset == 'synthetic':
+        data = SyntheticInstances(args.synthetic or 64, seed=args.seed, virtual_len=4096)
+    elif dataset == 'voc':
+        data = cmr.datasets.VOC2012InstanceSegmentationDataset(args.split or 'train',
+                                                               root_dir=args.voc_root)
+    elif dataset == 'sbd':
+        data = cmr.datasets.SBDInstanceSegmentationDataset(args.split or 'train',
+                                                           root_dir=args.sbd_root)
     else:
-        data = cmr.datasets.COCOInstanceSegmentationDataset(args.split, root_dir=args.coco_root)
+        data = cmr.datasets.COCOInstanceSegmentationDataset(args.split or 'minival',
+                                                            root_dir=args.coco_root)
     loop, model, chain, opt = build(data, args.layers, 'cuda:0', args.batch, args.seed,
-                                    prefetch=not args.no_prefetch, pooling_func=args.pooling_func)
+                                    prefetch=not args.no_prefetch, pooling_func=args.pooling_func,
+                                    model_settings=settings)
     for _ in range(int(os.environ.get('WARMUP', 3))):
         loop.step()
     opt.flush()
