@@ -41,30 +41,27 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BK = 32;
-// The forward-form kernel without mask staging fits 168 registers, so it runs with ONE LDS stage
-// (37 KB) and three workgroups per CU: a wave spends ~40 % of a K slice issuing MFMAs and
-// ~60 % staging (measured with s_memtime), so three interleaved waves per SIMD keep the pipe
-// fuller than two (res5 3x3: 129 vs 122 TFLOP/s).  The variants that stage a mask (16 more
-// registers) and the K-strided DGRAD gather would spill at 168 and keep two stages / two
+// The forward-form kernel fits 168 registers, so it runs with ONE LDS stage (37 KB) and three
+// workgroups per CU: a wave spends ~40 % of a K slice issuing MFMAs and ~60 % staging (measured
+// with s_memtime), so three interleaved waves per SIMD keep the pipe fuller than two (res5 3x3:
+// 129 vs 122 TFLOP/s).  The K-strided DGRAD gather would spill at 168 and keeps two stages / two
 // workgroups per CU.
-constexpr bool single_buffered(int tm, int mode, bool masked)
+constexpr bool single_buffered(int tm, int mode)
 {
-    if (tm == 1) return !masked && mode == 0;
-    return tm >= 2 && !masked && (mode == 0 || mode == 2);
+    if (tm == 1) return mode == 0;
+    return tm >= 2 && (mode == 0 || mode == 2);
 }
 // minimum workgroups per CU the register allocation must allow (256-thread workgroups: one
 // wave per SIMD each)
-constexpr int min_blocks(int tm, int mode, bool masked)
+constexpr int min_blocks(int tm, int mode)
 {
-    if (!single_buffered(tm, mode, masked)) return 1;
+    if (!single_buffered(tm, mode)) return 1;
     return tm == 4 ? 2 : (tm == 2 ? 3 : 6);
 }
 constexpr int KPAD = 4;  // K-contiguous LDS rows are 36 floats (conflict-free b128)
 
 // The stride-1 dgrad is also run in FWD mode: a forward convolution of gy with the flipped,
-// transposed filter (both operands K-contiguous).  MASKED (template flag of the kernel) adds
-// the fused epilogue-backward of the producing conv to the A staging: g = gy * (mask_y > 0) *
-// in_scale[k].
+// transposed filter (both operands K-contiguous).
 enum Mode { FWD = 0, DGRAD = 1, WGRAD = 2 };
 constexpr bool is_fwd(int m) { return m == FWD; }
 enum OutMode { OUT_PLAIN = 0, OUT_STRIDED = 1, OUT_DECONV = 2 };
@@ -101,10 +98,6 @@ struct GemmParams {
     // the same image block, whose pixels therefore stay in the XCD's L2.  perm_n = number of
     // images (M is padded to whole blocks), 0 = natural (image, y, x) order.
     int perm_n;
-    // Fused backward of the producing conv's epilogue, applied while gy is staged
-    // (DGRAD A operand / WGRAD A' operand):  g = gy * (mask_y > 0) * in_scale[k]
-    const float *mask_y;   // output of the ReLU that followed the conv (same shape as gy) or NULL
-    const float *in_scale; // AffineChannel2D scale of that conv (K_out) or NULL
     // backward-data epilogue: gx = (acc * scale[c] + res_g * (res_y > 0)) * (out_mask_y > 0)
     //   res_g / res_y : identity-shortcut gradient of a bottleneck (res_y NULL: res_g is added as is)
     //   out_mask_y    : output of the ReLU that produced this conv's INPUT, i.e. the epilogue-
@@ -113,7 +106,7 @@ struct GemmParams {
     // WGRAD epilogue: gw[k, :] *= scale[k]
     const float *res_g, *res_y, *out_mask_y;
     float *split_ws;     // host only: caller's split-K workspace (kSplitWsBytes) or NULL
-    unsigned a_bytes, b_bytes, c_bytes;  // buffer extents (bytes) of A (and mask_y), B, C
+    unsigned a_bytes, b_bytes, c_bytes;  // buffer extents (bytes) of A, B, C
     // Fused tail (FWD / DGRAD, gridDim.y == 1): workgroups [0, tail_first) run whole tiles as
     // usual; the workgroups behind them run the tiles of the LEFTOVER rows — the rows beyond the
     // last full round of resident workgroups — each cut along K into tail_splits pieces that
@@ -194,15 +187,6 @@ __device__ __forceinline__ void bstore8(__amdgpu_buffer_rsrc_t r, unsigned off, 
     u32x2 u;
     u.x = a; u.y = b;
     __builtin_amdgcn_raw_buffer_store_b64(u, r, off, 0, 0);
-}
-__device__ __forceinline__ float4 relu_mask(float4 v, float4 y)
-{
-    return make_float4(y.x > 0.f ? v.x : 0.f, y.y > 0.f ? v.y : 0.f, y.z > 0.f ? v.z : 0.f,
-                       y.w > 0.f ? v.w : 0.f);
-}
-__device__ __forceinline__ float4 mul4(float4 v, float4 s)
-{
-    return make_float4(v.x * s.x, v.y * s.y, v.z * s.z, v.w * s.w);
 }
 
 // fp32 pair -> three packed bf16 pairs (low half = a, high half = b) with a = hi + mid + lo
@@ -287,15 +271,15 @@ __device__ __forceinline__ void sgb_interleave()
 // VGPRs, +3 % on the head's 1x1 layers).  W8 implies it.  K3: the same for the 3x3 / stride 1 / pad 1
 // launches in natural row order (k3_plain(): the backbone's 3x3 layers and their transposed-filter data
 // gradients) — filter size, stride and padding are constants of the gather.  Same arithmetic, same bits.
-template <int TM, int TN, int MODE, bool MASKED, bool WPERM = false, bool SPLIT = false, bool W8 = false,
+template <int TM, int TN, int MODE, bool WPERM = false, bool SPLIT = false, bool W8 = false,
           bool PW = false, bool K3 = false>
 __global__ void __launch_bounds__(W8 ? 512 : 256,
-                                  SPLIT ? (TM == 2 ? 2 : 4) : min_blocks(TM, MODE, MASKED))
+                                  SPLIT ? (TM == 2 ? 2 : 4) : min_blocks(TM, MODE))
 conv_gemm_kernel(const GemmParams p)
 {
-    static_assert(!W8 || (SPLIT && MODE == FWD && TM == 2 && TN == 2 && !MASKED),
-                  "W8: the split-operand forward form on 64x64 wave tiles, unmasked");
-    static_assert(!WPERM || (MODE == WGRAD && !MASKED), "WPERM is a WGRAD-only variant");
+    static_assert(!W8 || (SPLIT && MODE == FWD && TM == 2 && TN == 2),
+                  "W8: the split-operand forward form on 64x64 wave tiles");
+    static_assert(!WPERM || MODE == WGRAD, "WPERM is a WGRAD-only variant");
     static_assert(!PW || MODE == FWD, "PW: forward form only");
     static_assert(!K3 || (MODE == FWD && !W8 && !PW), "K3: forward form only");
     constexpr bool PWC = W8 || PW;
@@ -306,16 +290,15 @@ conv_gemm_kernel(const GemmParams p)
     const int gStride = GEO ? 1 : p.stride, gPad = PWC ? 0 : K3 ? 1 : p.pad;
     const int gPermN = GEO ? 0 : p.perm_n;
     const bool gStem = !GEO && p.stem;
-    constexpr bool ILV = SPLIT && MODE == FWD && !MASKED;
+    constexpr bool ILV = SPLIT && MODE == FWD;
     static_assert(!SPLIT || (BK == 32 && TM == TN &&
                              ((MODE == FWD && (TM == 1 || TM == 2)) || (MODE == WGRAD && !WPERM && TM == 2))),
                   "SPLIT: forward form (128x128, 64x64) / weight gradient (128x128) only");
-    constexpr bool SINGLEBUF = !W8 && (SPLIT || single_buffered(TM, MODE, MASKED));
+    constexpr bool SINGLEBUF = !W8 && (SPLIT || single_buffered(TM, MODE));
     using C_ = Cfg<TM, TN, MODE>;
     constexpr int NT = W8 ? 512 : 256;                  // threads of the workgroup
     constexpr int BM = (W8 ? 2 : 1) * C_::BM, BN = C_::BN;
     constexpr int AV = BM * BK / 4 / NT, BV = BN * BK / 4 / NT;   // float4 per thread per slice
-    constexpr bool HAS_MASK = MASKED;
     constexpr bool FWDLIKE = is_fwd(MODE);
     // SPLIT stage: 3 planes per operand of [row][32 bf16 + 8 pad] (80-byte rows: conflict-free b128)
     // forward form: 64-byte rows, 16-byte slots XOR-swizzled by (row >> 2) & 3 — conflict-free for
@@ -346,8 +329,6 @@ conv_gemm_kernel(const GemmParams p)
     const int64_t zb = blockIdx.z;                      // batched launches: problem index
     const __amdgpu_buffer_rsrc_t rA = make_rsrc(p.A + zb * p.batch_a, p.a_bytes);
     const __amdgpu_buffer_rsrc_t rB = make_rsrc(p.B + zb * p.batch_b, p.b_bytes);
-    const __amdgpu_buffer_rsrc_t rMask = make_rsrc(p.mask_y, p.a_bytes);
-    const bool use_mask = HAS_MASK && p.mask_y != nullptr;
 
     // tile -> (m0, n0).  Workgroup b runs on XCD b % 8 (observed dispatch order); remap so
     // that each XCD owns a contiguous run of tile ids — N fastest — and neighbouring tiles,
@@ -509,11 +490,6 @@ conv_gemm_kernel(const GemmParams p)
     }
 
     float4 ra[AV], rb[BV];
-    float4 rm[HAS_MASK ? AV : 1];
-    float4 rscale = make_float4(1.f, 1.f, 1.f, 1.f);
-    const bool use_scale = HAS_MASK && p.in_scale != nullptr;
-    if (MODE == WGRAD && use_scale && m0 + wa_c4 * 4 < p.M)
-        rscale = *reinterpret_cast<const float4 *>(p.in_scale + m0 + wa_c4 * 4);
 
     // Loop-invariant parts of every load address (element offsets; an invalid row carries the
     // sentinel 0x20000000 so that 4 * offset lands beyond num_records and reads as zero).
@@ -556,7 +532,7 @@ conv_gemm_kernel(const GemmParams p)
                         p.gp == p.sh && p.gq == p.sw;      // uniform
     const int RS = gR * gS;
 
-    // ILV (SPLIT forward form without mask staging): load_slice only computes the byte offsets of
+    // ILV (SPLIT forward form): load_slice only computes the byte offsets of
     // the slice's loads; the loads themselves are issued INSIDE the following compute(), spread
     // between its MFMAs (issue_loads + the sched_group_barrier sequence there).  Issued as one
     // burst ahead of the MFMAs, the 8 .. 12 16-byte loads of every wave of the CU queue behind
@@ -568,7 +544,6 @@ conv_gemm_kernel(const GemmParams p)
             oa[i] = off;
         } else {
             ra[i] = bload4(rA, off);
-            if (HAS_MASK && use_mask) rm[i] = bload4(rMask, off);
         }
     };
     auto ldB = [&](int i, unsigned off) {
@@ -598,9 +573,6 @@ conv_gemm_kernel(const GemmParams p)
 #pragma unroll
             for (int i = 0; i < AV; ++i)
                 ldA(i, (c_ok && a_y[i] == 0) ? 4u * (a_base[i] + (unsigned)c0) : kOOB);
-            if (HAS_MASK && use_scale)
-                rscale = c_ok ? *reinterpret_cast<const float4 *>(p.in_scale + cc)
-                              : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
             for (int i = 0; i < BV; ++i) ldB(i, c_ok ? 4u * (b_base[i] + (unsigned)c0) : kOOB);
             return;
@@ -629,9 +601,6 @@ conv_gemm_kernel(const GemmParams p)
                 const bool ok = c_ok && (unsigned)iy < (unsigned)p.sh && (unsigned)ix < (unsigned)p.sw;
                 ldA(i, ok ? 4u * (a_base[i] + (unsigned)tap) : kOOB);
             }
-            if (HAS_MASK && use_scale)
-                rscale = cc < p.Kc ? *reinterpret_cast<const float4 *>(p.in_scale + cc)
-                                   : make_float4(0.f, 0.f, 0.f, 0.f);
             if (FWDLIKE) {
                 const unsigned wofs = (unsigned)(rs * p.Kc + c0);
 #pragma unroll
@@ -672,9 +641,7 @@ conv_gemm_kernel(const GemmParams p)
 #pragma unroll
             for (int i = 0; i < AV; ++i) {
                 const int m = kb + a_krow(i);
-                const unsigned off = m < k_end ? 4u * (a_base[i] + gofs) : kOOB;
-                ra[i] = bload4(rA, off);
-                if (use_mask) rm[i] = bload4(rMask, off);
+                ra[i] = bload4(rA, m < k_end ? 4u * (a_base[i] + gofs) : kOOB);
             }
             if (wpoint) {
                 // 1x1 / stride 1: pixel m of gy is pixel m of x
@@ -708,7 +675,7 @@ conv_gemm_kernel(const GemmParams p)
         }
     };
 
-    // registers -> LDS; the fused epilogue-backward (ReLU mask, affine scale) is applied here
+    // registers -> LDS
     auto store_slice = [&](int buf) {
         if constexpr (SPLIT) {
             unsigned short *pa = reinterpret_cast<unsigned short *>(smem[buf]);
@@ -743,10 +710,7 @@ conv_gemm_kernel(const GemmParams p)
                 float ea[4][4], eb[4][4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    float4 v = ra[i];
-                    if (HAS_MASK && use_mask) v = relu_mask(v, rm[i]);
-                    if (HAS_MASK && use_scale) v = mul4(v, rscale);
-                    ea[i][0] = v.x; ea[i][1] = v.y; ea[i][2] = v.z; ea[i][3] = v.w;
+                    ea[i][0] = ra[i].x; ea[i][1] = ra[i].y; ea[i][2] = ra[i].z; ea[i][3] = ra[i].w;
                     eb[i][0] = rb[i].x; eb[i][1] = rb[i].y; eb[i][2] = rb[i].z; eb[i][3] = rb[i].w;
                 }
                 put_t(pa, PLA, wa_c4 * 4, wa_k, ea);
@@ -755,10 +719,7 @@ conv_gemm_kernel(const GemmParams p)
             }
 #pragma unroll
             for (int i = 0; i < AV; ++i) {
-                float4 v = ra[i];
-                if (HAS_MASK && use_mask) v = relu_mask(v, rm[i]);
-                if (HAS_MASK && use_scale) v = mul4(v, rscale);
-                put(pa, PLA, kc_row + KC_RPP * i, v);
+                put(pa, PLA, kc_row + KC_RPP * i, ra[i]);
             }
 #pragma unroll
             for (int i = 0; i < BV; ++i) {
@@ -770,13 +731,10 @@ conv_gemm_kernel(const GemmParams p)
         float *sb = smem[buf] + C_::A_FLOATS;
 #pragma unroll
         for (int i = 0; i < AV; ++i) {
-            float4 v = ra[i];
-            if (HAS_MASK && use_mask) v = relu_mask(v, rm[i]);
-            if (HAS_MASK && use_scale) v = mul4(v, rscale);
             if (C_::A_KC)
-                *reinterpret_cast<float4 *>(sa + (kc_row + KC_RPP * i) * (BK + KPAD) + kc_c4 * 4) = v;
+                *reinterpret_cast<float4 *>(sa + (kc_row + KC_RPP * i) * (BK + KPAD) + kc_c4 * 4) = ra[i];
             else
-                *reinterpret_cast<float4 *>(sa + (wa_k + A_RPP * i) * BM + wa_c4 * 4) = v;
+                *reinterpret_cast<float4 *>(sa + (wa_k + A_RPP * i) * BM + wa_c4 * 4) = ra[i];
         }
         if (C_::B_KC) {
 #pragma unroll
@@ -1348,8 +1306,8 @@ inline bool k3_plain(const GemmParams &p)
            p.out_mode == OUT_PLAIN;
 }
 
-template <int TM, int TN, int MODE, bool MASKED>
-void launch_kernel_m(const GemmParams &p, int64_t tiles, int splits, hipStream_t s, int batch = 1)
+template <int TM, int TN, int MODE>
+void launch_kernel(const GemmParams &p, int64_t tiles, int splits, hipStream_t s, int batch = 1)
 {
     hipEvent_t ev0, ev1;          // kernel-only timing (ProfKernelScope of the caller), usually null
     mrcnn::prof_take(&ev0, &ev1);
@@ -1357,23 +1315,21 @@ void launch_kernel_m(const GemmParams &p, int64_t tiles, int splits, hipStream_t
         hipExtLaunchKernelGGL(kernel, dim3((unsigned)tiles, splits, batch), dim3(256), 0, s, ev0, ev1, 0, p);
     };
     if constexpr (MODE == WGRAD && TM == 2 && TN == 2) {
-        if ((g_split_bf16 & 1) && p.perm_n == 0) return go(conv_gemm_kernel<TM, TN, MODE, MASKED, false, true>);
+        if ((g_split_bf16 & 1) && p.perm_n == 0) return go(conv_gemm_kernel<TM, TN, MODE, false, true>);
     }
-    if constexpr (MODE == WGRAD && !MASKED) {
-        if (p.perm_n > 0) return go(conv_gemm_kernel<TM, TN, MODE, MASKED, true>);
+    if constexpr (MODE == WGRAD) {
+        if (p.perm_n > 0) return go(conv_gemm_kernel<TM, TN, MODE, true>);
     }
     if constexpr (MODE == FWD && TM == TN && (TM == 1 || TM == 2)) {
         if (g_split_bf16 & (TM == 2 ? 1 : 2)) {
-            if ((g_pw & 1) && pw_plain(p)) return go(conv_gemm_kernel<TM, TN, MODE, MASKED, false, true, false, true>);
+            if ((g_pw & 1) && pw_plain(p)) return go(conv_gemm_kernel<TM, TN, MODE, false, true, false, true>);
             if ((g_pw & 2) && k3_plain(p))
-                return go(conv_gemm_kernel<TM, TN, MODE, MASKED, false, true, false, false, true>);
-            return go(conv_gemm_kernel<TM, TN, MODE, MASKED, false, true>);
+                return go(conv_gemm_kernel<TM, TN, MODE, false, true, false, false, true>);
+            return go(conv_gemm_kernel<TM, TN, MODE, false, true>);
         }
     }
-    go(conv_gemm_kernel<TM, TN, MODE, MASKED>);
+    go(conv_gemm_kernel<TM, TN, MODE>);
 }
-
-inline bool is_masked(const GemmParams &p) { return p.mask_y != nullptr || p.in_scale != nullptr; }
 
 // ---- W8 launches (see the note above conv_gemm_kernel) -------------------------------------------
 constexpr int kW8BM = 256, kW8BN = 128;
@@ -1384,11 +1340,11 @@ inline bool w8_pointwise(const GemmParams &p)
            p.gp == p.sh && p.gq == p.sw;
 }
 
-// a forward-form launch qualifies: split-operand arithmetic, no mask staging, plain output rows,
+// a forward-form launch qualifies: split-operand arithmetic, plain output rows,
 // 1x1 / stride 1 gather, K >= 8 slices, at least three rounds of 256 tiles, rows that fill their tiles
 inline bool w8_ok(const GemmParams &p, int batch = 1)
 {
-    if (!g_w8 || !(g_split_bf16 & 1) || is_masked(p) || p.out_mode != OUT_PLAIN || !w8_pointwise(p) ||
+    if (!g_w8 || !(g_split_bf16 & 1) || p.out_mode != OUT_PLAIN || !w8_pointwise(p) ||
         p.split_len != 0 || p.m_lo != 0)
         return false;
     const int64_t tm = mrcnn::ceil_div(p.M, kW8BM), tn = mrcnn::ceil_div(p.N, kW8BN);
@@ -1401,15 +1357,8 @@ void launch_w8_kernel(const GemmParams &p, int64_t wgs, int batch, hipStream_t s
 {
     hipEvent_t ev0, ev1;
     mrcnn::prof_take(&ev0, &ev1);
-    hipExtLaunchKernelGGL((conv_gemm_kernel<2, 2, FWD, false, false, true, true>),
+    hipExtLaunchKernelGGL((conv_gemm_kernel<2, 2, FWD, false, true, true>),
                           dim3((unsigned)wgs, 1, batch), dim3(512), 0, s, ev0, ev1, 0, p);
-}
-
-template <int TM, int TN, int MODE>
-void launch_kernel(const GemmParams &p, int64_t tiles, int splits, hipStream_t s, int batch = 1)
-{
-    if (is_masked(p)) launch_kernel_m<TM, TN, MODE, true>(p, tiles, splits, s, batch);
-    else launch_kernel_m<TM, TN, MODE, false>(p, tiles, splits, s, batch);
 }
 
 // Profiler record of a forward-form / DGRAD launch over `rows` GEMM rows: the operation and byte
@@ -1729,7 +1678,7 @@ int launch(const GemmParams &p0, int splits, hipStream_t s)
         // the smallest leftover, run the leftover rows as 64x64 tiles
         // resident 128x128 workgroups per CU: 3 single-buffered fp32, 2 otherwise (and split-operand)
         const bool split_fwd = MODE == FWD && (g_split_bf16 & 1);
-        const int64_t max_per_cu = !split_fwd && single_buffered(2, MODE, is_masked(p)) ? 3 : 2;
+        const int64_t max_per_cu = !split_fwd && single_buffered(2, MODE) ? 3 : 2;
         int64_t main_tiles_m = tm, best_rem = T;
         for (int64_t k = max_per_cu; k >= 1; --k) {
             const int64_t slots = 256 * k, full = T / slots, rem = T - full * slots;
@@ -1920,21 +1869,19 @@ extern "C" int mrcnn_conv_stem_fwd(const float *x4, const float *w784, const flo
 }
 
 extern "C" int mrcnn_conv2d_dgrad_ex(const mrcnn_conv_desc *d, const float *gy, const float *w,
-                                     float *gx, int epi_flags, const float *mask_y,
-                                     const float *in_scale, const float *res_g,
+                                     float *gx, int epi_flags, const float *res_g,
                                      const float *res_y, const float *out_mask_y,
                                      const float *out_scale, void *split_ws, void *stream);
 
 extern "C" int mrcnn_conv2d_dgrad(const mrcnn_conv_desc *d, const float *gy, const float *w,
                                   float *gx, int epi_flags, void *stream)
 {
-    return mrcnn_conv2d_dgrad_ex(d, gy, w, gx, epi_flags, nullptr, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr, nullptr, stream);
+    return mrcnn_conv2d_dgrad_ex(d, gy, w, gx, epi_flags, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                 stream);
 }
 
 extern "C" int mrcnn_conv2d_dgrad_ex(const mrcnn_conv_desc *d, const float *gy, const float *w,
-                                     float *gx, int epi_flags, const float *mask_y,
-                                     const float *in_scale, const float *res_g,
+                                     float *gx, int epi_flags, const float *res_g,
                                      const float *res_y, const float *out_mask_y,
                                      const float *out_scale, void *split_ws, void *stream)
 {
@@ -1948,8 +1895,7 @@ extern "C" int mrcnn_conv2d_dgrad_ex(const mrcnn_conv_desc *d, const float *gy, 
     hipStream_t s = mrcnn::as_stream(stream);
     GemmParams p = {};
     p.A = gy; p.B = w; p.C = gx;
-    p.mask_y = mask_y; p.in_scale = in_scale; p.res_g = res_g; p.res_y = res_y;
-    p.out_mask_y = out_mask_y; p.scale = out_scale;
+    p.res_g = res_g; p.res_y = res_y; p.out_mask_y = out_mask_y; p.scale = out_scale;
     p.N = d->C; p.Kc = d->K; p.cin = d->C;
     p.R = d->R; p.S = d->S; p.pad = d->pad;
     p.lda = d->K; p.ldb = d->R * d->S * d->C; p.ldc = d->C;
@@ -2082,8 +2028,7 @@ extern "C" int mrcnn_filter_flip_transpose(const float *w, float *wT, int K, int
 // Stride-1 dgrad as a forward-form convolution of gy with wT = flip-transpose(w) (C,R,S,K):
 // both operands are K-contiguous (ds_read_b128 fragments, coalesced filter rows).
 extern "C" int mrcnn_conv2d_dgrad_wt(const mrcnn_conv_desc *d, const float *gy, const float *wT,
-                                     float *gx, int epi_flags, const float *mask_y,
-                                     const float *in_scale, const float *res_g,
+                                     float *gx, int epi_flags, const float *res_g,
                                      const float *res_y, const float *out_mask_y,
                                      const float *out_scale, void *split_ws, void *stream)
 {
@@ -2101,7 +2046,7 @@ extern "C" int mrcnn_conv2d_dgrad_wt(const mrcnn_conv_desc *d, const float *gy, 
         hipStream_t s = mrcnn::as_stream(stream);
         GemmParams p = {};
         p.A = gy; p.B = wT; p.C = gx;
-        p.mask_y = mask_y; p.in_scale = in_scale; p.scale = out_scale;
+        p.scale = out_scale;
         p.M = d->N * d->P * d->Q; p.N = d->C; p.Kc = d->K;
         p.gp = d->P; p.gq = d->Q; p.sh = d->P; p.sw = d->Q;
         p.R = 1; p.S = 1; p.stride = 1; p.pad = 0; p.ostride = d->stride;
@@ -2121,8 +2066,7 @@ extern "C" int mrcnn_conv2d_dgrad_wt(const mrcnn_conv_desc *d, const float *gy, 
     MRCNN_REQUIRE(!res_y || res_g, "conv2d_dgrad_wt: res_y without res_g");
     GemmParams p = {};
     p.A = gy; p.B = wT; p.C = gx;
-    p.mask_y = mask_y; p.in_scale = in_scale; p.res_g = res_g; p.res_y = res_y;
-    p.out_mask_y = out_mask_y; p.scale = out_scale;
+    p.res_g = res_g; p.res_y = res_y; p.out_mask_y = out_mask_y; p.scale = out_scale;
    
     p.split_ws = (float *)split_ws;
     p.M = d->N * d->H * d->W; p.N = d->C; p.Kc = d->K;
@@ -2148,12 +2092,11 @@ extern "C" int64_t mrcnn_conv2d_wgrad_workspace_bytes(const mrcnn_conv_desc *d)
 
 static int wgrad_impl(const float *gy, int ldg, const float *x, float *gw, int Kout, int64_t pixels,
                       int N_, int H, int W, int C, int P, int Q, int R, int S, int stride, int pad,
-                      void *ws, hipStream_t s, const float *mask_y = nullptr,
-                      const float *in_scale = nullptr, const float *out_row_scale = nullptr)
+                      void *ws, hipStream_t s, const float *out_row_scale = nullptr)
 {
     GemmParams p = {};
     p.A = gy; p.B = x;
-    p.mask_y = mask_y; p.in_scale = in_scale; p.scale = out_row_scale;
+    p.scale = out_row_scale;
     p.M = Kout; p.N = R * S * C; p.Kc = (int)pixels;
     p.gp = P; p.gq = Q; p.sh = H; p.sw = W;
     p.R = R; p.S = S; p.stride = stride; p.pad = pad;
@@ -2169,12 +2112,12 @@ static int wgrad_impl(const float *gy, int ldg, const float *x, float *gw, int K
     const int64_t tiles = use_big ? big : small;
     // block-position-major pixel order (WPERM kernel): border taps skip the positions where
     // they fall into the padding; the reduction then runs over whole blocks of BK images
-    if (C % (use_big ? 128 : 64) == 0 && N_ >= BK && !is_masked(p))
+    if (C % (use_big ? 128 : 64) == 0 && N_ >= BK)
         p.perm_n = choose_perm(N_, P, Q, R, S, stride, pad);
     const int64_t k_extent = p.perm_n ? mrcnn::ceil_div(N_, BK) * BK * P * Q : pixels;
     // resident 128x128 workgroups: 3 per CU single-buffered, 2 otherwise (and for the split-operand kernel)
     const bool split_kernel = (g_split_bf16 & 1) && p.perm_n == 0;
-    const int64_t slots_big = !split_kernel && single_buffered(2, WGRAD, is_masked(p)) ? 768 : kSlotsBig;
+    const int64_t slots_big = !split_kernel && single_buffered(2, WGRAD) ? 768 : kSlotsBig;
     int splits = wgrad_splits(tiles, pixels, use_big ? slots_big : kSlotsSmall);
     if (!ws) splits = 1;
     p.split_len = (int)(mrcnn::ceil_div(mrcnn::ceil_div(k_extent, splits), BK) * BK);
@@ -2203,8 +2146,7 @@ static int wgrad_impl(const float *gy, int ldg, const float *x, float *gw, int K
 }
 
 extern "C" int mrcnn_conv2d_wgrad_ex(const mrcnn_conv_desc *d, const float *x, const float *gy,
-                                     float *gw, void *ws, const float *mask_y,
-                                     const float *in_scale, const float *out_row_scale,
+                                     float *gw, void *ws, const float *out_row_scale,
                                      void *stream)
 {
     if (int rc = check_desc(d)) return rc;
@@ -2213,13 +2155,13 @@ extern "C" int mrcnn_conv2d_wgrad_ex(const mrcnn_conv_desc *d, const float *x, c
                   "conv2d_wgrad: pointers must be 16-byte aligned");
     return wgrad_impl(gy, d->K, x, gw, d->K, (int64_t)d->N * d->P * d->Q, d->N, d->H, d->W, d->C,
                       d->P, d->Q, d->R, d->S, d->stride, d->pad, ws, mrcnn::as_stream(stream),
-                      mask_y, in_scale, out_row_scale);
+                      out_row_scale);
 }
 
 extern "C" int mrcnn_conv2d_wgrad(const mrcnn_conv_desc *d, const float *x, const float *gy,
                                   float *gw, void *ws, void *stream)
 {
-    return mrcnn_conv2d_wgrad_ex(d, x, gy, gw, ws, nullptr, nullptr, nullptr, stream);
+    return mrcnn_conv2d_wgrad_ex(d, x, gy, gw, ws, nullptr, stream);
 }
 
 // ---- Deconvolution 2x2 stride 2 (= adjoint of a 2x2/2 convolution g: (N,2H,2W,K) -> (N,H,W,C)

@@ -644,7 +644,7 @@ extern "C" int mrcnn_conv3x3_wino_wgrad(const mrcnn_conv_desc *d, const float *x
     const bool big = p.M > 64 && p.N > 64;
     const int64_t tiles = big ? mrcnn::ceil_div(p.M, 128) * mrcnn::ceil_div(p.N, 128)
                               : mrcnn::ceil_div(p.M, 64) * mrcnn::ceil_div(p.N, 64);
-    const int64_t slots = big ? (single_buffered(2, WGRAD, false) ? 768 : kSlotsBig) : kSlotsSmall;
+    const int64_t slots = big ? (single_buffered(2, WGRAD) ? 768 : kSlotsBig) : kSlotsSmall;
     int splits = std::min(kWinoMaxSplits, wgrad_splits(tiles * kXi, g.T, slots));
     p.split_len = (int)(mrcnn::ceil_div(mrcnn::ceil_div(g.T, splits), BK) * BK);
     splits = (int)mrcnn::ceil_div(g.T, p.split_len);

@@ -152,9 +152,9 @@ def _sparse3x3_backward(ctx, d, x, Wc, g, hint, need_x, need_w, need_b):
     d1 = ConvDesc(n, 1, 1, 9 * d.C, d.K, 1, 1, 1, 0, 1, 1)
     gx = gW = gb = None
     if need_w:
-        gW = _wgrad_raw(d1, patches, g_rows, ctx.W_param, None, None)
+        gW = _wgrad_raw(d1, patches, g_rows, ctx.W_param)
     if need_x:
-        gp = _dgrad_raw(d1, g_rows, Wc, None, None)          # (rows, 3, 3, C) patch gradients
+        gp = _dgrad_raw(d1, g_rows, Wc)          # (rows, 3, 3, C) patch gradients
         gx = empty_nhwc((d.N, d.C, d.H, d.W), dev)
         _lib.call('mrcnn_sparse3x3_scatter', _lib.ptr(gp), _lib.ptr(hint.lookup), d.N, d.H, d.W,
                   d.C, _lib.ptr(gx), _lib.stream_ptr())
@@ -191,7 +191,7 @@ class _Conv2dFn(torch.autograd.Function):
                          or not (_CONV_RECORDS_GRAPH and any(ctx.needs_input_grad))):
             y, _ = wino_fwd(x, Wc, d, scale, shift if scale is not None else b, relu,
                             cache_for=None if _CONV_RECORDS_GRAPH else W,
-                            exact_signs=relu and _CONV_RECORDS_GRAPH and WINOGRAD_EXACT_SIGNS)
+                            exact_signs=relu and _CONV_RECORDS_GRAPH)
         else:
             y = empty_nhwc((d.N, d.K, d.P, d.Q), x.device)
             _lib.call('mrcnn_conv2d_fwd', ctx_desc(d), _lib.ptr(x), _lib.ptr(Wc), _lib.ptr(b),
@@ -229,10 +229,8 @@ class _Conv2dFn(torch.autograd.Function):
             return gx, gW, gb, None, None, None, None, None, None
         if need_w:
             W = ctx.W_param
-            if ctx.wino and WINOGRAD_WGRAD:
+            if ctx.wino:
                 gW = _wino_wgrad(d, x, None, g, W)
-            elif USE_WGRAD_STREAM:
-                gW = _wgrad_raw(d, x, g, W, None, None, wgrad_stream(gy.device))
             else:
                 direct = _direct_grad(W)
                 if direct:
@@ -247,8 +245,7 @@ class _Conv2dFn(torch.autograd.Function):
                           _lib.ptr(gWt), _lib.ptr(ws), _lib.stream_ptr())
                 gW = None if direct else gWt
         if need_x:
-            gx = wino_dgrad(d, g, Wc) if ctx.wino and WINOGRAD_DGRAD else \
-                _dgrad_raw(d, g, Wc, None, None)
+            gx = wino_dgrad(d, g, Wc) if ctx.wino else _dgrad_raw(d, g, Wc)
         if need_b:
             b = ctx.b_param
             direct = _direct_grad(b)
@@ -388,18 +385,7 @@ def linear(x, W, b=None):
     return y.reshape(n, W.shape[0])
 
 
-# ---------------------------------------------------------------------------------------
-# Whole-bottleneck op: chainer BottleneckA / BottleneckB as ONE autograd
-# node.  Forward = 3 (4) fused implicit-GEMM launches; backward = 3 (4) dgrad + 3 (4) wgrad
-# launches and NOTHING else: the ReLU masks and affine scales are applied while the
-# incoming gradient is staged into LDS, and the identity-shortcut gradient is added in the
-# dgrad epilogue, so there is no elementwise pass and no gradient-accumulation kernel.
-# ---------------------------------------------------------------------------------------
-
-# Measured on MI355X (round 1): queueing wgrads on a second stream did not overlap with the
-# dgrads in practice (68.9 vs 68.1 ms per step), so the single-stream order is the default.
-USE_WGRAD_STREAM = False
-
+# ---- raw GEMM launches of the fused stage (_StageFn below) -------------------------------------
 
 def _fwd_raw(x, Wc, d, scale, shift, residual, relu):
     flags = (EPI_AFFINE if scale is not None else 0) | (EPI_RESIDUAL if residual is not None else 0) \
@@ -409,9 +395,6 @@ def _fwd_raw(x, Wc, d, scale, shift, residual, relu):
               _lib.ptr(shift), _lib.ptr(residual), _lib.ptr(y), flags, _lib.ptr(split_ws(x.device)),
               _lib.stream_ptr())
     return y
-
-
-USE_TRANSPOSED_DGRAD = True
 
 
 def _flip_transpose(Wc, d, row_scale, out):
@@ -456,27 +439,22 @@ def _stage_transposes(blocks, scales, device):
     return out
 
 
-# Strided 1x1 / pad 0 data gradients (res3.a / res4.a conv1 and conv4) in forward form on the
-# transposed filter as well: dense gather of gy, rows scattered to the strided pixels of a zero-filled
-# gx (split-operand kernels; the K-strided form runs on fp32 MFMA).
-STRIDED_DGRAD_FORWARD_FORM = True
-
-
+# Data gradients in forward form on the flipped, transposed filter: stride-1 square filters, and
+# the strided 1x1 / pad 0 ones (res3.a / res4.a conv1 and conv4: dense gather of gy, rows scattered
+# to the strided pixels of a zero-filled gx).  Split-operand kernels; the K-strided form that the
+# other filters take runs on fp32 MFMA.
 def _uses_transposed_dgrad(d):
-    if not USE_TRANSPOSED_DGRAD:
-        return False
     if d.stride == 1:
         return d.R == d.S
-    return STRIDED_DGRAD_FORWARD_FORM and d.R == 1 and d.S == 1 and d.pad == 0
+    return d.R == 1 and d.S == 1 and d.pad == 0
 
 
-def _dgrad_raw(d, g, Wc, mask_y, in_scale, res_g=None, res_y=None, out=None, accum=False,
+def _dgrad_raw(d, g, Wc, res_g=None, res_y=None, out=None, accum=False,
                out_mask_y=None, out_scale=None, fold_scale=None, wT=None):
-    """gx = dgrad(g') with the fused pieces of include/mrcnn_hip.h "Extended backward entry
-    points": consumer-side ``mask_y`` / ``in_scale``, producer-side ``out_mask_y`` /
-    ``out_scale``, shortcut gradient ``res_g`` (masked by ``res_y`` if given).  ``fold_scale``
-    is a per-output-channel scale of the incoming gradient folded into the filter (stride 1)
-    or, for the strided kernel, passed as ``in_scale``."""
+    """gx = dgrad(g) with the fused pieces of include/mrcnn_hip.h "Extended backward entry
+    points": producer-side ``out_mask_y`` / ``out_scale``, shortcut gradient ``res_g`` (masked
+    by ``res_y`` if given).  ``fold_scale`` is a per-output-channel scale of the incoming
+    gradient folded into the transposed filter (forward form only)."""
     gx = out if out is not None else empty_nhwc((d.N, d.C, d.H, d.W), g.device)
     if _uses_transposed_dgrad(d):
         # forward-form dgrad on the flipped, transposed filter; ``wT`` = already built (with
@@ -485,17 +463,15 @@ def _dgrad_raw(d, g, Wc, mask_y, in_scale, res_g=None, res_y=None, out=None, acc
             wT = _flip_transpose(Wc, d, fold_scale,
                                  _lib.workspace(4 * d.K * d.R * d.S * d.C, g.device, 'wT'))
         _lib.call('mrcnn_conv2d_dgrad_wt', ctx_desc(d), _lib.ptr(g), _lib.ptr(wT), _lib.ptr(gx),
-                  EPI_ACCUM if accum else 0, _lib.ptr(mask_y), _lib.ptr(in_scale),
-                  _lib.ptr(res_g), _lib.ptr(res_y), _lib.ptr(out_mask_y), _lib.ptr(out_scale),
-                  _lib.ptr(split_ws(g.device)), _lib.stream_ptr())
+                  EPI_ACCUM if accum else 0, _lib.ptr(res_g), _lib.ptr(res_y), _lib.ptr(out_mask_y),
+                  _lib.ptr(out_scale), _lib.ptr(split_ws(g.device)), _lib.stream_ptr())
         return gx
     if fold_scale is not None:
-        assert in_scale is None
-        in_scale = fold_scale
+        raise ValueError('dgrad: fold_scale needs the forward form (stride-1 square filters or '
+                         '1x1 / pad 0), got %dx%d / stride %d / pad %d' % (d.R, d.S, d.stride, d.pad))
     _lib.call('mrcnn_conv2d_dgrad_ex', ctx_desc(d), _lib.ptr(g), _lib.ptr(Wc), _lib.ptr(gx),
-              EPI_ACCUM if accum else 0, _lib.ptr(mask_y), _lib.ptr(in_scale), _lib.ptr(res_g),
-              _lib.ptr(res_y), _lib.ptr(out_mask_y), _lib.ptr(out_scale),
-              _lib.ptr(split_ws(g.device)), _lib.stream_ptr())
+              EPI_ACCUM if accum else 0, _lib.ptr(res_g), _lib.ptr(res_y), _lib.ptr(out_mask_y),
+              _lib.ptr(out_scale), _lib.ptr(split_ws(g.device)), _lib.stream_ptr())
     return gx
 
 
@@ -540,9 +516,6 @@ WINOGRAD_MIN_WORK = int(_os.environ.get('MRCNN_WINO_MIN_WORK', 1 << 27))        
 # Without a graph (inference) every routed layer's forward takes it: only the per-op tolerance
 # applies there and it holds with a 30x margin.
 WINOGRAD_TRAIN_FORWARD = True         # False / 'conv2d' / 'stage' / True (both; default since round 3)
-WINOGRAD_EXACT_SIGNS = True          # recorded graphs: ReLU decisions recomputed directly near zero
-WINOGRAD_DGRAD = True        # developer switches (error attribution, A/B timing)
-WINOGRAD_WGRAD = True
 
 
 def uses_winograd(d):
@@ -717,6 +690,9 @@ def join_wgrad_stream(device=None):
 # they cost nothing (optimizers.MomentumSGD.defer_weight_gradients; same gradients, same update,
 # applied before the parameter is read again: results are bit-identical).
 class DeferQueue(object):
+    """``jobs``: (d, x, g, gW, row_scale, wino, v) per held-back weight gradient; ``wino``: on the
+    Winograd route, from the raw input ``x`` or the forward's kept transform ``v`` (the other is None)."""
+
     def __init__(self, params):
         self.ids = set(id(p) for p in params)
         self.jobs = []
@@ -735,18 +711,14 @@ def defer_stream(device):
 
 def run_deferred_wgrads(jobs):
     """Launch the held-back weight gradients on the current stream (the caller selects it)."""
-    for d, x, g, gW, mask_y, in_scale, row_scale in jobs:
-        if mask_y is _WINO:
-            wino_wgrad_into(d, x, in_scale, g, gW, row_scale, tag='wino-defer')
+    for d, x, g, gW, row_scale, wino, v in jobs:
+        if wino:
+            wino_wgrad_into(d, x, v, g, gW, row_scale, tag='wino-defer')
             continue
         ws = _lib.workspace(_lib.load().mrcnn_conv2d_wgrad_workspace_bytes(ctx_desc(d)),
                             g.device, 'wgrad-defer')
         _lib.call('mrcnn_conv2d_wgrad_ex', ctx_desc(d), _lib.ptr(x), _lib.ptr(g), _lib.ptr(gW),
-                  _lib.ptr(ws), _lib.ptr(mask_y), _lib.ptr(in_scale), _lib.ptr(row_scale),
-                  _lib.stream_ptr())
-
-
-_WINO = object()       # marker in the mask_y slot of a deferred job: Winograd weight gradient
+                  _lib.ptr(ws), _lib.ptr(row_scale), _lib.stream_ptr())
 
 
 def _wino_wgrad(d, x, v, g, W, row_scale=None):
@@ -754,123 +726,54 @@ def _wino_wgrad(d, x, v, g, W, row_scale=None):
     input ``v`` (the other is None); same gradient-ownership rules as _wgrad_raw."""
     direct = _direct_grad(W)
     if direct and _DEFER is not None and id(W) in _DEFER.ids:
-        _DEFER.jobs.append((d, x, g, W.grad, _WINO, v, row_scale))    # v rides in the in_scale slot
+        _DEFER.jobs.append((d, x, g, W.grad, row_scale, True, v))
         return None
     gW = W.grad if direct else empty_nhwc(tuple(W.shape), g.device)
     wino_wgrad_into(d, x, v, g, gW, row_scale)
     return None if direct else gW
 
 
-def _wgrad_raw(d, x, g, W, mask_y, in_scale, side=None, row_scale=None):
+def _wgrad_raw(d, x, g, W, side=None, row_scale=None):
     """Returns the tensor autograd should see for W (None when written in place).  With
     ``side`` (a stream) the launch is queued there, ordered after everything queued so far
     on the current stream; only arena-backed (direct) gradients may use it."""
     direct = _direct_grad(W)
     if direct and _DEFER is not None and id(W) in _DEFER.ids:
-        _DEFER.jobs.append((d, x, g, W.grad, mask_y, in_scale, row_scale))
+        _DEFER.jobs.append((d, x, g, W.grad, row_scale, False, None))
         return None
     gW = W.grad if direct else empty_nhwc(tuple(W.shape), g.device)
     if side is not None and direct:
         side.wait_stream(torch.cuda.current_stream(g.device))
-        for t in (x, g, mask_y):
-            if t is not None:
-                t.record_stream(side)
+        for t in (x, g):
+            t.record_stream(side)
         with torch.cuda.stream(side):
             ws = _lib.workspace(_lib.load().mrcnn_conv2d_wgrad_workspace_bytes(ctx_desc(d)),
                                 g.device, 'wgrad-side')
             _lib.call('mrcnn_conv2d_wgrad_ex', ctx_desc(d), _lib.ptr(x), _lib.ptr(g),
-                      _lib.ptr(gW), _lib.ptr(ws), _lib.ptr(mask_y), _lib.ptr(in_scale),
-                      _lib.ptr(row_scale), _lib.stream_ptr())
+                      _lib.ptr(gW), _lib.ptr(ws), _lib.ptr(row_scale), _lib.stream_ptr())
         return None
     ws = _lib.workspace(_lib.load().mrcnn_conv2d_wgrad_workspace_bytes(ctx_desc(d)),
                         g.device, 'wgrad')
     _lib.call('mrcnn_conv2d_wgrad_ex', ctx_desc(d), _lib.ptr(x), _lib.ptr(g), _lib.ptr(gW),
-              _lib.ptr(ws), _lib.ptr(mask_y), _lib.ptr(in_scale), _lib.ptr(row_scale),
-              _lib.stream_ptr())
+              _lib.ptr(ws), _lib.ptr(row_scale), _lib.stream_ptr())
     return None if direct else gW
-
-
-class _BottleneckFn(torch.autograd.Function):
-
-    @staticmethod
-    def forward(ctx, x, W1, s1, b1, W2, s2, b2, W3, s3, b3, W4, s4, b4, stride):
-        _lib.require_device(x, W1)
-        x = nhwc(x)
-        d1 = make_desc(x.shape, W1.shape, stride, 0)
-        h1 = _fwd_raw(x, nhwc(W1), d1, s1, b1, None, True)
-        d2 = make_desc(h1.shape, W2.shape, 1, 1)
-        h2 = _fwd_raw(h1, nhwc(W2), d2, s2, b2, None, True)
-        d4 = None
-        if W4 is not None:
-            d4 = make_desc(x.shape, W4.shape, stride, 0)
-            shortcut = _fwd_raw(x, nhwc(W4), d4, s4, b4, None, False)
-        else:
-            shortcut = x
-        d3 = make_desc(h2.shape, W3.shape, 1, 0)
-        y = _fwd_raw(h2, nhwc(W3), d3, s3, b3, shortcut, True)
-        ctx.descs = (d1, d2, d3, d4)
-        ctx.params = (W1, W2, W3, W4)
-        ctx.save_for_backward(x, h1, h2, y, s1, s2, s3, s4)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        x, h1, h2, y, s1, s2, s3, s4 = ctx.saved_tensors
-        d1, d2, d3, d4 = ctx.descs
-        W1, W2, W3, W4 = ctx.params
-        gy = nhwc(gy)
-        ng = ctx.needs_input_grad
-        gW1 = gW2 = gW3 = gW4 = gx = None
-        side = wgrad_stream(gy.device) if USE_WGRAD_STREAM else None
-        # conv3 <- relu/affine(bn3) of the block output; each wgrad is queued on the side
-        # stream right after the dgrad that produces its incoming gradient
-        if ng[7]:
-            gW3 = _wgrad_raw(d3, h2, gy, W3, y, s3, side)
-        if W4 is not None and ng[10]:
-            gW4 = _wgrad_raw(d4, x, gy, W4, y, s4, side)
-        gh2 = _dgrad_raw(d3, gy, nhwc(W3), y, s3)
-        if ng[4]:
-            gW2 = _wgrad_raw(d2, h1, gh2, W2, h2, s2, side)
-        gh1 = _dgrad_raw(d2, gh2, nhwc(W2), h2, s2)
-        if ng[1]:
-            gW1 = _wgrad_raw(d1, x, gh1, W1, h1, s1, side)
-        if ng[0]:
-            if W4 is None:
-                # identity shortcut: gx = dgrad(conv1) + gy * (y > 0), added in the epilogue
-                gx = _dgrad_raw(d1, gh1, nhwc(W1), h1, s1, res_g=gy, res_y=y)
-            else:
-                gx = _dgrad_raw(d1, gh1, nhwc(W1), h1, s1)
-                _dgrad_raw(d4, gy, nhwc(W4), y, s4, out=gx, accum=True)
-        return (gx, gW1, None, None, gW2, None, None, gW3, None, None, gW4, None, None, None)
-
-
-def bottleneck(x, conv1, bn1, conv2, bn2, conv3, bn3, conv4=None, bn4=None, stride=1):
-    """relu(bn3(conv3(relu(bn2(conv2(relu(bn1(conv1 x))))))) + shortcut) with
-    shortcut = bn4(conv4 x) (BottleneckA) or x (BottleneckB); stride lives in conv1/conv4."""
-    return _BottleneckFn.apply(
-        x, conv1.W, bn1.W, bn1.b, conv2.W, bn2.W, bn2.b, conv3.W, bn3.W, bn3.b,
-        None if conv4 is None else conv4.W, None if bn4 is None else bn4.W,
-        None if bn4 is None else bn4.b, stride)
 
 
 # ---------------------------------------------------------------------------------------
 # Whole-stage op: chainer BuildingBlock (BottleneckA + n x BottleneckB) as ONE autograd node.
-# Same launches as a chain of _BottleneckFn, but every gradient tensor inside the stage is
-# written ALREADY multiplied by the ReLU mask (and affine scale) of the conv that consumes it
-# — in the epilogue of the dgrad that produces it — so none of the stage's backward GEMMs
-# stages a mask: they all run the plain 168-register kernels, three workgroups per CU.  Only
-# the gradient entering the stage from autograd takes one elementwise masking pass.
+# Forward = 3 (4) fused implicit-GEMM launches per block; backward = 3 (4) dgrad + 3 (4) wgrad
+# launches per block and nothing else: every gradient tensor inside the stage is written ALREADY
+# multiplied by the ReLU mask (and affine scale) of the conv that consumes it — in the epilogue
+# of the dgrad that produces it — and the identity-shortcut gradient is added there too, so none
+# of the stage's backward GEMMs stages a mask: they all run the 168-register kernels, three
+# workgroups per CU.  Only the gradient entering the stage from autograd takes one elementwise
+# masking pass.
 # ---------------------------------------------------------------------------------------
 # Weight gradients of the backbone's small-M layers (<= 40 000 output pixels: res3 / res4) are
 # queued on a second HIP stream: such a launch has only 2-4 workgroups per CU, so the wgrad and
 # the next dgrad share the GPU (same-box A/B: 54.4 -> 54.0 ms per step).  For the large res5
-# launches the same trick measured no overlap (USE_WGRAD_STREAM above).
-SMALL_WGRAD_SIDE_STREAM = True
+# launches the same trick measured no overlap (round 1: 68.9 vs 68.1 ms per step).
 SMALL_WGRAD_MAX_PIXELS = int(_os.environ.get('MRCNN_SIDE_WGRAD_MAX_PIXELS', 40000))
-# Build the transposed filters of a stage during its forward, on the side stream (see _StageFn).
-# Measured (same-box A/B): 53.2 vs 53.0 ms per step — the 42 five-microsecond transposes cost
-# as much next to the forward GEMMs as between the backward ones; off by default.
-PRETRANSPOSE_FILTERS = False
 
 
 # ---- pooling AFTER res5.a's 1x1 projections ("projected pooling") --------------------------------
@@ -1035,7 +938,7 @@ class _StageFn(torch.autograd.Function):
                 h2, v2 = wino_fwd(h1, nhwc(W2), d2, s2, b2, True,
                                   keep_v=training and bool(ctx.needs_input_grad[6 + pos + 3]),
                                   cache_for=None if training else W2,
-                                  exact_signs=training and WINOGRAD_EXACT_SIGNS)
+                                  exact_signs=training)
             else:
                 h2 = _fwd_raw(h1, nhwc(W2), d2, s2, b2, None, True)
             d4 = None
@@ -1065,7 +968,6 @@ class _StageFn(torch.autograd.Function):
         ctx.n_saved = len(saved)
         ctx.wino_slots = [i for i, v in enumerate(wino_v) if v is not None]
         ctx.save_for_backward(*(saved + [wino_v[i] for i in ctx.wino_slots]))
-        ctx.wT = None
         ctx.tail = tail_rows is not None
         if ctx.tail:
             # the two consumers of the stage output, produced here so that backward receives
@@ -1080,20 +982,6 @@ class _StageFn(torch.autograd.Function):
                 slot = torch.full((R_,), -1, dtype=torch.int32, device=h.device)
                 slot[tail_rows] = torch.arange(tail_rows.numel(), dtype=torch.int32, device=h.device)
             ctx.tail_slot = slot
-        if PRETRANSPOSE_FILTERS and any(ctx.needs_input_grad):
-            # The backward's forward-form dgrads need every filter flipped and transposed
-            # (conv3 / conv4 with their affine scale folded in).  The weights are final for
-            # this step, so the ~40 tiny transposes run now on the side stream, next to the
-            # forward GEMMs, instead of between the backward GEMMs.
-            dev = x.device
-            side, main = wgrad_stream(dev), torch.cuda.current_stream(dev)
-            side.wait_stream(main)          # the previous step's SGD update of the weights
-            with torch.cuda.stream(side):
-                ctx.wT = _stage_transposes(
-                    blocks, [(params[p0 + 7], params[p0 + 10] if W4 is not None else None)
-                             for _, (_, _, _, W4), p0 in blocks], dev)
-                ctx.wT_ready = torch.cuda.Event()
-                ctx.wT_ready.record(side)
         if ctx.tail:
             return pooled.reshape(R_, C_, 1, 1), sub
         return h
@@ -1123,18 +1011,10 @@ class _StageFn(torch.autograd.Function):
         # second stream so that they can share the GPU with the next dgrad
         d_top = ctx.blocks[-1][0][2]
         dev_ = gy.device if gy is not None else g_rows.device
-        side = wgrad_stream(dev_) if (
-            SMALL_WGRAD_SIDE_STREAM and d_top.N * d_top.P * d_top.Q <= SMALL_WGRAD_MAX_PIXELS) else None
-        if ctx.wT is not None:
-            main = torch.cuda.current_stream(dev_)
-            main.wait_event(ctx.wT_ready)
-            for t in ctx.wT:
-                for buf in t.values():
-                    buf.record_stream(main)
-            stage_wT = ctx.wT
-        else:
-            # all the stage's filter transposes in one launch
-            stage_wT = _stage_transposes(ctx.blocks, [(a[6], a[7]) for a in acts], dev_)
+        side = wgrad_stream(dev_) if d_top.N * d_top.P * d_top.Q <= SMALL_WGRAD_MAX_PIXELS else None
+        # all the stage's filter transposes in one launch (built during the forward on the side
+        # stream instead, they measured no faster: 53.2 vs 53.0 ms per step)
+        stage_wT = _stage_transposes(ctx.blocks, [(a[6], a[7]) for a in acts], dev_)
         # gm: gradient w.r.t. the block output, already through that output's ReLU
         if ctx.tail:
             y_top = acts[-1][3]
@@ -1168,55 +1048,45 @@ class _StageFn(torch.autograd.Function):
                 _pool_bwd_alone(side, dev_)
                 gz4 = _roi_pool_bwd(gm, ctx.roi, (x.shape[0], d4.K, x.shape[2], x.shape[3]))
             if ng[base + 6]:
-                grads[base + 6] = _wgrad_raw(d3, h2, gm, W3, None, None, side, row_scale=s3)
+                grads[base + 6] = _wgrad_raw(d3, h2, gm, W3, side, row_scale=s3)
             if pooled_here:
                 if ng[base + 9]:
-                    grads[base + 9] = _wgrad_raw(d4, x, gz4, W4, None, None, side, row_scale=s4)
+                    grads[base + 9] = _wgrad_raw(d4, x, gz4, W4, side, row_scale=s4)
             elif W4 is not None and ng[base + 9]:
-                grads[base + 9] = _wgrad_raw(d4, x, gm, W4, None, None, side, row_scale=s4)
-            gh2 = _dgrad_raw(d3, gm, nhwc(W3), None, None, fold_scale=s3,
-                             out_mask_y=h2, out_scale=s2, wT=wT.get('3'))
+                grads[base + 9] = _wgrad_raw(d4, x, gm, W4, side, row_scale=s4)
+            gh2 = _dgrad_raw(d3, gm, nhwc(W3), fold_scale=s3, out_mask_y=h2, out_scale=s2,
+                             wT=wT.get('3'))
             if uses_winograd(d2):
                 if ng[base + 3]:
-                    if WINOGRAD_WGRAD:
-                        v2 = wino_v.get(i)
-                        grads[base + 3] = _wino_wgrad(d2, h1 if v2 is None else None, v2, gh2, W2)
-                    else:
-                        grads[base + 3] = _wgrad_raw(d2, h1, gh2, W2, None, None, side)
-                if WINOGRAD_DGRAD:
-                    gh1 = wino_dgrad(d2, gh2, nhwc(W2), out_scale=s1, out_mask_y=h1)
-                else:
-                    gh1 = _dgrad_raw(d2, gh2, nhwc(W2), None, None, out_mask_y=h1, out_scale=s1)
+                    v2 = wino_v.get(i)
+                    grads[base + 3] = _wino_wgrad(d2, h1 if v2 is None else None, v2, gh2, W2)
+                gh1 = wino_dgrad(d2, gh2, nhwc(W2), out_scale=s1, out_mask_y=h1)
             else:
                 if ng[base + 3]:
-                    grads[base + 3] = _wgrad_raw(d2, h1, gh2, W2, None, None, side)
-                gh1 = _dgrad_raw(d2, gh2, nhwc(W2), None, None, out_mask_y=h1, out_scale=s1,
-                                 wT=wT.get('2'))
+                    grads[base + 3] = _wgrad_raw(d2, h1, gh2, W2, side)
+                gh1 = _dgrad_raw(d2, gh2, nhwc(W2), out_mask_y=h1, out_scale=s1, wT=wT.get('2'))
             if pooled_here and (ng[base] or ng[0]):
                 _pool_bwd_alone(side, dev_)
                 gh1 = _roi_pool_bwd(gh1, ctx.roi, (x.shape[0], d1.K, x.shape[2], x.shape[3]))
             if ng[base]:
-                grads[base] = _wgrad_raw(d1, x, gh1, W1, None, None, side)
+                grads[base] = _wgrad_raw(d1, x, gh1, W1, side)
             if poll is not None:
                 poll()             # this block's weight gradients are queued
             if first and not ng[0]:
                 break
             if pooled_here:
-                gx = _dgrad_raw(d1, gh1, nhwc(W1), None, None, wT=wT.get('1'))
-                gm = _dgrad_raw(d4, gz4, nhwc(W4), None, None, fold_scale=s4, out=gx, accum=True,
-                                wT=wT.get('4'))
+                gx = _dgrad_raw(d1, gh1, nhwc(W1), wT=wT.get('1'))
+                gm = _dgrad_raw(d4, gz4, nhwc(W4), fold_scale=s4, out=gx, accum=True, wT=wT.get('4'))
                 continue
             if W4 is None:
-                gm = _dgrad_raw(d1, gh1, nhwc(W1), None, None, res_g=gm, out_mask_y=xm,
-                                wT=wT.get('1'))
+                gm = _dgrad_raw(d1, gh1, nhwc(W1), res_g=gm, out_mask_y=xm, wT=wT.get('1'))
             elif d1.stride == 1:
-                gx = _dgrad_raw(d1, gh1, nhwc(W1), None, None, wT=wT.get('1'))
-                gm = _dgrad_raw(d4, gm, nhwc(W4), None, None, fold_scale=s4, out=gx, accum=True,
+                gx = _dgrad_raw(d1, gh1, nhwc(W1), wT=wT.get('1'))
+                gm = _dgrad_raw(d4, gm, nhwc(W4), fold_scale=s4, out=gx, accum=True,
                                 out_mask_y=xm, wT=wT.get('4'))
             else:
-                gx = _dgrad_raw(d1, gh1, nhwc(W1), None, None, wT=wT.get('1'))
-                gm = _dgrad_raw(d4, gm, nhwc(W4), None, None, fold_scale=s4, out=gx, accum=True,
-                                wT=wT.get('4'))
+                gx = _dgrad_raw(d1, gh1, nhwc(W1), wT=wT.get('1'))
+                gm = _dgrad_raw(d4, gm, nhwc(W4), fold_scale=s4, out=gx, accum=True, wT=wT.get('4'))
                 if xm is not None:
                     gm = epilogue_bwd(gm, xm, None)
         if ng[0]:

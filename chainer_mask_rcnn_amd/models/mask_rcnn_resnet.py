@@ -103,13 +103,11 @@ class ResNetRoIHead(torch.nn.Module):
         res5_stride = self.roi_size // 7
         # Both consumers of res5 wanted and the mask branch on a row subset (training): the fused
         # stage hands back (pool5, res5[mask_rows]) and combines their gradients in one pass
-        fused_tail = pred_bbox and pred_mask and mask_rows is not None and \
-            getattr(self.res5, 'fused_stage', False) and self.fused_tail
+        fused_tail = pred_bbox and pred_mask and mask_rows is not None and self.fused_tail
         kw = dict(tail_rows=mask_rows) if fused_tail else {}
         from ..functions import conv as _conv
         projected = self.projected_pooling if self.projected_pooling is not None else _conv.PROJECTED_POOLING
-        projected = projected and self.pooling_func is functions.roi_align_2d and \
-            getattr(self.res5, 'fused_stage', False) and rois.shape[0] > 0
+        projected = projected and self.pooling_func is functions.roi_align_2d and rois.shape[0] > 0
         if not projected and indices_and_rois is None:
             indices_and_rois = rois5[:, [0, 2, 1, 4, 3]]      # the reference-order branches take 'yx' rows
         if projected:

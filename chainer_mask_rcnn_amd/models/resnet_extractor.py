@@ -65,14 +65,12 @@ class Bottleneck(torch.nn.Module):
             self.bn4 = AffineChannel2D(out_ch)
 
     def forward(self, x, stride=None):
-        if self.projection:
-            return F.bottleneck(x, self.conv1, self.bn1, self.conv2, self.bn2, self.conv3,
-                                self.bn3, self.conv4, self.bn4,
-                                stride=self.conv1.stride if stride is None else stride)
-        return F.bottleneck(x, self.conv1, self.bn1, self.conv2, self.bn2, self.conv3, self.bn3)
+        """The block as a one-block fused stage (functions/conv.py:_StageFn)."""
+        return F.building_block(x, [self], first_stride=stride)
 
     def forward_unfused(self, x):
-        """Same block as four separate fused-conv autograd nodes (kept for testing)."""
+        """Same block as four separate fused-conv autograd nodes, each with an elementwise
+        epilogue backward: the tests' reference for the fused stage."""
         h = self.conv1(x, self.bn1, relu=True)
         h = self.conv2(h, self.bn2, relu=True)
         shortcut = self.conv4(x, self.bn4) if self.projection else x
@@ -80,12 +78,8 @@ class Bottleneck(torch.nn.Module):
 
 
 class BuildingBlock(torch.nn.Module):
-    """chainer BuildingBlock(n_layer, in, mid, out, stride): children a, b1 .. b{n-1}.
-
-    ``fused_stage`` (default): the whole stage is one autograd node whose backward GEMMs
-    need no mask staging (functions/conv.py:_StageFn); False chains per-bottleneck nodes.
-    """
-    fused_stage = True
+    """chainer BuildingBlock(n_layer, in, mid, out, stride): children a, b1 .. b{n-1}, run as
+    one autograd node whose backward GEMMs need no mask staging (functions/conv.py:_StageFn)."""
 
     def __init__(self, n_layer, in_ch, mid_ch, out_ch, stride):
         super(BuildingBlock, self).__init__()
@@ -101,21 +95,12 @@ class BuildingBlock(torch.nn.Module):
 
     def forward(self, x, first_stride=None, tail_rows=None, roi=None):
         """``first_stride`` overrides the stride of block ``a`` (used by the RoI head when the
-        stride-2 subsampling has already been done by the pooling op).  ``tail_rows`` (fused
-        stage only): return ``(average_pooling_2d(y), y[tail_rows])`` instead of y.  ``roi`` (fused
-        stage only; a ``functions.conv.RoiSpec``): ``x`` is the feature map and the stage pools
-        inside block ``a``, behind its 1x1 projections (functions/conv.py "projected pooling")."""
-        if self.fused_stage:
-            return F.building_block(x, [getattr(self, n) for n in self._names], first_stride,
-                                    poll=self.grad_poll, tail_rows=tail_rows, roi=roi)
-        if tail_rows is not None or roi is not None:
-            raise ValueError('tail_rows / roi need the fused stage')
-        for name in self._names:
-            if name == 'a' and first_stride is not None:
-                x = self.a(x, stride=first_stride)
-            else:
-                x = getattr(self, name)(x)
-        return x
+        stride-2 subsampling has already been done by the pooling op).  ``tail_rows``: return
+        ``(average_pooling_2d(y), y[tail_rows])`` instead of y.  ``roi`` (a
+        ``functions.conv.RoiSpec``): ``x`` is the feature map and the stage pools inside block
+        ``a``, behind its 1x1 projections (functions/conv.py "projected pooling")."""
+        return F.building_block(x, [getattr(self, n) for n in self._names], first_stride,
+                                poll=self.grad_poll, tail_rows=tail_rows, roi=roi)
 
 
 def pad_image_nhwc4(x):

@@ -315,33 +315,26 @@ int64_t mrcnn_conv2d_wgrad_workspace_bytes(const mrcnn_conv_desc *d);
 int mrcnn_conv2d_wgrad(const mrcnn_conv_desc *d, const float *x, const float *gy,
                        float *gw, void *ws, void *stream);
 /* Extended backward entry points.  The backward of a conv's fused epilogue (AffineChannel2D
- * scale s[k], then ReLU with output y) can be applied at either end of the gradient tensor:
- *
- *  consumer side — while gy is staged into LDS: g = gy * (mask_y > 0) * in_scale[k]
- *      (mask_y: output of the ReLU that followed THIS conv, same shape as gy; in_scale: its
- *      affine scale (K); either may be NULL).  Costs 16 more registers per lane, so these
- *      variants run two workgroups per CU.
- *  producer side — in the dgrad epilogue that WRITES the gradient:
+ * scale s[k], then ReLU with output y) is applied producer side, in the dgrad epilogue that
+ * WRITES the gradient:
  *      gx = (acc * out_scale[c] + res_g * (res_y > 0)) * (out_mask_y > 0)
  *      out_mask_y / out_scale: ReLU output / affine scale of the conv that produced this
  *      conv's INPUT ((N,H,W,C) / (C); either may be NULL).  The next dgrad / wgrad down the
- *      chain then need no mask and run the plain, three-workgroups-per-CU kernels.
+ *      chain then need no mask and run the three-workgroups-per-CU kernels.
  *      res_g (+ optional res_y): identity-shortcut gradient of a bottleneck, (N,H,W,C);
  *      stride 1 only.  With MRCNN_EPI_ACCUM the previous gx is added before the mask.
  *  A per-output-channel scale that cannot go to the producer (the block-top gradient feeds
  *  conv3, conv4 and the shortcut with different scales) is folded into the filter for dgrad
  *  (row_scale of mrcnn_filter_flip_transpose) and applied to the rows of gw in the wgrad
  *  epilogue (out_row_scale): gw[k] = s[k] * sum_m gy[m,k] x[m].
- * Used by functions/conv.py:_StageFn (a whole ResNet stage as one autograd node) and
- * _BottleneckFn; chainer runs each of these as separate elementwise kernels. */
+ * Used by functions/conv.py:_StageFn (a whole ResNet stage as one autograd node); chainer runs
+ * each of these as separate elementwise kernels. */
 int mrcnn_conv2d_dgrad_ex(const mrcnn_conv_desc *d, const float *gy, const float *w,
-                          float *gx, int epi_flags, const float *mask_y,
-                          const float *in_scale, const float *res_g, const float *res_y,
+                          float *gx, int epi_flags, const float *res_g, const float *res_y,
                           const float *out_mask_y, const float *out_scale, void *split_ws,
                           void *stream);
 int mrcnn_conv2d_wgrad_ex(const mrcnn_conv_desc *d, const float *x, const float *gy,
-                          float *gw, void *ws, const float *mask_y, const float *in_scale,
-                          const float *out_row_scale, void *stream);
+                          float *gw, void *ws, const float *out_row_scale, void *stream);
 /* Winograd F(4x4,3x3) path (csrc/conv_winograd.h) for 3x3 / stride 1 / pad 1 convolutions —
  * the algorithm cuDNN selects for the same layers in the reference (chainer autotune off:
  * cudnnGetConvolutionForwardAlgorithm; call sites as mrcnn_conv2d_fwd).  A third of the MFMA
@@ -396,8 +389,7 @@ int mrcnn_filter_flip_transpose_batched(int n, const void *const *w, void *const
                                         const int *K, const int *R, const int *S, const int *C,
                                         const void *const *row_scale, void *stream);
 int mrcnn_conv2d_dgrad_wt(const mrcnn_conv_desc *d, const float *gy, const float *wT,
-                          float *gx, int epi_flags, const float *mask_y,
-                          const float *in_scale, const float *res_g, const float *res_y,
+                          float *gx, int epi_flags, const float *res_g, const float *res_y,
                           const float *out_mask_y, const float *out_scale, void *split_ws,
                           void *stream);
 /* Stem: conv1 7x7/2 pad 3 with bias of chainer ResNet50Layers (SURVEY.md A.1;

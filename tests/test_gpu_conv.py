@@ -346,8 +346,9 @@ def test_conv_linearity_at_full_size(dev):
 
 @pytest.mark.parametrize('proj,stride', [(True, 2), (True, 1), (False, 1)])
 def test_fused_bottleneck_matches_oracle(dev, proj, stride):
-    """Whole-bottleneck node (mask/scale fused into dgrad/wgrad staging, shortcut gradient in
-    the dgrad epilogue) vs the NumPy oracle composed layer by layer."""
+    """One bottleneck as a one-block fused stage (masks / scales and the shortcut gradient in the
+    dgrad epilogues, scales folded into the filters and wgrad rows) vs the NumPy oracle composed
+    layer by layer."""
     from chainer_mask_rcnn_amd.models.resnet_extractor import Bottleneck
     torch.manual_seed(1)
     rng = np.random.RandomState(17)
@@ -395,8 +396,9 @@ def test_fused_bottleneck_matches_oracle(dev, proj, stride):
     ((2, 160, 160), (128, 128, 256), 1),   # 128x128 tiles (three workgroups per CU)
 ])
 def test_fused_stage_matches_bottleneck_chain(dev, shape, chans, stride):
-    """_StageFn (producer-side masks: no backward GEMM stages a mask) vs the chain of
-    per-bottleneck nodes, which test_fused_bottleneck_matches_oracle pins to the oracle."""
+    """_StageFn (producer-side masks: no backward GEMM stages a mask) vs the blocks applied one
+    by one through Bottleneck.forward_unfused: per-convolution nodes whose backward takes the
+    ReLU mask and affine scale in separate elementwise passes, independent of _StageFn."""
     from chainer_mask_rcnn_amd.models.resnet_extractor import BuildingBlock
     torch.manual_seed(3)
     n, h, w = shape
@@ -412,11 +414,15 @@ def test_fused_stage_matches_bottleneck_chain(dev, shape, chans, stride):
     gy = None
     out = {}
     for fused in (False, True):
-        stage.fused_stage = fused
         for p in stage.parameters():
             p.grad = None
         xt = x.clone().requires_grad_(True)
-        y = stage(xt)
+        if fused:
+            y = stage(xt)
+        else:
+            y = xt
+            for name in stage._names:
+                y = getattr(stage, name).forward_unfused(y)
         if gy is None:
             gy = torch.randn_like(y)
         y.backward(gy)

@@ -1,12 +1,12 @@
 """Developer tool: A/B a switch on the same box, alternating blocks of train steps.
-usage: python tools/ab_step.py <toggle> [rounds] [steps]   toggles: fanout, stage, upload"""
+usage: python tools/ab_step.py <toggle> [rounds] [steps]   toggles: fanout, upload, wside_all, posmajor"""
 import os, sys, time
 import numpy as np
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 import chainer_mask_rcnn_amd.functions as F
-from chainer_mask_rcnn_amd.models import resnet_extractor, mask_rcnn_train_chain
+from chainer_mask_rcnn_amd.models import mask_rcnn_train_chain
 
 
 def toggles(name):
@@ -14,22 +14,11 @@ def toggles(name):
         orig = F.fanout_rows
         plain = lambda x, rows: (x, x.index_select(0, rows))
         return (lambda: setattr(F, 'fanout_rows', orig)), (lambda: setattr(F, 'fanout_rows', plain))
-    if name == 'stage':
-        B = resnet_extractor.BuildingBlock
-        return (lambda: setattr(B, 'fused_stage', True)), (lambda: setattr(B, 'fused_stage', False))
     if name == 'upload':
         orig = mask_rcnn_train_chain._upload
         plain = lambda a, dt, dev: torch.tensor(a, dtype=dt, device=dev)
         return (lambda: setattr(mask_rcnn_train_chain, '_upload', orig)), \
                (lambda: setattr(mask_rcnn_train_chain, '_upload', plain))
-    if name == 'wside':
-        import chainer_mask_rcnn_amd.functions.conv as C
-        return (lambda: setattr(C, 'SMALL_WGRAD_SIDE_STREAM', True)), \
-               (lambda: setattr(C, 'SMALL_WGRAD_SIDE_STREAM', False))
-    if name == 'pretranspose':
-        import chainer_mask_rcnn_amd.functions.conv as C
-        return (lambda: setattr(C, 'PRETRANSPOSE_FILTERS', True)), \
-               (lambda: setattr(C, 'PRETRANSPOSE_FILTERS', False))
     if name == 'wside_all':
         import chainer_mask_rcnn_amd.functions.conv as C
         return (lambda: setattr(C, 'SMALL_WGRAD_MAX_PIXELS', 1 << 30)), \

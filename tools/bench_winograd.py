@@ -25,12 +25,12 @@ ws = _lib.workspace(_lib.load().mrcnn_conv2d_wgrad_workspace_bytes(C.ctx_desc(d)
 
 def direct_wgrad():
     _lib.call('mrcnn_conv2d_wgrad_ex', C.ctx_desc(d), _lib.ptr(x), _lib.ptr(g), _lib.ptr(gW),
-              _lib.ptr(ws), None, None, None, _lib.stream_ptr())
+              _lib.ptr(ws), None, _lib.stream_ptr())
 
 
 def direct_dgrad():
     C._flip_transpose(w, d, None, wT)
-    C._dgrad_raw(d, g, w, None, None, out_mask_y=m, out_scale=sc[:Cc] if Cc <= K else None, wT=wT)
+    C._dgrad_raw(d, g, w, out_mask_y=m, out_scale=sc[:Cc] if Cc <= K else None, wT=wT)
 
 
 cases = [

@@ -44,7 +44,7 @@ def main():
         f = lambda: _lib.call('mrcnn_conv2d_fwd', ctx_desc(d), _lib.ptr(x), _lib.ptr(w), None, _lib.ptr(sc),
                               _lib.ptr(sh), _lib.ptr(res), _lib.ptr(y), 2 | 4 | 8, sw, sp)
         t = lambda: _lib.call('mrcnn_conv2d_dgrad_wt', ctx_desc(d), _lib.ptr(gy), _lib.ptr(wT), _lib.ptr(gx), 0,
-                              None, None, None, None, _lib.ptr(xm), _lib.ptr(sc2), sw, sp)
+                              None, None, _lib.ptr(xm), _lib.ptr(sc2), sw, sp)
         row, ref = '%-22s' % name, None
         for kn in knobs:
             _lib.check(lib.mrcnn_set_tuning(b'big_split_k', kn), 'set_tuning')
