@@ -144,6 +144,9 @@ SIGNATURES = {
     'mrcnn_label_instances': (c_int, [c_vp, c_int, c_vp] + [c_int] * 4 + [c_vp] * 3
                               + [c_int] * 4 + [c_vp] * 6),
     'mrcnn_instances_to_label': (c_int, [c_vp] * 3 + [c_int] * 3 + [c_vp] * 3),
+    'mrcnn_draw_instances': (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_i64,
+                                     ctypes.c_double, c_int, c_vp]),
+    'mrcnn_tile_images': (c_int, [c_vp] + [c_int] * 5 + [c_vp, c_vp]),
     'mrcnn_decode_cls_boxes': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_f32,
                                        ctypes.POINTER(ctypes.c_double),
                                        ctypes.POINTER(ctypes.c_double), c_f32, c_f32, c_vp]),

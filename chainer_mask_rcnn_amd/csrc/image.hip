@@ -11,26 +11,13 @@
 // fixed-point path (11-bit coefficients, result rounded to uint8 before the mean is subtracted),
 // which is what cv2.resize runs for the decoded images MaskRCNNTransform feeds.
 // Built with -ffp-contract=off.
+#include "bilinear.h"
 #include "common.h"
 
 namespace {
 
-struct Lin { int i0, i1; float t; };
-
-// OpenCV resizeLinear coordinate rule for one axis
-__device__ __forceinline__ Lin lin_coord(int d, double scale, int n_in)
-{
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (s < 0) { s = 0; f = 0.f; }
-    if (s >= n_in - 1) { s = n_in - 1; f = 0.f; }
-    Lin l;
-    l.i0 = s;
-    l.i1 = min(s + 1, n_in - 1);
-    l.t = f;
-    return l;
-}
+using mrcnn::Lin;
+using mrcnn::lin_coord;
 
 // src (C,H,W) fp32 or uint8 -> dst image n of an (N, dstH, dstW, C) NHWC batch, rows/cols
 // beyond (outH, outW) are left untouched (the caller zero-fills the batch).  flip_x writes

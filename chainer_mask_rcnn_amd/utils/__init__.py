@@ -5,3 +5,5 @@ from .evaluations import (eval_instseg_voc, eval_instseg_coco, calc_instseg_voc_
                           calc_detection_voc_ap, mask_iou)
 from .geometry import (label2instance_boxes, instance_boxes2label, mask_to_bbox, get_bbox_overlap,
                        get_mask_overlap)
+from .visualizations import (draw_instance_bboxes, draw_instance_boxes, label_colormap,
+                             get_tile_image)

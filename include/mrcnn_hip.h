@@ -581,6 +581,52 @@ int mrcnn_instances_to_label(const uint8_t *masks, const int32_t *order, const i
                              int N, int H, int W, int32_t *lbl_ins, int32_t *lbl_cls,
                              void *stream);
 
+/* ---- Instance drawing and the report mosaic (csrc/visualize.hip) ---------------------------
+ * Replaces draw_instance_bboxes (chainer_mask_rcnn/utils/visualizations.py) and fcn's
+ * get_tile_image as InstanceSegmentationVisReport (extensions/instance_segmentation_vis_
+ * report.py) uses them.  The drawing contract, restated in NumPy by tests/visualize_ref.py:
+ * for every instance i in order whose draw flag is set, inside its crop C_i = [y1, y2) x
+ * [x1, x2) clipped to the image, a pixel with mask bit set becomes
+ * trunc(double(v) * (1 - alpha) + t_i[c]) per channel (one fp64 multiply, one fp64 add), then
+ * a pixel whose 3x3 neighbourhood clamped to C_i holds both mask values becomes (200, 200,
+ * 200); the mask outside C_i is never read.  Then for every instance i in order: the pixels
+ * within Chebyshev distance thickness / 2 of the 1-pixel rectangle through (x1, y1) and
+ * (x2, y2) take its outline colour, then its caption coverage a (uint8) composites white:
+ * v = (255 * a + v * (255 - a) + 127) / 255.  Each pixel depends only on its own value and
+ * on mask bits: one thread per pixel, no atomics, bitwise deterministic. */
+#define MRCNN_DRAW_MAX_INSTANCES 4096
+#define MRCNN_TILE_MAX_CELLS 64
+typedef struct mrcnn_draw_instance {
+    double t[3];          /* mask colour term per channel: the fp32 color_inst * alpha, widened */
+    int32_t box[4];       /* truncated (y1, x1, y2, x2), not clipped */
+    int32_t draw;         /* nonzero: drawn; zero: skipped in both passes */
+    uint32_t rgb;         /* outline colour r | g << 8 | b << 16 */
+    int32_t cap[4];       /* caption rectangle (y0, x0, h, w) in image pixels; h or w 0: none */
+    int64_t cap_offset;   /* byte offset of its (h, w) coverage in the atlas */
+} mrcnn_draw_instance;    /* 72 bytes */
+/* img (H, W, 3) uint8 drawn in place.  packed (N, H, Wq) masks in the packed format above
+ * (NULL: no masks, pass 1 is skipped); extent (N, 4) their extents, used to skip tiles (NULL:
+ * every tile of the crop is visited).  inst (N) device records, atlas the captions' coverage
+ * bytes (atlas_bytes of them; a caption that reaches past them reads 0).  0 <= alpha <= 1,
+ * 1 <= thickness <= 32767, N <= MRCNN_DRAW_MAX_INSTANCES, H * W < 2^31, H <= 4 * 65535. */
+int mrcnn_draw_instances(uint8_t *img, int H, int W, const uint64_t *packed,
+                         const int32_t *extent, int N, const mrcnn_draw_instance *inst,
+                         const uint8_t *atlas, int64_t atlas_bytes, double alpha, int thickness,
+                         void *stream);
+typedef struct mrcnn_tile_cell {
+    const uint8_t *src;   /* device (h, w, 3) uint8 image */
+    int32_t h, w;         /* its size */
+    int32_t oh, ow;       /* the size it is scaled to, inside the cell; 0: an empty cell */
+    int32_t oy, ox;       /* offset of the scaled image in its cell */
+} mrcnn_tile_cell;        /* 32 bytes */
+/* out (rows * cell_h, cols * cell_w, 3) uint8: cell k = cells[k] (HOST array, k < n_cells,
+ * row-major) scaled with the half-pixel bilinear rule of mrcnn_prepare_image (fp32, truncated
+ * to uint8); margins and cells >= n_cells are 0.  n_cells <= rows * cols <=
+ * MRCNN_TILE_MAX_CELLS, output H * W < 2^31 and H <= 65535.  Replaces fcn.utils.get_tile_image (bilinear instead of skimage's
+ * anti-aliased resize). */
+int mrcnn_tile_images(const mrcnn_tile_cell *cells, int n_cells, int rows, int cols, int cell_h,
+                      int cell_w, uint8_t *out, void *stream);
+
 /* Second half of MaskRCNN._suppress (models/mask_rcnn.py:195-202): the rows kept by
  * mrcnn_nms_sorted_batched (keep (G,R), n_keep (G)) of every class packed densely, class after
  * class and in keep order: bbox (<= G*R, 4), label, score, *total = number of rows. */

@@ -5,6 +5,7 @@ examples/evaluate_common.py + examples/coco/evaluate.py.
     python tools/evaluate.py --coco-root DIR --snapshot snapshot_model.npz --evaluator voc
     python tools/evaluate.py --synthetic 16            # no dataset: random weights, synthetic images
     python tools/evaluate.py --dataset sbd --sbd-root DIR --snapshot snapshot_model.npz
+    python tools/evaluate.py --synthetic 4 --vis       # also writes iteration=best.jpg
 
 Runs the evaluator (predicted masks stay on the device; extensions/), prints the report and
 the seconds per image spent in prediction and in evaluation, and writes the result as YAML (or
@@ -65,6 +66,9 @@ def main():
     ap.add_argument('--synthetic', type=int, default=0, help='N synthetic images, no dataset')
     ap.add_argument('--batch', type=int, default=1)
     ap.add_argument('--out', default=None, help='result file (default: next to the weights)')
+    ap.add_argument('--vis', action='store_true',
+                    help='also write the visual report of the first 9 images as iteration=best.jpg '
+                         'next to the result file (examples/evaluate_common.py)')
     args = ap.parse_args()
     voc = args.dataset in ('voc', 'sbd') and not args.synthetic
     if args.evaluator is None:
@@ -146,6 +150,21 @@ def main():
         with open(out, 'w') as f:
             json.dump(payload, f, indent=1)
     print('Saved evaluation:', out)
+
+    if args.vis:
+        vis_dir = os.path.dirname(os.path.abspath(out))
+
+        class DummyTrainer(object):
+            class DummyUpdater(object):
+                iteration = 'best'
+            updater = DummyUpdater()
+            out = vis_dir
+
+        vis = ([transform(data[j])] for j in range(min(9, n)))
+        visualizer = cmr.extensions.InstanceSegmentationVisReport(
+            vis, model, label_names=class_names, file_name='iteration=%s.jpg', copy_latest=False)
+        visualizer(trainer=DummyTrainer())
+        print('Saved visualization:', os.path.join(DummyTrainer.out, 'iteration=best.jpg'))
 
 
 if __name__ == '__main__':
