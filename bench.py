@@ -13,9 +13,13 @@ configs[1]: batch 2 x 800x1333 fp32 per GPU, 512 RoIs/img, 81 classes.  Inputs a
 resident in HBM before the timed region.  Weak scaling: every rank runs its own batch of 2.
 
 Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel,
-HIP-event timed inside the run), `rotating_h2d` (the same step over rotating host batches with
-the image upload inside the timed region) and `cpu_baseline` (the oracle's restated Chainer CPU
-path timed on the host cores on BASELINE configs[0] in full, reported only).
+HIP-event timed inside the headline's steps).  A plain run does only that: it sets up, warms up,
+times the steps, writes --dump-outputs and prints the line.  `--full` adds every other measurement
+after the headline, each in runs of its own: the ROIAlign kernels in isolation, `rotating_h2d` (the
+same step over rotating host batches with the image upload inside the timed region), `fg_capped`,
+`trained_regime`, `device_targets`, `direct_head_forward`, `fp32_mfma`, `pipeline_h2d`, `r101` and
+`infer` (the other BASELINE workloads) and `cpu_baseline` (the oracle's restated Chainer CPU path
+timed on the host cores on BASELINE configs[0] in full, reported only).
 
 `--steps K` is the number of timed steps of the headline (`ms_per_step` = one of them);
 `--dump-outputs DIR` writes what the last of them computed as DIR/<name>.npy, so that two builds
@@ -613,7 +617,7 @@ def self_launch(args):
     raise SystemExit(subprocess.call(cmd, env=env))
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
@@ -676,25 +680,45 @@ def main():
                     help='developer: comma-separated mrcnn_set_tuning knobs, e.g. small_m_split=4')
     ap.add_argument('--bucket-mb', type=float, default=16.0,
                     help='gradient all-reduce bucket size (data-parallel runs)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, run every other measurement too: the ROIAlign kernels in '
+                         'isolation and the rotating_h2d, fg_capped, trained_regime, device_targets, '
+                         'direct_head_forward, fp32_mfma, pipeline_h2d, r101, infer and cpu_baseline legs '
+                         '(each can still be turned off by its own option; --gpus > 1: see --all-legs).  '
+                         'Default: the headline only')
     ap.add_argument('--all-legs', action='store_true',
-                    help='multi-GPU runs: also run the auxiliary single-GPU measurements (rotating_h2d, '
-                         'fg_capped, device_targets, direct_head_forward, fp32_mfma, pipeline_h2d); by default '
-                         'a run with --gpus > 1 times the headline region only')
+                    help='multi-GPU runs (implies --full): also run the auxiliary single-GPU measurements '
+                         '(rotating_h2d, fg_capped, device_targets, direct_head_forward, fp32_mfma, '
+                         'pipeline_h2d); with --full alone a run with --gpus > 1 adds the isolated ROIAlign '
+                         'kernels only')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help="after the headline's timed steps, write what its last step computed as "
                          'DIR/<name>.npy (train: the reported losses, and the parameters and momentum '
                          'buffers after the update; infer: the detections), at most 64 MB in all, '
                          'larger outputs as a fixed, seeded sample')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0 or args.repeats < 1:
         ap.error('--steps and --repeats must be >= 1 and --warmup >= 0')
+    if args.all_legs:
+        args.full = True
+    if not args.full:
+        # a plain run measures the headline and nothing else
+        args.rotate_batches = 0
+        args.pipeline_examples = 0
+        args.fg_capped = args.device_targets = args.direct_head_forward = args.fp32_mfma = False
+        args.extra_workloads = False
+        args.no_cpu_baseline = True
     if args.gpus > 1 and not args.all_legs:
         # the scaling runs need `value` per N; every auxiliary leg is one more place where eight
         # ranks must stay in step, and none of them says anything about scaling
         args.rotate_batches = 0
         args.pipeline_examples = 0
         args.fg_capped = args.device_targets = args.direct_head_forward = args.fp32_mfma = False
+    return args
 
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return self_launch(args)
     # stdout carries rank 0's ONE JSON line and nothing else: native libraries (gloo's
@@ -818,7 +842,7 @@ def main():
         # the last timed step's results, before any later measurement steps the model again
         write_outputs(args.dump_outputs, train_step_outputs(chain, opt))
     roi_iso = None
-    if not args.no_profile and 'sample_roi_indices' in chain.last_targets:
+    if args.full and not args.no_profile and 'sample_roi_indices' in chain.last_targets:
         roi_iso = roi_align_isolated(chain, device)
 
     # ---- second measurement: rotating host batches, image upload inside the timed region ----

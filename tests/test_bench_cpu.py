@@ -1,5 +1,6 @@
-"""bench.py pieces that run without a GPU: the power / clock sampler degrades to None fields, the
-multi-GPU default drops the auxiliary legs, and a run without a ROCm device fails loudly."""
+"""bench.py pieces that run without a GPU: the power / clock sampler degrades to None fields, a
+plain run drops every leg but the headline and --full restores them, the multi-GPU default drops the
+auxiliary legs, and a run without a ROCm device fails loudly."""
 import os
 import subprocess
 import sys
@@ -43,6 +44,29 @@ def test_smi_sampler_can_be_disabled_and_survives_a_library_without_the_symbols(
     with s:
         pass
     assert s.lib is None and s.summary()['power_w'] is None
+
+
+def _legs(args):
+    return dict(rotate=args.rotate_batches, pipeline=args.pipeline_examples, fg_capped=args.fg_capped,
+                device_targets=args.device_targets, direct=args.direct_head_forward, fp32=args.fp32_mfma,
+                extra=args.extra_workloads, cpu=not args.no_cpu_baseline)
+
+
+def test_plain_run_is_the_headline_only_and_full_restores_every_leg():
+    plain = bench.parse_args(['--steps', '3', '--warmup', '1'])
+    assert not plain.full and (plain.steps, plain.warmup) == (3, 1)
+    assert not any(_legs(plain).values())
+    full = bench.parse_args(['--full'])
+    assert full.full and _legs(full) == dict(rotate=4, pipeline=16, fg_capped=True, device_targets=True,
+                                             direct=True, fp32=True, extra=True, cpu=True)
+    # each leg's own switch still holds under --full
+    some = bench.parse_args(['--full', '--no-cpu-baseline', '--rotate-batches', '0', '--no-fp32-mfma'])
+    assert _legs(some) == dict(_legs(full), rotate=0, fp32=False, cpu=False)
+    # multi-GPU: --full adds no auxiliary leg, --all-legs implies --full and restores them
+    multi = bench.parse_args(['--gpus', '2', '--full'])
+    assert multi.full and not any(v for k, v in _legs(multi).items() if k not in ('extra', 'cpu'))
+    legs = bench.parse_args(['--gpus', '2', '--all-legs'])
+    assert legs.full and _legs(legs) == _legs(full)
 
 
 def test_multi_gpu_request_without_devices_is_refused():

@@ -1,5 +1,5 @@
 import sys, os, cProfile, pstats, threading
-sys.argv = ['bench.py', '--no-cpu-baseline', '--rotate-batches', '0', '--no-fg-capped', '--no-profile']
+sys.argv = ['bench.py', '--full', '--no-cpu-baseline', '--rotate-batches', '0', '--no-fg-capped', '--no-profile']
 sys.path.insert(0, os.environ['GRAFT_REPO_ROOT']); sys.path.insert(0, os.path.join(os.environ['GRAFT_REPO_ROOT'], 'tools'))
 import train_loop as TL
 orig = TL.TrainLoop._assemble

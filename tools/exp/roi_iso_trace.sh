@@ -1,6 +1,7 @@
 # developer: kernel-trace durations of the ROIAlign kernels over one short bench run (in-step launches first, then the isolated repetitions)
+R=$(cd "$(dirname "$0")/../.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d /tmp/rt -o rt -- python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --rotate-batches 0 --no-fg-capped --no-device-targets --no-direct-head-forward --no-split-bf16 --pipeline-examples 0 > /tmp/rt.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/rt -o rt -- python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --rotate-batches 0 --no-fg-capped --no-device-targets --no-direct-head-forward --no-split-bf16 --pipeline-examples 0 > /tmp/rt.log 2>&1
 python - <<'P'
 import csv, glob
 f = glob.glob('/tmp/rt/*kernel_trace.csv')[0]

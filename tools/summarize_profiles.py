@@ -1,9 +1,10 @@
-"""Copy the judged summaries of a gpurun profile collection into profiles/ (tracked)."""
+"""Copy the judged summaries of a profile collection (profile_out/, tools/collect_round_profiles.sh)
+into profiles/ (tracked)."""
 import collections, csv, json, os, shutil, sys
 tag = sys.argv[1]
 pmc_only = '--pmc-only' in sys.argv     # (on the GPU box, before the bench lines that cite the summary)
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-g, p = os.path.join(root, 'gpurun_out'), os.path.join(root, 'profiles')
+g, p = os.path.join(root, 'profile_out'), os.path.join(root, 'profiles')
 os.makedirs(p, exist_ok=True)
 if not pmc_only:
     shutil.copy(os.path.join(g, '%s_stats' % tag, '%s_kernel_stats.csv' % tag),
