@@ -108,6 +108,7 @@ SIGNATURES = {
     'mrcnn_smooth_l1': (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_f32, c_vp, c_vp, c_vp,
                                 c_vp]),
     'mrcnn_softmax': (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp]),
+    'mrcnn_observe_accumulate': (c_int, [ctypes.POINTER(c_vp), c_int, c_vp, c_vp]),
     'mrcnn_sgd_momentum_wd': (c_int, [c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32,
                                       c_vp]),
     'mrcnn_sgd_momentum_wd_ex': (c_int, [c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32,

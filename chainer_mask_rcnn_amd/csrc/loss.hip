@@ -373,3 +373,39 @@ extern "C" int mrcnn_smooth_l1(const float *pred, int ld, const int32_t *cls, co
                        gt_label, n, sigma2, (const Partials *)ws, parts, loss, gx);
     return mrcnn::check_launch("smooth_l1");
 }
+
+// ---- Loss observations of LogReport --------------------------------------------------------
+// chainer's reporter.Summary.add does `_x += value` with `value` a 0-d float32 device array:
+// a float32 running sum per key, in iteration order.  One launch per iteration, after the loss
+// kernels on the same stream: thread k adds key k's scalar to sums[k] (one fp32 add, no FMA
+// contraction possible), so the sums are bit-identical to a sequential float32 sum on the host.
+namespace {
+
+struct ObservePtrs {
+    const float *v[MRCNN_MAX_OBSERVED];
+};
+
+__global__ void __launch_bounds__(64) observe_accumulate_kernel(ObservePtrs p, int n,
+                                                                 float *__restrict__ sums)
+{
+    const int k = threadIdx.x;
+    if (k < n) sums[k] = sums[k] + *p.v[k];
+}
+
+}  // namespace
+
+extern "C" int mrcnn_observe_accumulate(const float *const *values, int n, float *sums,
+                                        void *stream)
+{
+    MRCNN_REQUIRE(n >= 0 && n <= MRCNN_MAX_OBSERVED, "observe_accumulate: n outside [0, 8]");
+    if (n == 0) return 0;
+    MRCNN_REQUIRE(values && sums, "observe_accumulate: null pointer");
+    ObservePtrs p = {};
+    for (int k = 0; k < n; ++k) {
+        MRCNN_REQUIRE(values[k], "observe_accumulate: null value pointer");
+        p.v[k] = values[k];
+    }
+    hipLaunchKernelGGL(observe_accumulate_kernel, dim3(1), dim3(64), 0, mrcnn::as_stream(stream),
+                       p, n, sums);
+    return mrcnn::check_launch("observe_accumulate");
+}

@@ -8,3 +8,4 @@ from .coco import COCOInstanceSegmentationDataset  # NOQA
 from .voc import VOC2012InstanceSegmentationDataset, SBDInstanceSegmentationDataset  # NOQA
 from .voc import VOC2012InstanceSeg, SBDInstanceSeg  # NOQA
 from .mask_rcnn import MaskRcnnDataset  # NOQA
+from .indexing_dataset import IndexingDataset  # NOQA

@@ -154,3 +154,27 @@ def softmax(x):
     _lib.call('mrcnn_softmax', _lib.ptr(x), x.stride(0), _lib.ptr(y), ncls, R, ncls,
               _lib.stream_ptr())
     return y
+
+
+MAX_OBSERVED = 8     # MRCNN_MAX_OBSERVED of include/mrcnn_hip.h
+
+
+def observe_accumulate(values, sums):
+    """``sums[k] = sums[k] + values[k]`` for each 0-dim float32 device tensor of ``values`` (at
+    most MAX_OBSERVED), one fp32 add per key in one launch on the current stream: chainer's
+    ``reporter.Summary.add`` (``_x += value``) for every reported scalar of an iteration, with no
+    read-back.  ``sums``: float32 device tensor of at least ``len(values)`` elements."""
+    import ctypes
+    n = len(values)
+    if n > MAX_OBSERVED:
+        raise ValueError('observe_accumulate: at most %d values, got %d' % (MAX_OBSERVED, n))
+    _lib.require_device(sums, *values)
+    if sums.dtype != torch.float32 or not sums.is_contiguous() or sums.numel() < n:
+        raise ValueError('observe_accumulate: sums must be a contiguous float32 tensor of >= %d '
+                         'elements' % n)
+    for v in values:
+        if v.dtype != torch.float32 or v.numel() != 1:
+            raise ValueError('observe_accumulate: values must be float32 scalars')
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[v.data_ptr() for v in values])
+    _lib.call('mrcnn_observe_accumulate', ptrs, n, _lib.ptr(sums), _lib.stream_ptr())
+    return sums

@@ -46,6 +46,23 @@ class _Deconvolution2D(torch.nn.Module):
 _BIN_STRIDE_POOLING = (functions.roi_align_2d, functions.roi_pooling_2d, functions.crop_and_resize)
 
 
+def _mask_std(initialW, chainer_shape):
+    """Standard deviation of the normal init of ``deconv6.W`` / ``mask.W`` for ``mask_initialW``:
+    None -> 0.01, a float -> that value, ``'he_normal'`` -> chainer's
+    ``HeNormal(fan_option='fan_out')`` (examples/train_common.py ``--initializer he_normal``),
+    ``sqrt(2 / fan_out)`` with chainer's fan rule on the CHAINER-layout shape of the array:
+    ``fan_out = shape[0] * prod(shape[2:])`` (2048 * 4 for the (2048, 256, 2, 2) deconvolution
+    filter, n_fg_class for the 1x1 mask convolution), whatever layout this package stores."""
+    if initialW is None:
+        return 0.01
+    if isinstance(initialW, str):
+        if initialW != 'he_normal':
+            raise ValueError('Unsupported mask_initialW: %r' % (initialW,))
+        fan_out = chainer_shape[0] * int(np.prod(chainer_shape[2:]))
+        return float(np.sqrt(2. / fan_out))
+    return float(initialW)
+
+
 class ResNetRoIHead(torch.nn.Module):
 
     mask_size = 14  # Size of the predicted mask.
@@ -60,15 +77,15 @@ class ResNetRoIHead(torch.nn.Module):
         self.cls_loc_score = _Linear(2048, n_fc)
         loc_std = 0.001 if loc_initialW is None else float(loc_initialW)
         score_std = 0.01 if score_initialW is None else float(score_initialW)
-        mask_std = 0.01 if mask_initialW is None else float(mask_initialW)
         with torch.no_grad():
             self.cls_loc_score.W[:4 * n_class].normal_(0., loc_std)
             self.cls_loc_score.W[4 * n_class:5 * n_class].normal_(0., score_std)
         self.cls_loc = _ConvView(self.cls_loc_score, 0, 4 * n_class)
         self.score = _ConvView(self.cls_loc_score, 4 * n_class, 5 * n_class)
         # 7 x 7 x 2048 -> 14 x 14 x 256 -> 14 x 14 x n_fg_class
-        self.deconv6 = _Deconvolution2D(2048, 256, mask_std)
-        self.mask = Convolution2D(256, n_class - 1, 1, std=mask_std)
+        self.deconv6 = _Deconvolution2D(2048, 256, _mask_std(mask_initialW, (2048, 256, 2, 2)))
+        self.mask = Convolution2D(256, n_class - 1, 1,
+                                  std=_mask_std(mask_initialW, (n_class - 1, 256, 1, 1)))
 
         self.n_class = n_class
         self.roi_size = roi_size
@@ -174,7 +191,13 @@ class MaskRCNNResNet(MaskRCNN):
                  loc_initialW=None, score_initialW=None, mask_initialW=None,
                  proposal_creator_params=dict(min_size=0, n_test_pre_nms=6000,
                                               n_test_post_nms=1000),
-                 pooling_func=functions.roi_align_2d, rpn_hidden=1024, roi_size=7):
+                 pooling_func=functions.roi_align_2d, rpn_hidden=1024, roi_size=7,
+                 imagenet_weights=None):
+        """``pretrained_model``: None (random init), the path of a snapshot ``.npz``, or
+        ``'imagenet'``: the backbone (res2..res4) and res5 of the head from chainer's ImageNet
+        ResNet weights (``imagenet_weights``, default chainer's download location;
+        serializers.load_imagenet_resnet), every other layer from its initialiser.
+        ``mask_initialW``: None, a float (std of a normal init) or ``'he_normal'``."""
         if n_layers == 50:
             extractor = ResNet50Extractor(remove_layers=['res5', 'fc6'])
         elif n_layers == 101:
@@ -199,6 +222,9 @@ class MaskRCNNResNet(MaskRCNN):
         super(MaskRCNNResNet, self).__init__(
             extractor, rpn, head, mean=mean, min_size=min_size, max_size=max_size)
 
-        if pretrained_model:
+        if pretrained_model == 'imagenet':
+            from ..serializers import load_imagenet_resnet
+            load_imagenet_resnet(imagenet_weights, self, n_layers=n_layers)
+        elif pretrained_model:
             from ..serializers import load_npz
             load_npz(pretrained_model, self)

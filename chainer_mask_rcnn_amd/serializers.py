@@ -180,3 +180,90 @@ def load_detectron(blobs_or_path, model, n_layers=None):
         n_layers = 101 if len(model.extractor.res4._names) == 23 else 50
     arrays = detectron_to_chainer(blobs, n_layers, model.rpn.n_anchor, model.head.n_class)
     return load_arrays(arrays, model)
+
+
+# ---------------------------------------------------------------------------------------------
+# chainer's ImageNet ResNet (ResNet-50-model.npz / ResNet-101-model.npz of ResNet50Layers /
+# ResNet101Layers) -> model: what the reference's MaskRCNNResNet does with
+# pretrained_model='auto' in its extractor and head (models/resnet_extractor.py:16-59,
+# models/mask_rcnn_resnet.py:152-166):
+#   conv1/W[:, ::-1]                 BGR -> RGB input channels; conv1/b copied
+#   bn*/{gamma,beta,avg_mean,avg_var} folded into the AffineChannel2D that replaces the BN:
+#                                    W = gamma / sqrt(avg_var + 1e-5), b = beta - avg_mean * W
+#   res2..res4                       -> extractor/res{S}/...,  res5 -> head/res5/...
+#   fc6/*, bn*/N                     ignored
+# The RPN, cls_loc / score, deconv6 and mask keep their initialisers.
+# ---------------------------------------------------------------------------------------------
+BN_EPS = 1e-5     # _get_affine_from_bn (not chainer's BatchNormalization default of 2e-5)
+
+
+def default_imagenet_path(n_layers):
+    """chainer's download location of the ImageNet ResNet weights:
+    ``$CHAINER_DATASET_ROOT/pfnet/chainer/models/ResNet-{50,101}-model.npz``."""
+    import os
+    root = os.environ.get('CHAINER_DATASET_ROOT',
+                          os.path.join(os.path.expanduser('~'), '.chainer', 'dataset'))
+    return os.path.join(root, 'pfnet', 'chainer', 'models', 'ResNet-%d-model.npz' % n_layers)
+
+
+def fold_bn(data, prefix):
+    """(W, b) of the AffineChannel2D equivalent to the BN ``prefix`` of a chainer npz, in float32
+    as the reference computes it."""
+    gamma = np.asarray(data[prefix + '/gamma'], np.float32)
+    beta = np.asarray(data[prefix + '/beta'], np.float32)
+    mean = np.asarray(data[prefix + '/avg_mean'], np.float32)
+    var = np.asarray(data[prefix + '/avg_var'], np.float32)
+    W = gamma / np.sqrt(var + np.float32(BN_EPS))
+    return W, beta - mean * W
+
+
+def imagenet_resnet_to_chainer(data, model):
+    """{chainer ResNet key: ndarray} -> {this model's chainer key: ndarray} for the backbone and
+    res5 (the block names are taken from ``model``, so a depth mismatch is a KeyError)."""
+    out = {}
+
+    def take(key):
+        if key not in data:
+            raise KeyError('ImageNet ResNet weights have no %r (ResNet-50 weights for a '
+                           'ResNet-101 model?)' % key)
+        return np.asarray(data[key], np.float32)
+
+    out['extractor/conv1/W'] = np.ascontiguousarray(take('conv1/W')[:, ::-1])
+    out['extractor/conv1/b'] = take('conv1/b')
+    take('bn1/gamma')
+    out['extractor/bn1/W'], out['extractor/bn1/b'] = fold_bn(data, 'bn1')
+    stages = [('extractor', 'res2', model.extractor.res2), ('extractor', 'res3', model.extractor.res3),
+              ('extractor', 'res4', model.extractor.res4), ('head', 'res5', model.head.res5)]
+    for owner, stage, block in stages:
+        for name in block._names:
+            n_conv = 4 if name == 'a' else 3
+            for k in range(1, n_conv + 1):
+                src = '%s/%s' % (stage, name)
+                dst = '%s/%s/%s' % (owner, stage, name)
+                out['%s/conv%d/W' % (dst, k)] = take('%s/conv%d/W' % (src, k))
+                take('%s/bn%d/gamma' % (src, k))
+                out['%s/bn%d/W' % (dst, k)], out['%s/bn%d/b' % (dst, k)] = \
+                    fold_bn(data, '%s/bn%d' % (src, k))
+        extra = '%s/b%d/conv1/W' % (stage, len(block._names))
+        if extra in data:
+            raise ValueError('ImageNet ResNet weights have more %s blocks than the model (%r): '
+                             'ResNet-101 weights for a ResNet-50 model?' % (stage, extra))
+    return out
+
+
+def load_imagenet_resnet(path, model, n_layers=None):
+    """Fill the backbone (conv1, bn1, res2..res4) and res5 of a MaskRCNNResNet from chainer's
+    ImageNet ResNet weights; every other parameter is left as it is.  ``path`` None: chainer's
+    location (``default_imagenet_path``).  There is no download: a missing file is an error."""
+    import os
+    if n_layers is None:
+        n_layers = 101 if len(model.extractor.res4._names) == 23 else 50
+    if path is None:
+        path = default_imagenet_path(n_layers)
+    if not os.path.exists(path):
+        raise IOError('ImageNet ResNet-%d weights not found at %s (chainer\'s ResNet-%d-model.npz; '
+                      'this package does not download them — pass imagenet_weights= / '
+                      '--imagenet-weights or place the file there)' % (n_layers, path, n_layers))
+    with np.load(path) as data:
+        arrays = imagenet_resnet_to_chainer(data, model)
+    return load_arrays(arrays, model, strict=False)

@@ -7,3 +7,4 @@ from .geometry import (label2instance_boxes, instance_boxes2label, mask_to_bbox,
                        get_mask_overlap)
 from .visualizations import (draw_instance_bboxes, draw_instance_boxes, label_colormap,
                              get_tile_image)
+from ._shutil import git_hash

@@ -476,6 +476,13 @@ int mrcnn_smooth_l1(const float *pred, int ld, const int32_t *cls,
 /* F.softmax(x) row-wise (models/mask_rcnn.py:208) */
 int mrcnn_softmax(const float *x, int ldx, float *y, int ldy, int R, int ncls,
                   void *stream);
+/* Replaces chainer's reporter.Summary.add (`_x += value`) for the trainer's LogReport of the
+ * reported losses (models/mask_rcnn_train_chain.py:182-188): sums[k] = sums[k] + *values[k]
+ * for k < n, one fp32 add per key, one launch on `stream` (after the loss kernels), no host
+ * synchronisation.  values: HOST array of n device pointers to float scalars, passed to the
+ * kernel by value; sums: device float[n].  0 <= n <= MRCNN_MAX_OBSERVED. */
+#define MRCNN_MAX_OBSERVED 8
+int mrcnn_observe_accumulate(const float *const *values, int n, float *sums, void *stream);
 
 /* ---- Optimizer (chainer MomentumSGD + WeightDecay, examples/train_common.py:176-180) */
 /* g += wd*p; v = momentum*v - lr*g; p += v, over one flat arena of n floats.

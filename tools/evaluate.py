@@ -6,6 +6,7 @@ examples/evaluate_common.py + examples/coco/evaluate.py.
     python tools/evaluate.py --synthetic 16            # no dataset: random weights, synthetic images
     python tools/evaluate.py --dataset sbd --sbd-root DIR --snapshot snapshot_model.npz
     python tools/evaluate.py --synthetic 4 --vis       # also writes iteration=best.jpg
+    python tools/evaluate.py --log-dir logs/20261016_120000 [--coco-root DIR]   # a tools/train.py run
 
 Runs the evaluator (predicted masks stay on the device; extensions/), prints the report and
 the seconds per image spent in prediction and in evaluation, and writes the result as YAML (or
@@ -69,7 +70,14 @@ def main():
     ap.add_argument('--vis', action='store_true',
                     help='also write the visual report of the first 9 images as iteration=best.jpg '
                          'next to the result file (examples/evaluate_common.py)')
+    ap.add_argument('--log-dir', default=None,
+                    help='a tools/train.py output directory: the model from its params.yaml, the '
+                         'weights from its snapshot_model.npz (examples/evaluate_common.py); writes '
+                         'snapshot_model.npz.eval_result.yaml and iteration=best.jpg there')
+    ap.add_argument('--custom-root', default=None, help='VOC-like directory (--log-dir of a custom run)')
     args = ap.parse_args()
+    if args.log_dir:
+        return evaluate_log_dir(args)
     voc = args.dataset in ('voc', 'sbd') and not args.synthetic
     if args.evaluator is None:
         args.evaluator = 'voc' if voc else 'coco'
@@ -165,6 +173,69 @@ def main():
             vis, model, label_names=class_names, file_name='iteration=%s.jpg', copy_latest=False)
         visualizer(trainer=DummyTrainer())
         print('Saved visualization:', os.path.join(DummyTrainer.out, 'iteration=best.jpg'))
+
+
+def evaluate_log_dir(args):
+    """examples/evaluate_common.py: the test split of the run's dataset (dataset roots from the
+    command line, else from params.yaml), the model as params.yaml describes it with the weights of
+    snapshot_model.npz, the visual report of the first 9 test images as iteration=best.jpg and the
+    evaluator's result as snapshot_model.npz.eval_result.yaml, both in the log directory."""
+    import yaml
+    import chainer_mask_rcnn_amd as cmr
+    import train as train_tool
+    with open(os.path.join(args.log_dir, 'params.yaml')) as f:
+        params = yaml.safe_load(f)
+    print('Training config:')
+    pprint.pprint(params)
+    run = argparse.Namespace(**params)
+    for key in ('coco_root', 'sbd_root', 'custom_root'):
+        if getattr(args, key, None):
+            setattr(run, key, getattr(args, key))
+    test_data, evaluator_type = train_tool.test_dataset(run)
+    class_names = list(params['class_names'])
+    pretrained_model = os.path.join(args.log_dir, 'snapshot_model.npz')
+    print('Using pretrained_model:', pretrained_model)
+    dev = torch.device('cuda:0')
+    model = cmr.models.MaskRCNNResNet(
+        n_layers=int(params['model'][len('resnet'):]), n_fg_class=len(class_names),
+        pretrained_model=pretrained_model,
+        pooling_func=getattr(cmr.functions, POOLING_FUNCS[params['pooling_func']]),
+        anchor_scales=tuple(params['anchor_scales']),
+        mean=tuple(params.get('mean', (123.152, 115.903, 103.063))),
+        min_size=params['min_size'], max_size=params['max_size'],
+        roi_size=params['roi_size']).to(dev)
+    model.eval()
+    transform = cmr.datasets.MaskRCNNTransform(model, train=False)
+
+    class DummyTrainer(object):
+        class DummyUpdater(object):
+            iteration = 'best'
+        updater = DummyUpdater()
+        out = args.log_dir
+
+    print('Visualizing...')
+    vis = ([transform(test_data[j])] for j in range(min(9, len(test_data))))
+    visualizer = cmr.extensions.InstanceSegmentationVisReport(
+        vis, model, label_names=class_names, file_name='iteration=%s.jpg', copy_latest=False)
+    visualizer(trainer=DummyTrainer())
+    print('Saved visualization:', os.path.join(args.log_dir, 'iteration=best.jpg'))
+
+    print('Evaluating...')
+    n = len(test_data) if not args.limit else min(args.limit, len(test_data))
+    batches = ([transform(test_data[j])] for j in range(n))
+    if evaluator_type == 'voc':
+        evaluator = cmr.extensions.InstanceSegmentationVOCEvaluator(
+            batches, model, use_07_metric=True, label_names=class_names)
+    else:
+        evaluator = cmr.extensions.InstanceSegmentationCOCOEvaluator(
+            batches, model, label_names=class_names)
+    result = {k: float(v) for k, v in evaluator.evaluate().items()}
+    yaml_file = pretrained_model + '.eval_result.yaml'
+    with open(yaml_file, 'w') as f:
+        yaml.safe_dump(result, f, default_flow_style=False)
+    print('Saved evaluation:', yaml_file)
+    pprint.pprint(result)
+    return result
 
 
 if __name__ == '__main__':

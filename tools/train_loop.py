@@ -204,6 +204,12 @@ class TrainLoop(object):
                 report(self, losses[-1])
         return losses
 
+    def settle(self):
+        """Wait until the worker has assembled the pending batch, without taking it: afterwards
+        nothing runs on the worker (nor draws from Python's `random`) until the next step."""
+        if self._pending is not None:
+            self._pending.result()
+
     def close(self):
         if self._pool is not None:
             if self._pending is not None:
@@ -257,12 +263,22 @@ VOC_MODEL = dict(n_fg_class=20, min_size=600, max_size=1000, anchor_scales=(4, 8
 def build_voc_trainer(n_layers, device, lr_batch, defer=5):
     """``bench.build_trainer`` (which is fixed to the COCO settings) with examples/voc/train.py's
     model: the same optimizer, frozen layers, synthetic-weight scaling and deferred gradients."""
+    import chainer_mask_rcnn_amd as cmr
+    model = cmr.models.MaskRCNNResNet(n_layers=n_layers, pretrained_model=None, roi_size=14,
+                                      pooling_func=cmr.functions.roi_align_2d, **VOC_MODEL)
+    chain, opt = setup_training(model, device, lr_batch, defer=defer)
+    return model, chain, opt, None
+
+
+def setup_training(model, device, lr_batch, defer=5, synthetic_weights=True):
+    """Train chain and optimizer of examples/train_common.py:171-190 for ``model``: MomentumSGD
+    (lr 0.00125 * batch, momentum 0.9) + WeightDecay(1e-4), conv1 / bn1 / res2 and every
+    AffineChannel2D frozen; ``synthetic_weights``: bench.stabilise_synthetic_weights (random
+    init); ``defer``: the res5 weight gradients held back into the next step (optimizers.py)."""
     import bench
     import chainer_mask_rcnn_amd as cmr
     from chainer_mask_rcnn_amd import optimizers
     from chainer_mask_rcnn_amd.links import AffineChannel2D
-    model = cmr.models.MaskRCNNResNet(n_layers=n_layers, pretrained_model=None, roi_size=14,
-                                      pooling_func=cmr.functions.roi_align_2d, **VOC_MODEL)
     chain = cmr.models.MaskRCNNTrainChain(model).to(device)
     chain.train()
     opt = optimizers.MomentumSGD(lr=0.00125 * lr_batch, momentum=0.9)
@@ -273,13 +289,14 @@ def build_voc_trainer(n_layers, device, lr_batch, defer=5):
     for m in chain.modules():
         if isinstance(m, AffineChannel2D):
             optimizers.disable_update(m)
-    bench.stabilise_synthetic_weights(model)
+    if synthetic_weights:
+        bench.stabilise_synthetic_weights(model)
     if defer > 0:
         a, b1, b2 = model.head.res5.a, model.head.res5.b1, model.head.res5.b2
         opt.defer_weight_gradients([a.conv2.W, a.conv3.W, b1.conv2.W, b1.conv1.W, b1.conv3.W,
                                     b2.conv2.W, b2.conv1.W, b2.conv3.W, a.conv1.W,
                                     a.conv4.W][:defer])
-    return model, chain, opt, None
+    return chain, opt
 
 
 def build(dataset, n_layers=50, device='cuda:0', batch_size=2, seed=0, defer=5, prefetch=True,
