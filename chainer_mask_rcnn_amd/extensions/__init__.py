@@ -1,4 +1,5 @@
 # flake8: noqa
 from .instance_segmentation_evaluators import (InstanceSegmentationVOCEvaluator,
-                                               InstanceSegmentationCOCOEvaluator)
+                                               InstanceSegmentationCOCOEvaluator,
+                                               create_multi_node_evaluator)
 from .instance_segmentation_vis_report import InstanceSegmentationVisReport

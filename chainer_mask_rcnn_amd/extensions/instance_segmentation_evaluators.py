@@ -107,7 +107,10 @@ class InstanceSegmentationVOCEvaluator(_InstanceSegmentationEvaluator):
         self.use_07_metric = use_07_metric
 
     def evaluate(self):
-        counts, pred_labels, pred_scores, gts = self.collect()
+        return self.evaluate_collected(*self.collect())
+
+    def evaluate_collected(self, counts, pred_labels, pred_scores, gts):
+        """The host half of ``evaluate``: matching and AP from ``collect()``'s records."""
         gt_labels = [g[1] for g in gts]
         gt_difficults = None
         if gts and len(gts[0]) == 4:
@@ -124,7 +127,10 @@ class InstanceSegmentationCOCOEvaluator(_InstanceSegmentationEvaluator):
     the sorted labels present, by label: DESIGN.md section 9)."""
 
     def evaluate(self):
-        counts, pred_labels, pred_scores, gts = self.collect()
+        return self.evaluate_collected(*self.collect())
+
+    def evaluate_collected(self, counts, pred_labels, pred_scores, gts):
+        """The host half of ``evaluate``: matching and AP from ``collect()``'s records."""
         gt_labels = [g[1] for g in gts]
         gt_crowdeds = gt_areas = None
         if gts and len(gts[0]) == 5:
@@ -133,6 +139,60 @@ class InstanceSegmentationCOCOEvaluator(_InstanceSegmentationEvaluator):
         result = matching.coco_results(matching.coco_evaluate_from_counts(
             counts, pred_labels, pred_scores, gt_labels, gt_crowdeds, gt_areas))
         return self._observation(coco_report(result, self.label_names))
+
+
+def strip_records(counts, pred_labels, pred_scores, gts):
+    """``collect()``'s records without what the host matching never reads: each ground-truth
+    tuple keeps its length and its labels (and difficult / crowd / area) but loses the boxes and
+    masks, which are by far the largest part."""
+    gts = [(None, g[1], None) + tuple(g[3:]) for g in gts]
+    return list(counts), list(pred_labels), list(pred_scores), gts
+
+
+def merge_records(per_rank):
+    """Concatenate the ranks' records (each ``(counts, pred_labels, pred_scores, gts)``) in rank
+    order, which is the test set's order when rank i holds the i-th contiguous shard."""
+    merged = ([], [], [], [])
+    for records in per_rank:
+        for out, part in zip(merged, records):
+            out.extend(part)
+    return merged
+
+
+def gather_records(records, group=None):
+    """Every rank's stripped records, merged in rank order, on every rank.  They travel on the
+    control plane (pickled into uint8 CPU tensors over gloo, parallel.all_gather_bytes)."""
+    from .. import parallel
+    return merge_records(parallel.all_gather_object_cpu(strip_records(*records), group))
+
+
+class _MultiNodeEvaluator(object):
+    """See create_multi_node_evaluator."""
+
+    def __init__(self, evaluator, group=None):
+        self.evaluator, self.group = evaluator, group
+
+    def __getattr__(self, name):
+        return getattr(self.evaluator, name)
+
+    def __call__(self, trainer=None):
+        return self.evaluate()
+
+    def evaluate(self):
+        records = gather_records(self.evaluator.collect(), self.group)
+        return self.evaluator.evaluate_collected(*records)
+
+
+def create_multi_node_evaluator(evaluator, group=None):
+    """chainermn.create_multi_node_evaluator's role for the instance-segmentation evaluators, with
+    an exact result: each rank runs ``collect()`` (the device part) on its own test shard, the
+    stripped records of all ranks are gathered in rank order and every rank runs the unchanged
+    host matching over all of them.  Every rank gets the same observation, the one a single
+    evaluator produces over the concatenated shards (chainermn averages the ranks' observations
+    instead, which is not the test set's mAP).  Batching pads images, so a prediction depends on
+    the images of its batch: the statement holds exactly when the test batches are the same,
+    e.g. with batch size 1."""
+    return _MultiNodeEvaluator(evaluator, group)
 
 
 def voc_report(ap, label_names=None):

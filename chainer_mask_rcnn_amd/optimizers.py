@@ -210,6 +210,10 @@ class MomentumSGD(object):
         self.launch_pending()
         self.join_pending()
 
+    def has_pending(self):
+        """Held-back work not yet launched (under data parallelism its launch is a collective)."""
+        return self._pending is not None
+
     def _build(self):
         never, affine = _gradient_free_parameters(self.target)
         seen, params = set(), []

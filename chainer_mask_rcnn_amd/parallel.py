@@ -451,3 +451,42 @@ def init_from_env(backend=None):
             torch.cuda.set_device(local)
         dist.init_process_group(backend, rank=rank, world_size=world)
     return rank, world, local
+
+
+# ---------------------------------------------------------------------------------------------
+# Control-plane objects: host data between ranks at log / evaluation boundaries
+# ---------------------------------------------------------------------------------------------
+def all_gather_bytes(payload, group=None):
+    """Every rank's ``payload`` (bytes), in rank order, over the process group's CPU backend
+    (gloo): the sizes first, then the payloads padded to the largest as uint8 CPU tensors.  CPU
+    tensors never take torch's nccl binding on a ``cpu:gloo,cuda:nccl`` group."""
+    world = dist.get_world_size(group)
+    size = torch.tensor([len(payload)], dtype=torch.int64)
+    sizes = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
+    dist.all_gather(sizes, size, group=group)
+    sizes = [int(s.item()) for s in sizes]
+    buf = torch.zeros(max(sizes), dtype=torch.uint8)
+    if payload:
+        buf[:len(payload)] = torch.frombuffer(bytearray(payload), dtype=torch.uint8)
+    bufs = [torch.zeros(max(sizes), dtype=torch.uint8) for _ in range(world)]
+    dist.all_gather(bufs, buf, group=group)
+    return [bytes(b[:n].numpy().tobytes()) for b, n in zip(bufs, sizes)]
+
+
+def all_gather_object_cpu(obj, group=None):
+    """``[obj of rank 0, obj of rank 1, ...]`` on every rank (pickled, all_gather_bytes)."""
+    import pickle
+    return [pickle.loads(b) for b in all_gather_bytes(pickle.dumps(obj, protocol=4), group)]
+
+
+def broadcast_object_cpu(obj, src=0, group=None):
+    """Rank ``src``'s ``obj`` on every rank (pickled, as uint8 CPU tensors over gloo)."""
+    import pickle
+    payload = pickle.dumps(obj, protocol=4) if dist.get_rank(group) == src else b''
+    size = torch.tensor([len(payload)], dtype=torch.int64)
+    dist.broadcast(size, src=src, group=group)
+    buf = torch.zeros(int(size.item()), dtype=torch.uint8)
+    if payload:
+        buf[:] = torch.frombuffer(bytearray(payload), dtype=torch.uint8)
+    dist.broadcast(buf, src=src, group=group)
+    return pickle.loads(buf.numpy().tobytes())

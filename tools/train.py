@@ -9,9 +9,22 @@ custom_dataset}/train.py, on tools/train_loop.py's loop and tools/trainer.py's T
 writes ``<logs-dir>/<YYYYmmdd_HHMMSS>/``: params.yaml, log (JSON), loss.png, accuracy.png,
 visualizations/, and snapshot_model.npz at the best ``validation/main/map``; read it back with
 ``tools/evaluate.py --log-dir`` and summarise runs with ``tools/summarize_logs.py``.
-One device only: data-parallel training (world size > 1) is refused.
+
+Data-parallel training (examples/train_common.py's ChainerMN set-up) is ``--multi-node`` under a
+launcher, one process per GPU:
+
+    torchrun --standalone --nproc-per-node 8 tools/train.py --multi-node --dataset voc --sbd-root DIR
+    mpirun -n 4 python tools/train.py --multi-node ...      # single node: Open MPI's variables
+
+The global batch is ``--batch-size-per-gpu`` x world size and the lr 0.00125 x global batch.  Every
+rank trains on its shard of the training set (datasets.scatter_dataset, equal lengths, shuffled
+with the run's seed), gradients are averaged by parallel.DataParallelGradSync, evaluation is
+sharded and exact (extensions.create_multi_node_evaluator), the logged losses are means over all
+ranks, and only rank 0 writes the run directory and prints.  Without --multi-node a world size
+above 1 is refused, and --multi-node is refused without a launcher's environment.
 """
 import argparse
+import collections
 import datetime
 import os
 import os.path as osp
@@ -43,7 +56,9 @@ def parse_args(argv=None):
                     help='epochs (180k iterations of batch 8 on COCO train+valminusminival)')
     ap.add_argument('--batch-size-per-gpu', type=int, default=1)
     ap.add_argument('--multi-node', action='store_true',
-                    help='data-parallel training: not supported (refused)')
+                    help='data-parallel training, one process per GPU, under torchrun '
+                         '(RANK / WORLD_SIZE / LOCAL_RANK) or mpirun (OMPI_COMM_WORLD_*); the global '
+                         'batch is --batch-size-per-gpu x world size')
     # this driver
     ap.add_argument('--dataset', choices=['coco', 'voc', 'custom', 'synthetic'], default='coco')
     ap.add_argument('--coco-root', default=None, help='COCO-layout directory')
@@ -64,10 +79,80 @@ def parse_args(argv=None):
     return ap.parse_args(argv)
 
 
-def world_size(args):
-    if args.multi_node:
-        return 2
-    return int(os.environ.get('WORLD_SIZE', '1') or 1)
+OMPI_TO_TORCH = (('OMPI_COMM_WORLD_RANK', 'RANK'), ('OMPI_COMM_WORLD_SIZE', 'WORLD_SIZE'),
+                 ('OMPI_COMM_WORLD_LOCAL_RANK', 'LOCAL_RANK'),
+                 ('OMPI_COMM_WORLD_LOCAL_SIZE', 'LOCAL_WORLD_SIZE'))
+
+
+def torch_env_from_ompi(environ):
+    """The torch launcher variables an Open MPI launch implies (``mpirun -n N``: one node,
+    rendezvous on 127.0.0.1), or {} where RANK is already set or Open MPI's are not."""
+    if environ.get('RANK') or not environ.get('OMPI_COMM_WORLD_RANK'):
+        return {}
+    env = {dst: environ[src] for src, dst in OMPI_TO_TORCH if environ.get(src)}
+    env.setdefault('LOCAL_RANK', env['RANK'])
+    if 'MASTER_ADDR' not in environ:
+        env['MASTER_ADDR'] = '127.0.0.1'
+    if 'MASTER_PORT' not in environ:
+        env['MASTER_PORT'] = '29500'
+    return env
+
+
+def world_size(environ=None):
+    environ = os.environ if environ is None else environ
+    return int(environ.get('WORLD_SIZE', '1') or 1)
+
+
+def launch_error(args, environ):
+    """Why this launch is refused, or None."""
+    if not args.multi_node and world_size(environ) > 1:
+        return ('tools/train.py: world size %d is not supported without --multi-node (launch one '
+                'process per GPU with --multi-node for data-parallel training)\n'
+                % world_size(environ))
+    if args.multi_node and not environ.get('RANK'):
+        return ('tools/train.py: --multi-node is not supported without a launcher (torchrun / '
+                'mpirun) environment: RANK / WORLD_SIZE or OMPI_COMM_WORLD_* are not set\n')
+    return None
+
+
+class Comm(collections.namedtuple('Comm', 'rank world local n_node device')):
+    """Where this process trains: its rank, the world size, the local rank, the number of hosts
+    and the device."""
+
+    @property
+    def parallel(self):
+        return self.world > 1
+
+    def gather(self, obj):
+        """Every rank's ``obj`` in rank order (the control plane: gloo, CPU tensors)."""
+        from chainer_mask_rcnn_amd import parallel
+        return parallel.all_gather_object_cpu(obj)
+
+    def broadcast(self, obj):
+        if not self.parallel:
+            return obj
+        from chainer_mask_rcnn_amd import parallel
+        return parallel.broadcast_object_cpu(obj, src=0)
+
+    def close(self):
+        import torch.distributed as dist
+        if self.parallel and dist.is_initialized():
+            dist.destroy_process_group()
+
+
+def setup_comm(args):
+    """Join the process group (``--multi-node``: parallel.init_from_env, which puts every rank on
+    device 0 under MRCNN_DP_REHEARSAL=1) and select the rank's device."""
+    import torch
+    if not args.multi_node:
+        return Comm(0, 1, 0, 1, torch.device('cuda:0'))
+    from chainer_mask_rcnn_amd import parallel
+    rank, world, local = parallel.init_from_env()
+    local_world = int(os.environ.get('LOCAL_WORLD_SIZE', str(world)) or world)
+    dev = torch.device('cuda', local)
+    if world > 1:
+        torch.cuda.set_device(dev)
+    return Comm(rank, world, local, max(1, world // local_world), dev)
 
 
 COCO_MODEL = dict(min_size=800, max_size=1333, anchor_scales=(2, 4, 8, 16, 32))
@@ -110,12 +195,103 @@ def datasets(args):
     return train_data, test_data, SYNTHETIC_CLASS_NAMES, COCO_MODEL, evaluator_type
 
 
+def configure(args, comm, class_names, settings, now=None):
+    """The run's derived settings (examples/train_common.py:96-136): seed, run directory (rank
+    0's clock, broadcast), n_gpu / n_node, global batch, lr, lr steps and the model settings;
+    then the seeds."""
+    import torch
+    args.seed = 0
+    if comm.rank == 0:
+        now = now or datetime.datetime.now()
+        args.timestamp = now.isoformat()
+        args.out = osp.join(args.logs_dir, now.strftime('%Y%m%d_%H%M%S'))
+    args.timestamp, args.out = comm.broadcast((getattr(args, 'timestamp', None),
+                                               getattr(args, 'out', None)))
+    args.n_node, args.n_gpu = comm.n_node, comm.world
+    args.batch_size = args.batch_size_per_gpu * args.n_gpu
+    args.lr = 0.00125 * args.batch_size
+    args.weight_decay = 0.0001
+    args.step_size = [(120e3 / 180e3) * args.max_epoch, (160e3 / 180e3) * args.max_epoch]
+    args.class_names = tuple(str(n) for n in class_names)
+    args.min_size, args.max_size = settings['min_size'], settings['max_size']
+    args.anchor_scales = settings['anchor_scales']
+    args.mean = (123.152, 115.903, 103.063)
+
+    random.seed(args.seed)
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+
+
+def build_model(args, weights, **kwargs):
+    """MaskRCNNResNet of the run (``kwargs``: further constructor arguments)."""
+    import chainer_mask_rcnn_amd as cmr
+    pooling_func = getattr(cmr.functions, train_loop.POOLING_FUNCS[args.pooling_func])
+    mask_initialW = 0.01 if args.initializer == 'normal' else 'he_normal'
+    return cmr.models.MaskRCNNResNet(
+        n_layers=int(args.model[len('resnet'):]), n_fg_class=len(args.class_names),
+        pooling_func=pooling_func, anchor_scales=args.anchor_scales, roi_size=args.roi_size,
+        min_size=args.min_size, max_size=args.max_size, mask_initialW=mask_initialW,
+        mean=args.mean, pretrained_model='imagenet' if weights else None,
+        imagenet_weights=weights, **kwargs)
+
+
+Run = collections.namedtuple('Run', 'trainer loop chain optimizer evaluator train test')
+
+
+def assemble(args, comm, model, train_data, test_data, evaluator_type, synthetic_weights,
+             print_out=sys.stdout, **intervals):
+    """Train chain, optimizer (with the gradient sync under data parallelism), the rank's shards
+    of the data, loop, evaluator and the trainer with the reference's extensions; ``intervals``:
+    eval_interval / log_interval / plot_interval / print_interval of
+    trainer.extend_reference_set.  Returns a Run; ``trainer.run()`` trains."""
+    import chainer_mask_rcnn_amd as cmr
+    make_sync = None
+    if comm.parallel:
+        from chainer_mask_rcnn_amd import parallel
+
+        def make_sync(opt):
+            return parallel.DataParallelGradSync(opt)
+    chain, opt = train_loop.setup_training(model, comm.device, args.batch_size,
+                                           synthetic_weights=synthetic_weights,
+                                           make_sync=make_sync)
+
+    # examples/train_common.py:200-205: scattered train / test data
+    train_data = cmr.datasets.scatter_dataset(train_data, comm.rank, comm.world, shuffle=True,
+                                              seed=args.seed)
+    test_data = cmr.datasets.scatter_dataset(test_data, comm.rank, comm.world,
+                                             force_equal_length=False)
+    train = train_loop.TransformDataset(train_data, cmr.datasets.MaskRCNNTransform(model))
+    test = train_loop.TransformDataset(test_data, cmr.datasets.MaskRCNNTransform(model, train=False))
+    loop = train_loop.TrainLoop(train_loop.SerialIterator(train, args.batch_size_per_gpu),
+                                chain, opt, comm.device)
+    test_iter = train_loop.SerialIterator(test, args.batch_size_per_gpu, shuffle=False)
+    if evaluator_type == 'voc':
+        evaluator = cmr.extensions.InstanceSegmentationVOCEvaluator(
+            test_iter, model, use_07_metric=True, label_names=args.class_names)
+    else:
+        evaluator = cmr.extensions.InstanceSegmentationCOCOEvaluator(
+            test_iter, model, label_names=args.class_names)
+    if comm.parallel:
+        evaluator = cmr.extensions.create_multi_node_evaluator(evaluator)
+
+    args.git_hash = cmr.utils.git_hash(__file__)
+    args.hostname = socket.gethostname()
+    params = {k: v for k, v in vars(args).items()}
+    tr = T.Trainer(loop, (args.max_epoch, 'epoch'), out=args.out if comm.rank == 0 else None)
+    T.extend_reference_set(tr, model, evaluator=evaluator, vis_iterator=test_iter,
+                           class_names=args.class_names, step_size=args.step_size,
+                           params=params, plot=not args.no_plot,
+                           print_out=print_out if comm.rank == 0 else None, rank=comm.rank,
+                           gather=comm.gather if comm.parallel else None, **intervals)
+    return Run(tr, loop, chain, opt, evaluator, train_data, test_data)
+
+
 def main(argv=None):
     args = parse_args(argv)
-    if world_size(args) > 1:
-        sys.stderr.write('tools/train.py trains on one device: world size %d is not supported '
-                         '(data-parallel training is not implemented in this driver)\n'
-                         % world_size(args))
+    os.environ.update(torch_env_from_ompi(os.environ))
+    err = launch_error(args, os.environ)
+    if err:
+        sys.stderr.write(err)
         return 2
     weights = args.imagenet_weights
     n_layers = int(args.model[len('resnet'):])
@@ -131,63 +307,22 @@ def main(argv=None):
     if args.dataset == 'synthetic':
         weights = None
 
-    import torch
-    import chainer_mask_rcnn_amd as cmr
-    train_data, test_data, class_names, settings, evaluator_type = datasets(args)
-
-    args.seed = 0
-    now = datetime.datetime.now()
-    args.timestamp = now.isoformat()
-    args.out = osp.join(args.logs_dir, now.strftime('%Y%m%d_%H%M%S'))
-    args.n_node, args.n_gpu = 1, 1
-    args.batch_size = args.batch_size_per_gpu * args.n_gpu
-    args.lr = 0.00125 * args.batch_size
-    args.weight_decay = 0.0001
-    args.step_size = [(120e3 / 180e3) * args.max_epoch, (160e3 / 180e3) * args.max_epoch]
-    args.class_names = tuple(str(n) for n in class_names)
-    args.min_size, args.max_size = settings['min_size'], settings['max_size']
-    args.anchor_scales = settings['anchor_scales']
-    args.mean = (123.152, 115.903, 103.063)
-
-    random.seed(args.seed)
-    np.random.seed(args.seed)
-    torch.manual_seed(args.seed)
-    dev = torch.device('cuda:0')
-    pooling_func = getattr(cmr.functions, train_loop.POOLING_FUNCS[args.pooling_func])
-    mask_initialW = 0.01 if args.initializer == 'normal' else 'he_normal'
-    model = cmr.models.MaskRCNNResNet(
-        n_layers=n_layers, n_fg_class=len(class_names), pooling_func=pooling_func,
-        anchor_scales=args.anchor_scales, roi_size=args.roi_size, min_size=args.min_size,
-        max_size=args.max_size, mask_initialW=mask_initialW, mean=args.mean,
-        pretrained_model='imagenet' if weights else None, imagenet_weights=weights)
-    args.imagenet_weights = weights
-    chain, opt = train_loop.setup_training(model, dev, args.batch_size,
-                                           synthetic_weights=weights is None)
-
-    train = train_loop.TransformDataset(train_data, cmr.datasets.MaskRCNNTransform(model))
-    test = train_loop.TransformDataset(test_data, cmr.datasets.MaskRCNNTransform(model, train=False))
-    loop = train_loop.TrainLoop(train_loop.SerialIterator(train, args.batch_size_per_gpu),
-                                chain, opt, dev)
-    test_iter = train_loop.SerialIterator(test, args.batch_size_per_gpu, shuffle=False)
-    if evaluator_type == 'voc':
-        evaluator = cmr.extensions.InstanceSegmentationVOCEvaluator(
-            test_iter, model, use_07_metric=True, label_names=args.class_names)
-    else:
-        evaluator = cmr.extensions.InstanceSegmentationCOCOEvaluator(
-            test_iter, model, label_names=args.class_names)
-
-    args.git_hash = cmr.utils.git_hash(__file__)
-    args.hostname = socket.gethostname()
-    params = {k: v for k, v in vars(args).items()}
-    tr = T.Trainer(loop, (args.max_epoch, 'epoch'), out=args.out)
-    T.extend_reference_set(tr, model, evaluator=evaluator, vis_iterator=test_iter,
-                           class_names=args.class_names, step_size=args.step_size,
-                           params=params, plot=not args.no_plot)
+    comm = setup_comm(args)
     try:
-        tr.run()
+        train_data, test_data, class_names, settings, evaluator_type = datasets(args)
+        configure(args, comm, class_names, settings)
+        model = build_model(args, weights)
+        args.imagenet_weights = weights
+        run = assemble(args, comm, model, train_data, test_data, evaluator_type,
+                       synthetic_weights=weights is None)
+        try:
+            run.trainer.run()
+        finally:
+            run.loop.close()
+        if comm.rank == 0:
+            print('Saved logs:', args.out)
     finally:
-        loop.close()
-    print('Saved logs:', args.out)
+        comm.close()
     return 0
 
 

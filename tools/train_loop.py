@@ -270,11 +270,13 @@ def build_voc_trainer(n_layers, device, lr_batch, defer=5):
     return model, chain, opt, None
 
 
-def setup_training(model, device, lr_batch, defer=5, synthetic_weights=True):
+def setup_training(model, device, lr_batch, defer=5, synthetic_weights=True, make_sync=None):
     """Train chain and optimizer of examples/train_common.py:171-190 for ``model``: MomentumSGD
     (lr 0.00125 * batch, momentum 0.9) + WeightDecay(1e-4), conv1 / bn1 / res2 and every
     AffineChannel2D frozen; ``synthetic_weights``: bench.stabilise_synthetic_weights (random
-    init); ``defer``: the res5 weight gradients held back into the next step (optimizers.py)."""
+    init); ``defer``: the res5 weight gradients held back into the next step (optimizers.py);
+    ``make_sync(opt)``: data parallel, creates the gradient sync (parallel.DataParallelGradSync)
+    before the deferred parameters are chosen, as bench.build_trainer does."""
     import bench
     import chainer_mask_rcnn_amd as cmr
     from chainer_mask_rcnn_amd import optimizers
@@ -291,6 +293,8 @@ def setup_training(model, device, lr_batch, defer=5, synthetic_weights=True):
             optimizers.disable_update(m)
     if synthetic_weights:
         bench.stabilise_synthetic_weights(model)
+    if make_sync is not None:
+        make_sync(opt)
     if defer > 0:
         a, b1, b2 = model.head.res5.a, model.head.res5.b1, model.head.res5.b2
         opt.defer_weight_gradients([a.conv2.W, a.conv3.W, b1.conv2.W, b1.conv1.W, b1.conv3.W,

@@ -230,14 +230,35 @@ class DictSummary(object):
                                  % (sorted(self._dev.keys), sorted(dev)))
             self._dev.add(dev)
 
-    def compute_mean(self):
+    def compute_mean(self, gather=None):
+        """``gather`` (data parallel): a collective returning every rank's ``(sums, n)`` in rank
+        order; the device means are then over all ranks (rank_order_mean).  Host numbers stay
+        this rank's own."""
         out = {k: x / n for k, (x, n) in self._host.items()}
         if self._dev is not None and self._dev.count:
             sums, n = self._dev.read_and_reset()
-            for k, s in zip(self._dev.keys, sums):
-                out[k] = np.float32(s) / np.float32(n)    # float32 _x / _n (Summary.compute_mean)
+            if gather is None:
+                for k, s in zip(self._dev.keys, sums):
+                    out[k] = np.float32(s) / np.float32(n)    # float32 _x / _n (Summary.compute_mean)
+            else:
+                per_rank = gather((self._dev.keys, sums, n))
+                if any(keys != self._dev.keys or m != n for keys, _, m in per_rank):
+                    raise RuntimeError('ranks closed a summary window over different keys or '
+                                       'iteration counts: %s' % [(k, m) for k, _, m in per_rank])
+                means = rank_order_mean([s for _, s, _ in per_rank], n)
+                out.update(zip(self._dev.keys, means))
         self._host = {}
         return out
+
+
+def rank_order_mean(sums_by_rank, n):
+    """Mean over ranks and over a window of ``n`` iterations from each rank's float32 window sums:
+    the sums added in rank order in float32, divided by float32(n * world).  Deterministic, and
+    the same on every rank."""
+    total = np.array(sums_by_rank[0], dtype=np.float32)
+    for s in sums_by_rank[1:]:
+        total = (total + np.asarray(s, dtype=np.float32)).astype(np.float32)
+    return total / np.float32(n * len(sums_by_rank))
 
 
 # ---- trainer ---------------------------------------------------------------------------------
@@ -281,6 +302,7 @@ class _Entry(object):
 class Trainer(object):
 
     def __init__(self, loop, stop_trigger, out='result'):
+        # out=None: a data-parallel rank other than 0, which writes nothing
         self.loop = loop
         self.updater = Updater(loop)
         self.stop_trigger = get_trigger(stop_trigger)
@@ -327,7 +349,8 @@ class Trainer(object):
     def run(self):
         if self._done:
             raise RuntimeError('cannot run training loop multiple times')
-        os.makedirs(self.out, exist_ok=True)
+        if self.out is not None:
+            os.makedirs(self.out, exist_ok=True)
         entries = self.ordered_entries()
         for e in entries:
             init = getattr(e.extension, 'initialize', None)
@@ -464,9 +487,11 @@ class LogReport(object):
     priority = PRIORITY_READER
     name = 'LogReport'
 
-    def __init__(self, trigger=(1, 'epoch'), log_name='log'):
+    def __init__(self, trigger=(1, 'epoch'), log_name='log', gather=None):
+        # gather: see DictSummary.compute_mean (log_name=None: the window is closed, not written)
         self._trigger = get_trigger(trigger)
         self._log_name = log_name
+        self._gather = gather
         self._summary = DictSummary()
         self.log = []
 
@@ -474,7 +499,7 @@ class LogReport(object):
         self._summary.add(trainer.observation)
         if not self._trigger(trainer):
             return
-        stats = {k: float(v) for k, v in self._summary.compute_mean().items()}
+        stats = {k: float(v) for k, v in self._summary.compute_mean(self._gather).items()}
         stats['epoch'] = trainer.updater.epoch
         stats['iteration'] = trainer.updater.iteration
         stats['elapsed_time'] = trainer.elapsed_time
@@ -527,7 +552,10 @@ class PlotReport(object):
 
     priority = PRIORITY_READER
 
-    def __init__(self, y_keys, file_name='plot.png', trigger=(1, 'epoch'), x_key='iteration'):
+    def __init__(self, y_keys, file_name='plot.png', trigger=(1, 'epoch'), x_key='iteration',
+                 gather=None, write=True):
+        # gather: see DictSummary.compute_mean; write=False: the windows are closed, not plotted
+        self._gather, self._write = gather, write
         self._y_keys = list(y_keys)
         self._file_name = file_name
         self._trigger = get_trigger(trigger)
@@ -540,12 +568,14 @@ class PlotReport(object):
                            if k in trainer.observation})
         if not self._trigger(trainer):
             return
-        stats = self._summary.compute_mean()
+        stats = self._summary.compute_mean(self._gather)
         self._summary = DictSummary()
         x = getattr(trainer.updater, self._x_key)
         for k in self._y_keys:
             if k in stats:
                 self._data[k].append((x, float(stats[k])))
+        if not self._write:
+            return
         import matplotlib
         matplotlib.use('Agg')
         import matplotlib.pyplot as plt
@@ -601,6 +631,32 @@ class ParamsReport(object):
         pass
 
 
+class RankZeroOnly(object):
+    """A rank-0-only extension that reads the parameters (snapshot, visual report) under data
+    parallelism.  Reading them flushes pending deferred updates, which launches the deferred
+    gradients' all-reduce (a collective): on rank 0 alone that would hang the job, so it raises
+    instead.  The all-rank evaluator flushes first at the same trigger."""
+
+    def __init__(self, extension):
+        self.extension = extension
+        for attr in ('trigger', 'priority', 'name'):
+            if hasattr(extension, attr):
+                setattr(self, attr, getattr(extension, attr))
+        self.name = getattr(extension, 'name', None) or type(extension).__name__
+        if hasattr(extension, 'initialize'):
+            self.initialize = extension.initialize
+        if hasattr(extension, 'finalize'):
+            self.finalize = extension.finalize
+
+    def __call__(self, trainer):
+        opt = trainer.updater.get_optimizer('main')
+        if getattr(opt, 'has_pending', lambda: False)():
+            raise RuntimeError('rank-0-only extension %s found deferred parameter updates pending: '
+                               'flushing them here would all-reduce on rank 0 alone; flush on every '
+                               'rank first (an all-rank extension at the same trigger)' % self.name)
+        return self.extension(trainer)
+
+
 def _plain(v):
     """YAML-safe copy (tuples -> lists, NumPy scalars -> Python numbers)."""
     if isinstance(v, dict):
@@ -621,31 +677,46 @@ LOG_KEYS = ['main/loss', 'main/roi_loc_loss', 'main/roi_cls_loss', 'main/roi_mas
 def extend_reference_set(trainer, model, evaluator=None, vis_iterator=None, class_names=None,
                          step_size=None, params=None, eval_interval=(1, 'epoch'),
                          log_interval=(20, 'iteration'), plot_interval=(0.1, 'epoch'),
-                         print_interval=(20, 'iteration'), plot=True, print_out=sys.stdout):
+                         print_interval=(20, 'iteration'), plot=True, print_out=sys.stdout,
+                         rank=0, gather=None):
     """The extensions of examples/train_common.py:251-372 (without dump_graph / ProgressBar)
-    with the same triggers and priorities; ``model``: the MaskRCNN (``chain.mask_rcnn``)."""
+    with the same triggers and priorities; ``model``: the MaskRCNN (``chain.mask_rcnn``).
+
+    Data parallel (``gather``: the control-plane all-gather, see DictSummary.compute_mean): the lr
+    shift, the evaluator (a multi-node one), observe_lr and the summaries of LogReport and the
+    loss PlotReport run on every rank, the loss means over all ranks; the snapshot, params.yaml,
+    the visual report, PrintReport and the files of the reports on rank 0 only (the snapshot and
+    the visual report, which read the parameters, behind RankZeroOnly)."""
     import chainer_mask_rcnn_amd as cmr
+    parallel = gather is not None
+    lead = rank == 0
+
+    def extend_lead(extension, reads_params=False, **kw):
+        if lead:
+            trainer.extend(RankZeroOnly(extension) if parallel and reads_params else extension, **kw)
     if step_size is not None:
         trainer.extend(ExponentialShift('lr', 0.1),
                        trigger=ManualScheduleTrigger(step_size, 'epoch'))
     if evaluator is not None:
         trainer.extend(Evaluator(evaluator), trigger=eval_interval)
-        trainer.extend(snapshot_object(model, 'snapshot_model.npz'),
-                       trigger=MaxValueTrigger('validation/main/map', eval_interval))
+        extend_lead(snapshot_object(model, 'snapshot_model.npz'), reads_params=True,
+                    trigger=MaxValueTrigger('validation/main/map', eval_interval))
     if params is not None:
-        trainer.extend(ParamsReport(params))
+        extend_lead(ParamsReport(params))
     if vis_iterator is not None:
-        trainer.extend(VisReport(cmr.extensions.InstanceSegmentationVisReport(
-            vis_iterator, model, label_names=class_names)), trigger=eval_interval)
+        extend_lead(VisReport(cmr.extensions.InstanceSegmentationVisReport(
+            vis_iterator, model, label_names=class_names)), reads_params=True,
+                    trigger=eval_interval)
     trainer.extend(observe_lr(), trigger=log_interval)
-    trainer.extend(LogReport(trigger=log_interval))
+    trainer.extend(LogReport(trigger=log_interval, log_name='log' if lead else None,
+                             gather=gather))
     if print_out is not None:
-        trainer.extend(PrintReport(['iteration', 'epoch', 'elapsed_time', 'lr'] + LOG_KEYS[:1]
-                                   + LOG_KEYS[1:] + ['validation/main/map'], out=print_out),
-                       trigger=print_interval)
+        extend_lead(PrintReport(['iteration', 'epoch', 'elapsed_time', 'lr'] + LOG_KEYS[:1]
+                                + LOG_KEYS[1:] + ['validation/main/map'], out=print_out),
+                    trigger=print_interval)
     if plot:
-        trainer.extend(PlotReport(LOG_KEYS, file_name='loss.png', trigger=plot_interval),
-                       trigger=plot_interval)
-        trainer.extend(PlotReport(['validation/main/map'], file_name='accuracy.png',
-                                  trigger=plot_interval), trigger=eval_interval)
+        trainer.extend(PlotReport(LOG_KEYS, file_name='loss.png', trigger=plot_interval,
+                                  gather=gather, write=lead), trigger=plot_interval)
+        extend_lead(PlotReport(['validation/main/map'], file_name='accuracy.png',
+                               trigger=plot_interval), trigger=eval_interval)
     return trainer
