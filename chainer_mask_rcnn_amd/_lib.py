@@ -141,6 +141,10 @@ SIGNATURES = {
     'mrcnn_mask_pack': (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mrcnn_paste_masks_packed': (c_int, [c_vp, c_vp, c_vp] + [c_int] * 5 + [c_vp] * 4),
     'mrcnn_mask_intersect': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp] + [c_int] * 3 + [c_vp, c_vp]),
+    'mrcnn_rle_encode': (c_int, [c_vp, c_vp] + [c_int] * 3 + [c_vp] * 4 + [c_int, c_vp, c_vp,
+                                                                          c_int, c_vp]),
+    'mrcnn_rle_decode': (c_int, [c_vp] * 3 + [c_int] * 3 + [c_vp] * 7),
+    'mrcnn_mask_unpack': (c_int, [c_vp] + [c_int] * 3 + [c_vp, c_vp]),
     'mrcnn_label_scan': (c_int, [c_vp, c_int, c_vp] + [c_int] * 4 + [c_vp] * 4),
     'mrcnn_label_instances': (c_int, [c_vp, c_int, c_vp] + [c_int] * 4 + [c_vp] * 3
                               + [c_int] * 4 + [c_vp] * 6),

@@ -76,15 +76,22 @@ class COCOInstanceSegmentationDataset(object):
                  root_dir=None):
         if root_dir is not None:
             self.root_dir = root_dir
+        test_dev = split == 'test-dev'
         if split == 'train':
             split = split + '2014'
             data_type = 'train2014'
         elif split in ['val', 'minival', 'valminusminival']:
             split = split + '2014'
             data_type = 'val2014'
+        elif test_dev:
+            data_type = 'test2015'
         else:
             raise ValueError
-        ann_file = osp.join(self.root_dir, 'annotations/instances_%s.json' % split)
+        if test_dev:
+            # no public annotations: the image list (with categories) of the test-dev server
+            ann_file = osp.join(self.root_dir, 'annotations/image_info_test-dev2015.json')
+        else:
+            ann_file = osp.join(self.root_dir, 'annotations/instances_%s.json' % split)
         if not osp.exists(ann_file):
             raise IOError('%s not found; the reference downloads it (coco.py:24-50), this '
                           'build has no network access: place the data there' % ann_file)
@@ -109,11 +116,15 @@ class COCOInstanceSegmentationDataset(object):
         class_names = np.asarray(class_names)
         class_names.setflags(write=0)
         self.cat_id_to_class_id = cat_id_to_class_id
+        self.class_id_to_cat_id = {c: cat for cat, c in cat_id_to_class_id.items()}
         self.class_names = class_names
+        # (height, width) of every listed image, as the JSON gives it
+        self.img_sizes = {img['id']: (int(img['height']), int(img['width']))
+                          for img in data.get('images', [])}
 
-        # filter images without any annotations (:96-102)
+        # filter images without any annotations (:96-102); test-dev keeps every listed image
         self.img_ids = [img['id'] for img in data.get('images', [])
-                        if len(self._anns_of_img.get(img['id'], [])) >= 1]
+                        if test_dev or len(self._anns_of_img.get(img['id'], [])) >= 1]
 
     def __len__(self):
         return len(self.img_ids)
@@ -134,8 +145,17 @@ class COCOInstanceSegmentationDataset(object):
             img = np.asarray(f if f.mode in ('L', 'RGB') else f.convert('RGB'))
         if img.ndim == 2:
             img = np.repeat(img[:, :, None], 3, axis=2)
-        example = self._annotations_to_example(self._anns_of_img[img_id], img.shape[0], img.shape[1])
+        example = self._annotations_to_example(self._anns_of_img.get(img_id, []), img.shape[0],
+                                               img.shape[1])
         return tuple([img] + example)
+
+    def get_annotations(self, i):
+        """``get_example(i)`` without the image: (bboxes, labels, masks[, crowds][, areas]) at
+        the height and width the JSON gives, without opening the JPEG (scoring a results file
+        needs only the annotation file)."""
+        img_id = self.img_ids[i]
+        height, width = self.img_sizes[img_id]
+        return tuple(self._annotations_to_example(self._anns_of_img.get(img_id, []), height, width))
 
     # -- annotations -> (bboxes, labels, masks[, crowds][, areas]) -------------------------------
     # Contract of the reference's datasets/coco.py:123-176 (pinned by tests/golden/coco_example.npz):

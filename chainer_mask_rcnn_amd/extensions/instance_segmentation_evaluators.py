@@ -15,6 +15,7 @@ import torch
 
 from ..utils.evaluations import masks as M
 from ..utils.evaluations import matching
+from ..utils.evaluations import rle
 
 
 def _batches(iterator):
@@ -38,6 +39,7 @@ def _batches(iterator):
 class _InstanceSegmentationEvaluator(object):
 
     name = 'validation'
+    results_sink = None
 
     def __init__(self, iterator, target, label_names=None):
         self.iterator = iterator
@@ -55,6 +57,8 @@ class _InstanceSegmentationEvaluator(object):
         ground-truth tuples): counts[i] = (inter (P,G), pred_area (P,), gt_area (G,)) host int64
         arrays; gt tuple = the example's entries after the image (bbox, label, mask, ...)."""
         target = self.target
+        sink = self.results_sink
+        n_seen = 0
         counts, pred_labels, pred_scores, gts = [], [], [], []
         for batch in _batches(self.iterator):
             batch = list(batch)
@@ -68,7 +72,7 @@ class _InstanceSegmentationEvaluator(object):
             bboxes, roi_masks, labels, scores = target.predict_prepared(
                 x, scales, sizes, masks_to_host=False)
             dev = x.device
-            queued = []
+            queued, encodes = [], []
             for j, ex in enumerate(batch):
                 gt_mask = ex[3]
                 H, W = sizes[j]
@@ -79,9 +83,15 @@ class _InstanceSegmentationEvaluator(object):
                 gt = M.pack_masks(gt_mask, device=dev)
                 inter = M.queue_intersections(pred, gt, W)
                 queued.append((inter, pred[1], gt[1]))
+                if sink is not None:          # the packed masks just intersected, encoded
+                    encodes.append(rle.queue_encode(pred[0], pred[1], pred[2], (H, W)))
             # one read-back for the whole batch
             flat = torch.cat([t.reshape(-1).to(torch.int64) for q in queued for t in q])
             host = flat.cpu().numpy()
+            if sink is not None:              # the batch's strings: one more small read-back
+                for j, segs in enumerate(rle.fetch_encoded(encodes)):
+                    sink(n_seen + j, bboxes[j], labels[j], scores[j], segs)
+            n_seen += len(batch)
             o = 0
             for (inter, pa, ga), l, s, ex in zip(queued, labels, scores, batch):
                 P, G = inter.shape
@@ -124,7 +134,17 @@ class InstanceSegmentationVOCEvaluator(_InstanceSegmentationEvaluator):
 class InstanceSegmentationCOCOEvaluator(_InstanceSegmentationEvaluator):
     """``validation/main/map`` (IoU .50:.95), ``map@0.5``, ``map@0.75`` and, with
     ``label_names``, ``ap/<name>`` keyed by the real label (the reference indexes the K axis,
-    the sorted labels present, by label: DESIGN.md section 9)."""
+    the sorted labels present, by label: DESIGN.md section 9).
+
+    ``results_sink`` (optional, off by default): a callable ``sink(i, bboxes, labels, scores,
+    segmentations)`` called for the i-th evaluated image with its detections and their masks as
+    COCO compressed RLE (``utils.evaluations.coco_results.ResultsWriter`` writes a results
+    file).  The packed masks that are intersected are the ones encoded, on the device; only the
+    strings come back, in one more read-back per batch."""
+
+    def __init__(self, iterator, target, label_names=None, results_sink=None):
+        super(InstanceSegmentationCOCOEvaluator, self).__init__(iterator, target, label_names)
+        self.results_sink = results_sink
 
     def evaluate(self):
         return self.evaluate_collected(*self.collect())

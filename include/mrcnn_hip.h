@@ -551,6 +551,42 @@ int mrcnn_mask_intersect(const uint64_t *a, const int32_t *ext_a, int P, const u
                          const int32_t *ext_b, int G, int H, int W, int32_t *inter,
                          void *stream);
 
+/* ---- COCO RLE of packed masks (csrc/mask_rle.hip) -----------------------------------------
+ * Uncompressed counts: runs over the column-major pixel index p = x * H + y, alternating 0 / 1
+ * starting with zeros (the first run may be 0), summing to H * W (pycocotools maskApi.c
+ * rleEncode).  Compressed string (rleToString): from the fourth count on, count[i] - count[i-2]
+ * is stored instead of count[i]; each value as 5-bit groups, low first, character = group + 48,
+ * bit 5 (0x20) = more groups follow, the last group's bit 4 is the sign.  Characters 48..111.
+ * Integer arithmetic only: outputs depend on the input alone. */
+/* Encode N packed masks (N,H,Wq) whose extents (N,4) contain every set bit (pack_masks' tight
+ * extents or paste_masks_packed's widened ones; only the extent's rows and words are read).
+ * Caller-owned: chg_off int32 (N*Wq+1) scratch; val_off int32 (N+1): counts of mask n are
+ * counts[val_off[n] .. val_off[n+1]); pos int32 (cap_values) scratch; counts int32
+ * (cap_values); str_off int32 (N+1): the string of mask n is chars[str_off[n] .. str_off[n+1]).
+ * val_off is always complete.  A mask whose counts end beyond cap_values writes no counts and
+ * has an empty string; chars are written only for masks whose string ends within cap_chars.  A
+ * caller that finds val_off[N] > cap_values or str_off[N] > cap_chars calls again with larger
+ * buffers (at most 7 characters per count).  N * (H * W + 1) * 7 < 2^31. */
+int mrcnn_rle_encode(const uint64_t *packed, const int32_t *extent, int N, int H, int W,
+                     int32_t *chg_off, int32_t *val_off, int32_t *pos, int32_t *counts,
+                     int cap_values, int32_t *str_off, char *chars, int cap_chars, void *stream);
+/* Decode N masks of an H x W image: either chars (compressed strings, mask n =
+ * chars[off[n] .. off[n+1])) or values (counts, values[off[n] .. off[n+1])), the other null.
+ * starts int32 (off[N]) scratch; nval int32 (N) runs per mask; status int32 (N) MRCNN_RLE_*.
+ * Output packed (N,H,Wq) (every word written; all zero for a mask whose status is not OK), exact
+ * area (N) and tight extent (N,4): ready for mrcnn_mask_intersect.  Reads and writes stay
+ * inside the buffers for any input. */
+#define MRCNN_RLE_OK 0
+#define MRCNN_RLE_BAD_CHAR 1        /* a character outside 48..111 */
+#define MRCNN_RLE_UNTERMINATED 2    /* the string ends inside a value, or a value has > 7 groups */
+#define MRCNN_RLE_NEGATIVE 3        /* a negative run */
+#define MRCNN_RLE_BAD_SUM 4         /* the runs do not sum to H * W */
+int mrcnn_rle_decode(const uint8_t *chars, const int32_t *values, const int32_t *off, int N,
+                     int H, int W, int32_t *starts, int32_t *nval, int32_t *status,
+                     uint64_t *packed, int32_t *area, int32_t *extent, void *stream);
+/* Packed (N,H,Wq) -> (N,H,W) uint8 {0,1}. */
+int mrcnn_mask_unpack(const uint64_t *packed, int N, int H, int W, uint8_t *out, void *stream);
+
 /* ---- Instance label images (csrc/instance_labels.hip) --------------------------------------
  * Replaces label2instance_boxes and instance_boxes2label (chainer_mask_rcnn/utils/
  * geometry.py:94-147).  ins and cls are (H, W) label images of elem_bytes 4 (int32) or 1

@@ -7,10 +7,16 @@ examples/evaluate_common.py + examples/coco/evaluate.py.
     python tools/evaluate.py --dataset sbd --sbd-root DIR --snapshot snapshot_model.npz
     python tools/evaluate.py --synthetic 4 --vis       # also writes iteration=best.jpg
     python tools/evaluate.py --log-dir logs/20261016_120000 [--coco-root DIR]   # a tools/train.py run
+    python tools/evaluate.py --coco-root DIR --detectron model.pkl --save-results res.json
+    python tools/evaluate.py --coco-root DIR --split test-dev --detectron model.pkl --save-results res.json
+    python tools/evaluate.py --coco-root DIR --results res.json   # score a results file (no model)
 
 Runs the evaluator (predicted masks stay on the device; extensions/), prints the report and
 the seconds per image spent in prediction and in evaluation, and writes the result as YAML (or
 JSON when PyYAML is missing) next to the snapshot as ``<snapshot>.eval_result.yaml``.
+``--save-results`` also writes the predictions as a COCO results file (masks as compressed RLE,
+encoded on the device); on test-dev, which has no public annotations, it writes the file and
+does not score.  ``--results`` scores such a file against the annotations alone.
 """
 import argparse
 import json
@@ -75,7 +81,22 @@ def main():
                          'weights from its snapshot_model.npz (examples/evaluate_common.py); writes '
                          'snapshot_model.npz.eval_result.yaml and iteration=best.jpg there')
     ap.add_argument('--custom-root', default=None, help='VOC-like directory (--log-dir of a custom run)')
+    ap.add_argument('--save-results', default=None, metavar='FILE',
+                    help='also write the predictions as a COCO results file (COCO only; with '
+                         '--split test-dev the file is written and nothing is scored)')
+    ap.add_argument('--results', default=None, metavar='FILE',
+                    help='score a COCO results file against --coco-root / --split (no model, '
+                         'no images needed)')
     args = ap.parse_args()
+    if args.results:
+        if args.coco_root is None:
+            ap.error('--results needs --coco-root')
+        return score_results(args)
+    if args.save_results and (args.synthetic or (args.dataset != 'coco' and not args.log_dir)):
+        ap.error('--save-results needs COCO data: VOC, SBD and --synthetic have no COCO image or '
+                 'category ids')
+    if args.save_results and args.evaluator == 'voc':
+        ap.error('--save-results needs the coco evaluator')
     if args.log_dir:
         return evaluate_log_dir(args)
     voc = args.dataset in ('voc', 'sbd') and not args.synthetic
@@ -105,6 +126,8 @@ def main():
             args.split, root_dir=args.coco_root, use_crowd=True, return_crowd=True,
             return_area=True)
         class_names = [str(n) for n in data.class_names]
+    if args.split == 'test-dev' and not args.save_results:
+        ap.error('--split test-dev has no annotations to score: use --save-results FILE')
 
     torch.manual_seed(0)
     # examples/voc/train.py: 600 / 1000 and anchor scales (4, 8, 16, 32); COCO: 800 / 1333
@@ -135,10 +158,23 @@ def main():
     cls = (cmr.extensions.InstanceSegmentationVOCEvaluator if args.evaluator == 'voc'
            else cmr.extensions.InstanceSegmentationCOCOEvaluator)
     kw = {'use_07_metric': True} if args.evaluator == 'voc' else {}
+    writer = _results_writer(args, data)
+    if writer is not None:
+        kw['results_sink'] = writer
     evaluator = cls(batches, target, label_names=class_names, **kw)
     t0 = time.perf_counter()
-    result = evaluator.evaluate()
+    if args.split == 'test-dev':
+        evaluator.collect()
+        result = {}
+        print('test-dev has no public annotations: results written to %s, not scored'
+              % args.save_results)
+    else:
+        result = evaluator.evaluate()
     total = time.perf_counter() - t0
+    if writer is not None:
+        writer.close()
+        print('Saved results: %s (%d entries, %d images)'
+              % (args.save_results, writer.n_entries, len(writer.image_ids)))
     result = {k: float(v) for k, v in result.items()}
     timing = {'images': n, 'predict_s_per_image': target.seconds / n,
               'eval_s_per_image': (total - target.seconds) / n}
@@ -149,6 +185,8 @@ def main():
                        'synthetic.eval_result.yaml')
     payload = {'result': result, 'timing': timing, 'evaluator': args.evaluator,
                'weights': weights, 'split': None if args.synthetic else args.split}
+    if args.save_results:
+        payload['results_file'] = os.path.abspath(args.save_results)
     try:
         import yaml
         with open(out, 'w') as f:
@@ -173,6 +211,54 @@ def main():
             vis, model, label_names=class_names, file_name='iteration=%s.jpg', copy_latest=False)
         visualizer(trainer=DummyTrainer())
         print('Saved visualization:', os.path.join(DummyTrainer.out, 'iteration=best.jpg'))
+
+
+def _results_writer(args, data):
+    """The COCO results file of --save-results: a streaming writer that maps the i-th evaluated
+    image to the dataset's image id and labels to its category ids."""
+    path = getattr(args, 'save_results', None)      # absent from callers' own namespaces
+    if not path:
+        return None
+    if not (hasattr(data, 'img_ids') and hasattr(data, 'class_id_to_cat_id')):
+        raise SystemExit('--save-results needs a COCO dataset (image and category ids)')
+    from chainer_mask_rcnn_amd.utils.evaluations.coco_results import ResultsWriter
+    return ResultsWriter(path, data.img_ids, data.class_id_to_cat_id)
+
+
+def score_results(args):
+    """--results: score a COCO results file against the annotations of --coco-root / --split
+    (the first --limit images); writes ``<results>.eval_result.yaml`` (or --out)."""
+    import chainer_mask_rcnn_amd as cmr
+    from chainer_mask_rcnn_amd.utils.evaluations.coco_results import eval_coco_results
+    split = args.split or 'minival'
+    if split == 'test-dev':
+        raise SystemExit('test-dev has no public annotations: its results are scored by the '
+                         'COCO evaluation server')
+    data = cmr.datasets.COCOInstanceSegmentationDataset(
+        split, root_dir=args.coco_root, use_crowd=True, return_crowd=True, return_area=True)
+    torch.cuda.set_device(0)
+    t0 = time.perf_counter()
+    result = eval_coco_results(args.results, data, limit=args.limit or None,
+                               label_names=[str(n) for n in data.class_names])
+    seconds = time.perf_counter() - t0
+    result = {k: float(v) for k, v in result.items()}
+    pprint.pprint(result)
+    n = len(data) if not args.limit else min(args.limit, len(data))
+    timing = {'images': n, 'eval_s_per_image': seconds / max(n, 1)}
+    print('timing:', json.dumps(timing))
+    out = args.out or (args.results + '.eval_result.yaml')
+    payload = {'result': result, 'timing': timing, 'evaluator': 'coco', 'split': split,
+               'results_file': os.path.abspath(args.results)}
+    try:
+        import yaml
+        with open(out, 'w') as f:
+            yaml.safe_dump(payload, f, default_flow_style=False)
+    except ImportError:
+        out = os.path.splitext(out)[0] + '.json'
+        with open(out, 'w') as f:
+            json.dump(payload, f, indent=1)
+    print('Saved evaluation:', out)
+    return result
 
 
 def evaluate_log_dir(args):
@@ -223,16 +309,25 @@ def evaluate_log_dir(args):
     print('Evaluating...')
     n = len(test_data) if not args.limit else min(args.limit, len(test_data))
     batches = ([transform(test_data[j])] for j in range(n))
+    writer = _results_writer(args, test_data)
+    if writer is not None and evaluator_type != 'coco':
+        raise SystemExit('--save-results needs the coco evaluator')
     if evaluator_type == 'voc':
         evaluator = cmr.extensions.InstanceSegmentationVOCEvaluator(
             batches, model, use_07_metric=True, label_names=class_names)
     else:
         evaluator = cmr.extensions.InstanceSegmentationCOCOEvaluator(
-            batches, model, label_names=class_names)
+            batches, model, label_names=class_names, results_sink=writer)
     result = {k: float(v) for k, v in evaluator.evaluate().items()}
     yaml_file = pretrained_model + '.eval_result.yaml'
     with open(yaml_file, 'w') as f:
         yaml.safe_dump(result, f, default_flow_style=False)
+    if writer is not None:
+        writer.close()
+        print('Saved results: %s (%d entries)' % (writer.path, writer.n_entries))
+        with open(yaml_file, 'a') as f:
+            yaml.safe_dump({'results_file': os.path.abspath(writer.path)}, f,
+                           default_flow_style=False)
     print('Saved evaluation:', yaml_file)
     pprint.pprint(result)
     return result
