@@ -93,7 +93,8 @@ static inline void prof_take(hipEvent_t *start, hipEvent_t *stop)
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// roi_align.hip's share of mrcnn_set_tuning ("roi_fwd_lanes", "roi_bwd_lanes"); 0 = name handled
+// roi_align.hip's share of mrcnn_set_tuning ("roi_fwd_lanes", "roi_bwd_lanes"): 0 = name handled
+// and value set, -1 = not one of its names, other = value rejected (mrcnn_last_error set)
 int roi_align_set_tuning(const char *name, int value);
 
 }  // namespace mrcnn

@@ -1812,7 +1812,7 @@ extern "C" int mrcnn_set_tuning(const char *name, int value)
         g_tiny_split = value;
         return 0;
     }
-    if (mrcnn::roi_align_set_tuning(name, value) == 0) return 0;     // roi_fwd_lanes / roi_bwd_lanes
+    if (int rc = mrcnn::roi_align_set_tuning(name, value); rc >= 0) return rc;   // roi_fwd_lanes / roi_bwd_lanes
     MRCNN_REQUIRE(false, "set_tuning: unknown option '%s'", name);
     return 1;
 }

@@ -878,9 +878,17 @@ int roi_align_fwd_launch(const float *x, const float *rois, float *y, int N, int
 
 int mrcnn::roi_align_set_tuning(const char *name, int value)     // behind mrcnn_set_tuning (conv_gemm.hip)
 {
-    if (strcmp(name, "roi_fwd_lanes") == 0) { g_roi_fwd_lanes = value; return 0; }
-    if (strcmp(name, "roi_bwd_lanes") == 0) { g_roi_bwd_lanes = value; return 0; }
-    return 1;
+    int *knob = strcmp(name, "roi_fwd_lanes") == 0 ? &g_roi_fwd_lanes
+              : strcmp(name, "roi_bwd_lanes") == 0 ? &g_roi_bwd_lanes : nullptr;
+    if (!knob) return -1;
+    // whole waves, at most the kernels' __launch_bounds__: the pixel-owner backward counts its
+    // list entries per wave (nwaves = nthr >> 6, lane 63 publishes) and sizes its LDS lists for
+    // kOwnThreads lanes, the forward is compiled for at most 256 lanes
+    MRCNN_REQUIRE(value == 0 || (value % 64 == 0 && value >= 64 && value <= kOwnThreads),
+                  "set_tuning: %s must be 0 or a multiple of 64 in [64, %d], got %d", name,
+                  kOwnThreads, value);
+    *knob = value;
+    return 0;
 }
 
 extern "C" int mrcnn_roi_align_fwd_ex(const float *x, const float *rois, float *y, int N, int H,

@@ -299,7 +299,9 @@ int64_t mrcnn_conv2d_split_workspace_bytes(void);
  *   differently from the 128x128 kernels, so those rows are summed in another order.
  *   "pw" (default 3): bit 0 = pointwise (1x1 / stride 1) forward-form launches, bit 1 = 3x3 / stride 1 /
  *   pad 1 ones run instantiations with that geometry as compile-time constants; bit-identical.
- *   "roi_fwd_lanes" / "roi_bwd_lanes" (default 0 = 256): cap of the lanes per ROIAlign workgroup. */
+ *   "roi_fwd_lanes" / "roi_bwd_lanes" (default 0 = 256): cap of the lanes per ROIAlign workgroup;
+ *   0 or a multiple of 64 in [64, 256] (whole waves), any other value is an error and keeps the
+ *   previous setting (the pixel-owner backward counts its RoI lists per wave). */
 int mrcnn_set_tuning(const char *name, int value);
 int mrcnn_conv2d_fwd(const mrcnn_conv_desc *d, const float *x, const float *w,
                      const float *bias, const float *scale, const float *shift,

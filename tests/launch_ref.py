@@ -1,0 +1,819 @@
+"""Launch checker: every call of a checked libmrcnn_hip.so entry point, compared with a float64
+restatement of the same operation (include/mrcnn_hip.h, the comment next to each declaration).
+
+``LaunchChecker.install(monkeypatch)`` wraps ``chainer_mask_rcnn_amd._lib.call`` — every library
+call of ``functions/`` goes through it.  Per checked call: synchronise the device, copy the
+operands out of the argument pointers (sizes from the descriptor / arguments; the output's prior
+contents where the call accumulates into it), make the call, synchronise, copy the output, build
+the reference in float64 with plain torch ops on the same device, compare, record, free.
+Operands are read by address with a device-to-device copy, so the host pointer arrays of
+mrcnn_filter_flip_transpose_batched are read like any other argument.
+
+State carried between calls: the filter ``w`` behind a Winograd transform ``u``
+(mrcnn_conv3x3_wino_filter), the input ``x`` behind a kept Winograd input transform ``v``, and
+the ``w`` / ``row_scale`` behind a flipped, transposed filter ``wT``.  ``wT`` itself is compared
+bit for bit; the data gradients on ``wT`` are referenced from ``w`` and ``row_scale``, so a wrong
+transpose cannot cancel out.
+
+The references themselves take and return float64 NCHW / row tensors and run on any device:
+tests/test_launch_ref_cpu.py checks them against the NumPy oracle on the CPU.
+
+Comparison (``ratio``): per element |got - ref| <= rel |ref| + floor max|ref| with the suite's
+convolution bound rel = 1e-4, floor = 1e-5 (tests/test_gpu_conv.py); the recorded figure is the
+worst |got - ref| / bound, a launch passes at <= 1.  Data movement and ops the header calls
+same-order are compared bit for bit against an fp32 restatement (``exact``).
+"""
+import collections
+import ctypes
+import math
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from chainer_mask_rcnn_amd import _lib
+from chainer_mask_rcnn_amd._lib import (EPI_ACCUM, EPI_AFFINE, EPI_BIAS, EPI_RELU,
+                                        EPI_RESIDUAL)
+
+F64 = torch.float64
+REL, FLOOR = 1e-4, 1e-5
+
+
+def _close(got, ref, rel=REL, floor=FLOOR):
+    """The suite's parity bound on NumPy arrays (float64 reference)."""
+    got = np.asarray(got, np.float64)
+    ref = np.asarray(ref, np.float64)
+    assert got.shape == ref.shape
+    scale = max(np.abs(ref).max(), 1e-6)
+    excess = np.abs(got - ref) - (rel * np.abs(ref) + floor * scale)
+    worst = excess.max()
+    assert worst <= 0, 'element %s: got %.9g ref %.9g (scale %.3e)' % (
+        np.unravel_index(excess.argmax(), excess.shape), got.flat[excess.argmax()],
+        ref.flat[excess.argmax()], scale)
+
+
+def ratio(got, ref, rel=REL, floor=FLOOR):
+    """Worst |got - ref| / (rel |ref| + floor max|ref|) over the elements, float64 on ref's device
+    (<= 1: within the bound).  Empty tensors give 0."""
+    ref = ref.to(F64)
+    got = got.to(device=ref.device, dtype=F64).reshape(ref.shape)
+    if ref.numel() == 0:
+        return 0.
+    scale = max(float(ref.abs().max()), 1e-6)
+    err = (got - ref).abs()
+    if not bool(torch.isfinite(got).all()):
+        return math.inf
+    return float((err / (rel * ref.abs() + floor * scale)).max())
+
+
+def exact(got, ref):
+    """0 when bit-identical (fp32 restatement), inf otherwise."""
+    return 0. if torch.equal(got.reshape(ref.shape), ref) else math.inf
+
+
+# ---- float64 references (NCHW activations, KCRS filters, as chainer) ---------------------------
+
+_CHUNK = 1 << 27      # elements of the largest temporary (1 GiB in float64)
+
+
+def conv_fwd(x, w, stride=1, pad=0):
+    """y (N,K,P,Q) = conv2d(x (N,C,H,W), w (K,C,R,S))."""
+    N, C, H, W = x.shape
+    K, _, R, S = w.shape
+    P, Q = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - S) // stride + 1
+    wm = w.reshape(K, C * R * S)
+    y = x.new_empty((N, K, P, Q))
+    per = max(1, _CHUNK // max(1, C * R * S * P * Q))
+    for n0 in range(0, N, per):
+        xs = x[n0:n0 + per]
+        if R == 1 and S == 1 and pad == 0:
+            cols = xs[:, :, ::stride, ::stride].reshape(xs.shape[0], C, P * Q)
+        else:
+            cols = F.unfold(xs, (R, S), padding=pad, stride=stride)
+        y[n0:n0 + per] = torch.matmul(wm, cols).view(-1, K, P, Q)
+    return y
+
+
+def conv_dgrad(gy, w, H, W, stride=1, pad=0):
+    """gx (N,C,H,W): the adjoint of conv_fwd applied to gy (N,K,P,Q)."""
+    N, K, P, Q = gy.shape
+    _, C, R, S = w.shape
+    wt = w.reshape(K, C * R * S).t()
+    gx = gy.new_zeros((N, C, H, W))
+    per = max(1, _CHUNK // max(1, C * R * S * P * Q))
+    for n0 in range(0, N, per):
+        cols = torch.matmul(wt, gy[n0:n0 + per].reshape(-1, K, P * Q))
+        if R == 1 and S == 1 and pad == 0:
+            gx[n0:n0 + per, :, ::stride, ::stride] = cols.view(-1, C, P, Q)
+        else:
+            gx[n0:n0 + per] = F.fold(cols, (H, W), (R, S), padding=pad, stride=stride)
+    return gx
+
+
+def conv_wgrad(x, gy, R, S, stride=1, pad=0):
+    """gw (K,C,R,S) = sum over n, p, q of gy x-patch."""
+    N, C, H, W = x.shape
+    K, P, Q = gy.shape[1:]
+    gw = x.new_zeros((K, C * R * S))
+    per = max(1, _CHUNK // max(1, C * R * S * P * Q))
+    for n0 in range(0, N, per):
+        xs = x[n0:n0 + per]
+        if R == 1 and S == 1 and pad == 0:
+            cols = xs[:, :, ::stride, ::stride].reshape(xs.shape[0], C, P * Q)
+        else:
+            cols = F.unfold(xs, (R, S), padding=pad, stride=stride)
+        g = gy[n0:n0 + per].reshape(-1, K, P * Q)
+        gw += torch.einsum('nkl,ncl->kc', g, cols)
+    return gw.view(K, C, R, S)
+
+
+def _per_c(v, nd=4):
+    return None if v is None else v.view((1, -1) + (1,) * (nd - 2))
+
+
+def fwd_epilogue(y, flags, bias=None, scale=None, shift=None, residual=None):
+    """MRCNN_EPI_*: bias, affine, residual, ReLU in the header's order (per-channel dim 1)."""
+    if flags & EPI_BIAS:
+        y = y + _per_c(bias, y.dim())
+    if flags & EPI_AFFINE:
+        y = y * _per_c(scale, y.dim()) + _per_c(shift, y.dim())
+    if flags & EPI_RESIDUAL:
+        y = y + residual
+    if flags & EPI_RELU:
+        y = y.clamp_min(0)
+    return y
+
+
+def dgrad_epilogue(acc, flags, prev=None, res_g=None, res_y=None, out_mask_y=None,
+                   out_scale=None):
+    """gx = (acc * out_scale[c] + res_g * (res_y > 0) [+ prev]) * (out_mask_y > 0)."""
+    g = acc if out_scale is None else acc * _per_c(out_scale)
+    if res_g is not None:
+        g = g + (res_g if res_y is None else res_g * (res_y > 0))
+    if flags & EPI_ACCUM:
+        g = g + prev
+    if out_mask_y is not None:
+        g = g * (out_mask_y > 0)
+    return g
+
+
+def deconv_fwd(x, w):
+    """Deconvolution2D(k=2, s=2): x (N,C,H,W), w (C,K,2,2) -> (N,K,2H,2W)."""
+    N, C, H, W = x.shape
+    K = w.shape[1]
+    y = torch.einsum('nchw,ckab->nkhawb', x, w)
+    return y.reshape(N, K, 2 * H, 2 * W)
+
+
+def deconv_dgrad(gy, w):
+    N, K, H2, W2 = gy.shape
+    g = gy.view(N, K, H2 // 2, 2, W2 // 2, 2)
+    return torch.einsum('nkhawb,ckab->nchw', g, w)
+
+
+def deconv_wgrad(x, gy):
+    N, K, H2, W2 = gy.shape
+    g = gy.view(N, K, H2 // 2, 2, W2 // 2, 2)
+    return torch.einsum('nchw,nkhawb->ckab', x, g)
+
+
+def roi_tables(rois, H, W, PH, PW, spatial_scale, sampling_ratio, bin_stride=1):
+    """Separable ROIAlign weights, geometry in fp32 exactly as the kernels (roi_align.hip: roi_geom,
+    tap1d, sample position start + p * bin + (i + .5) * bin / grid), weights in float64:
+    Ay (R, OH, H), Bx (R, OW, W) with y[r, oh, ow] = sum_hw Ay[r,oh,h] Bx[r,ow,w] x[b_r,h,w] /
+    count_r.  Returns (batch index (R), Ay, Bx, count (R) float64)."""
+    f = rois.to(torch.float32)
+    s = torch.tensor(spatial_scale, dtype=torch.float32)
+    batch = f[:, 0].long()
+
+    def axis(lo_, hi_, n_bins, size):
+        start = lo_ * s
+        end = hi_ * s
+        roi = torch.clamp_min(end - start, 1.)
+        bin_ = roi / float(n_bins)
+        if sampling_ratio > 0:
+            grid = torch.full_like(roi, sampling_ratio, dtype=torch.int64)
+        else:
+            grid = torch.ceil(roi / float(n_bins)).long()
+        G = int(grid.max()) if grid.numel() else 1
+        p = torch.arange(0, n_bins, bin_stride, device=f.device)
+        i = torch.arange(G, device=f.device)
+        # (R, O, G) positions, left to right in fp32
+        pos = (start[:, None, None] + p[None, :, None].float() * bin_[:, None, None]) \
+            + (i[None, None, :].float() + .5) * bin_[:, None, None] / grid[:, None, None].float()
+        use = (i[None, None, :] < grid[:, None, None]) & ~((pos < -1.) | (pos > float(size)))
+        pc = torch.clamp_min(pos, 0.)
+        lo = pc.long()
+        edge = lo >= size - 1
+        lo = torch.where(edge, torch.full_like(lo, size - 1), lo)
+        hi = torch.where(edge, lo, lo + 1)
+        pc = torch.where(edge, lo.float(), pc)
+        wl = (pc - lo.float())                     # weight of hi, fp32 as tap1d
+        wh = (1. - wl)                             # weight of lo
+        A = torch.zeros((f.shape[0], p.numel(), size), dtype=F64, device=f.device)
+        m = use.to(F64)
+        A.scatter_add_(2, lo.clamp(0, size - 1).view(f.shape[0], p.numel(), -1),
+                       (wh.to(F64) * m).view(f.shape[0], p.numel(), -1))
+        A.scatter_add_(2, hi.clamp(0, size - 1).view(f.shape[0], p.numel(), -1),
+                       (wl.to(F64) * m).view(f.shape[0], p.numel(), -1))
+        return A, grid
+
+    Ay, gh = axis(f[:, 2], f[:, 4], PH, H)
+    Bx, gw = axis(f[:, 1], f[:, 3], PW, W)
+    return batch, Ay, Bx, (gh * gw).to(F64)
+
+
+def roi_align_fwd(x, rois, PH, PW, spatial_scale, sampling_ratio=0, bin_stride=1, chunk=64):
+    """x (N,H,W,C) float64 -> y (R, OH, OW, C) float64 (NHWC, as the kernels)."""
+    N, H, W, C = x.shape
+    batch, Ay, Bx, count = roi_tables(rois, H, W, PH, PW, spatial_scale, sampling_ratio, bin_stride)
+    R, OH, OW = Ay.shape[0], Ay.shape[1], Bx.shape[1]
+    y = x.new_empty((R, OH, OW, C))
+    for n in range(N):
+        idx = torch.nonzero(batch == n).flatten()
+        for i0 in range(0, idx.numel(), chunk):
+            r = idx[i0:i0 + chunk]
+            t = torch.matmul(Ay[r].reshape(-1, H), x[n].reshape(H, W * C)).view(-1, OH, W, C)
+            y[r] = torch.einsum('rqw,rpwc->rpqc', Bx[r], t) / count[r].view(-1, 1, 1, 1)
+    y[(batch < 0) | (batch >= N)] = 0
+    return y
+
+
+def roi_align_bwd(gy, rois, x_shape, spatial_scale, sampling_ratio=0, bin_stride=1, PH=None,
+                  PW=None, chunk=64):
+    """gy (R, OH, OW, C) float64 -> gx (N,H,W,C) float64: the adjoint of roi_align_fwd."""
+    N, H, W, C = x_shape
+    PH = PH if PH is not None else gy.shape[1] * bin_stride
+    PW = PW if PW is not None else gy.shape[2] * bin_stride
+    batch, Ay, Bx, count = roi_tables(rois, H, W, PH, PW, spatial_scale, sampling_ratio, bin_stride)
+    gx = gy.new_zeros((N, H, W, C))
+    for n in range(N):
+        idx = torch.nonzero(batch == n).flatten()
+        for i0 in range(0, idx.numel(), chunk):
+            r = idx[i0:i0 + chunk]
+            s = torch.einsum('rqw,rpqc->rpwc', Bx[r], gy[r] / count[r].view(-1, 1, 1, 1))
+            gx[n] += torch.matmul(Ay[r].reshape(-1, H).t(), s.reshape(-1, W * C)).view(H, W, C)
+    return gx
+
+
+def sparse3x3_gather(x, g, rows):
+    """fp32 restatement: patches (n,3,3,C) of x (N,H,W,C) around rows (indices into N*H*W), zero
+    outside the map, and g_rows (n,K)."""
+    N, H, W, C = x.shape
+    n, hw = rows // (H * W), rows % (H * W)
+    h, w = hw // W, hw % W
+    xp = F.pad(x, (0, 0, 1, 1, 1, 1))
+    dy = torch.arange(3, device=x.device)
+    patches = xp[n[:, None, None], h[:, None, None] + dy[None, :, None],
+                 w[:, None, None] + dy[None, None, :]]
+    return patches, g.reshape(-1, g.shape[-1])[rows]
+
+
+def sparse3x3_scatter(g_patches, lookup, N, H, W, C):
+    """gx (N,H,W,C): every pixel sums the patch gradients of the listed rows whose 3x3 window
+    covers it (lookup: position -> row or -1)."""
+    gx = g_patches.new_zeros((N, H + 2, W + 2, C))
+    rows = torch.nonzero(lookup.view(-1) >= 0).flatten()
+    r = lookup.view(-1)[rows].long()
+    n, hw = rows // (H * W), rows % (H * W)
+    h, w = hw // W, hw % W
+    for dy in range(3):
+        for dx in range(3):
+            gx.index_put_((n, h + dy, w + dx), g_patches[r, dy, dx], accumulate=True)
+    return gx[:, 1:H + 1, 1:W + 1]
+
+
+def maxpool3x3s2p1(x):
+    """fp32 restatement (NCHW): F.max_pooling_2d(x, 3, 2, 1, cover_all=True)."""
+    return F.max_pool2d(x, 3, 2, 1, ceil_mode=True)
+
+
+def sgd(p, g, v, lr, momentum, wd, grad_scale):
+    """float64 update of sgd_momentum_wd: v' = m v - lr (g gs + wd p); p' = p + v'; and the
+    per-element tolerance (4 fp32 ulps of the operands)."""
+    v2 = momentum * v - lr * (g * grad_scale + wd * p)
+    p2 = p + v2
+    eps = 2. ** -23
+    tv = 4 * eps * (abs(momentum) * v.abs() + abs(lr) * ((g * grad_scale).abs() + abs(wd) * p.abs()))
+    tp = 4 * eps * (p.abs() + v2.abs()) + tv
+    return p2, v2, tp, tv
+
+
+# ---- reading operands by address -------------------------------------------------------------
+
+_hip = None
+
+
+def _hip_lib():
+    """The HIP runtime torch has loaded (its path from /proc/self/maps)."""
+    global _hip
+    if _hip is None:
+        path = None
+        with open('/proc/self/maps') as f:
+            for line in f:
+                if 'libamdhip64.so' in line:
+                    path = line.split()[-1]
+                    break
+        _hip = ctypes.CDLL(path or 'libamdhip64.so')
+        _hip.hipMemcpyAsync.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                        ctypes.c_int, ctypes.c_void_p]
+        _hip.hipMemcpyAsync.restype = ctypes.c_int
+    return _hip
+
+
+def _addr(a):
+    if a is None:
+        return 0
+    if isinstance(a, ctypes.c_void_p):
+        return a.value or 0
+    return int(a)
+
+
+def read(addr, shape, dtype=torch.float32, device='cuda'):
+    """A fresh tensor holding `shape` elements at device address `addr` (None for NULL)."""
+    addr = _addr(addr)
+    if not addr:
+        return None
+    t = torch.empty(tuple(int(s) for s in shape), dtype=dtype, device=device)
+    if t.numel():
+        # on the current torch stream, so that the torch ops that read `t` are ordered after the
+        # copy (a device-to-device hipMemcpy may return before it completes, and the null stream
+        # does not order a non-blocking side stream such as the deferred-gradient stream)
+        rc = _hip_lib().hipMemcpyAsync(ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(addr),
+                                       t.numel() * t.element_size(), 3,   # hipMemcpyDeviceToDevice
+                                       ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream))
+        if rc != 0:
+            raise RuntimeError('hipMemcpyAsync from 0x%x failed (%d)' % (addr, rc))
+    return t
+
+
+def _nchw(t, N, H, W, C):
+    """(N,H,W,C) fp32 buffer -> float64 NCHW."""
+    return None if t is None else t.view(N, H, W, C).permute(0, 3, 1, 2).to(F64)
+
+
+def _krsc(t, K, R, S, C):
+    return None if t is None else t.view(K, R, S, C).permute(0, 3, 1, 2).to(F64)
+
+
+def _nhwc(t):
+    return t.permute(0, 2, 3, 1)
+
+
+def _d(arg):
+    """ctypes.byref(ConvDesc) -> the descriptor."""
+    return arg._obj if hasattr(arg, '_obj') else arg.contents
+
+
+# ---- entry points that need no reference here ---------------------------------------------------
+
+# name -> the test that compares it bit-exactly or in float64 at realistic sizes (or: a query)
+ALLOWED = {
+    'mrcnn_nms_sorted': 'tests/test_gpu_proposal.py (vs the C oracle, exact keep lists)',
+    'mrcnn_nms_sorted_batched': 'tests/test_gpu_inference.py::test_c5_full_size_predict',
+    'mrcnn_topk_desc': 'tests/test_gpu_proposal.py',
+    'mrcnn_topk_desc_batched': 'tests/test_gpu_proposal.py',
+    'mrcnn_decode_clip': 'tests/test_gpu_proposal.py',
+    'mrcnn_gather_rows': 'tests/test_gpu_proposal.py',
+    'mrcnn_detect_sort': 'tests/test_gpu_inference.py::test_c5_full_size_predict',
+    'mrcnn_detect_compact': 'tests/test_gpu_inference.py::test_c5_full_size_predict',
+    'mrcnn_decode_cls_boxes': 'tests/test_gpu_inference.py',
+    'mrcnn_bbox_iou_argmax': 'tests/test_gpu_targets.py',
+    'mrcnn_anchor_labels': 'tests/test_gpu_targets.py',
+    'mrcnn_anchor_targets_finish': 'tests/test_gpu_targets.py',
+    'mrcnn_proposal_targets_gather': 'tests/test_gpu_targets.py',
+    'mrcnn_mask_targets': 'tests/test_gpu_targets.py',
+    'mrcnn_sigmoid_ce': 'tests/test_gpu_losses.py',
+    'mrcnn_mask_sigmoid_ce': 'tests/test_gpu_losses.py',
+    'mrcnn_softmax_ce': 'tests/test_gpu_losses.py',
+    'mrcnn_smooth_l1': 'tests/test_gpu_losses.py',
+    'mrcnn_softmax': 'tests/test_gpu_losses.py',
+    'mrcnn_observe_accumulate': 'tests/test_gpu_trainer.py (loss observation)',
+    'mrcnn_prepare_image': 'tests/test_gpu_inference.py (image preparation)',
+    'mrcnn_paste_masks': 'tests/test_gpu_inference.py (mask pasting)',
+    'mrcnn_paste_masks_packed': 'tests/test_gpu_mask_rle.py (mask pasting)',
+    'mrcnn_mask_pack': 'tests/test_gpu_mask_rle.py',
+}
+
+
+class LaunchChecker:
+    """Wraps _lib.call; see the module docstring.  ``stats[name] = [launches, worst ratio]``,
+    ``fails`` lists (name, detail, ratio) of every launch over its bound, ``unchecked`` the entry
+    points called that have neither a reference nor an ALLOWED entry."""
+
+    def __init__(self, allowed=ALLOWED):
+        self.allowed = allowed
+        self.stats = collections.OrderedDict()
+        self.fails = []
+        self.unchecked = collections.Counter()
+        self.u_of = {}      # u address -> (w fp32 (K,3,3,C), desc fields)
+        self.v_of = {}      # v address -> x fp32 (N,H,W,C)
+        self.wt_of = {}     # wT address -> (w fp32 (K,R,S,C), row_scale fp32 or None)
+        self._orig = None
+
+    def install(self, monkeypatch):
+        self._orig = _lib.call
+        monkeypatch.setattr(_lib, 'call', self.call)
+
+    # -- bookkeeping
+    def _record(self, name, r, detail):
+        st = self.stats.setdefault(name, [0, 0.])
+        st[0] += 1
+        st[1] = max(st[1], r)
+        if not r <= 1.:
+            self.fails.append((name, detail, r))
+
+    def table(self):
+        lines = ['%-40s %8s %12s' % ('entry point', 'launches', 'excess/bound')]
+        for k, (n, r) in sorted(self.stats.items()):
+            lines.append('%-40s %8d %12.4g' % (k, n, r))
+        for k, n in sorted(self.unchecked.items()):
+            lines.append('%-40s %8d %12s' % (k, n, 'UNCHECKED'))
+        return '\n'.join(lines)
+
+    def assert_clean(self):
+        assert not self.unchecked, 'entry points without a reference: %s' % dict(self.unchecked)
+        assert not self.fails, 'launches over the bound:\n' + '\n'.join(
+            '%s %s: %.4g' % f for f in self.fails[:20])
+
+    # -- the wrapper
+    def call(self, name, *args):
+        fn = getattr(self, '_' + name[len('mrcnn_'):], None)
+        if fn is None:
+            if name not in self.allowed:
+                self.unchecked[name] += 1
+            return self._orig(name, *args)
+        torch.cuda.synchronize()
+        post = fn(*args)                  # reads the operands, returns the checker of the outputs
+        self._orig(name, *args)
+        torch.cuda.synchronize()
+        with torch.no_grad():
+            for r, detail in post():
+                self._record(name, r, detail)
+        del post
+        torch.cuda.synchronize()
+
+    # ---- convolution family ------------------------------------------------------------------
+    @staticmethod
+    def _dims(d):
+        return (d.N, d.H, d.W, d.C, d.K, d.R, d.S, d.stride, d.pad, d.P, d.Q)
+
+    def _conv2d_fwd(self, dp, x, w, bias, scale, shift, residual, y, flags, split_ws, stream):
+        d = _d(dp)
+        N, H, W, C, K, R, S, st, pd, P, Q = self._dims(d)
+        X = _nchw(read(x, (N, H, W, C)), N, H, W, C)
+        Wt = _krsc(read(w, (K, R, S, C)), K, R, S, C)
+        b, sc, sh = (read(p, (K,)) for p in (bias, scale, shift))
+        res = _nchw(read(residual, (N, P, Q, K)), N, P, Q, K)
+
+        def post():
+            ref = fwd_epilogue(conv_fwd(X, Wt, st, pd), flags, *(None if t is None else t.to(F64)
+                                                               for t in (b, sc, sh)), res)
+            got = _nchw(read(y, (N, P, Q, K)), N, P, Q, K)
+            yield ratio(got, ref), _desc_str(d, flags)
+        return post
+
+    def _dgrad_common(self, d, gy, wfull, row_scale, gx, flags, res_g, res_y, mask, oscale,
+                      form):
+        N, H, W, C, K, R, S, st, pd, P, Q = self._dims(d)
+        G = _nchw(read(gy, (N, P, Q, K)), N, P, Q, K)
+        prev = _nchw(read(gx, (N, H, W, C)), N, H, W, C) if flags & EPI_ACCUM else None
+        rg = _nchw(read(res_g, (N, H, W, C)), N, H, W, C)
+        ry = _nchw(read(res_y, (N, H, W, C)), N, H, W, C)
+        my = _nchw(read(mask, (N, H, W, C)), N, H, W, C)
+        os_ = read(oscale, (C,))
+
+        def post():
+            g = G if row_scale is None else G * _per_c(row_scale.to(F64))
+            acc = conv_dgrad(g, wfull, H, W, st, pd)
+            ref = dgrad_epilogue(acc, flags, prev, rg, ry, my, None if os_ is None else os_.to(F64))
+            got = _nchw(read(gx, (N, H, W, C)), N, H, W, C)
+            yield ratio(got, ref), form + ' ' + _desc_str(d, flags)
+        return post
+
+    def _conv2d_dgrad(self, dp, gy, w, gx, flags, stream):
+        d = _d(dp)
+        Wt = _krsc(read(w, (d.K, d.R, d.S, d.C)), d.K, d.R, d.S, d.C)
+        return self._dgrad_common(d, gy, Wt, None, gx, flags, None, None, None, None, 'dgrad')
+
+    def _conv2d_dgrad_ex(self, dp, gy, w, gx, flags, res_g, res_y, mask, oscale, split_ws, stream):
+        d = _d(dp)
+        Wt = _krsc(read(w, (d.K, d.R, d.S, d.C)), d.K, d.R, d.S, d.C)
+        return self._dgrad_common(d, gy, Wt, None, gx, flags, res_g, res_y, mask, oscale,
+                                  'dgrad_ex')
+
+    def _conv2d_dgrad_wt(self, dp, gy, wT, gx, flags, res_g, res_y, mask, oscale, split_ws,
+                         stream):
+        d = _d(dp)
+        src = self.wt_of.get(_addr(wT))
+        if src is None:
+            raise AssertionError('mrcnn_conv2d_dgrad_wt: wT at 0x%x was not built by a checked '
+                                 'flip-transpose' % _addr(wT))
+        w, rs = src
+        Wt = _krsc(w, d.K, d.R, d.S, d.C)
+        return self._dgrad_common(d, gy, Wt, rs, gx, flags, res_g, res_y, mask, oscale, 'dgrad_wt')
+
+    def _wgrad_common(self, d, x, gy, gw, row_scale, form):
+        N, H, W, C, K, R, S, st, pd, P, Q = self._dims(d)
+        X = _nchw(read(x, (N, H, W, C)), N, H, W, C)
+        G = _nchw(read(gy, (N, P, Q, K)), N, P, Q, K)
+        rs = read(row_scale, (K,))
+
+        def post():
+            ref = conv_wgrad(X, G, R, S, st, pd)
+            if rs is not None:
+                ref = ref * rs.to(F64).view(-1, 1, 1, 1)
+            got = _krsc(read(gw, (K, R, S, C)), K, R, S, C)
+            yield ratio(got, ref), form + ' ' + _desc_str(d, 0)
+        return post
+
+    def _conv2d_wgrad(self, dp, x, gy, gw, ws, stream):
+        return self._wgrad_common(_d(dp), x, gy, gw, None, 'wgrad')
+
+    def _conv2d_wgrad_ex(self, dp, x, gy, gw, ws, row_scale, stream):
+        return self._wgrad_common(_d(dp), x, gy, gw, row_scale, 'wgrad_ex')
+
+    def _filter_flip_transpose(self, w, wT, K, R, S, C, row_scale, stream):
+        return self._flip_jobs([(w, wT, K, R, S, C, row_scale)])
+
+    def _filter_flip_transpose_batched(self, n, w, wT, K, R, S, C, row_scale, stream):
+        return self._flip_jobs([(w[i], wT[i], K[i], R[i], S[i], C[i], row_scale[i])
+                                for i in range(n)])
+
+    def _flip_jobs(self, jobs):
+        src = [(read(w, (K, R, S, C)), read(rs, (K,)), wT, (K, R, S, C)) for w, wT, K, R, S, C, rs
+               in jobs]
+
+        def post():
+            for w, rs, wT, (K, R, S, C) in src:
+                ref = w if rs is None else w * rs.view(-1, 1, 1, 1)
+                ref = ref.flip(1, 2).permute(3, 1, 2, 0).contiguous()     # (C,R,S,K)
+                self.wt_of[_addr(wT)] = (w, rs)
+                yield exact(read(wT, (C, R, S, K)), ref), 'K%d R%d S%d C%d' % (K, R, S, C)
+        return post
+
+    # ---- Winograd ----------------------------------------------------------------------------
+    def _conv3x3_wino_filter(self, dp, w, u, stream):
+        d = _d(dp)
+        W_ = read(w, (d.K, 3, 3, d.C))
+
+        def post():
+            self.u_of[_addr(u)] = W_
+            return iter(())
+        return post
+
+    def _conv3x3_wino_fwd(self, dp, x, w, u, scale, shift, y, flags, v, ws, stream):
+        d = _d(dp)
+        N, H, W, C, K, R, S, st, pd, P, Q = self._dims(d)
+        x32 = read(x, (N, H, W, C))
+        w32 = read(w, (K, 3, 3, C))
+        if w32 is None:
+            w32 = self.u_of.get(_addr(u))
+            if w32 is None:
+                raise AssertionError('wino_fwd: u at 0x%x has no checked filter transform' % _addr(u))
+        sc, sh = read(scale, (K,)), read(shift, (K,))
+
+        def post():
+            if _addr(v):
+                self.v_of[_addr(v)] = x32
+            X = _nchw(x32, N, H, W, C)
+            ref = conv_fwd(X, _krsc(w32, K, 3, 3, C), 1, 1)
+            f = flags & (EPI_AFFINE | EPI_BIAS | EPI_RELU)
+            if f & EPI_BIAS:
+                ref = fwd_epilogue(ref, f, bias=sh.to(F64))
+            else:
+                ref = fwd_epilogue(ref, f, scale=None if sc is None else sc.to(F64),
+                                   shift=None if sh is None else sh.to(F64))
+            got = _nchw(read(y, (N, P, Q, K)), N, P, Q, K)
+            yield ratio(got, ref), 'wino_fwd ' + _desc_str(d, flags)
+        return post
+
+    def _conv3x3_wino_dgrad(self, dp, gy, w, w_row_scale, gx, out_scale, out_mask_y, ws, stream):
+        d = _d(dp)
+        Wt = _krsc(read(w, (d.K, 3, 3, d.C)), d.K, 3, 3, d.C)
+        rs = read(w_row_scale, (d.K,))
+        return self._dgrad_common(d, gy, Wt, rs, gx, 0, None, None, out_mask_y, out_scale,
+                                  'wino_dgrad')
+
+    def _conv3x3_wino_wgrad(self, dp, x, v, gy, gw, out_row_scale, ws, stream):
+        d = _d(dp)
+        if not _addr(x):
+            src = self.v_of.get(_addr(v))
+            if src is None:
+                raise AssertionError('wino_wgrad: v at 0x%x has no checked forward' % _addr(v))
+            x = ctypes.c_void_p(src.data_ptr())
+            post = self._wgrad_common(d, x, gy, gw, out_row_scale, 'wino_wgrad(v)')
+            return post
+        return self._wgrad_common(d, x, gy, gw, out_row_scale, 'wino_wgrad(x)')
+
+    # ---- stem and deconvolution --------------------------------------------------------------
+    def _conv_stem_fwd(self, x4, w784, bias, scale, shift, y, N, H, W, K, flags, stream):
+        X = read(x4, (N, H, W, 4))[..., :3].permute(0, 3, 1, 2).to(F64)
+        Wt = read(w784, (K, 7, 8, 4))[:, :, :7, :3].permute(0, 3, 1, 2).to(F64)
+        b, sc, sh = (read(p, (K,)) for p in (bias, scale, shift))
+        P, Q = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+
+        def post():
+            ref = fwd_epilogue(conv_fwd(X, Wt, 2, 3), flags, *(None if t is None else t.to(F64)
+                                                            for t in (b, sc, sh)))
+            got = _nchw(read(y, (N, P, Q, K)), N, P, Q, K)
+            yield ratio(got, ref), 'stem N%d H%d W%d K%d f%d' % (N, H, W, K, flags)
+        return post
+
+    def _deconv_common(self, x, w, bias, y, N, H, W, C, K, flags, form):
+        X = _nchw(read(x, (N, H, W, C)), N, H, W, C)
+        b = read(bias, (K,))
+
+        def post():
+            ref = fwd_epilogue(deconv_fwd(X, w.view(C, 2, 2, K).permute(0, 3, 1, 2).to(F64)),
+                               flags, None if b is None else b.to(F64))
+            got = _nchw(read(y, (N, 2 * H, 2 * W, K)), N, 2 * H, 2 * W, K)
+            yield ratio(got, ref), '%s N%d H%d W%d C%d K%d f%d' % (form, N, H, W, C, K, flags)
+        return post
+
+    def _deconv2x2s2_fwd(self, x, w, bias, y, N, H, W, C, K, flags, stream):
+        return self._deconv_common(x, read(w, (C, 2, 2, K)), bias, y, N, H, W, C, K, flags,
+                                   'deconv_fwd')
+
+    def _deconv2x2s2_fwd_wt(self, x, wT, bias, y, N, H, W, C, K, flags, stream):
+        src = self.wt_of.get(_addr(wT))
+        if src is None or src[1] is not None:
+            raise AssertionError('deconv_fwd_wt: wT at 0x%x has no checked flip-transpose' % _addr(wT))
+        return self._deconv_common(x, src[0], bias, y, N, H, W, C, K, flags, 'deconv_fwd_wt')
+
+    def _deconv2x2s2_dgrad(self, gy, w, gx, N, H, W, C, K, stream):
+        G = _nchw(read(gy, (N, 2 * H, 2 * W, K)), N, 2 * H, 2 * W, K)
+        Wt = read(w, (C, 2, 2, K)).permute(0, 3, 1, 2).to(F64)
+
+        def post():
+            got = _nchw(read(gx, (N, H, W, C)), N, H, W, C)
+            yield ratio(got, deconv_dgrad(G, Wt)), 'deconv_dgrad N%d H%d W%d C%d K%d' % (N, H, W, C, K)
+        return post
+
+    def _deconv2x2s2_wgrad(self, x, gy, gw, N, H, W, C, K, ws, stream):
+        X = _nchw(read(x, (N, H, W, C)), N, H, W, C)
+        G = _nchw(read(gy, (N, 2 * H, 2 * W, K)), N, 2 * H, 2 * W, K)
+
+        def post():
+            got = read(gw, (C, 2, 2, K)).permute(0, 3, 1, 2)
+            yield ratio(got, deconv_wgrad(X, G)), 'deconv_wgrad N%d H%d W%d C%d K%d' % (N, H, W, C, K)
+        return post
+
+    # ---- row-sparse 3x3 backward ---------------------------------------------------------------
+    def _sparse3x3_gather(self, x, g, rows, n_rows, N, H, W, C, K, patches, g_rows, stream):
+        X = read(x, (N, H, W, C))
+        G = read(g, (N, H, W, K))
+        rw = read(rows, (n_rows,), torch.int32).long()
+
+        def post():
+            p_ref, g_ref = sparse3x3_gather(X, G, rw)
+            yield exact(read(patches, (n_rows, 3, 3, C)), p_ref), 'patches n%d C%d' % (n_rows, C)
+            yield exact(read(g_rows, (n_rows, K)), g_ref), 'g_rows n%d K%d' % (n_rows, K)
+        return post
+
+    def _sparse3x3_scatter(self, g_patches, lookup, N, H, W, C, gx, stream):
+        lk = read(lookup, (N, H, W), torch.int32)
+        n = int(lk.max()) + 1 if lk.numel() else 0
+        gp = read(g_patches, (max(n, 0), 3, 3, C))
+
+        def post():
+            ref = sparse3x3_scatter(gp.to(F64), lk, N, H, W, C)
+            yield ratio(read(gx, (N, H, W, C)), ref), 'scatter n%d N%d H%d W%d C%d' % (n, N, H, W, C)
+        return post
+
+    # ---- ROIAlign ------------------------------------------------------------------------------
+    def _roi_fwd(self, x, rois, y, N, H, W, C, R, PH, PW, bs, ss, sr, scale=None, shift=None,
+                 relu=0, form='roi_fwd_ex'):
+        X = read(x, (N, H, W, C))
+        ro = read(rois, (R, 5))
+        sc, sh = read(scale, (C,)), read(shift, (C,))
+        OH, OW = -(-PH // bs), -(-PW // bs)
+
+        def post():
+            ref = roi_align_fwd(X.to(F64), ro, PH, PW, ss, sr, bs)
+            if sc is not None:
+                ref = ref * sc.to(F64) + sh.to(F64)
+                if relu:
+                    ref = ref.clamp_min(0)
+            yield ratio(read(y, (R, OH, OW, C)), ref), '%s N%d H%d W%d C%d R%d %dx%d/%d relu%d' % (
+                form, N, H, W, C, R, PH, PW, bs, relu)
+        return post
+
+    def _roi_align_fwd_ex(self, x, rois, y, N, H, W, C, R, PH, PW, bs, ss, sr, order, stream):
+        return self._roi_fwd(x, rois, y, N, H, W, C, R, PH, PW, bs, ss, sr)
+
+    def _roi_align_fwd_affine(self, x, rois, y, N, H, W, C, R, PH, PW, bs, ss, sr, order, scale,
+                              shift, relu, stream):
+        return self._roi_fwd(x, rois, y, N, H, W, C, R, PH, PW, bs, ss, sr, scale, shift, relu,
+                             'roi_fwd_affine')
+
+    def _roi_align_bwd_ws(self, gy, rois, gx, N, H, W, C, R, PH, PW, bs, ss, sr, ws, ws_bytes,
+                          stream):
+        OH, OW = -(-PH // bs), -(-PW // bs)
+        G = read(gy, (R, OH, OW, C))
+        ro = read(rois, (R, 5))
+
+        def post():
+            ref = roi_align_bwd(G.to(F64), ro, (N, H, W, C), ss, sr, bs, PH, PW)
+            yield ratio(read(gx, (N, H, W, C)), ref), 'roi_bwd_ws N%d H%d W%d C%d R%d %dx%d/%d' % (
+                N, H, W, C, R, PH, PW, bs)
+        return post
+
+    # ---- elementwise, reductions, pools, optimiser -------------------------------------------
+    def _epilogue_bwd(self, gy, y, scale, g, M, C, stream):
+        G, Y, sc = read(gy, (M, C)), read(y, (M, C)), read(scale, (C,))
+
+        def post():
+            ref = G.to(F64)
+            if Y is not None:
+                ref = ref * (Y > 0)
+            if sc is not None:
+                ref = ref * sc.to(F64)
+            yield ratio(read(g, (M, C)), ref), 'M%d C%d' % (M, C)
+        return post
+
+    def _colsum(self, g, out, M, C, ws, stream):
+        G = read(g, (M, C))
+
+        def post():
+            yield ratio(read(out, (C,)), G.to(F64).sum(0)), 'M%d C%d' % (M, C)
+        return post
+
+    def _affine_fwd(self, x, w, b, y, M, C, stream):
+        X, Wt, B = read(x, (M, C)), read(w, (C,)), read(b, (C,))
+
+        def post():
+            yield ratio(read(y, (M, C)), X.to(F64) * Wt.to(F64) + B.to(F64)), 'M%d C%d' % (M, C)
+        return post
+
+    def _affine_bwd(self, x, w, gy, gx, gW, gb, M, C, ws, stream):
+        X, Wt, G = read(x, (M, C)), read(w, (C,)), read(gy, (M, C))
+
+        def post():
+            G64 = G.to(F64)
+            yield ratio(read(gx, (M, C)), G64 * Wt.to(F64)), 'gx M%d C%d' % (M, C)
+            if _addr(gW):
+                yield ratio(read(gW, (C,)), (G64 * X.to(F64)).sum(0)), 'gW M%d C%d' % (M, C)
+            if _addr(gb):
+                yield ratio(read(gb, (C,)), G64.sum(0)), 'gb M%d C%d' % (M, C)
+        return post
+
+    def _maxpool3x3s2p1_fwd(self, x, y, N, H, W, C, P, Q, stream):
+        X = read(x, (N, H, W, C))
+
+        def post():
+            ref = _nhwc(maxpool3x3s2p1(X.permute(0, 3, 1, 2)))
+            yield exact(read(y, (N, P, Q, C)), ref.contiguous()), 'N%d H%d W%d C%d' % (N, H, W, C)
+        return post
+
+    def _avgpool_fwd(self, x, y, R, HW, C, stream):
+        X = read(x, (R, HW, C))
+
+        def post():
+            yield ratio(read(y, (R, C)), X.to(F64).mean(1)), 'R%d HW%d C%d' % (R, HW, C)
+        return post
+
+    def _avgpool_bwd(self, gy, gx, R, HW, C, accumulate, stream):
+        G = read(gy, (R, C))
+        prev = read(gx, (R, HW, C)) if accumulate else None
+
+        def post():
+            ref = (G.to(F64) / HW)[:, None, :].expand(R, HW, C)
+            if prev is not None:
+                ref = ref + prev.to(F64)
+            yield ratio(read(gx, (R, HW, C)), ref), 'R%d HW%d C%d acc%d' % (R, HW, C, accumulate)
+        return post
+
+    def _head_tail_bwd(self, g_pool, g_rows, slot, y, g, R, HW, C, stream):
+        gp, Y = read(g_pool, (R, C)), read(y, (R, HW, C))
+        sl = read(slot, (R,), torch.int32)
+        gr = None
+        if sl is not None and _addr(g_rows):
+            nf = int(sl.max()) + 1 if R else 0
+            gr = read(g_rows, (max(nf, 0), HW, C))
+
+        def post():
+            ref = (gp.to(F64) / HW)[:, None, :].expand(R, HW, C).clone()
+            if gr is not None and gr.numel():
+                on = sl >= 0
+                ref[on] += gr.to(F64)[sl[on].long()]
+            ref = ref * (Y > 0)
+            yield ratio(read(g, (R, HW, C)), ref), 'R%d HW%d C%d' % (R, HW, C)
+        return post
+
+    def _sgd_momentum_wd_ex(self, p, g, v, n, lr, momentum, wd, grad_scale, zero_grad, stream):
+        P0, G0, V0 = read(p, (n,)), read(g, (n,)), read(v, (n,))
+
+        def post():
+            p2, v2, tp, tv = sgd(P0.to(F64), G0.to(F64), V0.to(F64), lr, momentum, wd, grad_scale)
+            for name, got, ref, tol in (('p', read(p, (n,)), p2, tp), ('v', read(v, (n,)), v2, tv)):
+                err = (got.to(F64) - ref).abs()
+                yield float((err / tol.clamp_min(1e-45)).max()) if n else 0., 'sgd %s n%d' % (name, n)
+            if zero_grad:
+                yield exact(read(g, (n,)), torch.zeros_like(G0)), 'sgd zero_grad n%d' % n
+        return post
+
+
+def _desc_str(d, flags):
+    return 'N%d H%d W%d C%d K%d %dx%d/s%d/p%d f%d' % (d.N, d.H, d.W, d.C, d.K, d.R, d.S, d.stride,
+                                                     d.pad, flags)

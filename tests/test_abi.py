@@ -127,6 +127,20 @@ def test_kernel_selection_switches_without_device(lib):
     assert rc != 0 and b'unknown option' in lib.mrcnn_last_error()
     with pytest.raises(_lib.MrcnnHipError):
         _lib.set_tuning('no_such_switch', 1)
+    # ROIAlign lane caps: whole waves up to the kernels' 256-lane bound; a rejected value keeps
+    # the previous one and leaves the library usable
+    for knob in (b'roi_fwd_lanes', b'roi_bwd_lanes'):
+        for bad in (32, 96, 320, -64, 1):
+            rc = lib.mrcnn_set_tuning(knob, bad)
+            assert rc != 0 and b'multiple of 64' in lib.mrcnn_last_error(), (knob, bad)
+        assert lib.mrcnn_set_tuning(knob, 64) == 0
+        assert lib.mrcnn_set_tuning(knob, 96) != 0
+        assert lib.mrcnn_set_tuning(knob, 0) == 0
+        with pytest.raises(_lib.MrcnnHipError, match='multiple of 64'):
+            _lib.set_tuning(knob.decode(), 32)
+        _lib.set_tuning(knob.decode(), 0)
+    assert lib.mrcnn_set_tuning(b'split_bf16', 3) == 0
+    assert lib.mrcnn_conv2d_split_workspace_bytes() > 0
     with pytest.raises(ValueError):
         conv.set_gemm_arithmetic('bf16')
     assert conv.DEFAULT_GEMM_ARITHMETIC == 'split_bf16x3'
