@@ -82,13 +82,15 @@ class _SoftmaxCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, t):
         _lib.require_device(x, t)
-        assert x.dim() == 2 and x.stride(1) == 1
+        # the strides of a tensor with fewer than two rows say nothing (an empty upload has (0, 0))
+        assert x.dim() == 2 and (x.stride(1) == 1 or x.shape[0] == 0)
         R, ncls = x.shape
+        ldx = x.stride(0) if R > 1 else ncls
         loss = _scalar(x.device)
         gx = torch.empty((R, ncls), dtype=torch.float32, device=x.device) \
             if x.requires_grad else None
         t = t.contiguous()
-        _lib.call('mrcnn_softmax_ce', _lib.ptr(x), x.stride(0), _lib.ptr(t), R,
+        _lib.call('mrcnn_softmax_ce', _lib.ptr(x), ldx, _lib.ptr(t), R,
                   ncls, _lib.ptr(loss), _lib.ptr(gx), ncls, _lib.ptr(_ws(x.device, R)),
                   _lib.stream_ptr())
         ctx.gx = gx

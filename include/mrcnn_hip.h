@@ -462,7 +462,10 @@ int mrcnn_sigmoid_ce(const float *x, const int32_t *t, int64_t n, float *loss,
                      float *gx, void *ws, void *stream);
 /* mask form: x (R, Kc, HW) NHWC rows = (R, HW, Kc); selects channel label[r]-1
  * for row r (models/mask_rcnn_train_chain.py:176-178); t (R,HW) in {-1,0,1};
- * gx (R,HW,Kc) fully written (zeros elsewhere). */
+ * gx (R,HW,Kc) fully written (zeros elsewhere).  A background row (label 0) selects
+ * channel Kc-1, as NumPy's index -1 does; its targets are normally all -1.
+ * Nothing counted (every t == -1, or R == 0): loss 0, gx 0, as mrcnn_sigmoid_ce and
+ * mrcnn_softmax_ce. */
 int mrcnn_mask_sigmoid_ce(const float *x, const int32_t *label, const int32_t *t,
                           int R, int HW, int Kc, float *loss, float *gx,
                           void *ws, void *stream);
@@ -471,7 +474,9 @@ int mrcnn_softmax_ce(const float *x, int ldx, const int32_t *t, int R, int ncls,
                      float *loss, float *gx, int ldg, void *ws, void *stream);
 /* _fast_rcnn_loc_loss: pred (n,4) [row r at pred + r*ld + 4*cls[r] when cls != NULL],
  * gt_loc (n,4), gt_label (n); in_weight = label>0; normaliser = #(label>=0).
- * gx written with the same addressing (caller zero-fills the rest). */
+ * gx written with the same addressing (caller zero-fills the rest).
+ * Nothing counted (every label < 0, or n == 0): loss is 0/0 = NaN, the original's
+ * unguarded division by #(label>=0); gx stays 0 (no row has label > 0). */
 int mrcnn_smooth_l1(const float *pred, int ld, const int32_t *cls,
                     const float *gt_loc, const int32_t *gt_label, int n,
                     float sigma, float *loss, float *gx, void *ws, void *stream);

@@ -21,7 +21,10 @@ tests/test_launch_ref_cpu.py checks them against the NumPy oracle on the CPU.
 Comparison (``ratio``): per element |got - ref| <= rel |ref| + floor max|ref| with the suite's
 convolution bound rel = 1e-4, floor = 1e-5 (tests/test_gpu_conv.py); the recorded figure is the
 worst |got - ref| / bound, a launch passes at <= 1.  Data movement and ops the header calls
-same-order are compared bit for bit against an fp32 restatement (``exact``).
+same-order are compared bit for bit against an fp32 restatement (``exact``).  The losses have
+bounds of their own, derived from the kernels' arithmetic in units of 2^-24 (``tol_ratio``, the
+comment above ``sigmoid_ce``): a loss is one number summed over up to 2^24 terms, and the suite's
+1e-4 would hide a lost element.
 """
 import collections
 import ctypes
@@ -69,6 +72,11 @@ def ratio(got, ref, rel=REL, floor=FLOOR):
 def exact(got, ref):
     """0 when bit-identical (fp32 restatement), inf otherwise."""
     return 0. if torch.equal(got.reshape(ref.shape), ref) else math.inf
+
+
+def _same_bits(got, ref):
+    """exact() on the bit patterns: untouched memory may hold NaNs."""
+    return exact(got.view(torch.int32), ref.view(torch.int32))
 
 
 # ---- float64 references (NCHW activations, KCRS filters, as chainer) ---------------------------
@@ -299,6 +307,233 @@ def sgd(p, g, v, lr, momentum, wd, grad_scale):
     return p2, v2, tp, tv
 
 
+# ---- losses (csrc/loss.hip) ------------------------------------------------------------------
+#
+# Bounds are in units of the fp32 unit roundoff u = 2^-24 (one correctly rounded operation has a
+# relative error of at most u; a function documented to n ulp has at most 2 n u).  The device math
+# library is built to the OpenCL full-profile limits expf <= 3 ulp, logf <= 3 ulp, log1pf <= 2 ulp
+# (the HIP math API documentation lists tighter figures; the wider, guaranteed ones are used), and
+# a / b is charged 1 ulp.  loss.hip is compiled without fast-math; FMA contraction only removes
+# roundings.
+#
+# Every loss is  (sum of element terms) / count  reduced as: each thread adds its grid-stride
+# elements in fp32 (`per_thread` adds), a 6-step fp32 butterfly over the 64 lanes, the four wave
+# sums and the <= 256 partials in double (errors of 2^-53, not counted), one division in double
+# and one rounding to fp32.  With every term of the sum bounded in magnitude by its share of
+# S = sum |term|, the error of the normalised loss is at most
+#     K_loss u S / count,     K_loss = K_el + per_thread + 6 + 1
+# where K_el bounds the relative error of one element term.  This is a worst-case (linear) bound;
+# the same reduction emulated on the CPU (tests/test_launch_ref_cpu.py) stays under 1 u at the
+# project's sizes, and one dropped element of mean size is 130 u at the RPN's n = 128 520 and
+# 83 u at the mask loss's 1024 x 196, so K_loss must stay under about 40 there (it is 22).
+#
+# Gradients are written per element as (f(x) - target) * (1 / count) with |f| <= 1, so their
+# bound is absolute in units of 1 / count:  K_g u max(1, A_r) / count  (A_r = 1 unless noted).
+U = 2. ** -24
+ULP_EXP, ULP_LOG, ULP_LOG1P, ULP_DIV = 3, 3, 2, 1
+# inv = 1.f / (float)count, then g * inv.  The conversion is exact below 2^24; above, its 1 u is
+# inside the slack of charging a correctly rounded division a full ulp.
+K_INV = 2 * ULP_DIV + 1
+
+# sigmoid CE element  max(x, 0) - x t + log1pf(expf(-|x|)):  x * (t - (x >= 0)) is a product with
+# -1, 0 or 1 (exact); e = expf(-|x|) carries 2 ULP_EXP u, which log1p passes on with a condition
+# number e / ((1 + e) log1p(e)) <= 1, plus log1pf's own 2 ULP_LOG1P u; both summands are >= 0, so
+# the final add costs 1 u of the element.
+K_SCE_EL = 2 * ULP_EXP + 2 * ULP_LOG1P + 1
+# sigmoid CE gradient (sigmoidf(x) - t) * inv,  sigmoidf = 1 / (1 + expf(-x)) <= 1: expf 2 ULP_EXP u
+# (condition of 1 / (1 + e) in e is <= 1), the add 1 u, the division 2 ULP_DIV u, then - t (|result|
+# <= 1) 1 u.  Absolute, because sigmoidf(20) - 1 is 0 in fp32 and -2e-9 in float64: the cancellation
+# is the formula's own (chainer's float32 sigmoid has it too).
+K_SCE_G = 2 * ULP_EXP + 1 + 2 * ULP_DIV + 1 + K_INV
+# smooth L1 element: d = pred - gt 1 u of d.  |d| < 1 / sigma^2: (sigma^2 / 2) d d, d's error twice,
+# two products, sigma * sigma: 5 u.  Otherwise |d| - 0.5 / sigma^2 >= |d| / 2: d's error doubles to
+# 2 u, the constant's division 2 ULP_DIV u of a term no larger than the result, the subtraction
+# 1 u, sigma * sigma 1 u: 6 u.  Value and gradient are continuous at the switch, so a branch taken
+# differently in fp32 and float64 changes nothing beyond these roundings.
+K_SL1_EL = 4 + 2 * ULP_DIV
+# smooth L1 gradient: sigma^2 d (|.| < 1): d 1 u, sigma * sigma 1 u, the product 1 u; or +-1, 0.
+K_SL1_G = 3 + K_INV
+
+
+def flat_parts(n):
+    """parts_for(n) of loss.hip: workgroups of the flat kernels' first pass."""
+    return max(1, min(256, -(-int(n) // 1024)))
+
+
+def row_parts(R):
+    """First-pass workgroups of softmax CE (four rows, one per wave, per workgroup)."""
+    return max(1, min(256, -(-int(R) // 4)))
+
+
+def k_loss(k_el, per_thread):
+    return k_el + per_thread + 6 + 1
+
+
+def k_softmax_z(ncls):
+    """Relative error of z = sum_k expf(x_k - m), in u: expf 2 ULP_EXP; the rounding of x_k - m is
+    u |x_k - m| in the exponent, weighted by p_k it sums to at most u ln(ncls) (the mean of m - x_k
+    under the softmax weights is the entropy minus ln z); ceil(ncls / 64) adds per lane and 6
+    butterfly steps on non-negative terms."""
+    return 2 * ULP_EXP + math.log(ncls) + -(-ncls // 64) + 6
+
+
+def k_softmax_lse(ncls):
+    """Absolute error of lse = m + logf(z) in u max(1, |lse|): z's relative error is an absolute
+    error of log z; logf 2 ULP_LOG u of log z <= ln(ncls); the add 1 u of lse."""
+    return k_softmax_z(ncls) + 2 * ULP_LOG * max(1., math.log(ncls)) + 1
+
+
+def _tol_like(valid, value):
+    return torch.where(valid, value, torch.zeros_like(value))
+
+
+def tol_ratio(got, ref, tol):
+    """Worst |got - ref| / tol over the elements (<= 1: within the bound).  Where tol is 0 the
+    values must be equal.  NaN matches NaN; a value equal to the float64 reference rounded to
+    fp32 always passes (a reference beyond FLT_MAX rounds to inf, and so must the kernel).  Any
+    other non-finite value or difference gives inf.  Empty tensors give 0."""
+    ref = ref.to(F64)
+    got = got.to(device=ref.device, dtype=F64).reshape(ref.shape)
+    if ref.numel() == 0:
+        return 0.
+    tol = torch.as_tensor(tol, dtype=F64, device=ref.device).expand(ref.shape)
+    same = (got == ref) | (got == ref.float().to(F64)) | (torch.isnan(got) & torch.isnan(ref))
+    err = (got - ref).abs()
+    r = torch.where(same, torch.zeros_like(err), err / tol)
+    r = torch.where(torch.isnan(r), torch.full_like(r, math.inf), r)
+    return float(r.max())
+
+
+def _sce_terms(x, t):
+    valid = t != -1
+    tt = t.to(F64)
+    el = x.clamp_min(0) - x * tt + torch.log1p(torch.exp(-x.abs()))
+    el = torch.where(valid, el, torch.zeros_like(el))
+    g = torch.where(valid, torch.sigmoid(x) - tt, torch.zeros_like(x))
+    return valid, el, g
+
+
+def sigmoid_ce(x, t):
+    """F.sigmoid_cross_entropy(x, t): x float64 (any shape), t integer in {-1, 0, 1}, -1 ignored;
+    loss = sum over the rest of  max(x, 0) - x t + log1p(exp(-|x|))  / max(count, 1),
+    gx = (sigmoid(x) - t) / max(count, 1), 0 where ignored.
+    Returns (loss, gx, loss_tol, gx_tol): the bounds of the module comment with K_el = K_SCE_EL,
+    per_thread = ceil(n / (256 flat_parts(n))), K_g = K_SCE_G; gx_tol is 0 where t is ignored (the
+    kernel writes an exact 0 there)."""
+    valid, el, g = _sce_terms(x, t)
+    n = x.numel()
+    count = max(int(valid.sum()), 1)
+    per_thread = -(-n // (256 * flat_parts(n)))
+    S = el.sum()
+    loss_tol = k_loss(K_SCE_EL, per_thread) * U * S / count
+    g_tol = _tol_like(valid, torch.full_like(x, K_SCE_G * U / count))
+    return S / count, g / count, loss_tol, g_tol
+
+
+def mask_sigmoid_ce(x, label, t):
+    """F.sigmoid_cross_entropy(x[arange(R), :, label - 1], t): x (R, HW, Kc) float64, label (R),
+    t (R, HW).  The channel index label - 1 follows NumPy: a background row (label 0) selects
+    channel Kc - 1.  gx (R, HW, Kc) is 0 outside the selected channel.  Bounds as sigmoid_ce with
+    n = R HW; gx_tol is 0 wherever gx must be an exact 0."""
+    R, HW, Kc = x.shape
+    ch = torch.remainder(label.long() - 1, Kc)
+    sel = torch.gather(x, 2, ch.view(R, 1, 1).expand(R, HW, 1)).squeeze(2)
+    loss, g_sel, loss_tol, g_sel_tol = sigmoid_ce(sel, t)
+    gx = torch.zeros_like(x)
+    g_tol = torch.zeros_like(x)
+    idx = ch.view(R, 1, 1).expand(R, HW, 1)
+    gx.scatter_(2, idx, g_sel.unsqueeze(2))
+    g_tol.scatter_(2, idx, g_sel_tol.unsqueeze(2))
+    return loss, gx, loss_tol, g_tol
+
+
+def _softmax_scale(x, lse):
+    """max(1, A_r), A_r = max(|lse_r|, max_k |x_rk|) over the finite logits: the operands whose
+    rounding enters expf's argument."""
+    finite = torch.where(torch.isfinite(x), x.abs(), torch.zeros_like(x))
+    return torch.maximum(lse.abs(), finite.max(1).values).clamp_min(1.)
+
+
+def softmax_ce(x, t):
+    """F.softmax_cross_entropy(x (R, ncls) float64, t (R) integer), ignore_label -1:
+    loss = sum over valid rows of (lse_r - x[r, t_r]) / max(count, 1), lse = logsumexp,
+    gx[r, k] = (exp(x_rk - lse_r) - [k == t_r]) / max(count, 1), rows of 0 where ignored.
+    Loss bound: S = sum over valid rows of |lse_r| + |x[r, t_r]| (the two cancel for a confident
+    row), K_el = k_softmax_lse(ncls) + 1 (the subtraction), per_thread = rows per wave
+    = ceil(R / (4 row_parts(R))).  The part of lse's error that does not scale with |lse| (z's
+    relative error, logf's error of log z) is charged to S as if |lse_r| + |x[r, t_r]| >= 1 on the
+    average row, which holds for every input of the suite and the step (lse is near ln(ncls) for an
+    untrained head) but not for rows whose target logit is dominant and exactly 0.
+    Gradient bound: K_g u max(1, A_r) / count with A_r of _softmax_scale and
+    K_g = 2 (x - lse rounds to u (|x| + |lse|) in expf's argument) + k_softmax_lse + 2 ULP_EXP
+    + 1 (the subtraction) + K_INV; 0 on ignored rows."""
+    R, ncls = x.shape
+    valid = t != -1
+    count = max(int(valid.sum()), 1)
+    lse = torch.logsumexp(x, 1) if R else x.new_zeros((0,))
+    tt = torch.where(valid, t, torch.zeros_like(t)).long()
+    xt = torch.gather(x, 1, tt.view(R, 1)).squeeze(1) if R else x.new_zeros((0,))
+    zero = torch.zeros_like(lse)
+    loss = torch.where(valid, lse - xt, zero).sum() / count
+    S = torch.where(valid, lse.abs() + xt.abs(), zero).sum()
+    per_thread = -(-R // (4 * row_parts(R)))
+    loss_tol = k_loss(k_softmax_lse(ncls) + 1, per_thread) * U * S / count
+    p = torch.exp(x - lse.view(R, 1))
+    onehot = torch.zeros_like(x)
+    if R:
+        onehot.scatter_(1, tt.view(R, 1), 1.)
+    gx = torch.where(valid.view(R, 1), (p - onehot) / count, torch.zeros_like(x))
+    k_g = 2 + k_softmax_lse(ncls) + 2 * ULP_EXP + 1 + K_INV
+    g_tol = torch.where(valid, k_g * U * _softmax_scale(x, lse) / count, zero)
+    g_tol = g_tol.view(R, 1).expand(R, ncls)
+    return loss, gx, loss_tol, g_tol
+
+
+def softmax(x):
+    """F.softmax(x (R, ncls) float64, axis 1).  Returns (y, y_tol): expf(x - m) / z with
+    K = 2 (x - m rounds to u (|x| + |m|) in expf's argument, y <= 1) + 2 ULP_EXP + k_softmax_z
+    + 2 ULP_DIV, times u max(1, A_r)."""
+    R, ncls = x.shape
+    if R == 0:
+        return x.clone(), x.clone()
+    lse = torch.logsumexp(x, 1)
+    y = torch.exp(x - lse.view(R, 1))
+    k = 2 + 2 * ULP_EXP + k_softmax_z(ncls) + 2 * ULP_DIV
+    return y, (k * U * _softmax_scale(x, lse)).view(R, 1).expand(R, ncls)
+
+
+def smooth_l1(pred, cls, gt_loc, gt_label, sigma):
+    """_fast_rcnn_loc_loss: pred (n, ld) float64, row r's 4-vector at columns 4 cls[r] .. + 4
+    (0 .. 4 when cls is None), gt_loc (n, 4), gt_label (n).  With d = pred4 - gt_loc on rows of label > 0:
+    element = (sigma^2 / 2) d^2 if |d| < 1 / sigma^2 else |d| - 0.5 / sigma^2, loss = sum / count,
+    count = #(label >= 0) WITHOUT a guard: nothing counted gives 0 / 0 = NaN, as the original.
+    gx (n, ld) = (sigma^2 d | sign(d)) / count in the selected columns of label > 0 rows, else 0.
+    Bounds: K_el = K_SL1_EL, per_thread = 4 ceil(n / (256 flat_parts(n))), K_g = K_SL1_G; gx_tol
+    is 0 wherever gx is an exact 0 (rows of label <= 0, columns outside the selection)."""
+    n, ld = pred.shape
+    s2 = float(sigma) ** 2
+    c = torch.zeros((n,), dtype=torch.int64, device=pred.device) if cls is None else cls.long()
+    cols = (4 * c).view(n, 1) + torch.arange(4, device=pred.device).view(1, 4)
+    d = torch.gather(pred, 1, cols) - gt_loc if n else pred.new_zeros((0, 4))
+    fg = (gt_label > 0).view(n, 1)
+    a = d.abs()
+    quad = a < 1. / s2
+    el = torch.where(quad, (s2 / 2.) * d * d, a - 0.5 / s2)
+    el = torch.where(fg, el, torch.zeros_like(el))
+    g = torch.where(quad, s2 * d, torch.sign(d))
+    count = (gt_label >= 0).sum().to(F64)
+    S = el.sum()
+    per_thread = 4 * -(-n // (256 * flat_parts(n)))
+    loss_tol = k_loss(K_SL1_EL, per_thread) * U * S / count
+    gx = torch.zeros_like(pred)
+    g_tol = torch.zeros_like(pred)
+    if n:
+        gx.scatter_(1, cols, torch.where(fg, g / count, torch.zeros_like(g)))
+        g_tol.scatter_(1, cols, torch.where(fg, (K_SL1_G * U / count).expand(n, 4),
+                                            torch.zeros_like(g)))
+    return S / count, gx, loss_tol, g_tol
+
+
 # ---- reading operands by address -------------------------------------------------------------
 
 _hip = None
@@ -383,11 +618,6 @@ ALLOWED = {
     'mrcnn_anchor_targets_finish': 'tests/test_gpu_targets.py',
     'mrcnn_proposal_targets_gather': 'tests/test_gpu_targets.py',
     'mrcnn_mask_targets': 'tests/test_gpu_targets.py',
-    'mrcnn_sigmoid_ce': 'tests/test_gpu_losses.py',
-    'mrcnn_mask_sigmoid_ce': 'tests/test_gpu_losses.py',
-    'mrcnn_softmax_ce': 'tests/test_gpu_losses.py',
-    'mrcnn_smooth_l1': 'tests/test_gpu_losses.py',
-    'mrcnn_softmax': 'tests/test_gpu_losses.py',
     'mrcnn_observe_accumulate': 'tests/test_gpu_trainer.py (loss observation)',
     'mrcnn_prepare_image': 'tests/test_gpu_inference.py (image preparation)',
     'mrcnn_paste_masks': 'tests/test_gpu_inference.py (mask pasting)',
@@ -811,6 +1041,91 @@ class LaunchChecker:
                 yield float((err / tol.clamp_min(1e-45)).max()) if n else 0., 'sgd %s n%d' % (name, n)
             if zero_grad:
                 yield exact(read(g, (n,)), torch.zeros_like(G0)), 'sgd zero_grad n%d' % n
+        return post
+
+    # ---- losses ----------------------------------------------------------------------------------
+    @staticmethod
+    def _rows(addr, R, ncols, ld, dtype=torch.float32):
+        """(R, ncols) view of the rows at `addr` with row stride ld, and the flat copy behind it."""
+        if R == 0 or not _addr(addr):
+            return torch.empty((R, ncols), dtype=dtype, device='cuda'), None
+        flat = read(addr, ((R - 1) * ld + ncols,), dtype)
+        return flat.as_strided((R, ncols), (ld, 1)), flat
+
+    def _loss_post(self, loss, gx, ref, detail, got_gx):
+        """The checks every loss shares: ref = (loss, gx, loss_tol, gx_tol) in float64."""
+        l_ref, g_ref, l_tol, g_tol = ref
+        yield tol_ratio(read(loss, ()), l_ref, l_tol), 'loss ' + detail
+        if _addr(gx):
+            yield tol_ratio(got_gx(), g_ref, g_tol), 'gx ' + detail
+
+    def _sigmoid_ce(self, x, t, n, loss, gx, ws, stream):
+        X = read(x, (n,)) if n else torch.empty((0,), device='cuda')
+        T = read(t, (n,), dtype=torch.int32) if n else torch.empty((0,), dtype=torch.int32,
+                                                                   device='cuda')
+
+        def post():
+            yield from self._loss_post(loss, gx, sigmoid_ce(X.to(F64), T), 'n%d' % n,
+                                       lambda: read(gx, (n,)) if n else X)
+        return post
+
+    def _mask_sigmoid_ce(self, x, label, t, R, HW, Kc, loss, gx, ws, stream):
+        def rd(a, shape, dtype=torch.float32):
+            return read(a, shape, dtype) if R else torch.empty(shape, dtype=dtype, device='cuda')
+        X, Lb, T = rd(x, (R, HW, Kc)), rd(label, (R,), torch.int32), rd(t, (R, HW), torch.int32)
+
+        def post():
+            yield from self._loss_post(loss, gx, mask_sigmoid_ce(X.to(F64), Lb, T),
+                                       'R%d HW%d Kc%d' % (R, HW, Kc), lambda: rd(gx, (R, HW, Kc)))
+        return post
+
+    def _softmax_ce(self, x, ldx, t, R, ncls, loss, gx, ldg, ws, stream):
+        X, _ = self._rows(x, R, ncls, ldx)
+        T = read(t, (R,), dtype=torch.int32) if R else torch.empty((0,), dtype=torch.int32,
+                                                                   device='cuda')
+        _, before = self._rows(gx, R, ncls, ldg)
+        detail = 'R%d ncls%d ldx%d ldg%d' % (R, ncls, ldx, ldg)
+
+        def post():
+            got, after = self._rows(gx, R, ncls, ldg)
+            yield from self._loss_post(loss, gx, softmax_ce(X.to(F64), T), detail, lambda: got)
+            if after is not None and ldg > ncls:
+                before.as_strided((R, ncls), (ldg, 1)).copy_(got)
+                yield _same_bits(after, before), 'gx padding untouched ' + detail
+        return post
+
+    def _softmax(self, x, ldx, y, ldy, R, ncls, stream):
+        X, _ = self._rows(x, R, ncls, ldx)
+        _, before = self._rows(y, R, ncls, ldy)
+        detail = 'R%d ncls%d ldx%d ldy%d' % (R, ncls, ldx, ldy)
+
+        def post():
+            got, after = self._rows(y, R, ncls, ldy)
+            ref, tol = softmax(X.to(F64))
+            yield tol_ratio(got, ref, tol), 'y ' + detail
+            if after is not None and ldy > ncls:
+                before.as_strided((R, ncls), (ldy, 1)).copy_(got)
+                yield _same_bits(after, before), 'y padding untouched ' + detail
+        return post
+
+    def _smooth_l1(self, pred, ld, cls, gt_loc, gt_label, n, sigma, loss, gx, ws, stream):
+        def rd(a, shape, dtype=torch.float32):
+            return read(a, shape, dtype) if n else torch.empty(shape, dtype=dtype, device='cuda')
+        P, G, Lb = rd(pred, (n, ld)), rd(gt_loc, (n, 4)), rd(gt_label, (n,), torch.int32)
+        C = rd(cls, (n,), torch.int32) if _addr(cls) else None
+        before = rd(gx, (n, ld)) if _addr(gx) else None
+        detail = 'n%d ld%d cls%d sigma%g' % (n, ld, C is not None, sigma)
+
+        def post():
+            ref = smooth_l1(P.to(F64), C, G.to(F64), Lb, sigma)
+            after = rd(gx, (n, ld)) if before is not None else None
+            yield from self._loss_post(loss, gx, ref, detail, lambda: after)
+            if after is not None and n:
+                # the kernel writes the selected 4-vector of every row and nothing else
+                c = torch.zeros((n,), dtype=torch.int64, device='cuda') if C is None else C.long()
+                cols = (4 * c).view(n, 1) + torch.arange(4, device='cuda').view(1, 4)
+                expect = before.scatter(1, cols, torch.gather(after, 1, cols))
+                yield _same_bits(after, expect), 'gx outside the selection untouched ' + detail
         return post
 
 

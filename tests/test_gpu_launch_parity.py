@@ -7,7 +7,9 @@ the final flush, and during a full-size batch-8 inference, is compared with its 
 restatement on the device — at the shapes where the GEMM host code takes the routes the small
 tests never reach (W8 256x128 tiles, the one-round big_split_k rule, fused-tail K-split pieces,
 tiny_split, strided 1x1 data gradients on the transposed filter, split-K weight gradients, the
-PW / K3 instantiations, the Winograd route at the shipped threshold).  Then the non-default
+PW / K3 instantiations, the Winograd route at the shipped threshold).  The five losses and the
+inference softmax are among them: in place, with the step's label distributions and the strides of
+the fused cls_loc / score layer's output, under the bounds derived in tests/launch_ref.py.  Then the non-default
 settings of those routes and the ROIAlign lane caps on a RoI-head and a backbone block.
 """
 import ctypes
@@ -35,6 +37,9 @@ TRAIN_CHECKED = {
     'mrcnn_roi_align_fwd_affine', 'mrcnn_roi_align_bwd_ws', 'mrcnn_avgpool_fwd',
     'mrcnn_head_tail_bwd', 'mrcnn_deconv2x2s2_fwd_wt', 'mrcnn_deconv2x2s2_dgrad',
     'mrcnn_deconv2x2s2_wgrad', 'mrcnn_colsum', 'mrcnn_sgd_momentum_wd_ex',
+    # the five losses, in place: 256 sampled anchors of 128 520, 1024 RoIs on the fused
+    # cls_loc / score layer's 408-wide rows, the foreground-only mask rows
+    'mrcnn_sigmoid_ce', 'mrcnn_smooth_l1', 'mrcnn_softmax_ce', 'mrcnn_mask_sigmoid_ce',
 }
 
 
@@ -139,7 +144,8 @@ def test_inference_launches_match_float64(dev, monkeypatch):
     chk.assert_clean()
     assert sum(len(b) for b in bboxes) > 0
     assert {'mrcnn_conv_stem_fwd', 'mrcnn_maxpool3x3s2p1_fwd', 'mrcnn_conv2d_fwd',
-            'mrcnn_conv3x3_wino_fwd', 'mrcnn_avgpool_fwd'} <= set(chk.stats), sorted(chk.stats)
+            'mrcnn_conv3x3_wino_fwd', 'mrcnn_avgpool_fwd', 'mrcnn_softmax'} <= set(chk.stats), \
+        sorted(chk.stats)
 
 
 def _head_block(dev):
