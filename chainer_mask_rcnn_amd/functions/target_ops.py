@@ -9,10 +9,13 @@ from .. import _lib
 
 def bbox_iou_argmax(boxes_a, boxes_b, want_matrix=False):
     """chainercv ``bbox_iou(a, b)`` reduced per row of ``a``: (max_iou (na,) f32, argmax (na,)
-    i32[, iou (na,g), col_max (g,)])."""
+    i32[, iou (na,g), col_max (g,)]).  No rows and ``want_matrix``: ValueError, as NumPy's max of
+    an empty column (the library writes no col_max then)."""
     _lib.require_device(boxes_a, boxes_b)
     boxes_a, boxes_b = boxes_a.contiguous(), boxes_b.contiguous()
     na, g = boxes_a.shape[0], boxes_b.shape[0]
+    if want_matrix and na == 0:
+        raise ValueError('bbox_iou_argmax: column maxima of an IoU matrix without rows')
     dev = boxes_a.device
     best = torch.empty((na,), dtype=torch.float32, device=dev)
     arg = torch.empty((na,), dtype=torch.int32, device=dev)

@@ -702,7 +702,9 @@ int mrcnn_decode_cls_boxes(const float *roi, const float *cls_loc, int ld_loc,
  * targets, 14x14 mask targets.  The np.random draws stay with the caller (host), which reads
  * max_iou / the anchor labels back, draws, and passes the chosen indices in. */
 /* chainercv bbox_iou(boxes_a (na,4), boxes_b (g,4)) reduced per row: max_iou (na), first
- * argmax (na); optional full matrix iou (na,g) and its column maxima col_max (g). */
+ * argmax (na); optional full matrix iou (na,g) and its column maxima col_max (g).
+ * na == 0 returns at once and writes nothing: an empty column has no maximum (NumPy's max
+ * raises), so col_max keeps its contents and the caller must not read it. */
 int mrcnn_bbox_iou_argmax(const float *boxes_a, int na, const float *boxes_b, int g,
                           float *iou, float *max_iou, int32_t *argmax, float *col_max,
                           void *stream);

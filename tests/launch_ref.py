@@ -25,6 +25,18 @@ same-order are compared bit for bit against an fp32 restatement (``exact``).  Th
 bounds of their own, derived from the kernels' arithmetic in units of 2^-24 (``tol_ratio``, the
 comment above ``sigmoid_ce``): a loss is one number summed over up to 2^24 terms, and the suite's
 1e-4 would hide a lost element.
+
+The device half of the target creators (csrc/targets.hip) produces integer decisions, so it is
+checked in two layers (the comment above ``K_IOU``).  Arithmetic — the IoU matrix, its row and
+column maxima, ``bbox2loc`` — against a float64 restatement under bounds derived from the kernels'
+operation count, again in units of 2^-24: K_IOU = 16 relative for an IoU; for ``bbox2loc``
+dy, dx:  u ((|src centre| + |dst centre| + (|src size| + |dst size|) / 2) / size + 3 |dy|),
+dh, dw:  u (3 + |dh|), and the normalised target adds 2 u of itself; non-finite values must sit at
+the reference's positions with its class and sign.  Decisions — argmax, labels, gathers, scatter
+patterns, mask targets — exactly: as functions of the kernel's own fp32 values where those are
+outputs, else against the NumPy fp32 restatement in the reference's operation order.  These
+references are NumPy on the host (the arrays are small) and are pure functions of the operands and
+outputs, so tests/test_launch_ref_cpu.py runs them on emulated kernels, right and wrong.
 """
 import collections
 import ctypes
@@ -534,6 +546,206 @@ def smooth_l1(pred, cls, gt_loc, gt_label, sigma):
     return S / count, gx, loss_tol, g_tol
 
 
+# ---- target creators (csrc/targets.hip) ------------------------------------------------------
+#
+# NumPy on the host: each check_* takes the operands and the kernel's outputs as arrays and yields
+# (ratio, what) like a LaunchChecker post().  Box coordinates are fp32 values, so every first
+# difference (br - tl, y1 - y0) of exact inputs carries one rounding, 1 u relative.
+#
+# IoU = I / ((A + B) - I):  I, A, B are products of two such differences: 3 u each.  A + B: 4 u of
+# A + B.  D = (A + B) - I:  4 u (A + B) + 3 u I + 1 u D in absolute terms; I <= min(A, B) gives
+# A + B <= 2 D and I <= D, so D carries 12 u.  The division adds 1 u:  K_IOU = 3 + 12 + 1 = 16,
+# relative to the IoU (an IoU of exactly 0 has I = 0 exactly and must be 0).  A row or column
+# maximum is one of those values, so it is within 16 u of the float64 maximum.  0 / 0 (two
+# zero-area boxes) is NaN in both.
+K_IOU = 16
+# bbox2loc (src -> dst), per axis with s = src size, c_s = src centre, d, c_d likewise:
+#   s, d:  1 u.   c = lo + 0.5 s:  0.5 u |s| + 1 u |c| absolute (0.5 s is exact).
+#   dy = (c_d - c_s) / max(s, eps):  numerator u (0.5 |s| + |c_s| + 0.5 |d| + |c_d| + |c_d - c_s|),
+#     the divisor's 1 u and the division's 1 u:
+#     tol_dy = u ((0.5 |s| + |c_s| + 0.5 |d| + |c_d|) / s + 3 |dy|)
+#   dh = (float) log((double) (d / s)):  d / s carries 3 u, which the logarithm turns into 3 u
+#     absolute; the double log is exact at this scale; the rounding to fp32 1 u of |dh|:
+#     tol_dh = u (3 + |dh|).   d = 0 gives -inf, d < 0 NaN, in both.
+#   normalised (x - mean) / std with fp32 mean, std:  tol_x / |std| + 2 u |result|.
+
+
+def _np_tol(got, ref, tol):
+    """tol_ratio on NumPy arrays; the bound counts only where the reference is finite."""
+    ref = np.asarray(ref, np.float64)
+    tol = np.where(np.isfinite(ref), np.broadcast_to(np.asarray(tol, np.float64), ref.shape), 0.)
+    got = np.asarray(got)
+    if got.shape != ref.shape:
+        return math.inf
+    return tol_ratio(torch.from_numpy(np.ascontiguousarray(got)), torch.from_numpy(ref),
+                     torch.from_numpy(np.ascontiguousarray(tol)))
+
+
+def _np_exact(got, ref):
+    """0 when equal element for element (NaN equal to NaN, -0 to 0), inf otherwise."""
+    got, ref = np.asarray(got), np.asarray(ref)
+    if got.shape != ref.shape:
+        return math.inf
+    if got.dtype.kind == 'f' or ref.dtype.kind == 'f':
+        return 0. if np.array_equal(got, ref, equal_nan=True) else math.inf
+    return 0. if np.array_equal(got, ref) else math.inf
+
+
+def _np_bits(got, ref):
+    """0 when the two arrays hold the same bytes."""
+    got, ref = np.ascontiguousarray(got), np.ascontiguousarray(ref)
+    same = got.shape == ref.shape and got.dtype == ref.dtype and got.tobytes() == ref.tobytes()
+    return 0. if same else math.inf
+
+
+def bbox_iou_f64(a, b):
+    """chainercv bbox_iou in float64: (na, g)."""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    out = np.empty((len(a), len(b)))
+    with np.errstate(invalid='ignore', divide='ignore'):
+        area_b = np.prod(b[:, 2:] - b[:, :2], axis=1)
+        for i0 in range(0, len(a), 8192):
+            x = a[i0:i0 + 8192]
+            tl = np.maximum(x[:, None, :2], b[None, :, :2])
+            br = np.minimum(x[:, None, 2:], b[None, :, 2:])
+            inter = np.prod(br - tl, axis=2) * (tl < br).all(axis=2)
+            area_a = np.prod(x[:, 2:] - x[:, :2], axis=1)
+            out[i0:i0 + 8192] = inter / (area_a[:, None] + area_b[None, :] - inter)
+    return out
+
+
+def bbox_iou_f32(a, b):
+    """oracle.np_ref.bbox_iou (fp32, the reference's operation order), in row chunks."""
+    from oracle import np_ref
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        parts = [np_ref.bbox_iou(a[i0:i0 + 8192], b) for i0 in range(0, len(a), 8192)]
+    return np.concatenate(parts, 0) if parts else np.empty((0, len(b)), np.float32)
+
+
+def check_bbox_iou_argmax(a, b, max_iou, argmax, iou=None, col_max=None):
+    """mrcnn_bbox_iou_argmax.  The matrix against float64 under K_IOU; max_iou / argmax / col_max as
+    np.max / np.argmax (first index of the maximum, a NaN wins and propagates) of the kernel's own
+    matrix when it is an output, else of the fp32 restatement; both maxima against float64."""
+    na = len(a)
+    if na == 0:
+        return
+    ref = bbox_iou_f64(a, b)
+    if iou is not None:
+        yield _np_tol(iou, ref, K_IOU * U * np.abs(ref)), 'iou vs float64'
+    own = iou if iou is not None else bbox_iou_f32(a, b)
+    yield _np_exact(max_iou, own.max(axis=1)), 'max_iou is the row maximum'
+    yield _np_exact(argmax, own.argmax(axis=1).astype(np.int32)), 'argmax is its first index'
+    m = ref.max(axis=1)
+    yield _np_tol(max_iou, m, K_IOU * U * np.abs(m)), 'max_iou vs float64'
+    if col_max is not None:
+        yield _np_exact(col_max, own.max(axis=0)), 'col_max is the column maximum'
+        m = ref.max(axis=0)
+        yield _np_tol(col_max, m, K_IOU * U * np.abs(m)), 'col_max vs float64'
+
+
+def anchor_labels_ref(iou, max_iou, gt_max, neg_iou_thresh, pos_iou_thresh):
+    """chainercv AnchorTargetCreator._create_label before the draws, in its statement order, on
+    fp32 values (the thresholds arrive as C floats)."""
+    label = np.full((len(iou),), -1, np.int32)
+    with np.errstate(invalid='ignore'):
+        label[max_iou < np.float32(neg_iou_thresh)] = 0
+        label[(iou == gt_max[None, :]).any(axis=1)] = 1
+        label[max_iou >= np.float32(pos_iou_thresh)] = 1
+    return label
+
+
+def check_anchor_labels(iou, max_iou, gt_max, neg_iou_thresh, pos_iou_thresh, label):
+    yield _np_exact(label, anchor_labels_ref(iou, max_iou, gt_max, neg_iou_thresh,
+                                             pos_iou_thresh)), 'labels'
+
+
+def bbox2loc_f64(src, dst):
+    """chainercv bbox2loc in float64 and its bound (the comment above): (loc (n, 4), tol (n, 4))."""
+    s, d = np.asarray(src, np.float64), np.asarray(dst, np.float64)
+    eps = float(np.finfo(np.float32).eps)
+    loc, tol = np.empty((len(s), 4)), np.empty((len(s), 4))
+    with np.errstate(invalid='ignore', divide='ignore'):
+        for ax in (0, 1):
+            ss, ds = s[:, 2 + ax] - s[:, ax], d[:, 2 + ax] - d[:, ax]
+            cs, cd = s[:, ax] + 0.5 * ss, d[:, ax] + 0.5 * ds
+            sc = np.maximum(ss, eps)
+            dy = (cd - cs) / sc
+            dh = np.log(ds / sc)
+            loc[:, ax], loc[:, 2 + ax] = dy, dh
+            tol[:, ax] = U * ((0.5 * np.abs(ss) + np.abs(cs) + 0.5 * np.abs(ds) + np.abs(cd)) / sc
+                              + 3 * np.abs(dy))
+            tol[:, 2 + ax] = U * (3 + np.abs(dh))
+    return loc, tol
+
+
+def check_anchor_targets_finish(anchor_inside, inside_index, label_inside_before, argmax, bbox,
+                                disabled, n_anchor, label_inside_after, loc, label):
+    """mrcnn_anchor_targets_finish: label_inside changed at exactly the disabled entries; label is
+    -1 and loc +0 on every row inside_index does not name; the named rows carry label_inside and
+    bbox2loc(anchor, bbox[argmax])."""
+    expect_li = label_inside_before.copy()
+    expect_li[disabled] = -1
+    yield _np_exact(label_inside_after, expect_li), 'label_inside: exactly the disabled entries'
+    expect = np.full((n_anchor,), -1, np.int32)
+    expect[inside_index] = expect_li
+    yield _np_exact(label, expect), 'label scatter'
+    outside = np.ones((n_anchor,), bool)
+    outside[inside_index] = False
+    yield _np_bits(loc[outside], np.zeros((int(outside.sum()), 4), np.float32)), 'loc outside is 0'
+    if len(inside_index):
+        ref, tol = bbox2loc_f64(anchor_inside, bbox[argmax])
+        yield _np_tol(loc[inside_index], ref, tol), 'loc vs float64'
+
+
+def check_proposal_targets_gather(cand, bbox, gt_label, assigned, chosen, n_fg, mean, std,
+                                  sample_roi, loc, label, gt_index):
+    """mrcnn_proposal_targets_gather: sample_roi a bit-equal gather, gt_index = assigned[chosen],
+    gt_roi_label = class + 1 on the first n_fg rows and 0 after, gt_roi_loc against float64."""
+    a = assigned[chosen]
+    yield _np_bits(sample_roi, cand[chosen]), 'sample_roi is cand[chosen]'
+    yield _np_exact(gt_index, a), 'gt_index'
+    expect = (gt_label[a] + 1).astype(np.int32)
+    expect[n_fg:] = 0
+    yield _np_exact(label, expect), 'gt_roi_label'
+    ref, tol = bbox2loc_f64(cand[chosen], bbox[a])
+    m = np.asarray(mean, np.float32).astype(np.float64)
+    s = np.asarray(std, np.float32).astype(np.float64)
+    out = (ref - m) / s
+    yield _np_tol(loc, out, tol / np.abs(s) + 2 * U * np.abs(out)), 'gt_roi_loc vs float64'
+
+
+def mask_targets_ref(masks, sample_roi, gt_index, n_fg, M):
+    """The modelled project's construction (ProposalTargetCreator.__call__, as oracle/np_targets.py
+    states it): integer box by np.round (half to even), Python slice of the ground-truth mask,
+    one-hot of the crop, bilinear resize of each channel in fp32, argmax over the channels.  The
+    resize is oracle.np_ref.resize_bilinear, the oracle's restatement of OpenCV's documented
+    half-pixel INTER_LINEAR rule: cv2 itself is not available, so the rule stays pinned only to
+    that restatement and to tests/golden/proposal_target_creator.npz.  A ground-truth mask is
+    {0, 1} there; the kernel takes uint8 and reads any non-zero value as 1, so the crop is
+    binarised first.  Sampled RoIs lie inside the image; a negative coordinate (where a Python
+    slice would wrap) is outside the contract and is clamped to 0 here as in the kernel.  Rows
+    >= n_fg are -1; an empty crop is all 0 (the documented deviation: the original raises)."""
+    from oracle import np_ref
+    n = len(sample_roi)
+    out = -np.ones((n, M, M), np.int32)
+    for i in range(n_fg):
+        r = np.maximum(np.round(sample_roi[i]).astype(np.int32), 0)
+        m = (masks[gt_index[i]][r[0]:r[2], r[1]:r[3]] != 0).astype(np.int32)
+        if m.size == 0:
+            out[i] = 0
+            continue
+        score = (np.arange(m.max() + 1) == m[..., None]).astype(np.float32)
+        score = np.stack([np_ref.resize_bilinear(score[..., c], M, M)
+                          for c in range(score.shape[2])], axis=2)
+        out[i] = np.argmax(score, axis=2).astype(np.int32)
+    return out
+
+
+def check_mask_targets(masks, sample_roi, gt_index, n_fg, M, out):
+    yield _np_exact(out, mask_targets_ref(masks, sample_roi, gt_index, n_fg, M)), 'mask targets'
+
+
 # ---- reading operands by address -------------------------------------------------------------
 
 _hip = None
@@ -613,11 +825,6 @@ ALLOWED = {
     'mrcnn_detect_sort': 'tests/test_gpu_inference.py::test_c5_full_size_predict',
     'mrcnn_detect_compact': 'tests/test_gpu_inference.py::test_c5_full_size_predict',
     'mrcnn_decode_cls_boxes': 'tests/test_gpu_inference.py',
-    'mrcnn_bbox_iou_argmax': 'tests/test_gpu_targets.py',
-    'mrcnn_anchor_labels': 'tests/test_gpu_targets.py',
-    'mrcnn_anchor_targets_finish': 'tests/test_gpu_targets.py',
-    'mrcnn_proposal_targets_gather': 'tests/test_gpu_targets.py',
-    'mrcnn_mask_targets': 'tests/test_gpu_targets.py',
     'mrcnn_observe_accumulate': 'tests/test_gpu_trainer.py (loss observation)',
     'mrcnn_prepare_image': 'tests/test_gpu_inference.py (image preparation)',
     'mrcnn_paste_masks': 'tests/test_gpu_inference.py (mask pasting)',
@@ -629,10 +836,14 @@ ALLOWED = {
 class LaunchChecker:
     """Wraps _lib.call; see the module docstring.  ``stats[name] = [launches, worst ratio]``,
     ``fails`` lists (name, detail, ratio) of every launch over its bound, ``unchecked`` the entry
-    points called that have neither a reference nor an ALLOWED entry."""
+    points called that have neither a reference nor an ALLOWED entry, ``launches[name]`` the calls
+    checked.  With ``only`` (a set of names) the other entry points are passed through unchecked;
+    one that has neither a reference nor an ALLOWED entry is still reported."""
 
-    def __init__(self, allowed=ALLOWED):
+    def __init__(self, allowed=ALLOWED, only=None):
         self.allowed = allowed
+        self.only = None if only is None else frozenset(only)
+        self.launches = collections.Counter()
         self.stats = collections.OrderedDict()
         self.fails = []
         self.unchecked = collections.Counter()
@@ -673,6 +884,9 @@ class LaunchChecker:
             if name not in self.allowed:
                 self.unchecked[name] += 1
             return self._orig(name, *args)
+        if self.only is not None and name not in self.only:
+            return self._orig(name, *args)
+        self.launches[name] += 1
         torch.cuda.synchronize()
         post = fn(*args)                  # reads the operands, returns the checker of the outputs
         self._orig(name, *args)
@@ -1126,6 +1340,105 @@ class LaunchChecker:
                 cols = (4 * c).view(n, 1) + torch.arange(4, device='cuda').view(1, 4)
                 expect = before.scatter(1, cols, torch.gather(after, 1, cols))
                 yield _same_bits(after, expect), 'gx outside the selection untouched ' + detail
+        return post
+
+    # ---- target creators ---------------------------------------------------------------------
+    @staticmethod
+    def _host(addr, shape, dtype=torch.float32):
+        """NumPy copy of `shape` elements at a device address (empty for NULL / no elements)."""
+        shape = tuple(int(s) for s in shape)
+        if not _addr(addr) or 0 in shape:
+            return torch.zeros(shape, dtype=dtype).numpy()
+        return read(addr, shape, dtype).cpu().numpy()
+
+    def _bbox_iou_argmax(self, a, na, b, g, iou, max_iou, argmax, col_max, stream):
+        A, B = self._host(a, (na, 4)), self._host(b, (g, 4))
+        detail = 'na%d g%d matrix%d' % (na, g, bool(_addr(iou)))
+        # na = 0 writes nothing (include/mrcnn_hip.h): col_max keeps its contents
+        before = self._host(col_max, (g,), torch.int32) if na == 0 else None
+
+        def post():
+            if na == 0:
+                yield _np_bits(self._host(col_max, (g,), torch.int32), before), \
+                    'nothing written ' + detail
+                return
+            I = self._host(iou, (na, g)) if _addr(iou) else None
+            C = self._host(col_max, (g,)) if _addr(col_max) else None
+            for r, what in check_bbox_iou_argmax(A, B, self._host(max_iou, (na,)),
+                                                 self._host(argmax, (na,), torch.int32), I, C):
+                yield r, what + ' ' + detail
+            yield _np_bits(self._host(a, (na, 4)), A), 'boxes_a untouched ' + detail
+            yield _np_bits(self._host(b, (g, 4)), B), 'boxes_b untouched ' + detail
+        return post
+
+    def _anchor_labels(self, iou, max_iou, gt_max, na, g, neg, pos, label, stream):
+        I, Mx, Gm = self._host(iou, (na, g)), self._host(max_iou, (na,)), self._host(gt_max, (g,))
+
+        def post():
+            for r, what in check_anchor_labels(I, Mx, Gm, neg, pos,
+                                               self._host(label, (na,), torch.int32)):
+                yield r, '%s na%d g%d' % (what, na, g)
+        return post
+
+    def _anchor_targets_finish(self, anchor_inside, inside_index, label_inside, argmax, bbox,
+                               n_inside, disabled, n_disabled, n_anchor, loc, label, stream):
+        i32 = torch.int32
+        A = self._host(anchor_inside, (n_inside, 4))
+        idx = self._host(inside_index, (n_inside,), i32)
+        li = self._host(label_inside, (n_inside,), i32)
+        am = self._host(argmax, (n_inside,), i32)
+        B = self._host(bbox, (int(am.max()) + 1 if n_inside else 0, 4))
+        dis = self._host(disabled, (n_disabled,), i32)
+        detail = 'n_anchor%d n_inside%d n_disabled%d' % (n_anchor, n_inside, n_disabled)
+
+        def post():
+            for r, what in check_anchor_targets_finish(
+                    A, idx, li, am, B, dis, n_anchor, self._host(label_inside, (n_inside,), i32),
+                    self._host(loc, (n_anchor, 4)), self._host(label, (n_anchor,), i32)):
+                yield r, what + ' ' + detail
+            same = all(_np_bits(self._host(p, x.shape, t), x) == 0. for p, x, t in (
+                (anchor_inside, A, torch.float32), (inside_index, idx, i32), (argmax, am, i32),
+                (bbox, B, torch.float32), (disabled, dis, i32)))
+            yield 0. if same else math.inf, 'operands untouched ' + detail
+        return post
+
+    def _proposal_targets_gather(self, cand, bbox, gt_label, assigned, chosen, n, n_fg, mean4,
+                                 std4, sample_roi, loc, label, gt_index, stream):
+        i32 = torch.int32
+        ch = self._host(chosen, (n,), i32)
+        nc = int(ch.max()) + 1 if n else 0
+        C, asg = self._host(cand, (nc, 4)), self._host(assigned, (nc,), i32)
+        g = int(asg[ch].max()) + 1 if n else 0
+        B, gl = self._host(bbox, (g, 4)), self._host(gt_label, (g,), i32)
+        mean, std = [float(v) for v in mean4], [float(v) for v in std4]
+        detail = 'n%d n_fg%d' % (n, n_fg)
+
+        def post():
+            for r, what in check_proposal_targets_gather(
+                    C, B, gl, asg, ch, n_fg, mean, std, self._host(sample_roi, (n, 4)),
+                    self._host(loc, (n, 4)), self._host(label, (n,), i32),
+                    self._host(gt_index, (n,), i32)):
+                yield r, what + ' ' + detail
+            same = all(_np_bits(self._host(p, x.shape, t), x) == 0. for p, x, t in (
+                (cand, C, torch.float32), (bbox, B, torch.float32), (gt_label, gl, i32),
+                (assigned, asg, i32), (chosen, ch, i32)))
+            yield 0. if same else math.inf, 'operands untouched ' + detail
+        return post
+
+    def _mask_targets(self, masks, G, H, W, sample_roi, gt_index, n, n_fg, M, out, stream):
+        i32 = torch.int32
+        mk = read(masks, (G, H, W), torch.uint8)
+        roi, gi = self._host(sample_roi, (n, 4)), self._host(gt_index, (n,), i32)
+        detail = 'G%d H%d W%d n%d n_fg%d M%d' % (G, H, W, n, n_fg, M)
+
+        def post():
+            for r, what in check_mask_targets(mk.cpu().numpy(), roi, gi, n_fg, M,
+                                              self._host(out, (n, M, M), i32)):
+                yield r, what + ' ' + detail
+            same = torch.equal(read(masks, (G, H, W), torch.uint8), mk) \
+                and _np_bits(self._host(sample_roi, (n, 4)), roi) == 0. \
+                and _np_bits(self._host(gt_index, (n,), i32), gi) == 0.
+            yield 0. if same else math.inf, 'operands untouched ' + detail
         return post
 
 

@@ -263,3 +263,59 @@ def test_roi_lane_caps_match_float64(dev, monkeypatch, C):
         assert chk.stats, 'no ROIAlign launch was checked'
         same[lanes] = (torch.equal(got[0], base[0]), torch.equal(got[1], base[1]))
     print('bit-identical to 256 lanes (forward, backward): %s' % same)
+
+
+TARGET_ENTRY_POINTS = ('mrcnn_bbox_iou_argmax', 'mrcnn_anchor_labels', 'mrcnn_anchor_targets_finish',
+                       'mrcnn_proposal_targets_gather', 'mrcnn_mask_targets')
+
+
+@pytest.mark.parametrize('n_gt', [8, 100])
+def test_device_targets_launches_at_full_size(shipped, monkeypatch, n_gt):
+    """The headline step's forward with chain.device_targets: the five target entry points of
+    csrc/targets.hip under their references (64 260 anchors, 2 000 + G candidates, 512 RoIs per
+    image, 800 x 1333 masks), once with host masks and once with device masks (only then does
+    mrcnn_mask_targets run), and the same sampled RoIs, labels, mask / RPN targets and np.random
+    position as the host creators.  n_gt = 100: a crowded COCO image."""
+    import random
+    dev = shipped
+    random.seed(0)
+    np.random.seed(0)
+    torch.manual_seed(0)
+    imgs, bboxes, labels, masks, scales = bench.synthetic_batch(np.random.RandomState(0), BATCH, H, W,
+                                                                n_gt=n_gt)
+    model, chain, opt, _ = bench.build_trainer(50, dev, 1, BATCH, defer=5)
+    chain.mask_branch_fg_only = True
+    x = torch.tensor(imgs, device=dev).contiguous(memory_format=torch.channels_last)
+    out = {}
+    for mode in ('host', 'device', 'device-masks'):
+        chain.device_targets = mode != 'host'
+        mm = masks if mode != 'device-masks' else [torch.tensor(m, device=dev) for m in masks]
+        chk = launch_ref.LaunchChecker(only=TARGET_ENTRY_POINTS)
+        with monkeypatch.context() as m:
+            chk.install(m)
+            np.random.seed(123)
+            with torch.no_grad():
+                chain(x, bboxes, labels, mm, scales)
+            torch.cuda.synchronize()
+        t = chain.last_targets
+        out[mode] = ({k: t[k].cpu().numpy() for k in ('sample_rois', 'gt_roi_labels', 'gt_roi_masks',
+                                                       'gt_rpn_labels')},
+                     np.random.randint(0, 2 ** 31 - 1))
+        del mm
+        _report('device targets, n_gt %d, %s' % (n_gt, mode), chk)
+        chk.assert_clean()
+        expect = {} if mode == 'host' else {
+            'mrcnn_bbox_iou_argmax': 2 * BATCH, 'mrcnn_anchor_labels': BATCH,
+            'mrcnn_anchor_targets_finish': BATCH, 'mrcnn_proposal_targets_gather': BATCH}
+        if mode == 'device-masks':
+            expect['mrcnn_mask_targets'] = BATCH
+        assert dict(chk.launches) == expect, (mode, dict(chk.launches))
+        assert set(chk.stats) == set(expect)
+    chain.device_targets = False
+    host = out['host']
+    assert host[0]['sample_rois'].shape == (BATCH * 512, 4)
+    assert (host[0]['gt_roi_labels'] > 0).sum() > 0 and (host[0]['gt_rpn_labels'] == 1).sum() > 0
+    for mode in ('device', 'device-masks'):
+        for k, v in host[0].items():
+            assert np.array_equal(out[mode][0][k], v), (mode, k)
+        assert out[mode][1] == host[1], mode

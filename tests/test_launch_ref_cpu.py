@@ -450,3 +450,263 @@ def test_gradient_bound_flags_a_count_off_by_one():
     for c, ok in ((count, True), (count + 1, False)):
         g32 = (g * (np.float32(1) / np.float32(c))).astype(np.float32)
         assert (L.tol_ratio(torch.tensor(g32), gx, g_tol) <= 1.) == ok, c
+
+
+# ---- target creators: the references on NumPy emulations of csrc/targets.hip -------------------
+
+import target_cases as TC
+from oracle import np_targets
+from test_targets_cpu import _scene
+
+
+def _worst(checks):
+    return max([r for r, _ in checks] + [0.])
+
+
+def _emu_iou_argmax(a, b, last_argmax=False, col_skip_last=False):
+    """iou_argmax_kernel / iou_colmax_kernel: fp32 in the reference's order, first argmax."""
+    iou = L.bbox_iou_f32(a, b)
+    arg = iou.argmax(1) if not last_argmax else iou.shape[1] - 1 - iou[:, ::-1].argmax(1)
+    col = (iou[:-1] if col_skip_last else iou).max(0)
+    return iou.max(1), arg.astype(np.int32), iou, col
+
+
+def _emu_anchor_labels(iou, mx, gt_max, neg, pos, order='neg,gt,pos'):
+    label = np.full(len(iou), -1, np.int32)
+    with np.errstate(invalid='ignore'):
+        for rule in order.split(','):
+            if rule == 'neg':
+                label[mx < np.float32(neg)] = 0
+            elif rule == 'gt':
+                label[(iou == gt_max[None]).any(1)] = 1
+            else:
+                label[mx >= np.float32(pos)] = 1
+    return label
+
+
+def _emu_mask_targets(masks, roi, gt_index, n_fg, M, half_away=False, ge=False, force_t=True):
+    """mask_targets_kernel line by line (rintf, clamp, mask_axis, fp32 blend, prob > 0.5)."""
+    Hh, Ww = masks.shape[1:]
+    out = -np.ones((len(roi), M, M), np.int32)
+    rnd = TC.round_half_away if half_away else np.round
+    f32 = np.float32
+
+    def axis(n_in, start, limit):
+        n = float(max(n_in, 1))
+        pos = (np.arange(M, dtype=np.float64) + 0.5) * (n / float(M)) - 0.5
+        i0 = np.floor(pos).astype(np.int64)
+        t = (pos - i0).astype(f32)
+        last = int(n) - 1
+        if force_t:
+            t[(i0 < 0) | (i0 >= last)] = 0
+        i0 = np.clip(i0, 0, last)
+        i1 = np.minimum(i0 + 1, last)
+        return np.clip(i0 + start, 0, limit - 1), np.clip(i1 + start, 0, limit - 1), t
+
+    for r in range(n_fg):
+        y0, x0, y1, x1 = (int(v) for v in rnd(roi[r].astype(np.float64)))
+        y0, y1 = min(max(y0, 0), Hh), min(max(y1, 0), Hh)
+        x0, x1 = min(max(x0, 0), Ww), min(max(x1, 0), Ww)
+        h, w = max(y1 - y0, 0), max(x1 - x0, 0)
+        if h == 0 or w == 0:
+            out[r] = 0
+            continue
+        ya, yb, ty = axis(h, y0, Hh)
+        xa, xb, tx = axis(w, x0, Ww)
+        m = (masks[gt_index[r]] > 0).astype(f32)
+        tx_, ty_ = tx[None, :], ty[:, None]
+        top = m[ya][:, xa] * (f32(1) - tx_) + m[ya][:, xb] * tx_
+        bot = m[yb][:, xa] * (f32(1) - tx_) + m[yb][:, xb] * tx_
+        prob = top * (f32(1) - ty_) + bot * ty_
+        out[r] = (prob >= f32(0.5)) if ge else (prob > f32(0.5))
+    return out
+
+
+@pytest.mark.parametrize('na,g,degenerate', [(1, 1, False), (255, 2, False), (257, 9, True),
+                                             (2008, 100, True), (21000, 9, False)])
+def test_bbox_iou_reference_accepts_right_and_rejects_wrong(na, g, degenerate):
+    a, b = TC.iou_boxes(na, g, degenerate=degenerate)
+    mx, arg, iou, col = _emu_iou_argmax(a, b)
+    assert np.array_equal(iou, np_ref.bbox_iou(a, b), equal_nan=True)
+    if degenerate:
+        # every zero-area row against the zero-area box is 0 / 0
+        assert np.isnan(iou).sum() == 2 and np.isnan(mx).sum() == 2 and np.isnan(col).sum() == 1
+    assert _worst(L.check_bbox_iou_argmax(a, b, mx, arg, iou, col)) <= 1.
+    assert _worst(L.check_bbox_iou_argmax(a, b, mx, arg)) <= 1.
+    if g >= 3 and na > 8:                       # b[1] = b[0], a[0] = b[0]: a tied row
+        _, arg_last, _, _ = _emu_iou_argmax(a, b, last_argmax=True)
+        assert _worst(L.check_bbox_iou_argmax(a, b, mx, arg_last, iou, col)) > 1.
+        assert _worst(L.check_bbox_iou_argmax(a, b, mx, arg_last)) > 1.
+    if na > 1:                                  # the last row holds its column's only IoU 1
+        _, _, _, col_bad = _emu_iou_argmax(a, b, col_skip_last=True)
+        assert _worst(L.check_bbox_iou_argmax(a, b, mx, arg, iou, col_bad)) > 1.
+    # arithmetic: one ulp-scale slip passes, a dropped "- inter" does not
+    bad = iou.copy()
+    k = np.nanargmax(np.where(iou < 1, iou, 0))
+    bad.flat[k] = np.float32(bad.flat[k] * (1 + 64 * L.U))
+    assert _worst(L.check_bbox_iou_argmax(a, b, bad.max(1), bad.argmax(1).astype(np.int32), bad,
+                                          bad.max(0))) > 1.
+
+
+def test_bbox_iou_bound_holds_on_scene_and_golden(golden_dir):
+    import os
+    d = np.load(os.path.join(golden_dir, 'proposal_target_creator.npz'))
+    for roi, bbox in [(_scene(s)[0], _scene(s)[1]) for s in (0, 1, 2)] + [(d['roi'], d['bbox'])]:
+        cand = np.concatenate([roi, bbox], 0)
+        mx, arg, iou, col = _emu_iou_argmax(cand, bbox)
+        checks = list(L.check_bbox_iou_argmax(cand, bbox, mx, arg, iou, col))
+        assert _worst(checks) <= 1., checks
+        print('iou vs float64: %.3f of the bound' % checks[0][0])
+
+
+def _label_scenes():
+    """(anchors, boxes, neg, pos): IoU exactly 0.25 and 0.5 at the thresholds; an anchor below neg
+    that is a column maximum; a box no anchor overlaps; a NaN column."""
+    A = np.array([[0, 0, 10, 10], [100, 100, 110, 110], [100, 100, 105, 105],
+                  [200, 200, 240, 240], [300, 300, 310, 310], [7, 7, 7, 7]], np.float32)
+    base = np.array([[0, 0, 10, 5], [100, 100, 105, 105], [200, 200, 210, 210]], np.float32)
+    yield A[:5], base, 0.25, 0.5
+    yield A[:5], np.concatenate([base, [[600, 600, 650, 650]]]).astype(np.float32), 0.25, 0.5
+    yield A, np.concatenate([base, [[7, 7, 7, 7]]]).astype(np.float32), 0.25, 0.5
+    yield A[:5], base, 0.3, 0.7
+
+
+def test_anchor_labels_reference_follows_the_oracle_and_rejects_wrong_orders():
+    expected_first = [1, -1, 1, 1, 0]            # 0.5 >= pos; 0.25 is not < neg; max; col max; none
+    for n, (a, b, neg, pos) in enumerate(_label_scenes()):
+        mx, arg, iou, col = _emu_iou_argmax(a, b)
+        good = _emu_anchor_labels(iou, mx, col, neg, pos)
+        # chainercv's _create_label without its draws (n_sample large enough)
+        atc = np_ref.AnchorTargetCreator(n_sample=4 * len(a), neg_iou_thresh=neg,
+                                         pos_iou_thresh=pos, pos_ratio=1.)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            _, ref = atc._create_label(np.arange(len(a)), a, b)
+        assert np.array_equal(good, ref), (n, good, ref)
+        if n == 0:
+            assert good.tolist() == expected_first
+        if n == 1:
+            assert (good == 1).all()            # gt_max = 0: every zero-IoU anchor is positive
+        assert _worst(L.check_anchor_labels(iou, mx, col, neg, pos, good)) <= 1.
+        harmless = _emu_anchor_labels(iou, mx, col, neg, pos, 'neg,pos,gt')
+        assert np.array_equal(harmless, good)
+        if n in (0, 3):
+            bad = _emu_anchor_labels(iou, mx, col, neg, pos, 'gt,pos,neg')
+            assert _worst(L.check_anchor_labels(iou, mx, col, neg, pos, bad)) > 1.
+    # >= instead of > / < at equality
+    a, b, neg, pos = next(_label_scenes())
+    mx, arg, iou, col = _emu_iou_argmax(a, b)
+    lt = _emu_anchor_labels(iou, mx, col, np.nextafter(np.float32(neg), np.float32(1)), pos)
+    assert _worst(L.check_anchor_labels(iou, mx, col, neg, pos, lt)) > 1.
+
+
+@pytest.mark.parametrize('seed', [0, 1])
+def test_anchor_targets_finish_reference(seed):
+    _, bbox, _, _, size = _scene(seed)
+    ab = np_ref.generate_anchor_base(16, (0.5, 1, 2), (2, 4, 8, 16, 32))
+    anchor = np_ref.enumerate_shifted_anchor(ab, 16, 30, 40).astype(np.float32)
+    np.random.seed(5)
+    loc_ref, label_ref = np_ref.AnchorTargetCreator()(bbox, anchor, size)
+    inside = np.where((anchor[:, 0] >= 0) & (anchor[:, 1] >= 0) & (anchor[:, 2] <= size[0])
+                      & (anchor[:, 3] <= size[1]))[0].astype(np.int32)
+    a = anchor[inside]
+    mx, arg, iou, col = _emu_iou_argmax(a, bbox)
+    before = _emu_anchor_labels(iou, mx, col, 0.3, 0.7)
+    after = label_ref[inside]
+    disabled = np.where(before != after)[0].astype(np.int32)
+    assert len(disabled) and (after[disabled] == -1).all()
+    args = (a, inside, before, arg, bbox, disabled, len(anchor), after)
+    assert _worst(L.check_anchor_targets_finish(*args, loc_ref, label_ref)) <= 1.
+    bad = label_ref.copy()
+    bad[np.setdiff1d(np.arange(len(anchor)), inside)[0]] = 0          # a write outside
+    assert _worst(L.check_anchor_targets_finish(*args, loc_ref, bad)) > 1.
+    bad = loc_ref.copy()
+    bad[inside[3], 2] = np.float32(bad[inside[3], 2] * (1 + 2e-6) + 2e-6)
+    assert _worst(L.check_anchor_targets_finish(*args, bad, label_ref)) > 1.
+    bad = after.copy()
+    bad[np.where(before == after)[0][0]] ^= 1                          # label_inside elsewhere
+    assert _worst(L.check_anchor_targets_finish(*args[:-1], bad, loc_ref, label_ref)) > 1.
+
+
+def test_proposal_gather_and_mask_references_match_the_oracle(golden_dir):
+    import os
+    d = np.load(os.path.join(golden_dir, 'proposal_target_creator.npz'))
+    cases = [_scene(s)[:4] for s in (0, 1, 2)] + [(d['roi'], d['bbox'], d['label'],
+                                                   d['mask'].astype(np.int32))]
+    for roi, bbox, label, mask in cases:
+        np.random.seed(7)
+        s_roi, loc, lab, gt_mask = np_targets.ProposalTargetCreator(n_sample=128)(
+            roi, bbox, label, mask)
+        cand = np.concatenate([roi, bbox], 0)
+        iou = np_ref.bbox_iou(cand, bbox)
+        assigned = iou.argmax(1).astype(np.int32)
+        # recover the draws from the sampled boxes (candidates are distinct)
+        chosen = np.array([np.where((cand == r).all(1))[0][0] for r in s_roi], np.int32)
+        n_fg = int((lab > 0).sum())
+        gi = assigned[chosen]
+        mean, std = (0., 0., 0., 0.), (0.1, 0.1, 0.2, 0.2)
+        args = (cand, bbox, label.astype(np.int32), assigned, chosen, n_fg, mean, std)
+        checks = list(L.check_proposal_targets_gather(*args, s_roi, loc, lab, gi))
+        assert _worst(checks) <= 1., checks
+        bad = loc.copy()
+        bad[0, 0] = np.float32(bad[0, 0] + 1e-4 * max(abs(bad[0, 0]), 1))
+        assert _worst(L.check_proposal_targets_gather(*args, s_roi, bad, lab, gi)) > 1.
+        bad = lab.copy()
+        bad[n_fg] = 1
+        assert _worst(L.check_proposal_targets_gather(*args, s_roi, loc, bad, gi)) > 1.
+        m8 = (mask != 0).astype(np.uint8)
+        assert np.array_equal(L.mask_targets_ref(m8, s_roi, gi, n_fg, 14), gt_mask)
+        assert np.array_equal(_emu_mask_targets(m8, s_roi, gi, n_fg, 14), gt_mask)
+
+
+def test_proposal_gather_reference_non_finite_positions():
+    cand = np.array([[10, 10, 10, 30], [10, 10, 50, 30], [5, 5, 25, 45]], np.float32)
+    bbox = np.array([[10, 10, 40, 30], [20, 20, 20, 60]], np.float32)     # second: zero height
+    assigned, chosen = np.array([0, 1, 1], np.int32), np.array([0, 1, 2, 2], np.int32)
+    label = np.array([3, 7], np.int32)
+    mean, std = (0.1, -0.2, 0.3, 0.05), (0.1, 0.3, 0.2, 0.7)
+    from chainer_mask_rcnn_amd.utils.bbox import bbox2loc
+    with np.errstate(divide='ignore'):
+        loc = ((bbox2loc(cand[chosen], bbox[assigned[chosen]]) - np.array(mean, np.float32))
+               / np.array(std, np.float32)).astype(np.float32)
+    assert np.isneginf(loc[1:, 2]).all() and np.isfinite(loc[0]).all()
+    args = (cand, bbox, label, assigned, chosen, 2, mean, std, cand[chosen])
+    lab, gi = np.array([4, 8, 0, 0], np.int32), assigned[chosen]
+    assert _worst(L.check_proposal_targets_gather(*args, loc, lab, gi)) <= 1.
+    for v in (0., np.inf, np.nan):
+        bad = loc.copy()
+        bad[1, 2] = v
+        assert _worst(L.check_proposal_targets_gather(*args, bad, lab, gi)) > 1.
+
+
+def test_mask_reference_on_the_edge_crops_rejects_wrong_kernels():
+    """The crop set of tests/target_cases.py on 800 x 1333 masks: the literal one-hot / resize /
+    argmax reference equals the emulated kernel on every row, and differs from round-half-away,
+    from prob >= 0.5 and from an unclamped border weight."""
+    G = 12
+    masks = TC.mask_patterns(G)
+    roi, gt = TC.mask_rows(G)
+    n = len(roi)
+    prob, valid = TC.tie_stats(masks, roi, gt)
+    ties = (prob == 392) & valid[:, None, None]
+    ref = L.mask_targets_ref(masks, roi, gt, n, 14)
+    assert np.array_equal(ref[valid], (prob[valid] > 392).astype(np.int32)) and (ref[~valid] == 0).all()
+    mixed = np.array([len(np.unique(r)) == 2 for r in ref])
+    print('rows %d, half-way rows %d, tie pixels %d, tie pixels in mixed rows %d'
+          % (n, TC.halfway_rows(roi).sum(), ties.sum(), ties[mixed].sum()))
+    assert TC.halfway_rows(roi).sum() >= 100 and ties.sum() >= 1000 and ties[mixed].sum() > 0
+    good = _emu_mask_targets(masks, roi, gt, n, 14)
+    assert _worst(L.check_mask_targets(masks, roi, gt, n, 14, good)) <= 1.
+    for kw in (dict(half_away=True), dict(ge=True), dict(force_t=False)):
+        bad = _emu_mask_targets(masks, roi, gt, n, 14, **kw)
+        rows = int((bad != good).any((1, 2)).sum())
+        print('%s: %d rows differ' % (kw, rows))
+        assert rows > 0 and _worst(L.check_mask_targets(masks, roi, gt, n, 14, bad)) > 1.
+    for M in (7, 28):
+        sub = slice(0, n, 5)
+        good = _emu_mask_targets(masks, roi[sub], gt[sub], len(roi[sub]), M)
+        assert _worst(L.check_mask_targets(masks, roi[sub], gt[sub], len(roi[sub]), M, good)) <= 1.
+    half = _emu_mask_targets(masks, roi, gt, n // 2, 14)
+    assert (half[n // 2:] == -1).all()
+    assert _worst(L.check_mask_targets(masks, roi, gt, n // 2, 14, half)) <= 1.
+    full = _emu_mask_targets(masks, roi, gt, n, 14)
+    assert _worst(L.check_mask_targets(masks, roi, gt, n // 2, 14, full)) > 1.
