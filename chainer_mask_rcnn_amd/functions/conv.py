@@ -9,6 +9,10 @@ reference's logical shapes — x (N,C,H,W), conv W (out,in,kh,kw), deconv W
 (in,out,kh,kw), linear W (out,in) — stored channels-last, which is exactly the
 NHWC / KRSC layout the HIP kernels consume.
 """
+import collections
+import ctypes
+import os as _os
+
 import torch
 
 from .. import _lib
@@ -29,6 +33,25 @@ def _direct_grad(p):
     return False
 
 
+def _grad_target(p):
+    """The gradient-ownership rule in one place: ``(buffer, result)`` for parameter ``p`` — the
+    buffer the producing kernel writes (not adds) p's gradient into and what the autograd node
+    returns for p: ``(p.grad, None)`` when the arena slot could be claimed, else the same fresh
+    tensor twice (autograd accumulates it)."""
+    if _direct_grad(p):
+        return p.grad, None
+    g = empty_nhwc(tuple(p.shape), p.device) if p.dim() == 4 else \
+        torch.empty(tuple(p.shape), dtype=torch.float32, device=p.device)
+    return g, g
+
+
+def _bias_grad(b, g, M):
+    """Bias gradient = column sum of the (M, len(b)) gradient ``g``; returns what autograd gets."""
+    gb, result = _grad_target(b)
+    _colsum(_lib.ptr(g), M, b.shape[0], gb, g.device)
+    return result
+
+
 def conv_out_size(size, k, s, p):
     return (size + 2 * p - k) // s + 1
 
@@ -42,6 +65,10 @@ def make_desc(x_shape, w_shape, stride, pad):
         raise ValueError('conv: input has %d channels, filter expects %d' % (C, Cw))
     return ConvDesc(N, H, W, C, K, R, S, stride, pad,
                     conv_out_size(H, R, stride, pad), conv_out_size(W, S, stride, pad))
+
+
+def ctx_desc(d):
+    return ctypes.byref(d)
 
 
 def _colsum(g2d_ptr, M, C, out, device):
@@ -64,8 +91,6 @@ def epilogue_bwd(gy, y=None, scale=None):
               M, C, _lib.stream_ptr())
     return g
 
-
-_CONV_RECORDS_GRAPH = True
 
 # Test hook: when set to a list, every ReLU output this module produces (fused conv epilogues, the
 # three activations of each bottleneck of a fused stage, the deconvolution) is appended as
@@ -152,18 +177,14 @@ def _sparse3x3_backward(ctx, d, x, Wc, g, hint, need_x, need_w, need_b):
     d1 = ConvDesc(n, 1, 1, 9 * d.C, d.K, 1, 1, 1, 0, 1, 1)
     gx = gW = gb = None
     if need_w:
-        gW = _wgrad_raw(d1, patches, g_rows, ctx.W_param)
+        gW = _wgrad(d1, patches, g_rows, ctx.W_param)
     if need_x:
         gp = _dgrad_raw(d1, g_rows, Wc)          # (rows, 3, 3, C) patch gradients
         gx = empty_nhwc((d.N, d.C, d.H, d.W), dev)
         _lib.call('mrcnn_sparse3x3_scatter', _lib.ptr(gp), _lib.ptr(hint.lookup), d.N, d.H, d.W,
                   d.C, _lib.ptr(gx), _lib.stream_ptr())
     if need_b:
-        b = ctx.b_param
-        direct = _direct_grad(b)
-        gbt = b.grad if direct else torch.empty((d.K,), dtype=torch.float32, device=dev)
-        _colsum(_lib.ptr(g_rows), n, d.K, gbt, dev)
-        gb = None if direct else gbt
+        gb = _bias_grad(ctx.b_param, g_rows, n)
     return gx, gW, gb
 
 
@@ -171,7 +192,9 @@ class _Conv2dFn(torch.autograd.Function):
     """y = relu?( affine?( conv(x, W) + b? ) + residual? )"""
 
     @staticmethod
-    def forward(ctx, x, W, b, scale, shift, residual, stride, pad, relu):
+    def forward(ctx, x, W, b, scale, shift, residual, stride, pad, relu, records_graph):
+        # ``records_graph``: torch.is_grad_enabled() at the call (in here grad mode is always off and
+        # ctx.needs_input_grad reports the inputs' requires_grad flags even under torch.no_grad())
         _lib.require_device(x, W)
         x = nhwc(x)
         Wc = nhwc(W) if W.dim() == 4 else W.contiguous()
@@ -187,11 +210,10 @@ class _Conv2dFn(torch.autograd.Function):
         if relu:
             flags |= EPI_RELU
         ctx.wino = uses_winograd(d) and residual is None and (b is None or scale is None)
-        if ctx.wino and (WINOGRAD_TRAIN_FORWARD in (True, 'conv2d')
-                         or not (_CONV_RECORDS_GRAPH and any(ctx.needs_input_grad))):
+        if ctx.wino and _wino_forward('conv2d', records_graph and any(ctx.needs_input_grad)):
             y, _ = wino_fwd(x, Wc, d, scale, shift if scale is not None else b, relu,
-                            cache_for=None if _CONV_RECORDS_GRAPH else W,
-                            exact_signs=relu and _CONV_RECORDS_GRAPH)
+                            cache_for=None if records_graph else W,
+                            exact_signs=relu and records_graph)
         else:
             y = empty_nhwc((d.N, d.K, d.P, d.Q), x.device)
             _lib.call('mrcnn_conv2d_fwd', ctx_desc(d), _lib.ptr(x), _lib.ptr(Wc), _lib.ptr(b),
@@ -220,45 +242,26 @@ class _Conv2dFn(torch.autograd.Function):
         # through ReLU, then through the affine scale
         gr = epilogue_bwd(gy, y, None) if ctx.relu else gy
         g = epilogue_bwd(gr, None, scale) if scale is not None else gr
-        M = d.N * d.P * d.Q
         gx = gW = gb = None
         hint = ctx.sparse_hint
         if hint is not None and SPARSE_CONV_BACKWARD and hint.valid_for(d, gy.device):
             gx, gW, gb = _sparse3x3_backward(ctx, d, x, Wc, g, hint, need_x, need_w, need_b)
             hint.clear()
-            return gx, gW, gb, None, None, None, None, None, None
+            return gx, gW, gb, None, None, None, None, None, None, None
         if need_w:
-            W = ctx.W_param
             if ctx.wino:
-                gW = _wino_wgrad(d, x, None, g, W)
+                gW = _wgrad(d, x, g, ctx.W_param, wino=True)
             else:
-                direct = _direct_grad(W)
-                if direct:
-                    gWt = W.grad
-                elif W.dim() == 4:
-                    gWt = empty_nhwc(tuple(W.shape), gy.device)
-                else:
-                    gWt = torch.empty_like(W)
-                ws = _lib.workspace(_lib.load().mrcnn_conv2d_wgrad_workspace_bytes(ctx_desc(d)),
-                                    gy.device, 'wgrad')
-                _lib.call('mrcnn_conv2d_wgrad', ctx_desc(d), _lib.ptr(x), _lib.ptr(g),
-                          _lib.ptr(gWt), _lib.ptr(ws), _lib.stream_ptr())
-                gW = None if direct else gWt
+                # the plain entry point, and NOT through the defer queue (MomentumSGD.step raises
+                # for a deferred parameter whose gradient came this way)
+                gWt, gW = _grad_target(ctx.W_param)
+                _launch_wgrad(d, x, g, gWt, ex=False)
         if need_x:
             gx = wino_dgrad(d, g, Wc) if ctx.wino else _dgrad_raw(d, g, Wc)
         if need_b:
-            b = ctx.b_param
-            direct = _direct_grad(b)
-            gbt = b.grad if direct else torch.empty((d.K,), dtype=torch.float32, device=gy.device)
-            _colsum(_lib.ptr(g), M, d.K, gbt, gy.device)
-            gb = None if direct else gbt
+            gb = _bias_grad(ctx.b_param, g, d.N * d.P * d.Q)
         gres = gr if ctx.has_res and ctx.needs_input_grad[5] else None
-        return gx, gW, gb, None, None, gres, None, None, None
-
-
-def ctx_desc(d):
-    import ctypes
-    return ctypes.byref(d)
+        return gx, gW, gb, None, None, gres, None, None, None, None
 
 
 def conv2d(x, W, b=None, stride=1, pad=0, scale=None, shift=None, residual=None, relu=False):
@@ -268,12 +271,8 @@ def conv2d(x, W, b=None, stride=1, pad=0, scale=None, shift=None, residual=None,
     produced for them — the reference computes but never uses it,
     examples/train_common.py:188-190).
     """
-    global _CONV_RECORDS_GRAPH
-    _CONV_RECORDS_GRAPH = torch.is_grad_enabled()     # see _STAGE_RECORDS_GRAPH
-    try:
-        return _Conv2dFn.apply(x, W, b, scale, shift, residual, stride, pad, relu)
-    finally:
-        _CONV_RECORDS_GRAPH = True
+    return _Conv2dFn.apply(x, W, b, scale, shift, residual, stride, pad, relu,
+                           torch.is_grad_enabled())
 
 
 class _StemFn(torch.autograd.Function):
@@ -355,21 +354,14 @@ class _Deconv2x2Fn(torch.autograd.Function):
             _lib.call('mrcnn_deconv2x2s2_dgrad', _lib.ptr(g), _lib.ptr(Wc), _lib.ptr(gx),
                       N, H, Wd, C, K, _lib.stream_ptr())
         if ctx.needs_input_grad[1]:
-            W = ctx.W_param
-            direct = _direct_grad(W)
-            gWt = W.grad if direct else empty_nhwc(tuple(W.shape), gy.device)
+            gWt, gW = _grad_target(ctx.W_param)
             ws = _lib.workspace(
                 _lib.load().mrcnn_deconv2x2s2_wgrad_workspace_bytes(N, H, Wd, C, K),
                 gy.device, 'wgrad')
             _lib.call('mrcnn_deconv2x2s2_wgrad', _lib.ptr(x), _lib.ptr(g), _lib.ptr(gWt),
                       N, H, Wd, C, K, _lib.ptr(ws), _lib.stream_ptr())
-            gW = None if direct else gWt
         if ctx.b_param is not None and ctx.needs_input_grad[2]:
-            b = ctx.b_param
-            direct = _direct_grad(b)
-            gbt = b.grad if direct else torch.empty((K,), dtype=torch.float32, device=gy.device)
-            _colsum(_lib.ptr(g), N * 4 * H * Wd, K, gbt, gy.device)
-            gb = None if direct else gbt
+            gb = _bias_grad(ctx.b_param, g, N * 4 * H * Wd)
         return gx, gW, gb, None
 
 
@@ -403,17 +395,15 @@ def _flip_transpose(Wc, d, row_scale, out):
     return out
 
 
-def _stage_transposes(blocks, scales, device):
+def _stage_transposes(blocks, device):
     """Flipped / transposed filters of every stride-1 convolution of a stage, built by ONE
-    launch into one buffer.  ``blocks``: ((d1,d2,d3,d4), (W1,W2,W3,W4), _) per bottleneck,
-    ``scales``: (s3, s4) per bottleneck (folded into conv3 / conv4).  Returns a dict
-    {'1','2','3','4'} -> flat tensor per block."""
-    import ctypes
+    launch into one buffer.  ``blocks``: one ``_StageBlock`` per bottleneck (the affine scales
+    s3 / s4 are folded into conv3 / conv4).  Returns a dict {'1','2','3','4'} -> flat tensor
+    per block."""
     jobs = []
-    for bi, ((d1, d2, d3, d4), (W1, W2, W3, W4), _) in enumerate(blocks):
-        s3, s4 = scales[bi]
-        for key, W, d, sc in (('1', W1, d1, None), ('2', W2, d2, None), ('3', W3, d3, s3),
-                              ('4', W4, d4, s4)):
+    for bi, b in enumerate(blocks):
+        for key, W, d, sc in (('1', b.W1, b.d1, None), ('2', b.W2, b.d2, None),
+                              ('3', b.W3, b.d3, b.s3), ('4', b.W4, b.d4, b.s4)):
             if W is not None and _uses_transposed_dgrad(d) and not uses_winograd(d):
                 jobs.append((bi, key, nhwc(W), d, sc))
     out = [dict() for _ in blocks]
@@ -426,12 +416,10 @@ def _stage_transposes(blocks, scales, device):
     w, wT, sc = vp(), vp(), vp()
     K, R, S, C = ci(), ci(), ci(), ci()
     off = 0
-    keep = []
     for i, (bi, key, Wc, d, scale) in enumerate(jobs):
         t = buf[off:off + Wc.numel()]
         off += Wc.numel()
         out[bi][key] = t
-        keep.append(Wc)
         w[i], wT[i] = Wc.data_ptr(), t.data_ptr()
         sc[i] = scale.data_ptr() if scale is not None else None
         K[i], R[i], S[i], C[i] = d.K, d.R, d.S, d.C
@@ -487,7 +475,6 @@ USE_WINOGRAD = True
 # (1024 -> 1024) and, at inference batch sizes, res4 (256 -> 256).  Narrow layers (C < 256) and
 # the two-image res4 maps of a train step stay on the implicit-GEMM kernel: their GEMMs would
 # be 2-8 K slices deep and the transform passes would cost what the MFMAs save.
-import os as _os
 WINOGRAD_MIN_CHANNELS = int(_os.environ.get('MRCNN_WINO_MIN_CH', 256))
 WINOGRAD_MIN_WORK = int(_os.environ.get('MRCNN_WINO_MIN_WORK', 1 << 27))          # tiles x C x K
 # Which passes take the Winograd route.  Backward-data and backward-filter always do: their
@@ -523,6 +510,13 @@ def uses_winograd(d):
         return False
     tiles = d.N * ((d.H + 3) // 4) * ((d.W + 3) // 4)
     return min(d.C, d.K) >= WINOGRAD_MIN_CHANNELS and tiles * d.C * d.K >= WINOGRAD_MIN_WORK
+
+
+def _wino_forward(kind, training):
+    """Does the FORWARD of a routed layer (``uses_winograd``) take the Winograd route?  ``kind``:
+    'conv2d' (F.conv2d) or 'stage' (a fused stage's conv2); ``training``: the call records a graph
+    (see WINOGRAD_TRAIN_FORWARD above; without one every routed forward takes it)."""
+    return WINOGRAD_TRAIN_FORWARD in (True, kind) or not training
 
 
 def _wino_ws(d, device, tag='wino'):
@@ -689,13 +683,39 @@ def join_wgrad_stream(device=None):
 # held back at the end of a step and run INSIDE the next step's window on a second stream, where
 # they cost nothing (optimizers.MomentumSGD.defer_weight_gradients; same gradients, same update,
 # applied before the parameter is read again: results are bit-identical).
+class WgradJob(object):
+    """One weight gradient: ``gW`` = backward-filter of descriptor ``d`` from the input ``x`` and
+    the output gradient ``g`` (rows scaled by ``row_scale`` if given).  ``wino``: on the Winograd
+    route, from the raw input ``x`` or the forward's kept transform ``v`` (the other is None)."""
+
+    def __init__(self, d, x, g, gW, row_scale=None, wino=False, v=None):
+        self.d, self.x, self.g, self.gW = d, x, g, gW
+        self.row_scale, self.wino, self.v = row_scale, wino, v
+
+    def launch(self, stream_tag=''):
+        """On the current stream; ``stream_tag`` ('', '-side', '-defer') names the scratch, which
+        two streams must not share."""
+        if self.wino:
+            wino_wgrad_into(self.d, self.x, self.v, self.g, self.gW, self.row_scale,
+                            tag='wino' + stream_tag)
+        else:
+            _launch_wgrad(self.d, self.x, self.g, self.gW, self.row_scale, 'wgrad' + stream_tag)
+
+    def tensors(self):
+        """The operands a held-back job keeps alive."""
+        return [t for t in (self.x, self.g, self.gW, self.row_scale, self.v) if t is not None]
+
+
 class DeferQueue(object):
-    """``jobs``: (d, x, g, gW, row_scale, wino, v) per held-back weight gradient; ``wino``: on the
-    Winograd route, from the raw input ``x`` or the forward's kept transform ``v`` (the other is None)."""
+    """``jobs``: one ``WgradJob`` per held-back weight gradient of the parameters ``params``."""
 
     def __init__(self, params):
         self.ids = set(id(p) for p in params)
         self.jobs = []
+
+    def grad_ptrs(self):
+        """Addresses of the gradient buffers the held-back jobs will write."""
+        return set(j.gW.data_ptr() for j in self.jobs)
 
 
 _DEFER = None          # set by MomentumSGD.update around backward
@@ -711,52 +731,38 @@ def defer_stream(device):
 
 def run_deferred_wgrads(jobs):
     """Launch the held-back weight gradients on the current stream (the caller selects it)."""
-    for d, x, g, gW, row_scale, wino, v in jobs:
-        if wino:
-            wino_wgrad_into(d, x, v, g, gW, row_scale, tag='wino-defer')
-            continue
-        ws = _lib.workspace(_lib.load().mrcnn_conv2d_wgrad_workspace_bytes(ctx_desc(d)),
-                            g.device, 'wgrad-defer')
-        _lib.call('mrcnn_conv2d_wgrad_ex', ctx_desc(d), _lib.ptr(x), _lib.ptr(g), _lib.ptr(gW),
-                  _lib.ptr(ws), _lib.ptr(row_scale), _lib.stream_ptr())
+    for job in jobs:
+        job.launch('-defer')
 
 
-def _wino_wgrad(d, x, v, g, W, row_scale=None):
-    """Weight gradient on the Winograd route from the raw input ``x`` or the kept transformed
-    input ``v`` (the other is None); same gradient-ownership rules as _wgrad_raw."""
-    direct = _direct_grad(W)
+def _launch_wgrad(d, x, g, gW, row_scale=None, tag='wgrad', ex=True):
+    """The implicit-GEMM weight gradient into the buffer ``gW``, on the current stream.  ``ex``
+    False: the plain entry point (no ``row_scale``)."""
+    ws = _lib.workspace(_lib.load().mrcnn_conv2d_wgrad_workspace_bytes(ctx_desc(d)), g.device, tag)
+    tail = (_lib.ptr(row_scale), _lib.stream_ptr()) if ex else (_lib.stream_ptr(),)
+    _lib.call('mrcnn_conv2d_wgrad_ex' if ex else 'mrcnn_conv2d_wgrad', ctx_desc(d), _lib.ptr(x),
+              _lib.ptr(g), _lib.ptr(gW), _lib.ptr(ws), *tail)
+
+
+def _wgrad(d, x, g, W, side=None, row_scale=None, wino=False, v=None):
+    """Weight gradient of parameter ``W``; returns the tensor autograd should see for W (None when
+    written in place or held back in the defer queue).  ``wino`` / ``v``: see ``WgradJob``.  With
+    ``side`` (a stream) the launch is queued there, ordered after everything queued so far on the
+    current stream; only arena-backed (direct) gradients may use it."""
+    gW, result = _grad_target(W)
+    job = WgradJob(d, x, g, gW, row_scale, wino, v)
+    direct = result is None
     if direct and _DEFER is not None and id(W) in _DEFER.ids:
-        _DEFER.jobs.append((d, x, g, W.grad, row_scale, True, v))
-        return None
-    gW = W.grad if direct else empty_nhwc(tuple(W.shape), g.device)
-    wino_wgrad_into(d, x, v, g, gW, row_scale)
-    return None if direct else gW
-
-
-def _wgrad_raw(d, x, g, W, side=None, row_scale=None):
-    """Returns the tensor autograd should see for W (None when written in place).  With
-    ``side`` (a stream) the launch is queued there, ordered after everything queued so far
-    on the current stream; only arena-backed (direct) gradients may use it."""
-    direct = _direct_grad(W)
-    if direct and _DEFER is not None and id(W) in _DEFER.ids:
-        _DEFER.jobs.append((d, x, g, W.grad, row_scale, False, None))
-        return None
-    gW = W.grad if direct else empty_nhwc(tuple(W.shape), g.device)
-    if side is not None and direct:
+        _DEFER.jobs.append(job)
+    elif direct and side is not None:
         side.wait_stream(torch.cuda.current_stream(g.device))
         for t in (x, g):
             t.record_stream(side)
         with torch.cuda.stream(side):
-            ws = _lib.workspace(_lib.load().mrcnn_conv2d_wgrad_workspace_bytes(ctx_desc(d)),
-                                g.device, 'wgrad-side')
-            _lib.call('mrcnn_conv2d_wgrad_ex', ctx_desc(d), _lib.ptr(x), _lib.ptr(g),
-                      _lib.ptr(gW), _lib.ptr(ws), _lib.ptr(row_scale), _lib.stream_ptr())
-        return None
-    ws = _lib.workspace(_lib.load().mrcnn_conv2d_wgrad_workspace_bytes(ctx_desc(d)),
-                        g.device, 'wgrad')
-    _lib.call('mrcnn_conv2d_wgrad_ex', ctx_desc(d), _lib.ptr(x), _lib.ptr(g), _lib.ptr(gW),
-              _lib.ptr(ws), _lib.ptr(row_scale), _lib.stream_ptr())
-    return None if direct else gW
+            job.launch('-side')
+    else:
+        job.launch()
+    return result
 
 
 # ---------------------------------------------------------------------------------------
@@ -885,15 +891,53 @@ def _pool_bwd_alone(side, device):
         torch.cuda.current_stream(device).wait_stream(side)
 
 
-# set by building_block() around _StageFn.apply: inside forward() grad mode is always off and
-# ctx.needs_input_grad reports the inputs' requires_grad flags even under torch.no_grad()
-_STAGE_RECORDS_GRAPH = True
+class _StageBlock(object):
+    """One bottleneck of a stage node, built once by ``_StageFn.forward``: the filters W1..W4 with
+    their affine vectors s* / b* (conv4's are None without a projection shortcut), the
+    descriptors d1..d4 (d4 None likewise) and ``i1..i4``, the index of each filter among
+    ``forward``'s inputs — that of its flag in ``needs_input_grad`` and of its gradient in what
+    ``backward`` returns."""
+
+    def __init__(self, params, at, has_proj):
+        """From forward's flat ``params``, this block's starting at ``params[at]``."""
+        self.n_params = 12 if has_proj else 9
+        (self.W1, self.s1, self.b1, self.W2, self.s2, self.b2,
+         self.W3, self.s3, self.b3) = params[at:at + 9]
+        self.W4, self.s4, self.b4 = params[at + 9:at + 12] if has_proj else (None, None, None)
+        w1 = _StageFn.FIXED_INPUTS + at
+        self.i1, self.i2, self.i3, self.i4 = w1, w1 + 3, w1 + 6, w1 + 9
+        self.d1 = self.d2 = self.d3 = self.d4 = None
+
+
+# The activations of one bottleneck that backward reads: its input and its three ReLU outputs.
+_StageActs = collections.namedtuple('_StageActs', 'x h1 h2 y')
+
+
+def _save_stage(ctx, x, acts, wino_v):
+    """Saved tensors of a stage node: the input, (h1, h2, y) per block, then the kept Winograd
+    input transforms (``wino_v[i]`` of block i, or None)."""
+    ctx.wino_slots = [i for i, v in enumerate(wino_v) if v is not None]
+    ctx.save_for_backward(x, *([t for a in acts for t in a] + [wino_v[i] for i in ctx.wino_slots]))
+
+
+def _saved_stage(ctx):
+    """Inverse of ``_save_stage``: ([_StageActs per block], {block index: kept transform})."""
+    saved = ctx.saved_tensors
+    acts, xin = [], saved[0]
+    for i in range(len(ctx.blocks)):
+        acts.append(_StageActs(xin, *saved[1 + 3 * i:4 + 3 * i]))
+        xin = acts[-1].y
+    return acts, dict(zip(ctx.wino_slots, saved[1 + 3 * len(acts):]))
 
 
 class _StageFn(torch.autograd.Function):
 
+    # inputs of forward in front of *params (x .. records_graph): a change of the signature below
+    # changes this number, and nothing else
+    FIXED_INPUTS = 7
+
     @staticmethod
-    def forward(ctx, x, strides, proj, poll, tail_rows, roi, *params):
+    def forward(ctx, x, strides, proj, poll, tail_rows, roi, records_graph, *params):
         """``roi`` (a ``RoiSpec`` or None): with it ``x`` is the FEATURE MAP and block 0 (which must
         have a projection shortcut) runs its two 1x1 convolutions on the map and pools their outputs
         (projected pooling, see above) — the stage then equals ``stage(roi_align(x, roi))``.
@@ -904,70 +948,70 @@ class _StageFn(torch.autograd.Function):
         the node then returns ``(average_pooling(y) (N,C,1,1), y[tail_rows])`` instead of the
         stage output y (the RoI head's two consumers of res5, models/mask_rcnn_resnet.py:186-195),
         and its backward forms the gradient entering the last block from both in ONE pass,
-        ReLU mask included (``mrcnn_head_tail_bwd``); ``params``: per block
+        ReLU mask included (``mrcnn_head_tail_bwd``); ``records_graph``: torch.is_grad_enabled()
+        at the call (in here grad mode is always off and ctx.needs_input_grad reports the inputs'
+        requires_grad flags even under torch.no_grad()); ``params``: per block
         W1,s1,b1,W2,s2,b2,W3,s3,b3 (+ W4,s4,b4 when proj[i])."""
+        assert len(ctx.needs_input_grad) == _StageFn.FIXED_INPUTS + len(params)
         _lib.require_device(x, params[0])
         x = nhwc(x)
-        blocks, saved, pos, wino_v = [], [x], 0, []
-        h = x
+        ng = ctx.needs_input_grad
+        training = records_graph and any(ng)
+        blocks, at = [], 0
+        for pj in proj:
+            blocks.append(_StageBlock(params, at, pj))
+            at += blocks[-1].n_params
         if roi is not None:
-            if roi.proj is not None and _STAGE_RECORDS_GRAPH and any(ctx.needs_input_grad):
+            if roi.proj is not None and training:
                 raise ValueError('RoiSpec(proj=) is for graph-free calls (the projections would be '
                                  'outside the recorded graph)')
-            if not (proj[0] and strides[0] == 1 and params[0].shape[2] == 1 and params[9].shape[2] == 1):
+            a = blocks[0]
+            if not (a.W4 is not None and strides[0] == 1 and a.W1.shape[2] == 1 and a.W4.shape[2] == 1):
                 raise ValueError('projected pooling needs a first block with 1x1 conv1 / conv4 at stride 1 '
                                  '(the RoI bins of the stride are selected by RoiSpec.bin_stride)')
-        for bi, (stride, pj) in enumerate(zip(strides, proj)):
-            n = 12 if pj else 9
-            W1, s1, b1, W2, s2, b2, W3, s3, b3 = params[pos:pos + 9]
-            W4, s4, b4 = params[pos + 9:pos + 12] if pj else (None, None, None)
-            pooled_here = roi is not None and bi == 0
-            d1 = make_desc(h.shape, W1.shape, stride, 0)
+        acts, wino_v = [], []
+        h = x
+        for b, stride in zip(blocks, strides):
+            pooled_here = roi is not None and b is blocks[0]
+            b.d1 = make_desc(h.shape, b.W1.shape, stride, 0)
             if pooled_here:
                 # conv1 on the map, then pooled with bn1 + ReLU in ROIAlign's epilogue
-                z1 = roi.proj[0] if roi.proj is not None else _fwd_raw(h, nhwc(W1), d1, None, None, None, False)
-                h1 = _roi_pool_affine(z1, roi, s1, b1, True)
+                z1 = roi.proj[0] if roi.proj is not None else _fwd_raw(h, nhwc(b.W1), b.d1, None, None, None, False)
+                h1 = _roi_pool_affine(z1, roi, b.s1, b.b1, True)
                 del z1
             else:
-                h1 = _fwd_raw(h, nhwc(W1), d1, s1, b1, None, True)
-            d2 = make_desc(h1.shape, W2.shape, 1, 1)
+                h1 = _fwd_raw(h, nhwc(b.W1), b.d1, b.s1, b.b1, None, True)
+            b.d2 = make_desc(h1.shape, b.W2.shape, 1, 1)
             v2 = None
-            training = _STAGE_RECORDS_GRAPH and any(ctx.needs_input_grad)
-            if uses_winograd(d2) and (WINOGRAD_TRAIN_FORWARD in (True, 'stage') or not training):
+            if uses_winograd(b.d2) and _wino_forward('stage', training):
                 # (with a weight gradient to come, the transformed input is kept for it)
-                h2, v2 = wino_fwd(h1, nhwc(W2), d2, s2, b2, True,
-                                  keep_v=training and bool(ctx.needs_input_grad[6 + pos + 3]),
-                                  cache_for=None if training else W2,
+                h2, v2 = wino_fwd(h1, nhwc(b.W2), b.d2, b.s2, b.b2, True,
+                                  keep_v=training and bool(ng[b.i2]),
+                                  cache_for=None if training else b.W2,
                                   exact_signs=training)
             else:
-                h2 = _fwd_raw(h1, nhwc(W2), d2, s2, b2, None, True)
-            d4 = None
-            if pj:
-                d4 = make_desc(h.shape, W4.shape, stride, 0)
+                h2 = _fwd_raw(h1, nhwc(b.W2), b.d2, b.s2, b.b2, None, True)
+            if b.W4 is None:
+                shortcut = h
+            else:
+                b.d4 = make_desc(h.shape, b.W4.shape, stride, 0)
                 if pooled_here:
-                    z4 = roi.proj[1] if roi.proj is not None else _fwd_raw(h, nhwc(W4), d4, None, None, None, False)
-                    shortcut = _roi_pool_affine(z4, roi, s4, b4, False)
+                    z4 = roi.proj[1] if roi.proj is not None else _fwd_raw(h, nhwc(b.W4), b.d4, None, None, None, False)
+                    shortcut = _roi_pool_affine(z4, roi, b.s4, b.b4, False)
                     del z4
                 else:
-                    shortcut = _fwd_raw(h, nhwc(W4), d4, s4, b4, None, False)
-            else:
-                shortcut = h
-            d3 = make_desc(h2.shape, W3.shape, 1, 0)
-            y = _fwd_raw(h2, nhwc(W3), d3, s3, b3, shortcut, True)
-            blocks.append(((d1, d2, d3, d4), (W1, W2, W3, W4), pos))
+                    shortcut = _fwd_raw(h, nhwc(b.W4), b.d4, b.s4, b.b4, None, False)
+            b.d3 = make_desc(h2.shape, b.W3.shape, 1, 0)
+            y = _fwd_raw(h2, nhwc(b.W3), b.d3, b.s3, b.b3, shortcut, True)
             if RELU_TAP is not None:
                 RELU_TAP.append(('block', (h1, h2, y)))
-            saved += [h1, h2, y, s1, s2, s3] + ([s4] if pj else [])
+            acts.append((h1, h2, y))
             wino_v.append(v2)
-            pos += n
             h = y
         ctx.blocks = blocks
-        ctx.proj = tuple(proj)
         ctx.poll = poll
         ctx.roi = roi
-        ctx.n_saved = len(saved)
-        ctx.wino_slots = [i for i, v in enumerate(wino_v) if v is not None]
-        ctx.save_for_backward(*(saved + [wino_v[i] for i in ctx.wino_slots]))
+        _save_stage(ctx, x, acts, wino_v)
         ctx.tail = tail_rows is not None
         if ctx.tail:
             # the two consumers of the stage output, produced here so that backward receives
@@ -988,36 +1032,26 @@ class _StageFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, g_rows=None):
-        saved = list(ctx.saved_tensors)
-        wino_v = dict(zip(ctx.wino_slots, saved[ctx.n_saved:]))
-        saved = saved[:ctx.n_saved]
+        acts, wino_v = _saved_stage(ctx)
+        blocks = ctx.blocks
         ng = ctx.needs_input_grad
         grads = [None] * len(ng)
         poll = ctx.poll
         if poll is not None:
             poll()                 # everything upstream of this stage has queued its gradients
-        # unpack per-block activations
-        acts, pos, xin = [], 1, saved[0]
-        for pj in ctx.proj:
-            n = 7 if pj else 6
-            h1, h2, y, s1, s2, s3 = saved[pos:pos + 6]
-            s4 = saved[pos + 6] if pj else None
-            acts.append((xin, h1, h2, y, s1, s2, s3, s4))
-            xin = y
-            pos += n
         if not ctx.tail:
             gy = nhwc(gy)
         # small-M layers (backbone stages) leave CUs idle: their weight gradients go to a
         # second stream so that they can share the GPU with the next dgrad
-        d_top = ctx.blocks[-1][0][2]
+        d_top = blocks[-1].d3
         dev_ = gy.device if gy is not None else g_rows.device
         side = wgrad_stream(dev_) if d_top.N * d_top.P * d_top.Q <= SMALL_WGRAD_MAX_PIXELS else None
         # all the stage's filter transposes in one launch (built during the forward on the side
         # stream instead, they measured no faster: 53.2 vs 53.0 ms per step)
-        stage_wT = _stage_transposes(ctx.blocks, [(a[6], a[7]) for a in acts], dev_)
+        stage_wT = _stage_transposes(blocks, dev_)
         # gm: gradient w.r.t. the block output, already through that output's ReLU
+        y_top = acts[-1].y
         if ctx.tail:
-            y_top = acts[-1][3]
             R_, C_, Hh, Ww = y_top.shape
             if gy is None:
                 gy = torch.zeros((R_, C_), dtype=torch.float32, device=dev_)
@@ -1028,67 +1062,60 @@ class _StageFn(torch.autograd.Function):
                       _lib.ptr(ctx.tail_slot) if gr is not None else None, _lib.ptr(y_top),
                       _lib.ptr(gm), R_, Hh * Ww, C_, _lib.stream_ptr())
         else:
-            gm = epilogue_bwd(gy, acts[-1][3], None)
-        for i in range(len(acts) - 1, -1, -1):
-            x, h1, h2, y, s1, s2, s3, s4 = acts[i]
-            (d1, d2, d3, d4), (W1, W2, W3, W4), p0 = ctx.blocks[i]
-            wT = stage_wT[i]
-            base = 6 + p0                      # index of W1 among the forward inputs
+            gm = epilogue_bwd(gy, y_top, None)
+        for i in range(len(blocks) - 1, -1, -1):
+            b, wT = blocks[i], stage_wT[i]
+            x, h1, h2, _ = acts[i]
             first = i == 0
             pooled_here = first and ctx.roi is not None
+            need_w4 = b.W4 is not None and ng[b.i4]
             # what the gradient leaving this block must be masked with: the previous block's
             # output ReLU (= this block's input); the stage input belongs to someone else
             xm = None if first else x
-            gz4 = None
-            if pooled_here and (ng[base + 9] or ng[0]):
-                # the shortcut's gradient back on the map (ROIAlign's adjoint commutes with the
+            # the gradient the shortcut's conv4 reads: the block output's, or with pooling ...
+            g4 = gm
+            if pooled_here and (need_w4 or ng[0]):
+                # ... that gradient back on the map (ROIAlign's adjoint commutes with the
                 # per-channel scale s4, which stays folded into conv4's filter / gradient rows).
                 # Queued BEFORE this block's weight gradients go to the side stream, and with the side
                 # stream drained: see _pool_bwd_alone.
                 _pool_bwd_alone(side, dev_)
-                gz4 = _roi_pool_bwd(gm, ctx.roi, (x.shape[0], d4.K, x.shape[2], x.shape[3]))
-            if ng[base + 6]:
-                grads[base + 6] = _wgrad_raw(d3, h2, gm, W3, side, row_scale=s3)
-            if pooled_here:
-                if ng[base + 9]:
-                    grads[base + 9] = _wgrad_raw(d4, x, gz4, W4, side, row_scale=s4)
-            elif W4 is not None and ng[base + 9]:
-                grads[base + 9] = _wgrad_raw(d4, x, gm, W4, side, row_scale=s4)
-            gh2 = _dgrad_raw(d3, gm, nhwc(W3), fold_scale=s3, out_mask_y=h2, out_scale=s2,
+                g4 = _roi_pool_bwd(gm, ctx.roi, (x.shape[0], b.d4.K, x.shape[2], x.shape[3]))
+            if ng[b.i3]:
+                grads[b.i3] = _wgrad(b.d3, h2, gm, b.W3, side, row_scale=b.s3)
+            if need_w4:
+                grads[b.i4] = _wgrad(b.d4, x, g4, b.W4, side, row_scale=b.s4)
+            gh2 = _dgrad_raw(b.d3, gm, nhwc(b.W3), fold_scale=b.s3, out_mask_y=h2, out_scale=b.s2,
                              wT=wT.get('3'))
-            if uses_winograd(d2):
-                if ng[base + 3]:
+            if uses_winograd(b.d2):
+                if ng[b.i2]:
                     v2 = wino_v.get(i)
-                    grads[base + 3] = _wino_wgrad(d2, h1 if v2 is None else None, v2, gh2, W2)
-                gh1 = wino_dgrad(d2, gh2, nhwc(W2), out_scale=s1, out_mask_y=h1)
+                    grads[b.i2] = _wgrad(b.d2, h1 if v2 is None else None, gh2, b.W2, wino=True, v=v2)
+                gh1 = wino_dgrad(b.d2, gh2, nhwc(b.W2), out_scale=b.s1, out_mask_y=h1)
             else:
-                if ng[base + 3]:
-                    grads[base + 3] = _wgrad_raw(d2, h1, gh2, W2, side)
-                gh1 = _dgrad_raw(d2, gh2, nhwc(W2), out_mask_y=h1, out_scale=s1, wT=wT.get('2'))
-            if pooled_here and (ng[base] or ng[0]):
+                if ng[b.i2]:
+                    grads[b.i2] = _wgrad(b.d2, h1, gh2, b.W2, side)
+                gh1 = _dgrad_raw(b.d2, gh2, nhwc(b.W2), out_mask_y=h1, out_scale=b.s1, wT=wT.get('2'))
+            if pooled_here and (ng[b.i1] or ng[0]):
                 _pool_bwd_alone(side, dev_)
-                gh1 = _roi_pool_bwd(gh1, ctx.roi, (x.shape[0], d1.K, x.shape[2], x.shape[3]))
-            if ng[base]:
-                grads[base] = _wgrad_raw(d1, x, gh1, W1, side)
+                gh1 = _roi_pool_bwd(gh1, ctx.roi, (x.shape[0], b.d1.K, x.shape[2], x.shape[3]))
+            if ng[b.i1]:
+                grads[b.i1] = _wgrad(b.d1, x, gh1, b.W1, side)
             if poll is not None:
                 poll()             # this block's weight gradients are queued
             if first and not ng[0]:
                 break
-            if pooled_here:
-                gx = _dgrad_raw(d1, gh1, nhwc(W1), wT=wT.get('1'))
-                gm = _dgrad_raw(d4, gz4, nhwc(W4), fold_scale=s4, out=gx, accum=True, wT=wT.get('4'))
+            if b.W4 is None:
+                gm = _dgrad_raw(b.d1, gh1, nhwc(b.W1), res_g=gm, out_mask_y=xm, wT=wT.get('1'))
                 continue
-            if W4 is None:
-                gm = _dgrad_raw(d1, gh1, nhwc(W1), res_g=gm, out_mask_y=xm, wT=wT.get('1'))
-            elif d1.stride == 1:
-                gx = _dgrad_raw(d1, gh1, nhwc(W1), wT=wT.get('1'))
-                gm = _dgrad_raw(d4, gm, nhwc(W4), fold_scale=s4, out=gx, accum=True,
-                                out_mask_y=xm, wT=wT.get('4'))
-            else:
-                gx = _dgrad_raw(d1, gh1, nhwc(W1), wT=wT.get('1'))
-                gm = _dgrad_raw(d4, gm, nhwc(W4), fold_scale=s4, out=gx, accum=True, wT=wT.get('4'))
-                if xm is not None:
-                    gm = epilogue_bwd(gm, xm, None)
+            # projection shortcut: both data gradients into one buffer; the input's ReLU mask is
+            # fused into the second where conv1 has stride 1, else applied by a pass of its own
+            fused = b.d1.stride == 1
+            gx = _dgrad_raw(b.d1, gh1, nhwc(b.W1), wT=wT.get('1'))
+            gm = _dgrad_raw(b.d4, g4, nhwc(b.W4), fold_scale=b.s4, out=gx, accum=True,
+                            out_mask_y=xm if fused else None, wT=wT.get('4'))
+            if xm is not None and not fused:
+                gm = epilogue_bwd(gm, xm, None)
         if ng[0]:
             grads[0] = gm
         return tuple(grads)
@@ -1107,9 +1134,5 @@ def building_block(x, blocks, first_stride=None, poll=None, tail_rows=None, roi=
                    b.conv3.W, b.bn3.W, b.bn3.b]
         if b.projection:
             params += [b.conv4.W, b.bn4.W, b.bn4.b]
-    global _STAGE_RECORDS_GRAPH
-    _STAGE_RECORDS_GRAPH = torch.is_grad_enabled()
-    try:
-        return _StageFn.apply(x, tuple(strides), tuple(proj), poll, tail_rows, roi, *params)
-    finally:
-        _STAGE_RECORDS_GRAPH = True
+    return _StageFn.apply(x, tuple(strides), tuple(proj), poll, tail_rows, roi,
+                          torch.is_grad_enabled(), *params)

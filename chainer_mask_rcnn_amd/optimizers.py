@@ -193,9 +193,8 @@ class MomentumSGD(object):
                           float(lr), float(momentum), float(wd), float(scale), 1, _lib.stream_ptr())
             conv.weights_changed()
             for job in jobs:                       # keep the operands alive until S2 is done
-                for t in job[1:]:
-                    if isinstance(t, torch.Tensor):
-                        t.record_stream(side)
+                for t in job.tensors():
+                    t.record_stream(side)
             ev = torch.cuda.Event()
             ev.record(side)
         self._join = ev
@@ -280,9 +279,9 @@ class MomentumSGD(object):
             # Data parallel: a deferred parameter is in NO in-backward bucket (the bucket plan
             # leaves it to reduce_deferred).  If its weight gradient was not actually held back
             # this step (the in-place claim failed: gradient view dropped, parameter used twice,
-            # a route that bypasses _wgrad_raw), nothing would all-reduce it and the ranks would
+            # a route that bypasses conv._wgrad), nothing would all-reduce it and the ranks would
             # drift apart silently — fail loudly instead.
-            queued = set(j[3].data_ptr() for j in deferred.jobs)
+            queued = deferred.grad_ptrs()
             missing = [i for i, p in enumerate(a.params)
                        if id(p) in deferred.ids and p._grad_epoch == a.epoch
                        and p.grad.data_ptr() not in queued]
@@ -295,7 +294,7 @@ class MomentumSGD(object):
         if deferred is not None and deferred.jobs:
             # parameters whose gradient kernels were held back: their slices are updated by
             # launch_pending(), after those kernels, in the next step's proposal window
-            grads = set(j[3].data_ptr() for j in deferred.jobs)
+            grads = deferred.grad_ptrs()
             held = set(i for i, p in enumerate(a.params) if p.grad.data_ptr() in grads)
             self._pending = (deferred.jobs,
                              [a.slice_bounds(f, l) for f, l in _runs([i in held for i in range(len(a.params))])],
