@@ -10,13 +10,18 @@ rasterised with ``PIL.ImageDraw`` exactly as the reference does (:136-143).
     dataset[i] -> img (H,W,3) uint8 RGB, bboxes (G,4) f32 (y1,x1,y2,x2), labels (G,) i32,
                   masks (G,H,W) i32 {0,1} [, crowds (G,) i32] [, areas (G,) f32]
 
-which is what ``datasets.MaskRCNNTransform`` consumes (datasets/transforms.py:10-51).
+With ``packed_masks=True`` the mask field is a ``datasets.PackedMasks`` of the same rasters (bits,
+1/256 of the int32 stack, which is then never built); ``unpack()`` gives the array above.
+
+This is what ``datasets.MaskRCNNTransform`` consumes (datasets/transforms.py:10-51).
 There is no network here: the data must already be under ``root_dir``.
 """
 import json
 import os.path as osp
 
 import numpy as np
+
+from .packed_masks import PackedMasks
 
 
 def rle_counts_from_string(s):
@@ -73,7 +78,7 @@ class COCOInstanceSegmentationDataset(object):
     root_dir = osp.expanduser('~/data/datasets/COCO')
 
     def __init__(self, split, use_crowd=False, return_crowd=False, return_area=False,
-                 root_dir=None):
+                 root_dir=None, packed_masks=False):
         if root_dir is not None:
             self.root_dir = root_dir
         test_dev = split == 'test-dev'
@@ -98,6 +103,7 @@ class COCOInstanceSegmentationDataset(object):
         self._use_crowd = use_crowd
         self._return_crowd = return_crowd
         self._return_area = return_area
+        self._packed_masks = packed_masks
 
         with open(ann_file) as f:
             data = json.load(f)
@@ -191,7 +197,8 @@ class COCOInstanceSegmentationDataset(object):
         example = [
             col(lambda a, m: mask_to_bbox(m), np.float32).reshape((-1, 4)),       # y1, x1, y2, x2
             col(lambda a, m: self.cat_id_to_class_id[a['category_id']], np.int32),
-            col(lambda a, m: m, np.int32).reshape((-1, height, width)),
+            PackedMasks.from_instances([m for _, m in kept], height, width) if self._packed_masks
+            else col(lambda a, m: m, np.int32).reshape((-1, height, width)),
         ]
         if self._return_crowd:
             example.append(col(lambda a, m: a['iscrowd'], np.int32))

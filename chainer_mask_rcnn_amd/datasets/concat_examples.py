@@ -4,7 +4,8 @@
 Same arguments.  ``device`` is a torch device (or None: leave everything where it is);
 entries listed in ``indices_to_device`` become device tensors, the others stay NumPy.
 Image entries that are already device tensors (``MaskRCNNTransform``) are zero-padded and
-stacked on the device, in channels-last memory — the layout the extractor reads."""
+stacked on the device, in channels-last memory — the layout the extractor reads; device masks
+(``MaskRCNNTransform(device_masks=True)``, uint8) are zero-padded and stacked in row-major order."""
 import numpy as np
 import torch
 
@@ -23,7 +24,10 @@ def _concat_arrays(arrays, padding):
         if padding is None:
             return torch.stack(list(arrays))
         shape = (len(arrays),) + _pad_shape(arrays)
-        fmt = torch.channels_last if len(shape) == 4 else torch.contiguous_format
+        # images (float) in the layout the extractor reads; a mask batch (N, G, H, W) uint8 stays
+        # in plain row-major order: mrcnn_mask_targets reads each image's (G, H, W) block as is
+        fmt = torch.channels_last if len(shape) == 4 and first.is_floating_point() \
+            else torch.contiguous_format
         out = torch.full(shape, padding, dtype=first.dtype, device=first.device).contiguous(
             memory_format=fmt)
         for i, a in enumerate(arrays):

@@ -4,13 +4,16 @@ Same call protocol and return tuple as the reference.  What moves: the image is 
 once as it was decoded (HWC, usually uint8) and resized / mean-subtracted / flipped by ONE
 device kernel (``mrcnn_prepare_image``), so the transform returns a device tensor for the
 image; boxes, labels and masks stay host NumPy arrays because the target creators that
-consume them run on the host (``MaskRCNNTrainChain``).  The random flip consumes one
+consume them run on the host (``MaskRCNNTrainChain``).  ``device_masks=True`` moves the masks too:
+they are uploaded as bits and resized / flipped by ``mrcnn_mask_resize_nearest``.  The random flip consumes one
 ``random.choice([True, False])`` from Python's global generator, exactly what
 ``chainercv.transforms.random_flip(img, x_random=True)`` draws.
 """
 import random
 
 import numpy as np
+
+from .packed_masks import PackedMasks
 
 
 def resize_bbox(bbox, in_size, out_size):
@@ -93,11 +96,18 @@ class MaskRCNNTransform(object):
     """``MaskRCNNTransform(mask_rcnn, train=True)(in_data)`` with ``in_data`` =
     ``(img HWC, bbox, label, mask)`` or the 6-tuple that also carries ``crowd, area``.
     Evaluation mode only transposes the image; training mode returns
-    ``(img, bbox, label, mask, scale)``."""
+    ``(img, bbox, label, mask, scale)``.
 
-    def __init__(self, mask_rcnn, train=True):
+    ``mask`` may be a ``datasets.PackedMasks``.  With ``device_masks=True`` (training mode) the
+    masks cross PCIe as bits — a dense stack is packed on the host first — and the returned mask
+    is the (G, o_H, o_W) uint8 device tensor that ``mrcnn_mask_resize_nearest`` builds on the
+    image's stream; the draw from ``random``, boxes, labels, image and scale are the same.
+    Otherwise a ``PackedMasks`` is unpacked and takes the host path."""
+
+    def __init__(self, mask_rcnn, train=True, device_masks=False):
         self.mask_rcnn = mask_rcnn
         self.train = train
+        self.device_masks = device_masks
 
     def __call__(self, in_data):
         if len(in_data) not in (4, 6):
@@ -120,6 +130,10 @@ class MaskRCNNTransform(object):
             bbox = resize_bbox(bbox, in_size, out_size)
         bbox = flip_bbox(bbox, out_size, x_flip=x_flip)
 
+        if self.device_masks:
+            return x, bbox, label, self._device_mask(mask, out_size, x_flip, x.device), scales[0]
+        if isinstance(mask, PackedMasks):
+            mask = mask.unpack()
         stack = mask[None] if mask.ndim == 2 else mask
         if len(mask) > 0:
             stack = resize_nearest(stack, out_size, x_flip=x_flip)
@@ -127,3 +141,14 @@ class MaskRCNNTransform(object):
             stack = flip(stack, x_flip=x_flip)
         mask = stack[0] if mask.ndim == 2 else stack
         return x, bbox, label, mask, scales[0]
+
+    @staticmethod
+    def _device_mask(mask, out_size, x_flip, device):
+        """The network-size masks as a uint8 device tensor; only the packed words are uploaded."""
+        from ..functions import gt_masks
+        flat = not isinstance(mask, PackedMasks) and mask.ndim == 2
+        if not isinstance(mask, PackedMasks):
+            mask = PackedMasks.from_dense(mask[None] if flat else mask)
+        out = gt_masks.resize_masks_nearest(gt_masks.upload_packed_masks(mask, device), out_size,
+                                            x_flip=x_flip)
+        return out[0] if flat else out

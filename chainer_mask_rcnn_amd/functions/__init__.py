@@ -20,3 +20,4 @@ from .rows import fanout_rows
 from .loss import (sigmoid_cross_entropy, softmax_cross_entropy, fast_rcnn_loc_loss,
                    mask_sigmoid_cross_entropy, softmax)
 from .proposal_ops import non_maximum_suppression
+from .gt_masks import resize_masks_nearest, upload_packed_masks

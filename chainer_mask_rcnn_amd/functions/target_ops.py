@@ -63,12 +63,15 @@ def proposal_targets_gather(cand, bbox, gt_label, assigned, chosen, n_fg, mean, 
     return sample_roi, loc, label, gt_index
 
 
-def mask_targets(masks_u8, sample_roi, gt_index, n_fg, mask_size):
-    """masks_u8 (G,H,W) uint8 device -> (n, M, M) int32 {-1,0,1}."""
+def mask_targets(masks_u8, sample_roi, gt_index, n_fg, mask_size, n=None):
+    """masks_u8 (G,H,W) uint8 device -> (n, M, M) int32 {-1,0,1}.  ``n`` defaults to the rows of
+    ``sample_roi``; a caller that holds only the ``n_fg`` foreground rows (the library reads no
+    others) passes the full row count."""
     _lib.require_device(masks_u8, sample_roi)
     assert masks_u8.dtype == torch.uint8 and masks_u8.is_contiguous()
     G, H, W = masks_u8.shape
-    n = int(sample_roi.shape[0])
+    n = int(sample_roi.shape[0]) if n is None else int(n)
+    assert int(n_fg) <= min(n, int(sample_roi.shape[0]), int(gt_index.shape[0]))
     out = torch.empty((n, mask_size, mask_size), dtype=torch.int32, device=sample_roi.device)
     _lib.call('mrcnn_mask_targets', _lib.ptr(masks_u8), G, H, W, _lib.ptr(sample_roi),
               _lib.ptr(gt_index), n, int(n_fg), int(mask_size), _lib.ptr(out), _lib.stream_ptr())

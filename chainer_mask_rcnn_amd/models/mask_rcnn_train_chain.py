@@ -162,7 +162,9 @@ class MaskRCNNTrainChain(torch.nn.Module):
 
     def forward(self, imgs, bboxes, labels, masks, scales):
         """imgs (N,3,H,W) device tensor; bboxes / labels / masks: per-image sequences of
-        host (or device) arrays (G,4) f32 / (G,) i32 / (G,H,W) i32; scales (N,) floats."""
+        host (or device) arrays (G,4) f32 / (G,) i32 / (G,H,W) i32; scales (N,) floats.  Masks
+        that are device tensors (uint8, ``MaskRCNNTransform(device_masks=True)``) are never copied
+        back: their mask targets come from ``mrcnn_mask_targets`` in both target paths."""
         tl = self.host_timeline
         mark = (lambda label: tl.append((label, time.perf_counter()))) if tl is not None \
             else (lambda label: None)
@@ -280,7 +282,7 @@ class MaskRCNNTrainChain(torch.nn.Module):
             roi = host_rois[batch_index]
             if split:
                 sample_roi, gt_roi_loc, gt_roi_label, job = ptc.sample(roi, bbox, label)
-                mask_jobs.append((job, mask))
+                mask_jobs.append((job, mask, sample_roi))
             else:
                 sample_roi, gt_roi_loc, gt_roi_label, gt_roi_mask = \
                     ptc(roi, bbox, label, to_np(mask))
@@ -329,9 +331,22 @@ class MaskRCNNTrainChain(torch.nn.Module):
 
         mark('head queued')
         # the head is now queued on the GPU: build the 14x14 mask targets on the host meanwhile
-        if split:
-            gt_roi_masks = [ptc.mask_targets(job, to_np(mask)) for job, mask in mask_jobs]
-        gt_roi_masks = up(gt_roi_masks, torch.int32)
+        on_device = lambda m: isinstance(m, torch.Tensor) and m.is_cuda
+        if split and any(on_device(mask) for _, mask, _ in mask_jobs):
+            # ground-truth masks that already live on the device (MaskRCNNTransform's
+            # device_masks) stay there: mrcnn_mask_targets crops them at the foreground rows of
+            # the host's sample (it rounds half-even, as np.round does in ptc.sample)
+            parts = []
+            for job, mask, sample_roi in mask_jobs:
+                if on_device(mask):
+                    parts.append(self._mask_targets_of_device_mask(job, mask, sample_roi, dev))
+                else:
+                    parts.append(_upload(ptc.mask_targets(job, to_np(mask)), torch.int32, dev))
+            gt_roi_masks = torch.cat(parts, 0)
+        else:
+            if split:
+                gt_roi_masks = [ptc.mask_targets(job, to_np(mask)) for job, mask, _ in mask_jobs]
+            gt_roi_masks = up(gt_roi_masks, torch.int32)
         mark('mask targets')
 
         # RPN targets (host) — after all ProposalTargetCreator calls, as in the reference,
@@ -369,6 +384,21 @@ class MaskRCNNTrainChain(torch.nn.Module):
         mark('rpn targets')
         return (rpn_locs, rpn_scores, sample_rois, sample_roi_indices, gt_roi_locs, gt_roi_labels,
                 gt_roi_masks, gt_rpn_locs, gt_rpn_labels, roi_cls_locs, roi_scores, roi_masks, mask_rows)
+
+    def _mask_targets_of_device_mask(self, job, mask, sample_roi, dev):
+        """(n, M, M) int32 mask targets of one image of the host-target path whose ground-truth
+        masks (G, H, W) are a device tensor: only the image's foreground rows of the sampled RoIs
+        and their ground-truth indices are uploaded; background rows are -1."""
+        from ..functions import target_ops as T
+        n, n_fg, _, gt_index = job
+        M = self.proposal_target_creator.mask_size
+        if n_fg == 0:
+            return torch.full((n, M, M), -1, dtype=torch.int32, device=dev)
+        roi_d, gt_index_d = _upload_many([sample_roi[:n_fg], gt_index], [torch.float32, torch.int32],
+                                         dev)
+        m = mask.to(device=dev)
+        m = m if m.dtype == torch.uint8 else (m != 0).to(torch.uint8)
+        return T.mask_targets(m.contiguous(), roi_d, gt_index_d, n_fg, M, n=n)
 
     def _forward_device_targets(self, features, img_size, scales, bboxes, labels, masks, anchor_h,
                                 mark):

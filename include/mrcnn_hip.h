@@ -732,6 +732,19 @@ int mrcnn_proposal_targets_gather(const float *cand, const float *bbox, const in
 int mrcnn_mask_targets(const uint8_t *masks, int G, int H, int W, const float *sample_roi,
                        const int32_t *gt_index, int n, int n_fg, int M, int32_t *out,
                        void *stream);
+/* Ground-truth masks at the network size from packed source-size masks ("Packed masks" above):
+ * packed (G,H,Wq) device, ys (outH) / xs (outW) device tables of the source row / column of each
+ * output row / column -> out (G,outH,outW) uint8 {0,1}, out[g,y,x] = bit (g, ys[y], xs[x]); the
+ * input mrcnn_mask_targets reads.  Replaces the host resize and flip of the dense mask stack,
+ * datasets/transforms.py:resize_nearest (the reference's
+ * chainer_mask_rcnn/datasets/transforms.py:36-38 `transforms.resize(mask, interpolation=0)` and
+ * :45-49 `transforms.flip`): the caller builds the tables with the cv2 INTER_NEAREST index rule
+ * and reverses xs for a horizontal flip, so only bits cross PCIe.  Table entries are clamped to
+ * [0, H-1] / [0, W-1]: reads and writes stay inside the buffers whatever the tables hold.  G = 0
+ * is a no-op.  H * W < 2^31, G * outH * outW < 2^31, W <= 524288 (a source row is staged in
+ * LDS). */
+int mrcnn_mask_resize_nearest(const uint64_t *packed, int G, int H, int W, const int32_t *ys,
+                              const int32_t *xs, int outH, int outW, uint8_t *out, void *stream);
 
 /* ---- Gradient exchange over RCCL / xGMI ---------------------------------------------- */
 /* Replaces ChainerMN's communicator as the reference uses it

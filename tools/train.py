@@ -74,6 +74,9 @@ def parse_args(argv=None):
                          "$CHAINER_DATASET_ROOT)")
     ap.add_argument('--allow-random-init', action='store_true',
                     help='train a real dataset from random weights when no ImageNet weights exist')
+    ap.add_argument('--device-masks', action='store_true',
+                    help='ground-truth masks cross PCIe as bits and are resized / flipped by a HIP '
+                         'kernel (COCO: the dataset also keeps them packed on the host)')
     ap.add_argument('--logs-dir', default=osp.join(ROOT, 'logs'))
     ap.add_argument('--no-plot', action='store_true', help='do not write loss.png / accuracy.png')
     return ap.parse_args(argv)
@@ -181,9 +184,12 @@ def datasets(args):
     import chainer_mask_rcnn_amd as cmr
     test_data, evaluator_type = test_dataset(args)
     if args.dataset == 'coco':
+        packed = getattr(args, 'device_masks', False)
         train_data = T.ConcatenatedDataset(
-            cmr.datasets.COCOInstanceSegmentationDataset('train', root_dir=args.coco_root),
-            cmr.datasets.COCOInstanceSegmentationDataset('valminusminival', root_dir=args.coco_root))
+            cmr.datasets.COCOInstanceSegmentationDataset('train', root_dir=args.coco_root,
+                                                         packed_masks=packed),
+            cmr.datasets.COCOInstanceSegmentationDataset('valminusminival', root_dir=args.coco_root,
+                                                         packed_masks=packed))
         return train_data, test_data, test_data.class_names, COCO_MODEL, evaluator_type
     if args.dataset == 'voc':
         train_data = cmr.datasets.SBDInstanceSegmentationDataset('train', root_dir=args.sbd_root)
@@ -260,7 +266,8 @@ def assemble(args, comm, model, train_data, test_data, evaluator_type, synthetic
                                               seed=args.seed)
     test_data = cmr.datasets.scatter_dataset(test_data, comm.rank, comm.world,
                                              force_equal_length=False)
-    train = train_loop.TransformDataset(train_data, cmr.datasets.MaskRCNNTransform(model))
+    train = train_loop.TransformDataset(train_data, cmr.datasets.MaskRCNNTransform(
+        model, device_masks=getattr(args, 'device_masks', False)))
     test = train_loop.TransformDataset(test_data, cmr.datasets.MaskRCNNTransform(model, train=False))
     loop = train_loop.TrainLoop(train_loop.SerialIterator(train, args.batch_size_per_gpu),
                                 chain, opt, comm.device)

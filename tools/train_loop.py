@@ -25,6 +25,7 @@ gives bit-identical losses (tests/test_gpu_train_loop.py).
     python tools/train_loop.py --coco-root DIR --iterations 100      # a COCO-layout directory
     python tools/train_loop.py --synthetic 64 --iterations 20        # in-memory synthetic examples
     python tools/train_loop.py --dataset sbd --sbd-root DIR --split train   # VOC settings (20 classes)
+    python tools/train_loop.py --synthetic 64 --device-masks        # masks as bits, resized on the device
 """
 import functools
 import os
@@ -170,7 +171,11 @@ class TrainLoop(object):
         if ready is not None:
             main = torch.cuda.current_stream(self.device)
             main.wait_event(ready)
-            batch[0].record_stream(main)
+            # allocated on the copy stream, read on the compute stream: the image batch and, with
+            # device masks, the mask batch (the allocator must not reuse either under the step)
+            for field in batch:
+                if isinstance(field, torch.Tensor) and field.is_cuda:
+                    field.record_stream(main)
         return batch
 
     def _peek_next_images(self):
@@ -304,10 +309,11 @@ def setup_training(model, device, lr_batch, defer=5, synthetic_weights=True, mak
 
 
 def build(dataset, n_layers=50, device='cuda:0', batch_size=2, seed=0, defer=5, prefetch=True,
-          world=1, pooling_func='align', model_settings='coco'):
+          world=1, pooling_func='align', model_settings='coco', device_masks=False):
     """Model, optimizer and loop as examples/train_common.py:135-231 builds them (COCO settings of
     examples/coco/train.py:36-38, or with ``model_settings='voc'`` those of
-    examples/voc/train.py); ``pooling_func`` one of POOLING_FUNCS."""
+    examples/voc/train.py); ``pooling_func`` one of POOLING_FUNCS; ``device_masks``: the
+    ground-truth masks travel as bits and are resized on the device (MaskRCNNTransform)."""
     import bench
     import chainer_mask_rcnn_amd as cmr
     random.seed(seed)                                   # :135-136
@@ -326,7 +332,8 @@ def build(dataset, n_layers=50, device='cuda:0', batch_size=2, seed=0, defer=5, 
     else:
         raise ValueError('model_settings must be coco or voc, got %r' % (model_settings,))
     model.head.pooling_func = getattr(cmr.functions, POOLING_FUNCS[pooling_func])
-    train_data = TransformDataset(dataset, cmr.datasets.MaskRCNNTransform(model))
+    train_data = TransformDataset(dataset, cmr.datasets.MaskRCNNTransform(
+        model, device_masks=device_masks))
     it = SerialIterator(train_data, batch_size)
     return TrainLoop(it, chain, opt, device, prefetch=prefetch), model, chain, opt
 
@@ -350,6 +357,9 @@ def main():
     ap.add_argument('--pooling-func', default='align', choices=sorted(POOLING_FUNCS),
                     help='RoI feature extractor of the head: align (roi_align_2d), pooling '
                          '(roi_pooling_2d) or resize (crop_and_resize)')
+    ap.add_argument('--device-masks', action='store_true',
+                    help='ground-truth masks cross PCIe as bits and are resized / flipped by a HIP '
+                         'kernel (COCO: the dataset also keeps them packed on the host)')
     args = ap.parse_args()
     import chainer_mask_rcnn_amd as cmr
     if os.environ.get('TORCH_THREADS'):
@@ -366,10 +376,11 @@ def main():
                                                            root_dir=args.sbd_root)
     else:
         data = cmr.datasets.COCOInstanceSegmentationDataset(args.split or 'minival',
-                                                            root_dir=args.coco_root)
+                                                            root_dir=args.coco_root,
+                                                            packed_masks=args.device_masks)
     loop, model, chain, opt = build(data, args.layers, 'cuda:0', args.batch, args.seed,
                                     prefetch=not args.no_prefetch, pooling_func=args.pooling_func,
-                                    model_settings=settings)
+                                    model_settings=settings, device_masks=args.device_masks)
     for _ in range(int(os.environ.get('WARMUP', 3))):
         loop.step()
     opt.flush()
