@@ -14,9 +14,11 @@
 #include <algorithm>
 #include <cstring>
 
-#include "common.h"
+#include "roi_common.h"
 
 namespace {
+
+using namespace mrcnn::roi;
 
 struct RoiGeom {
     int batch;
@@ -73,13 +75,36 @@ __device__ __forceinline__ Tap1D tap1d(float p, int size)
     return t;
 }
 
-// Streaming stores for the pooled output (written once, read by the next kernel after 200 MB of
-// other traffic): keeps the feature map's taps resident in L2.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void store_stream(float *p, float v) { __builtin_nontemporal_store(v, p); }
-__device__ __forceinline__ void store_stream(float4 *p, float4 v)
+// rows / columns of the map that any sample of the RoI can touch
+struct RoiExtent { int ylo, yhi, xlo, xhi; };
+
+__device__ __forceinline__ RoiExtent roi_extent(const RoiGeom &g, int H, int W, int PH, int PW)
 {
-    __builtin_nontemporal_store((f32x4){v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4 *>(p));
+    const float y_first = g.start_h + .5f * g.bin_h / (float)g.grid_h;
+    const float y_last = g.start_h + (PH - 1) * g.bin_h + (g.grid_h - .5f) * g.bin_h / (float)g.grid_h;
+    const float x_first = g.start_w + .5f * g.bin_w / (float)g.grid_w;
+    const float x_last = g.start_w + (PW - 1) * g.bin_w + (g.grid_w - .5f) * g.bin_w / (float)g.grid_w;
+    RoiExtent e;
+    e.ylo = max(0, min(H - 1, (int)floorf(fmaxf(y_first, 0.f)) - 1));
+    e.yhi = max(0, min(H - 1, (int)floorf(fmaxf(y_last, 0.f)) + 2));
+    e.xlo = max(0, min(W - 1, (int)floorf(fmaxf(x_first, 0.f)) - 1));
+    e.xhi = max(0, min(W - 1, (int)floorf(fmaxf(x_last, 0.f)) + 2));
+    return e;
+}
+
+// Weight that the valid samples of bin p (first sample at start + p * bin, `grid` samples per bin)
+// put on row / column `at` of a map axis of `size` pixels: one factor of the separable backward.
+__device__ __forceinline__ float axis_weight(float start, float bin, int grid, int p, int size, int at)
+{
+    float a = 0.f;
+    for (int i = 0; i < grid; ++i) {
+        const float pos = start + p * bin + (float)(i + .5f) * bin / (float)grid;
+        const Tap1D t = tap1d(pos, size);
+        if (!t.valid) continue;
+        if (t.lo == at) a += t.h;
+        if (t.hi == at) a += t.l;
+    }
+    return a;
 }
 
 // Optional fused epilogue of the forward: y = relu?(v * scale[c] + shift[c]) — the AffineChannel2D
@@ -117,7 +142,6 @@ template <> struct VecOps<float> {
     {
         return acc + (w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4);
     }
-    static __device__ __forceinline__ float div(float a, float c) { return a / c; }
 };
 template <> struct VecOps<float4> {
     static __device__ __forceinline__ float4 zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
@@ -130,10 +154,6 @@ template <> struct VecOps<float4> {
         acc.z += (w1 * v1.z + w2 * v2.z + w3 * v3.z + w4 * v4.z);
         acc.w += (w1 * v1.w + w2 * v2.w + w3 * v3.w + w4 * v4.w);
         return acc;
-    }
-    static __device__ __forceinline__ float4 div(float4 a, float c)
-    {
-        return make_float4(a.x / c, a.y / c, a.z / c, a.w / c);
     }
 };
 
@@ -194,6 +214,7 @@ __device__ __forceinline__ void fwd_bins(const V *__restrict__ img, V *__restric
                 wt[b][s][1] = ty.h * tx.l;
                 wt[b][s][2] = ty.l * tx.h;
                 wt[b][s][3] = ty.l * tx.l;
+                // repeated in fwd_bin_rows deliberately: one shared helper cost 272 bytes/lane of scratch
                 const int sp = ix > 0 ? s - 1 : s;      // the left neighbour's registers
                 if (ix > 0 && tx.lo == plo && tx.hi == phi) {
                     v[b][s][0] = v[b][sp][0]; v[b][s][1] = v[b][sp][1];
@@ -255,6 +276,7 @@ __device__ __forceinline__ void fwd_bin_rows(const V *__restrict__ img, V *__res
                 wt[ix][1] = ty.h * tx.l;
                 wt[ix][2] = ty.l * tx.h;
                 wt[ix][3] = ty.l * tx.l;
+                // repeated from fwd_bins deliberately: one shared helper cost 272 bytes/lane of scratch
                 const int sp = ix > 0 ? ix - 1 : ix;    // the left neighbour's registers
                 if (ix > 0 && tx.lo == plo && tx.hi == phi) {
                     v[ix][0] = v[sp][0]; v[ix][1] = v[sp][1]; v[ix][2] = v[sp][2]; v[ix][3] = v[sp][3];
@@ -312,7 +334,7 @@ roi_align_fwd_kernel(const V *__restrict__ x, const float *__restrict__ rois, V 
 {
     // output bin (oh, ow) is bin (oh*BS, ow*BS) of the PH x PW grid (BS = 1: every bin)
     // an XCD (workgroup id mod 8) owns a contiguous run of rows (n*OH + oh): the OH rows of a
-    // RoI, which re-read each other's taps, share one L2
+    // RoI, which re-read each other's taps, share one L2 (xcd_row(), kept inline in this body)
     const int per = ((int)gridDim.x + 7) / 8;
     const int row = (int)(blockIdx.x % 8) * per + (int)(blockIdx.x / 8);
     if (row >= rows) return;
@@ -434,48 +456,21 @@ roi_align_bwd_gather_kernel(const V *__restrict__ gy, const float *__restrict__ 
     const int n = blockIdx.y;
     const RoiGeom g = roi_geom(rois + 5 * n, spatial_scale, PH, PW, sampling_ratio);
 
-    // rows/cols any sample of this RoI can touch
-    const float y_first = g.start_h + .5f * g.bin_h / (float)g.grid_h;
-    const float y_last = g.start_h + (PH - 1) * g.bin_h + (g.grid_h - .5f) * g.bin_h / (float)g.grid_h;
-    const float x_first = g.start_w + .5f * g.bin_w / (float)g.grid_w;
-    const float x_last = g.start_w + (PW - 1) * g.bin_w + (g.grid_w - .5f) * g.bin_w / (float)g.grid_w;
-    const int ylo = max(0, min(H - 1, (int)floorf(fmaxf(y_first, 0.f)) - 1));
-    const int yhi = max(0, min(H - 1, (int)floorf(fmaxf(y_last, 0.f)) + 2));
-    const int xlo = max(0, min(W - 1, (int)floorf(fmaxf(x_first, 0.f)) - 1));
-    const int xhi = max(0, min(W - 1, (int)floorf(fmaxf(x_last, 0.f)) + 2));
-    const int y = ylo + blockIdx.x;
-    if (y > yhi) return;
-    const int PX = xhi - xlo + 1;
+    const RoiExtent ex = roi_extent(g, H, W, PH, PW);
+    const int xlo = ex.xlo;
+    const int y = ex.ylo + blockIdx.x;
+    if (y > ex.yhi) return;
+    const int PX = ex.xhi - xlo + 1;
 
     float *Ay = lds;                       // [PH]
     float *Bx = lds + PH;                  // [PX][PW]
     int *pwlo = reinterpret_cast<int *>(Bx + (W + 4) * PW);  // [PX]
     int *pwhi = pwlo + (W + 4);
-    for (int oh = threadIdx.x; oh < OH; oh += blockDim.x) {
-        const int ph = oh * BS;
-        float a = 0.f;
-        for (int iy = 0; iy < g.grid_h; ++iy) {
-            const float yy = g.start_h + ph * g.bin_h + (float)(iy + .5f) * g.bin_h / (float)g.grid_h;
-            const Tap1D t = tap1d(yy, H);
-            if (!t.valid) continue;
-            if (t.lo == y) a += t.h;
-            if (t.hi == y) a += t.l;
-        }
-        Ay[oh] = a;
-    }
+    for (int oh = threadIdx.x; oh < OH; oh += blockDim.x)
+        Ay[oh] = axis_weight(g.start_h, g.bin_h, g.grid_h, oh * BS, H, y);
     for (int e = threadIdx.x; e < PX * OW; e += blockDim.x) {
         const int xi = e / OW, ow_ = e - xi * OW;
-        const int pw = ow_ * BS;
-        const int x = xlo + xi;
-        float b = 0.f;
-        for (int ix = 0; ix < g.grid_w; ++ix) {
-            const float xx = g.start_w + pw * g.bin_w + (float)(ix + .5f) * g.bin_w / (float)g.grid_w;
-            const Tap1D t = tap1d(xx, W);
-            if (!t.valid) continue;
-            if (t.lo == x) b += t.h;
-            if (t.hi == x) b += t.l;
-        }
-        Bx[e] = b;
+        Bx[e] = axis_weight(g.start_w, g.bin_w, g.grid_w, ow_ * BS, W, xlo + xi);
     }
     __syncthreads();
     for (int xi = threadIdx.x; xi < PX; xi += blockDim.x) {
@@ -536,22 +531,6 @@ roi_align_bwd_gather_kernel(const V *__restrict__ gy, const float *__restrict__ 
 // The first version of this form rebuilt the weights of four RoIs per barrier pair inside
 // every tile (tap arithmetic with divisions, for all RoIs of the ROW) and issued one
 // dependent gy load per bin: latency-bound at 0.12 of the HBM peak.
-struct RoiExtent { int ylo, yhi, xlo, xhi; };
-
-__device__ __forceinline__ RoiExtent roi_extent(const RoiGeom &g, int H, int W, int PH, int PW)
-{
-    const float y_first = g.start_h + .5f * g.bin_h / (float)g.grid_h;
-    const float y_last = g.start_h + (PH - 1) * g.bin_h + (g.grid_h - .5f) * g.bin_h / (float)g.grid_h;
-    const float x_first = g.start_w + .5f * g.bin_w / (float)g.grid_w;
-    const float x_last = g.start_w + (PW - 1) * g.bin_w + (g.grid_w - .5f) * g.bin_w / (float)g.grid_w;
-    RoiExtent e;
-    e.ylo = max(0, min(H - 1, (int)floorf(fmaxf(y_first, 0.f)) - 1));
-    e.yhi = max(0, min(H - 1, (int)floorf(fmaxf(y_last, 0.f)) + 2));
-    e.xlo = max(0, min(W - 1, (int)floorf(fmaxf(x_first, 0.f)) - 1));
-    e.xhi = max(0, min(W - 1, (int)floorf(fmaxf(x_last, 0.f)) + 2));
-    return e;
-}
-
 constexpr int kOwnXT = 8;        // pixels of a row per workgroup
 constexpr int kOwnThreads = 256; // upper bound of the workgroup size (LDS list capacities)
 constexpr int kOwnScan = 4;      // RoIs tested per thread and chunk
@@ -574,37 +553,14 @@ roi_bwd_tables_kernel(const float *__restrict__ rois, int H, int W, int Wp, int 
     float *__restrict__ ay = Ay + (int64_t)r * H * OH;
     for (int i = threadIdx.x; i < H * OH; i += blockDim.x) {
         const int y = i / OH, oh = i - y * OH;
-        float a = 0.f;
-        if (y >= e.ylo && y <= e.yhi) {
-            const int ph = oh * BS;
-            for (int iy = 0; iy < g.grid_h; ++iy) {
-                const float yy = g.start_h + ph * g.bin_h +
-                                 (float)(iy + .5f) * g.bin_h / (float)g.grid_h;
-                const Tap1D t = tap1d(yy, H);
-                if (!t.valid) continue;
-                if (t.lo == y) a += t.h;
-                if (t.hi == y) a += t.l;
-            }
-            a = a / g.count;
-        }
-        ay[i] = a;
+        ay[i] = y >= e.ylo && y <= e.yhi
+                    ? axis_weight(g.start_h, g.bin_h, g.grid_h, oh * BS, H, y) / g.count : 0.f;
     }
     float *__restrict__ bx = Bx + (int64_t)r * OW * Wp;
     for (int i = threadIdx.x; i < OW * Wp; i += blockDim.x) {
         const int ow_ = i / Wp, x = i - ow_ * Wp;
-        float b = 0.f;
-        if (x >= e.xlo && x <= e.xhi) {
-            const int pw = ow_ * BS;
-            for (int ix = 0; ix < g.grid_w; ++ix) {
-                const float xx = g.start_w + pw * g.bin_w +
-                                 (float)(ix + .5f) * g.bin_w / (float)g.grid_w;
-                const Tap1D t = tap1d(xx, W);
-                if (!t.valid) continue;
-                if (t.lo == x) b += t.h;
-                if (t.hi == x) b += t.l;
-            }
-        }
-        bx[i] = b;
+        bx[i] = x >= e.xlo && x <= e.xhi
+                    ? axis_weight(g.start_w, g.bin_w, g.grid_w, ow_ * BS, W, x) : 0.f;
     }
 }
 
@@ -647,7 +603,7 @@ roi_align_bwd_owner_kernel(const V *__restrict__ gy, const int4 *__restrict__ ex
     __shared__ __attribute__((aligned(16))) float sW[CAP][XT];
 
     // tile id: an XCD (workgroup id mod 8) owns a contiguous run of (image, row, tile) ids, so
-    // the rows that re-read a RoI's gy bins share one L2
+    // the rows that re-read a RoI's gy bins share one L2 (xcd_row(), kept inline in this body)
     const int tiles_x = (W + XT - 1) / XT;
     const int total = tiles_x * H * N;
     const int per = (total + 7) / 8;
@@ -694,6 +650,8 @@ roi_align_bwd_owner_kernel(const V *__restrict__ gy, const int4 *__restrict__ ex
                 }
                 lcnt += in[j] ? 1 : 0;
             }
+            // this scan and the one of step B are block_scan (roi_common.h) inlined by hand,
+            // deliberately: calling it cost the float4 instantiation 36 bytes/lane of scratch
             int linc = lcnt;
 #pragma unroll
             for (int d = 1; d < 64; d <<= 1) {
@@ -746,6 +704,7 @@ roi_align_bwd_owner_kernel(const V *__restrict__ gy, const int4 *__restrict__ ex
                         }
                     }
                 }
+                // block_scan again, repeated deliberately (36 bytes/lane of scratch otherwise)
                 const int lc = (mk[0] != 0) + (mk[1] != 0);
                 int inc = lc;
 #pragma unroll
@@ -807,38 +766,24 @@ roi_align_bwd_owner_kernel(const V *__restrict__ gy, const int4 *__restrict__ ex
 int g_roi_fwd_lanes = 0;     // mrcnn_set_tuning("roi_fwd_lanes"): cap of the forward's lanes per workgroup (0 = 256)
 int g_roi_bwd_lanes = 0;     // mrcnn_set_tuning("roi_bwd_lanes"): same for the pixel-owner backward
 
-inline int pick_threads(int cv)
-{
-    int t = ((cv + 63) / 64) * 64;
-    return t > 256 ? 256 : (t < 64 ? 64 : t);
-}
-
+// the family's shape check plus ROIAlign's own argument
 int check_args(const void *a, const void *b, const void *c, int N, int H, int W, int C, int R,
-               int PH, int PW, int sampling_ratio)
+               int PH, int PW, int bin_stride, int sampling_ratio)
 {
-    MRCNN_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && R >= 0 && PH > 0 && PW > 0,
-                  "roi_align: bad shape N=%d H=%d W=%d C=%d R=%d PH=%d PW=%d", N, H, W, C, R, PH,
-                  PW);
     MRCNN_REQUIRE(sampling_ratio >= 0, "roi_align: sampling_ratio must be >= 0");
-    MRCNN_REQUIRE(R == 0 || (a && b && c), "roi_align: null pointer");
-    MRCNN_REQUIRE((int64_t)R * PH * PW < (int64_t)INT32_MAX, "roi_align: too many bins");
-    return 0;
+    return check("roi_align", a, b, c, N, H, W, C, R, PH, PW, bin_stride);
 }
 
-}  // namespace
-
-namespace {
 int roi_align_fwd_launch(const float *x, const float *rois, float *y, int N, int H, int W, int C, int R,
                          int PH, int PW, int bin_stride, float spatial_scale, int sampling_ratio,
                          const int *order, const float *scale, const float *shift, int relu,
                          void *stream)
 {
-    if (int rc = check_args(x, rois, y, N, H, W, C, R, PH, PW, sampling_ratio)) return rc;
-    MRCNN_REQUIRE(bin_stride >= 1, "roi_align: bin_stride must be >= 1");
+    if (int rc = check_args(x, rois, y, N, H, W, C, R, PH, PW, bin_stride, sampling_ratio)) return rc;
     const bool epi = scale != nullptr || shift != nullptr;
     MRCNN_REQUIRE(!epi || (scale && shift), "roi_align_fwd_affine: scale and shift go together");
     if (R == 0) return 0;
-    const int OH = (PH + bin_stride - 1) / bin_stride, OW = (PW + bin_stride - 1) / bin_stride;
+    const int OH = out_bins(PH, bin_stride), OW = out_bins(PW, bin_stride);
     const int bins = R * OH * OW;
     hipStream_t s = mrcnn::as_stream(stream);
     // algorithmic bytes: write R*OH*OW*C, read the feature maps once
@@ -851,27 +796,14 @@ int roi_align_fwd_launch(const float *x, const float *rois, float *y, int N, int
     const dim3 grid((R * OH + 7) / 8 * 8, (cvl + nthr - 1) / nthr);
     const bool vec = C % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0) &&
                      (!epi || (((uintptr_t)scale % 16 == 0) && ((uintptr_t)shift % 16 == 0)));
-    if (vec) {
-        const int cv = C / 4;
-        if (epi)
-            hipExtLaunchKernelGGL((roi_align_fwd_kernel<float4, true>), grid, dim3(nthr), 0, s,
-                                  ev0, ev1, 0, (const float4 *)x, rois, (float4 *)y, H, W, cv, PH, PW,
-                                  spatial_scale, sampling_ratio, OH, OW, bin_stride, R * OH, order,
-                                  (const float4 *)scale, (const float4 *)shift, relu);
-        else
-            hipExtLaunchKernelGGL((roi_align_fwd_kernel<float4, false>), grid, dim3(nthr), 0, s,
-                                  ev0, ev1, 0, (const float4 *)x, rois, (float4 *)y, H, W, cv, PH, PW,
-                                  spatial_scale, sampling_ratio, OH, OW, bin_stride, R * OH, order,
-                                  (const float4 *)nullptr, (const float4 *)nullptr, 0);
-    } else if (epi) {
-        hipExtLaunchKernelGGL((roi_align_fwd_kernel<float, true>), grid, dim3(nthr), 0, s, ev0,
-                              ev1, 0, x, rois, y, H, W, C, PH, PW, spatial_scale, sampling_ratio, OH, OW,
-                              bin_stride, R * OH, order, scale, shift, relu);
-    } else {
-        hipExtLaunchKernelGGL((roi_align_fwd_kernel<float, false>), grid, dim3(nthr), 0, s, ev0,
-                              ev1, 0, x, rois, y, H, W, C, PH, PW, spatial_scale, sampling_ratio, OH, OW,
-                              bin_stride, R * OH, order, (const float *)nullptr, (const float *)nullptr, 0);
-    }
+    dispatch_vec(vec, [&](auto tag) {
+        typedef decltype(tag) V;
+        const auto kernel = epi ? roi_align_fwd_kernel<V, true> : roi_align_fwd_kernel<V, false>;
+        hipExtLaunchKernelGGL(kernel, grid, dim3(nthr), 0, s, ev0, ev1, 0, (const V *)x, rois, (V *)y, H,
+                              W, vec ? C / 4 : C, PH, PW, spatial_scale, sampling_ratio, OH, OW,
+                              bin_stride, R * OH, order, (const V *)scale, (const V *)shift,
+                              epi ? relu : 0);
+    });
     return mrcnn::check_launch("roi_align_fwd");
 }
 }  // namespace
@@ -928,12 +860,12 @@ struct OwnerWs {
 inline OwnerWs owner_ws(int H, int W, int R, int OH, int OW)
 {
     OwnerWs w;
-    auto up = [](int64_t v) { return (v + 255) / 256 * 256; };
+    Carver c;
     w.Wp = (W + kOwnXT - 1) / kOwnXT * kOwnXT;
-    w.ext = 0;
-    w.ay = up((int64_t)R * 16);
-    w.bx = w.ay + up((int64_t)R * H * OH * 4);
-    w.total = w.bx + up((int64_t)R * OW * w.Wp * 4);
+    w.ext = c.take((int64_t)R * 16);
+    w.ay = c.take((int64_t)R * H * OH * 4);
+    w.bx = c.take((int64_t)R * OW * w.Wp * 4);
+    w.total = c.total;
     return w;
 }
 }  // namespace
@@ -942,8 +874,7 @@ extern "C" int64_t mrcnn_roi_align_bwd_workspace_bytes(int N, int H, int W, int 
                                                        int bin_stride)
 {
     if (N <= 0 || H <= 0 || W <= 0 || R <= 0 || PH <= 0 || PW <= 0 || bin_stride < 1) return 0;
-    const int OH = (PH + bin_stride - 1) / bin_stride, OW = (PW + bin_stride - 1) / bin_stride;
-    return owner_ws(H, W, R, OH, OW).total;
+    return owner_ws(H, W, R, out_bins(PH, bin_stride), out_bins(PW, bin_stride)).total;
 }
 
 extern "C" int mrcnn_roi_align_bwd_ex(const float *gy, const float *rois, float *gx, int N, int H,
@@ -961,15 +892,15 @@ extern "C" int mrcnn_roi_align_bwd_ws(const float *gy, const float *rois, float 
                                       float spatial_scale, int sampling_ratio, void *ws,
                                       int64_t ws_bytes, void *stream)
 {
-    if (int rc = check_args(gy, rois, gx, N, H, W, C, R, PH, PW, sampling_ratio)) return rc;
-    MRCNN_REQUIRE(bin_stride >= 1, "roi_align: bin_stride must be >= 1");
+    if (int rc = check_args(gy, rois, gx, N, H, W, C, R, PH, PW, bin_stride, sampling_ratio)) return rc;
     MRCNN_REQUIRE(ws == nullptr || ws_bytes >= mrcnn_roi_align_bwd_workspace_bytes(N, H, W, R, PH, PW, bin_stride),
                   "roi_align_bwd: workspace smaller than mrcnn_roi_align_bwd_workspace_bytes(N, H, W, R, PH, PW, bin_stride)");
     hipStream_t s = mrcnn::as_stream(stream);
     MRCNN_REQUIRE(gx != nullptr, "roi_align_bwd: null gx");
-    const int OH = (PH + bin_stride - 1) / bin_stride, OW = (PW + bin_stride - 1) / bin_stride;
+    const int OH = out_bins(PH, bin_stride), OW = out_bins(PW, bin_stride);
     const int bins = R * OH * OW;
     const bool vec = C % 4 == 0 && ((uintptr_t)gx % 16 == 0) && ((uintptr_t)gy % 16 == 0);
+    const int cv = vec ? C / 4 : C;
     const int64_t tiles = (int64_t)((W + kOwnXT - 1) / kOwnXT) * H * N;
     if (ws && R > 0 && H <= 65535 && W <= 65535 && tiles + 8 < (int64_t)INT32_MAX &&
         (uintptr_t)ws % 16 == 0) {
@@ -985,16 +916,14 @@ extern "C" int mrcnn_roi_align_bwd_ws(const float *gy, const float *rois, float 
         hipExtLaunchKernelGGL(roi_bwd_tables_kernel, dim3(R), dim3(256), 0, s, ev0, nullptr, 0, rois, H,
                               W, w.Wp, PH, PW, OH, OW, bin_stride, spatial_scale, sampling_ratio, ext,
                               Ay, Bx);
-        int nthr = pick_threads(vec ? C / 4 : C);
+        int nthr = pick_threads(cv);
         if (g_roi_bwd_lanes > 0) nthr = std::min(nthr, g_roi_bwd_lanes);
-        const dim3 grid((unsigned)((tiles + 7) / 8 * 8), (unsigned)(((vec ? C / 4 : C) + nthr - 1) / nthr));
-        if (vec)
-            hipExtLaunchKernelGGL(roi_align_bwd_owner_kernel<float4>, grid, dim3(nthr),
-                                  0, s, nullptr, ev1, 0, (const float4 *)gy, ext, Ay, Bx, (float4 *)gx,
-                                  R, N, H, W, w.Wp, C / 4, OH, OW);
-        else
-            hipExtLaunchKernelGGL(roi_align_bwd_owner_kernel<float>, grid, dim3(nthr), 0, s,
-                                  nullptr, ev1, 0, gy, ext, Ay, Bx, gx, R, N, H, W, w.Wp, C, OH, OW);
+        const dim3 grid((unsigned)((tiles + 7) / 8 * 8), (unsigned)((cv + nthr - 1) / nthr));
+        dispatch_vec(vec, [&](auto tag) {
+            typedef decltype(tag) V;
+            hipExtLaunchKernelGGL(roi_align_bwd_owner_kernel<V>, grid, dim3(nthr), 0, s, nullptr, ev1,
+                                  0, (const V *)gy, ext, Ay, Bx, (V *)gx, R, N, H, W, w.Wp, cv, OH, OW);
+        });
         return mrcnn::check_launch("roi_align_bwd");
     }
     MRCNN_HIP_TRY(hipMemsetAsync(gx, 0, sizeof(float) * (size_t)N * H * W * C, s));
@@ -1005,23 +934,19 @@ extern "C" int mrcnn_roi_align_bwd_ws(const float *gy, const float *rois, float 
     const size_t lds = sizeof(float) * ((size_t)PH + (size_t)(W + 4) * PW) + sizeof(int) * 2 * (W + 4);
     if (lds <= 48 * 1024 && H <= 65535 && R <= 65535) {
         // gather form: one workgroup per (roi, feature row), one atomic per (pixel, channel)
-        if (vec)
-            hipLaunchKernelGGL(roi_align_bwd_gather_kernel<float4>, dim3(H, R),
-                               dim3(pick_threads(C / 4)), lds, s, (const float4 *)gy, rois,
-                               (float4 *)gx, H, W, C / 4, PH, PW, spatial_scale, sampling_ratio,
-                               OH, OW, bin_stride);
-        else
-            hipLaunchKernelGGL(roi_align_bwd_gather_kernel<float>, dim3(H, R), dim3(pick_threads(C)),
-                               lds, s, gy, rois, gx, H, W, C, PH, PW, spatial_scale, sampling_ratio,
-                               OH, OW, bin_stride);
-    } else if (vec) {
-        hipLaunchKernelGGL(roi_align_bwd_kernel<float4>, dim3(bins), dim3(pick_threads(C / 4)), 0, s,
-                           (const float4 *)gy, rois, (float4 *)gx, H, W, C / 4, PH, PW,
-                           spatial_scale, sampling_ratio, OH, OW, bin_stride);
+        dispatch_vec(vec, [&](auto tag) {
+            typedef decltype(tag) V;
+            hipLaunchKernelGGL(roi_align_bwd_gather_kernel<V>, dim3(H, R), dim3(pick_threads(cv)), lds,
+                               s, (const V *)gy, rois, (V *)gx, H, W, cv, PH, PW, spatial_scale,
+                               sampling_ratio, OH, OW, bin_stride);
+        });
     } else {
-        hipLaunchKernelGGL(roi_align_bwd_kernel<float>, dim3(bins), dim3(pick_threads(C)), 0, s, gy,
-                           rois, gx, H, W, C, PH, PW, spatial_scale, sampling_ratio, OH, OW,
-                           bin_stride);
+        dispatch_vec(vec, [&](auto tag) {
+            typedef decltype(tag) V;
+            hipLaunchKernelGGL(roi_align_bwd_kernel<V>, dim3(bins), dim3(pick_threads(cv)), 0, s,
+                               (const V *)gy, rois, (V *)gx, H, W, cv, PH, PW, spatial_scale,
+                               sampling_ratio, OH, OW, bin_stride);
+        });
     }
     return mrcnn::check_launch("roi_align_bwd");
 }

@@ -6,8 +6,9 @@
 // of a RoI (roi, oh, all ow), the lanes run across channels (16 B/lane loads and stores when
 // C % 4 == 0, one float per lane otherwise), every bin's geometry is wave-uniform arithmetic.
 //
-// Backwards are the pixel-owner form of mrcnn_roi_align_bwd_ws, written separately here so that
-// the ROIAlign kernels' code is untouched:
+// Backwards are the pixel-owner form of mrcnn_roi_align_bwd_ws, with kernels of their own (the
+// ROIAlign kernels sit at a register-allocation cliff); the host side of the contract is shared
+// (roi_common.h):
 //   pv_tables_kernel  (one thread per RoI)  per RoI: its pixel extent, and per produced bin row /
 //                                           column either the pooling window [start, end) or the
 //                                           two bilinear taps and their weights
@@ -29,9 +30,11 @@
 // tests/pool_variants_ref.py.
 #include <cstring>
 
-#include "common.h"
+#include "roi_common.h"
 
 namespace {
+
+using namespace mrcnn::roi;
 
 constexpr int kPvXT = 8;          // pixels of a row per owner workgroup
 constexpr int kPvThreads = 256;   // workgroup size bound (LDS list capacities)
@@ -129,13 +132,6 @@ __device__ __forceinline__ LinTap lin_tap(int p, int n, int m, double step)
 __device__ __forceinline__ double lin_step(int n, int m) { return n > 1 ? (double)(m - 1) / (double)(n - 1) : 0.0; }
 
 // ---- vector helpers -----------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void store_stream(float *p, float v) { __builtin_nontemporal_store(v, p); }
-__device__ __forceinline__ void store_stream(float4 *p, float4 v)
-{
-    __builtin_nontemporal_store((f32x4){v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4 *>(p));
-}
-
 template <typename V> struct PV;
 template <> struct PV<float> {
     typedef int I;
@@ -186,14 +182,6 @@ template <> struct PV<float4> {
                            PV<float>::add_if(acc.z, a.z, pix, g.z), PV<float>::add_if(acc.w, a.w, pix, g.w));
     }
 };
-
-// row index of the workgroup: an XCD (workgroup id mod 8) owns a contiguous run of (RoI, oh) rows,
-// the rows of a RoI re-read each other's inputs (as roi_align_fwd_kernel)
-__device__ __forceinline__ int xcd_row()
-{
-    const int per = ((int)gridDim.x + 7) / 8;
-    return (int)(blockIdx.x % 8) * per + (int)(blockIdx.x / 8);
-}
 
 // ---- forwards -----------------------------------------------------------------------------
 // y (R, OH, OW, C), argmax (R, OH, OW, C) int32: output bin (oh, ow) is bin (oh*BS, ow*BS) of the
@@ -299,7 +287,7 @@ crop_resize_fwd_kernel(const V *__restrict__ x, const float *__restrict__ rois,
 }
 
 // ---- pixel-owner backwards ------------------------------------------------------------------
-// ext[r] = (batch or -1, ylo | yhi << 16, xlo | xhi << 16, output row of the RoI)
+// ext[r] = (ylo | yhi << 16, xlo | xhi << 16, batch or -1, output row of the RoI)
 // rowt[r][oh] / colt[r][ow]:  max pool (start, end, 0, 0) of the window;
 //                             crop-and-resize (tap0, tap1, bits of w0, bits of w1), map coordinates
 template <bool POOL>
@@ -362,29 +350,6 @@ __device__ __forceinline__ bool pv_hits(const int4 t, int lo, int len)
 __device__ __forceinline__ float pv_weight(const int4 t, int p)
 {
     return (t.x == p ? __int_as_float(t.z) : 0.f) + (t.y == p ? __int_as_float(t.w) : 0.f);
-}
-
-// inclusive prefix sum over the workgroup of one int per thread; *total = the workgroup's sum
-__device__ __forceinline__ int block_scan(int v, int *sWave, int *total)
-{
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6, nwaves = (int)blockDim.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d);
-        if (lane >= d) inc += t;
-    }
-    __syncthreads();
-    if (lane == 63) sWave[wave] = inc;
-    __syncthreads();
-    int off = 0, m = 0;
-    for (int w = 0; w < nwaves; ++w) {
-        const int cw = sWave[w];
-        if (w < wave) off += cw;
-        m += cw;
-    }
-    *total = m;
-    return off + inc;
 }
 
 template <typename V, bool POOL>
@@ -506,44 +471,35 @@ pv_bwd_owner_kernel(const V *__restrict__ gy, const typename PV<V>::I *__restric
     }
 }
 
-inline int pick_threads(int cv)
-{
-    int t = ((cv + 63) / 64) * 64;
-    return t > 256 ? 256 : (t < 64 ? 64 : t);
-}
-
+// the family's shape check plus the limit of the variants' tables (16-bit extents, int pixel index)
 int pv_check(const char *what, const void *a, const void *b, const void *c, int N, int H, int W,
              int C, int R, int PH, int PW, int bin_stride)
 {
-    MRCNN_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && R >= 0 && PH > 0 && PW > 0,
-                  "%s: bad shape N=%d H=%d W=%d C=%d R=%d outh=%d outw=%d", what, N, H, W, C, R,
-                  PH, PW);
-    MRCNN_REQUIRE(bin_stride >= 1, "%s: bin_stride must be >= 1", what);
-    MRCNN_REQUIRE(R == 0 || (a && b && c), "%s: null pointer", what);
-    MRCNN_REQUIRE((int64_t)R * PH * PW < (int64_t)INT32_MAX, "%s: too many bins", what);
+    if (int rc = check(what, a, b, c, N, H, W, C, R, PH, PW, bin_stride)) return rc;
     MRCNN_REQUIRE(H <= 32767 && W <= 32767 && (int64_t)H * W < (int64_t)INT32_MAX,
                   "%s: feature map too large (H, W <= 32767)", what);
     return 0;
 }
 
+// workspace sections of the pixel-owner backwards, 256-byte aligned
 struct PvWs {
     int64_t ext, rowt, colt, total;
 };
 inline PvWs pv_ws(int R, int OH, int OW)
 {
-    auto up = [](int64_t v) { return (v + 255) / 256 * 256; };
     PvWs w;
-    w.ext = 0;
-    w.rowt = up((int64_t)R * 16);
-    w.colt = w.rowt + up((int64_t)R * OH * 16);
-    w.total = w.colt + up((int64_t)R * OW * 16);
+    Carver c;
+    w.ext = c.take((int64_t)R * 16);
+    w.rowt = c.take((int64_t)R * OH * 16);
+    w.colt = c.take((int64_t)R * OW * 16);
+    w.total = c.total;
     return w;
 }
 
 int64_t pv_ws_bytes(int N, int H, int W, int R, int PH, int PW, int bin_stride)
 {
     if (N <= 0 || H <= 0 || W <= 0 || R <= 0 || PH <= 0 || PW <= 0 || bin_stride < 1) return 0;
-    return pv_ws(R, (PH + bin_stride - 1) / bin_stride, (PW + bin_stride - 1) / bin_stride).total;
+    return pv_ws(R, out_bins(PH, bin_stride), out_bins(PW, bin_stride)).total;
 }
 
 template <bool POOL>
@@ -564,7 +520,7 @@ int pv_bwd(const char *what, const float *gy, const int *argmax, const float *ro
         MRCNN_HIP_TRY(hipMemsetAsync(gx, 0, sizeof(float) * (size_t)N * H * W * C, s));
         return 0;
     }
-    const int OH = (PH + bin_stride - 1) / bin_stride, OW = (PW + bin_stride - 1) / bin_stride;
+    const int OH = out_bins(PH, bin_stride), OW = out_bins(PW, bin_stride);
     const int64_t tiles = (int64_t)((W + kPvXT - 1) / kPvXT) * H * N;
     MRCNN_REQUIRE(tiles + 8 < (int64_t)INT32_MAX, "%s: feature map too large", what);
     const PvWs w = pv_ws(R, OH, OW);
@@ -578,13 +534,12 @@ int pv_bwd(const char *what, const float *gy, const int *argmax, const float *ro
     const int cv = vec ? C / 4 : C;
     const int nthr = pick_threads(cv);
     const dim3 grid((unsigned)((tiles + 7) / 8 * 8), (unsigned)((cv + nthr - 1) / nthr));
-    if (vec)
-        hipLaunchKernelGGL((pv_bwd_owner_kernel<float4, POOL>), grid, dim3(nthr), 0, s,
-                           (const float4 *)gy, (const int4 *)argmax, ext, rowt, colt, (float4 *)gx,
-                           R, N, H, W, cv, OH, OW);
-    else
-        hipLaunchKernelGGL((pv_bwd_owner_kernel<float, POOL>), grid, dim3(nthr), 0, s, gy, argmax,
-                           ext, rowt, colt, gx, R, N, H, W, cv, OH, OW);
+    dispatch_vec(vec, [&](auto tag) {
+        typedef decltype(tag) V;
+        hipLaunchKernelGGL((pv_bwd_owner_kernel<V, POOL>), grid, dim3(nthr), 0, s, (const V *)gy,
+                           (const typename PV<V>::I *)argmax, ext, rowt, colt, (V *)gx, R, N, H, W, cv,
+                           OH, OW);
+    });
     return mrcnn::check_launch(what);
 }
 
@@ -597,20 +552,19 @@ extern "C" int mrcnn_roi_pool_fwd(const float *x, const float *rois, float *y, i
     if (int rc = pv_check("roi_pool_fwd", x, rois, y, N, H, W, C, R, PH, PW, bin_stride)) return rc;
     MRCNN_REQUIRE(R == 0 || argmax, "roi_pool_fwd: null argmax");
     if (R == 0) return 0;
-    const int OH = (PH + bin_stride - 1) / bin_stride, OW = (PW + bin_stride - 1) / bin_stride;
+    const int OH = out_bins(PH, bin_stride), OW = out_bins(PW, bin_stride);
     hipStream_t s = mrcnn::as_stream(stream);
     const bool vec = C % 4 == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0 &&
                      (uintptr_t)argmax % 16 == 0;
     const int cv = vec ? C / 4 : C;
     const int nthr = pick_threads(cv);
     const dim3 grid((R * OH + 7) / 8 * 8, (cv + nthr - 1) / nthr);
-    if (vec)
-        hipLaunchKernelGGL(roi_pool_fwd_kernel<float4>, grid, dim3(nthr), 0, s, (const float4 *)x,
-                           rois, (float4 *)y, (int4 *)argmax, N, H, W, cv, PH, PW, OH, OW,
-                           bin_stride, spatial_scale, R, order);
-    else
-        hipLaunchKernelGGL(roi_pool_fwd_kernel<float>, grid, dim3(nthr), 0, s, x, rois, y, argmax,
-                           N, H, W, cv, PH, PW, OH, OW, bin_stride, spatial_scale, R, order);
+    dispatch_vec(vec, [&](auto tag) {
+        typedef decltype(tag) V;
+        hipLaunchKernelGGL(roi_pool_fwd_kernel<V>, grid, dim3(nthr), 0, s, (const V *)x, rois, (V *)y,
+                           (typename PV<V>::I *)argmax, N, H, W, cv, PH, PW, OH, OW, bin_stride,
+                           spatial_scale, R, order);
+    });
     return mrcnn::check_launch("roi_pool_fwd");
 }
 
@@ -636,19 +590,18 @@ extern "C" int mrcnn_crop_resize_fwd(const float *x, const float *rois, const in
 {
     if (int rc = pv_check("crop_resize_fwd", x, rois, y, N, H, W, C, R, PH, PW, bin_stride)) return rc;
     if (R == 0) return 0;
-    const int OH = (PH + bin_stride - 1) / bin_stride, OW = (PW + bin_stride - 1) / bin_stride;
+    const int OH = out_bins(PH, bin_stride), OW = out_bins(PW, bin_stride);
     hipStream_t s = mrcnn::as_stream(stream);
     const bool vec = C % 4 == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)y % 16 == 0;
     const int cv = vec ? C / 4 : C;
     const int nthr = pick_threads(cv);
     const dim3 grid((R * OH + 7) / 8 * 8, (cv + nthr - 1) / nthr);
-    if (vec)
-        hipLaunchKernelGGL(crop_resize_fwd_kernel<float4>, grid, dim3(nthr), 0, s,
-                           (const float4 *)x, rois, out_rows, (float4 *)y, N, H, W, cv, PH, PW, OH,
-                           OW, bin_stride, spatial_scale, R, order);
-    else
-        hipLaunchKernelGGL(crop_resize_fwd_kernel<float>, grid, dim3(nthr), 0, s, x, rois, out_rows,
-                           y, N, H, W, cv, PH, PW, OH, OW, bin_stride, spatial_scale, R, order);
+    dispatch_vec(vec, [&](auto tag) {
+        typedef decltype(tag) V;
+        hipLaunchKernelGGL(crop_resize_fwd_kernel<V>, grid, dim3(nthr), 0, s, (const V *)x, rois,
+                           out_rows, (V *)y, N, H, W, cv, PH, PW, OH, OW, bin_stride, spatial_scale, R,
+                           order);
+    });
     return mrcnn::check_launch("crop_resize_fwd");
 }
 

@@ -18,6 +18,8 @@ import torch
 from .. import _lib
 from .._lib import ConvDesc, EPI_BIAS, EPI_AFFINE, EPI_RESIDUAL, EPI_RELU, EPI_ACCUM, EPI_EXACT_SIGNS
 from ._layout import nhwc, empty_nhwc
+from ._roi_extractor import out_size
+from .roi_align_2d import roi_align_backward
 
 
 def _direct_grad(p):
@@ -817,8 +819,7 @@ class RoiSpec(object):
 
     @property
     def out_hw(self):
-        bs = self.bin_stride
-        return (self.outh + bs - 1) // bs, (self.outw + bs - 1) // bs
+        return out_size(self.outh, self.bin_stride), out_size(self.outw, self.bin_stride)
 
 
 # The projections of one feature map, kept while the SAME map is pooled again without a graph
@@ -860,16 +861,8 @@ def _roi_pool_affine(z, roi, scale, shift, relu):
 
 def _roi_pool_bwd(g, roi, map_shape):
     """ROIAlign's adjoint: g (R, C, oh, ow) -> (N, C, H, W), pixel-owner form (no atomics)."""
-    N, C, H, W = map_shape
-    R = roi.rois.shape[0]
-    gz = empty_nhwc((N, C, H, W), g.device)
-    nbytes = _lib.load().mrcnn_roi_align_bwd_workspace_bytes(N, H, W, R, roi.outh, roi.outw, roi.bin_stride)
-    ws = _lib.workspace(nbytes, g.device, 'roi_align_bwd')
-    _lib.call('mrcnn_roi_align_bwd_ws', _lib.ptr(g), _lib.ptr(roi.rois), _lib.ptr(gz), N, H, W, C, R,
-              roi.outh, roi.outw, roi.bin_stride, roi.spatial_scale, roi.sampling_ratio, _lib.ptr(ws),
-              int(ws.numel() * ws.element_size()), _lib.stream_ptr())
-    return gz
-
+    return roi_align_backward(g, roi.rois, map_shape, roi.outh, roi.outw, roi.bin_stride,
+                              roi.spatial_scale, roi.sampling_ratio)
 
 
 def _pool_bwd_alone(side, device):

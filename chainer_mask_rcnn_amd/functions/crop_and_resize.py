@@ -7,9 +7,7 @@ channels-last); the arithmetic is the HIP kernel behind ``mrcnn_crop_resize_fwd 
 """
 import torch
 
-from .. import _lib
-from ._layout import nhwc, empty_nhwc
-from .roi_pooling_2d import _check_args, _check_inputs, _check_order
+from . import _roi_extractor as _re
 
 
 def _output_rows(rois):
@@ -22,43 +20,13 @@ def _output_rows(rois):
     return rows
 
 
-class _CropAndResizeFn(torch.autograd.Function):
-
-    @staticmethod
-    def forward(ctx, x, rois, outh, outw, spatial_scale, bin_stride=1, order=None):
-        _lib.require_device(x, rois)
-        x = nhwc(x)
-        rois = rois.contiguous()
-        N, C, H, W = x.shape
-        R = rois.shape[0]
-        oh = (outh + bin_stride - 1) // bin_stride
-        ow = (outw + bin_stride - 1) // bin_stride
-        y = empty_nhwc((R, C, oh, ow), x.device)
-        _check_order(order, R, x.device, 'crop_and_resize')
-        rows = _output_rows(rois) if R > 0 else None
-        _lib.call('mrcnn_crop_resize_fwd', _lib.ptr(x), _lib.ptr(rois), _lib.ptr(rows), _lib.ptr(y),
-                  N, H, W, C, R, outh, outw, bin_stride, spatial_scale,
-                  _lib.ptr(order) if order is not None and R > 0 else None, _lib.stream_ptr())
-        ctx.save_for_backward(rois, rows)
-        ctx.x_shape = (N, C, H, W)
-        ctx.args = (outh, outw, spatial_scale, bin_stride)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        rois, rows = ctx.saved_tensors
-        N, C, H, W = ctx.x_shape
-        outh, outw, spatial_scale, bin_stride = ctx.args
-        gy = nhwc(gy)
-        gx = empty_nhwc((N, C, H, W), gy.device)
-        R = rois.shape[0]
-        nbytes = _lib.load().mrcnn_crop_resize_bwd_workspace_bytes(N, H, W, R, outh, outw, bin_stride)
-        ws = _lib.workspace(nbytes, gy.device, 'crop_resize_bwd')
-        _lib.call('mrcnn_crop_resize_bwd_ws', _lib.ptr(gy), _lib.ptr(rois), _lib.ptr(rows),
-                  _lib.ptr(gx), N, H, W, C, R, outh, outw, bin_stride, spatial_scale,
-                  _lib.ptr(ws), int(ws.numel() * ws.element_size()), _lib.stream_ptr())
-        # no gradient w.r.t. rois
-        return gx, None, None, None, None, None, None
+# mrcnn_crop_resize_fwd(x, rois, out_rows, y, N .. bin_stride, spatial_scale, order, stream),
+# mrcnn_crop_resize_bwd_ws(gy, rois, out_rows, gx, N .. bin_stride, spatial_scale, ws, ws_bytes, stream)
+_EXT = _re.Extractor('crop_and_resize', 'mrcnn_crop_resize_fwd', 'mrcnn_crop_resize_bwd_workspace_bytes',
+                     'mrcnn_crop_resize_bwd_ws', 'crop_resize_bwd', fwd_ptrs=('x', 'rois', 'extra', 'y'),
+                     bwd_ptrs=('gy', 'rois', 'extra', 'gx'),
+                     extra=lambda rois, shape: _output_rows(rois) if shape[0] > 0 else None)
+_CropAndResizeFn = _EXT.function('_CropAndResizeFn')
 
 
 class CropAndResize(object):
@@ -66,13 +34,13 @@ class CropAndResize(object):
     """Crop-and-resize RoI feature transformation (reference: crop_and_resize.py:7-41)."""
 
     def __init__(self, outh, outw, spatial_scale, bin_stride=1, order=None):
-        self.spatial_scale = _check_args('CropAndResize', outh, outw, spatial_scale, bin_stride)
+        self.spatial_scale = _re.check_args(outh, outw, spatial_scale, bin_stride)
         self.outh, self.outw = outh, outw
         self.bin_stride = bin_stride
         self.order = order
 
     def __call__(self, x, rois):
-        _check_inputs('CropAndResize', x, rois)
+        _re.check_inputs('CropAndResize', x, rois)
         return _CropAndResizeFn.apply(x, rois, self.outh, self.outw, self.spatial_scale,
                                       self.bin_stride, self.order)
 
@@ -102,8 +70,5 @@ def crop_and_resize(x, rois, outh, outw, spatial_scale, axes='xy', bin_stride=1,
     permutation of the RoI rows, the sequence in which they are processed; the result does not
     depend on it.
     """
-    if axes not in ['xy', 'yx']:
-        raise ValueError('Unsupported axes: {}'.format(axes))
-    if axes == 'yx':
-        rois = rois[:, [0, 2, 1, 4, 3]]
+    rois = _re.swap_axes(rois, axes)
     return CropAndResize(outh, outw, spatial_scale, bin_stride, order)(x, rois)

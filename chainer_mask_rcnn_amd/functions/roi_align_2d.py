@@ -6,65 +6,29 @@ Same names, argument meaning and error behaviour; tensors are PyTorch-ROCm
 tensors with the reference's logical NCHW shapes (physically channels-last),
 arithmetic is the hand-written HIP kernel behind ``mrcnn_roi_align_fwd/bwd``.
 """
-import torch
-
-from .. import _lib
-from ._layout import nhwc, empty_nhwc
+from . import _roi_extractor as _re
 
 
 # Pixel-owner backward (no atomics, fixed summation order); False = atomic gather form.
 DETERMINISTIC_BACKWARD = True
-# debug / test switch: check that ``order`` is a permutation of 0..R-1 (one device sort + a read-back)
-VALIDATE_ORDER = False
+
+# mrcnn_roi_align_fwd_ex(x, rois, y, N .. bin_stride, spatial_scale, sampling_ratio, order, stream),
+# mrcnn_roi_align_bwd_ws(gy, rois, gx, N .. bin_stride, spatial_scale, sampling_ratio, ws, ws_bytes, stream)
+_EXT = _re.Extractor('roi_align_2d', 'mrcnn_roi_align_fwd_ex', 'mrcnn_roi_align_bwd_workspace_bytes',
+                     'mrcnn_roi_align_bwd_ws', 'roi_align_bwd', scalars=('sampling_ratio',),
+                     wants_ws=lambda: DETERMINISTIC_BACKWARD)
+# apply(x, rois, outh, outw, spatial_scale, sampling_ratio, bin_stride=1, order=None); only rois
+# are retained (roi_align_2d.py:62-63 retain_inputs((1,))), no gradient w.r.t. them (:389, :524)
+_ROIAlign2DFn = _EXT.function('_ROIAlign2DFn')
 
 
-class _ROIAlign2DFn(torch.autograd.Function):
-
-    @staticmethod
-    def forward(ctx, x, rois, outh, outw, spatial_scale, sampling_ratio, bin_stride=1, order=None):
-        _lib.require_device(x, rois)
-        x = nhwc(x)
-        rois = rois.contiguous()
-        N, C, H, W = x.shape
-        R = rois.shape[0]
-        oh = (outh + bin_stride - 1) // bin_stride
-        ow = (outw + bin_stride - 1) // bin_stride
-        y = empty_nhwc((R, C, oh, ow), x.device)
-        if order is not None:
-            if not (order.dtype == torch.int32 and order.is_contiguous() and order.device == x.device
-                    and tuple(order.shape) == (R,)):
-                raise TypeError('roi_align_2d: order must be a contiguous int32 device tensor of '
-                                'shape (R,) — a permutation of the RoI rows')
-            if VALIDATE_ORDER and R > 0 and not torch.equal(
-                    torch.sort(order.long())[0], torch.arange(R, device=order.device)):
-                raise ValueError('roi_align_2d: order is not a permutation of 0..R-1 (a duplicate '
-                                 'leaves output rows unwritten, an out-of-range value reads past rois)')
-        _lib.call('mrcnn_roi_align_fwd_ex', _lib.ptr(x), _lib.ptr(rois), _lib.ptr(y),
-                  N, H, W, C, R, outh, outw, bin_stride, spatial_scale, sampling_ratio,
-                  _lib.ptr(order) if order is not None and R > 0 else None, _lib.stream_ptr())
-        # only rois are retained (roi_align_2d.py:62-63 retain_inputs((1,)))
-        ctx.save_for_backward(rois)
-        ctx.x_shape = (N, C, H, W)
-        ctx.args = (outh, outw, spatial_scale, sampling_ratio, bin_stride)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        rois, = ctx.saved_tensors
-        N, C, H, W = ctx.x_shape
-        outh, outw, spatial_scale, sampling_ratio, bin_stride = ctx.args
-        gy = nhwc(gy)
-        gx = empty_nhwc((N, C, H, W), gy.device)
-        R = rois.shape[0]
-        ws = _lib.workspace(_lib.load().mrcnn_roi_align_bwd_workspace_bytes(
-            N, H, W, R, outh, outw, bin_stride), gy.device,
-                            'roi_align_bwd') if DETERMINISTIC_BACKWARD else None
-        _lib.call('mrcnn_roi_align_bwd_ws', _lib.ptr(gy), _lib.ptr(rois), _lib.ptr(gx),
-                  N, H, W, C, R, outh, outw, bin_stride, spatial_scale,
-                  sampling_ratio, _lib.ptr(ws),
-                  int(ws.numel() * ws.element_size()) if ws is not None else 0, _lib.stream_ptr())
-        # no gradient w.r.t. rois (roi_align_2d.py:389, :524)
-        return gx, None, None, None, None, None, None, None
+def roi_align_backward(gy, rois, map_shape, outh, outw, bin_stride, spatial_scale, sampling_ratio,
+                       deterministic=True):
+    """ROIAlign's adjoint: gy (R, C, oh, ow) -> the (N, C, H, W) = ``map_shape`` gradient of the
+    map, for contiguous ``(batch, x1, y1, x2, y2)`` rois; pixel-owner form (no atomics) unless
+    ``deterministic`` is False."""
+    return _EXT.backward(gy, rois, None, map_shape, outh, outw, spatial_scale, (sampling_ratio,),
+                         bin_stride, use_ws=deterministic)
 
 
 class ROIAlign2D(object):
@@ -92,13 +56,7 @@ class ROIAlign2D(object):
 
     def check_type_forward(self, x, rois):
         # roi_align_2d.py:49-59
-        if not (x.dtype == torch.float32 and x.dim() == 4 and
-                rois.dtype == torch.float32 and rois.dim() == 2 and
-                rois.shape[1] == 5):
-            raise TypeError(
-                'ROIAlign2D expects x: float32 (N,C,H,W), rois: float32 (R,5); got '
-                '{} {} and {} {}'.format(x.dtype, tuple(x.shape), rois.dtype,
-                                         tuple(rois.shape)))
+        _re.check_inputs('ROIAlign2D', x, rois)
 
     def __call__(self, x, rois):
         self.check_type_forward(x, rois)
@@ -133,8 +91,5 @@ def roi_align_2d(x, rois, outh, outw, spatial_scale, sampling_ratio=0, axes='xy'
     ``order`` (extension, default None): int32 device permutation of the RoI rows — the sequence
     in which the forward kernel PROCESSES them (``spatial_order``); the result does not depend on it.
     """
-    if axes not in ['xy', 'yx']:
-        raise ValueError('Unsupported axes: {}'.format(axes))
-    if axes == 'yx':
-        rois = rois[:, [0, 2, 1, 4, 3]]
+    rois = _re.swap_axes(rois, axes)
     return ROIAlign2D(outh, outw, spatial_scale, sampling_ratio, bin_stride, order)(x, rois)

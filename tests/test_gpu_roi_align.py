@@ -120,15 +120,16 @@ def test_processing_order_does_not_change_the_result(dev):
     # debug switch: a non-permutation (duplicate / out-of-range entries) is rejected, and the
     # backward entry point refuses a workspace smaller than its own size query
     import importlib
-    ra_mod = importlib.import_module('chainer_mask_rcnn_amd.functions.roi_align_2d')
+    ra_mod = importlib.import_module('chainer_mask_rcnn_amd.functions._roi_extractor')
     from chainer_mask_rcnn_amd import _lib
     ra_mod.VALIDATE_ORDER = True
     try:
         bad = torch.tensor(orders[1], device=dev).clone()
         bad[3] = bad[4]
-        with pytest.raises(ValueError):
-            F.roi_align_2d(torch.tensor(x, device=dev), torch.tensor(rois, device=dev), 14, 14, 1 / 16.,
-                           axes='yx', order=bad)
+        for fn in (F.roi_align_2d, F.roi_pooling_2d, F.crop_and_resize):
+            with pytest.raises(ValueError):
+                fn(torch.tensor(x, device=dev), torch.tensor(rois, device=dev), 14, 14, 1 / 16.,
+                   axes='yx', order=bad)
         F.roi_align_2d(torch.tensor(x, device=dev), torch.tensor(rois, device=dev), 14, 14, 1 / 16.,
                        axes='yx', order=torch.tensor(orders[1], device=dev))
     finally:
