@@ -13,20 +13,12 @@
 // two logs of bbox2loc are evaluated in double and rounded once (<= 1 ulp from np.log).
 #include <math.h>
 
+#include "bbox_iou.h"
 #include "common.h"
 
 namespace {
 
-// chainercv bbox_iou for one pair, fp32 exactly as NumPy evaluates it
-__device__ __forceinline__ float iou_pair(const float *a, const float *b)
-{
-    const float tl0 = fmaxf(a[0], b[0]), tl1 = fmaxf(a[1], b[1]);
-    const float br0 = fminf(a[2], b[2]), br1 = fminf(a[3], b[3]);
-    const float inter = (tl0 < br0 && tl1 < br1) ? (br0 - tl0) * (br1 - tl1) : 0.f * ((br0 - tl0) * (br1 - tl1));
-    const float area_a = (a[2] - a[0]) * (a[3] - a[1]);
-    const float area_b = (b[2] - b[0]) * (b[3] - b[1]);
-    return inter / (area_a + area_b - inter);
-}
+using mrcnn::iou_pair;   // chainercv bbox_iou for one pair (bbox_iou.h)
 
 // per row of `a`: max IoU over the G boxes of `b` and its first argmax (np.argmax / np.max:
 // a NaN wins and propagates).  Optionally writes the whole (na, g) matrix.

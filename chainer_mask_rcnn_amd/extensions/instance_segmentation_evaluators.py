@@ -7,12 +7,24 @@ chainer_mask_rcnn/extensions/instance_segmentation_{voc,coco}_evaluator.py.
 against the uploaded and packed ground truth, all queued before one read-back of the counts
 and areas.  Boxes, labels and scores come back as ``predict_prepared`` returns them.  Matching
 and accumulation run on the host from those counts (utils/evaluations/matching.py).
+
+``iou_types=('segm', 'bbox')`` adds box AP under ``validation/main/bbox/...``: the batch's box IoU
+tables (predicted boxes against the examples' ``bbox`` field) are made in one more launch
+(utils/evaluations/boxes.py), queued before the same single read-back, and scored by the same
+matching loops — the VOC evaluator as chainercv's ``eval_detection_voc`` would (float32, +1 on the
+max corners), the COCO evaluator as pycocotools' iouType 'bbox' would (float64 x, y, w, h, crowd
+rule).  The ground-truth boxes are whatever the dataset puts in the example, which is what
+chainercv's detection evaluators are fed: for this project's COCO dataset that is the mask's tight
+box, not the annotation's ``bbox``.  ``('bbox',)`` alone skips the paste,
+pack and intersect work and reports only the ``bbox/`` keys.
 """
 import copy
 
 import numpy as np
 import torch
 
+from ..utils.evaluations import boxes as B
+from ..utils.evaluations import eval_detection as D
 from ..utils.evaluations import masks as M
 from ..utils.evaluations import matching
 from ..utils.evaluations import rle
@@ -40,11 +52,17 @@ class _InstanceSegmentationEvaluator(object):
 
     name = 'validation'
     results_sink = None
+    box_convention = None     # 'voc' | 'coco': boxes.queue_box_ious' convention
 
-    def __init__(self, iterator, target, label_names=None):
+    def __init__(self, iterator, target, label_names=None, iou_types=('segm',)):
         self.iterator = iterator
         self.target = target
         self.label_names = label_names
+        iou_types = (iou_types,) if isinstance(iou_types, str) else tuple(iou_types)
+        if not iou_types or any(t not in ('segm', 'bbox') for t in iou_types):
+            raise ValueError("iou_types: a non-empty subset of ('segm', 'bbox'), got %r"
+                             % (iou_types,))
+        self.iou_types = iou_types
 
     def __call__(self, trainer=None):
         return self.evaluate()
@@ -52,14 +70,30 @@ class _InstanceSegmentationEvaluator(object):
     def _observation(self, report):
         return {'%s/main/%s' % (self.name, k): v for k, v in report.items()}
 
+    def _queue_box_ious(self, bboxes, batch, dev):
+        """The batch's box IoU tables, queued: (flat device tensor, shapes, per-image areas)."""
+        gt_boxes = [ex[1] for ex in batch]
+        if self.box_convention == 'voc':
+            iou, shapes = B.queue_box_ious(bboxes, gt_boxes, 'voc', device=dev)
+            return iou, shapes, None
+        pred, gt = [B.to_xywh64(b) for b in bboxes], [B.to_xywh64(b) for b in gt_boxes]
+        crowd = [ex[4] for ex in batch] if len(batch[0]) == 6 else None
+        iou, shapes = B.queue_box_ious(pred, gt, 'coco', crowd_b=crowd, device=dev)
+        return iou, shapes, [(D.box_areas(p), D.box_areas(g)) for p, g in zip(pred, gt)]
+
     def collect(self):
         """Run the model over the iterator.  Returns (counts, pred_labels, pred_scores,
         ground-truth tuples): counts[i] = (inter (P,G), pred_area (P,), gt_area (G,)) host int64
-        arrays; gt tuple = the example's entries after the image (bbox, label, mask, ...)."""
+        arrays; gt tuple = the example's entries after the image (bbox, label, mask, ...).
+
+        With ``'bbox'`` in ``iou_types`` a fifth list follows, the images' box IoU records: the
+        float32 (P, G) table (VOC evaluator) or ``(iou float64 (P,G), dt_area (P,), gt_box_area
+        (G,))`` (COCO evaluator).  Without ``'segm'`` every counts[i] is None."""
         target = self.target
         sink = self.results_sink
+        segm, bbox = 'segm' in self.iou_types, 'bbox' in self.iou_types
         n_seen = 0
-        counts, pred_labels, pred_scores, gts = [], [], [], []
+        counts, pred_labels, pred_scores, gts, box_ious = [], [], [], [], []
         for batch in _batches(self.iterator):
             batch = list(batch)
             if not batch:
@@ -73,7 +107,7 @@ class _InstanceSegmentationEvaluator(object):
                 x, scales, sizes, masks_to_host=False)
             dev = x.device
             queued, encodes = [], []
-            for j, ex in enumerate(batch):
+            for j, ex in enumerate(batch if segm else ()):
                 gt_mask = ex[3]
                 H, W = sizes[j]
                 if tuple(gt_mask.shape[1:]) != (H, W):
@@ -85,50 +119,92 @@ class _InstanceSegmentationEvaluator(object):
                 queued.append((inter, pred[1], gt[1]))
                 if sink is not None:          # the packed masks just intersected, encoded
                     encodes.append(rle.queue_encode(pred[0], pred[1], pred[2], (H, W)))
+            parts = [t.reshape(-1).to(torch.int64) for q in queued for t in q]
+            if bbox:
+                # the IoU bit patterns ride at the end of the int64 buffer (a float32 pattern
+                # widened from int32, a float64 one reinterpreted): exact both ways
+                iou_d, shapes, areas = self._queue_box_ious(bboxes, batch, dev)
+                parts.append(iou_d.view(torch.int32).to(torch.int64)
+                             if iou_d.dtype == torch.float32 else iou_d.view(torch.int64))
             # one read-back for the whole batch
-            flat = torch.cat([t.reshape(-1).to(torch.int64) for q in queued for t in q])
+            flat = torch.cat(parts)
             host = flat.cpu().numpy()
             if sink is not None:              # the batch's strings: one more small read-back
-                for j, segs in enumerate(rle.fetch_encoded(encodes)):
+                all_segs = rle.fetch_encoded(encodes) if segm else [None] * len(batch)
+                for j, segs in enumerate(all_segs):
                     sink(n_seen + j, bboxes[j], labels[j], scores[j], segs)
             n_seen += len(batch)
             o = 0
-            for (inter, pa, ga), l, s, ex in zip(queued, labels, scores, batch):
-                P, G = inter.shape
-                c_inter = host[o:o + P * G].reshape(P, G)
-                o += P * G
-                c_pa = host[o:o + P]
-                o += P
-                c_ga = host[o:o + G]
-                o += G
-                counts.append((c_inter, c_pa, c_ga))
+            for j, (l, s, ex) in enumerate(zip(labels, scores, batch)):
+                if segm:
+                    P, G = queued[j][0].shape
+                    c_inter = host[o:o + P * G].reshape(P, G)
+                    o += P * G
+                    c_pa = host[o:o + P]
+                    o += P
+                    c_ga = host[o:o + G]
+                    o += G
+                    counts.append((c_inter, c_pa, c_ga))
+                else:
+                    counts.append(None)
                 pred_labels.append(l)
                 pred_scores.append(s)
                 gts.append(tuple(ex[1:]))
+            if bbox:
+                tail = host[o:]
+                tail = (tail.astype(np.int32).view(np.float32) if self.box_convention == 'voc'
+                        else tail.view(np.float64))
+                tables = B.split_tables(tail, shapes)
+                box_ious.extend(tables if areas is None else
+                                [(t,) + a for t, a in zip(tables, areas)])
+        if bbox:
+            return counts, pred_labels, pred_scores, gts, box_ious
         return counts, pred_labels, pred_scores, gts
+
+    def _prefixed(self, report):
+        return {'bbox/' + k: v for k, v in report.items()}
+
+    def _check_records(self, box_ious):
+        if 'bbox' in self.iou_types and box_ious is None:
+            raise ValueError("iou_types has 'bbox' but the records carry no box IoU tables")
 
 
 class InstanceSegmentationVOCEvaluator(_InstanceSegmentationEvaluator):
     """``validation/main/map`` and, with ``label_names``, ``validation/main/ap/<name>``
-    (class l's AP is ``ap[l]``; NaN for a class that never occurs)."""
+    (class l's AP is ``ap[l]``; NaN for a class that never occurs).  With ``'bbox'`` in
+    ``iou_types``: ``validation/main/bbox/map`` and ``bbox/ap/<name>``, chainercv's
+    ``eval_detection_voc`` of the predicted boxes against the examples' boxes."""
 
-    def __init__(self, iterator, target, use_07_metric=False, label_names=None):
-        super(InstanceSegmentationVOCEvaluator, self).__init__(iterator, target, label_names)
+    box_convention = 'voc'
+
+    def __init__(self, iterator, target, use_07_metric=False, label_names=None,
+                 iou_types=('segm',)):
+        super(InstanceSegmentationVOCEvaluator, self).__init__(iterator, target, label_names,
+                                                               iou_types)
         self.use_07_metric = use_07_metric
 
     def evaluate(self):
         return self.evaluate_collected(*self.collect())
 
-    def evaluate_collected(self, counts, pred_labels, pred_scores, gts):
+    def evaluate_collected(self, counts, pred_labels, pred_scores, gts, box_ious=None):
         """The host half of ``evaluate``: matching and AP from ``collect()``'s records."""
+        self._check_records(box_ious)
         gt_labels = [g[1] for g in gts]
         gt_difficults = None
         if gts and len(gts[0]) == 4:
             gt_difficults = [g[3] for g in gts]
-        prec, rec = matching.voc_prec_rec_from_counts(counts, pred_labels, pred_scores, gt_labels,
-                                                      gt_difficults)
-        ap = matching.calc_detection_voc_ap(prec, rec, use_07_metric=self.use_07_metric)
-        return self._observation(voc_report(ap, self.label_names))
+        report = {}
+        if 'segm' in self.iou_types:
+            prec, rec = matching.voc_prec_rec_from_counts(counts, pred_labels, pred_scores,
+                                                          gt_labels, gt_difficults)
+            ap = matching.calc_detection_voc_ap(prec, rec, use_07_metric=self.use_07_metric)
+            report.update(voc_report(ap, self.label_names))
+        if 'bbox' in self.iou_types:
+            prec, rec = matching.voc_prec_rec_from_ious(box_ious, pred_labels, pred_scores,
+                                                        gt_labels, gt_difficults)
+            ap = matching.calc_detection_voc_ap(prec, rec, use_07_metric=self.use_07_metric)
+            report.update(self._prefixed(voc_report(ap, self.label_names)))
+        return self._observation(report)
 
 
 class InstanceSegmentationCOCOEvaluator(_InstanceSegmentationEvaluator):
@@ -140,39 +216,63 @@ class InstanceSegmentationCOCOEvaluator(_InstanceSegmentationEvaluator):
     segmentations)`` called for the i-th evaluated image with its detections and their masks as
     COCO compressed RLE (``utils.evaluations.coco_results.ResultsWriter`` writes a results
     file).  The packed masks that are intersected are the ones encoded, on the device; only the
-    strings come back, in one more read-back per batch."""
+    strings come back, in one more read-back per batch.  Without ``'segm'`` in ``iou_types`` the
+    sink gets ``segmentations=None`` (bbox-only entries).
 
-    def __init__(self, iterator, target, label_names=None, results_sink=None):
-        super(InstanceSegmentationCOCOEvaluator, self).__init__(iterator, target, label_names)
+    With ``'bbox'`` in ``iou_types``: ``validation/main/bbox/map``, ``bbox/map@0.5``,
+    ``bbox/map@0.75`` and ``bbox/ap/<name>``: pycocotools' iouType 'bbox' on the predicted boxes
+    against the examples' boxes (the mask's tight box for this project's COCO dataset), crowds and
+    areas as for the masks."""
+
+    box_convention = 'coco'
+
+    def __init__(self, iterator, target, label_names=None, results_sink=None,
+                 iou_types=('segm',)):
+        super(InstanceSegmentationCOCOEvaluator, self).__init__(iterator, target, label_names,
+                                                                iou_types)
         self.results_sink = results_sink
 
     def evaluate(self):
         return self.evaluate_collected(*self.collect())
 
-    def evaluate_collected(self, counts, pred_labels, pred_scores, gts):
+    def evaluate_collected(self, counts, pred_labels, pred_scores, gts, box_ious=None):
         """The host half of ``evaluate``: matching and AP from ``collect()``'s records."""
+        self._check_records(box_ious)
         gt_labels = [g[1] for g in gts]
         gt_crowdeds = gt_areas = None
         if gts and len(gts[0]) == 5:
             gt_crowdeds = [g[3] for g in gts]
             gt_areas = [g[4] for g in gts]
-        result = matching.coco_results(matching.coco_evaluate_from_counts(
-            counts, pred_labels, pred_scores, gt_labels, gt_crowdeds, gt_areas))
-        return self._observation(coco_report(result, self.label_names))
+        report = {}
+        if 'segm' in self.iou_types:
+            result = matching.coco_results(matching.coco_evaluate_from_counts(
+                counts, pred_labels, pred_scores, gt_labels, gt_crowdeds, gt_areas))
+            report.update(coco_report(result, self.label_names))
+        if 'bbox' in self.iou_types:
+            result = matching.coco_results(matching.coco_evaluate_from_ious(
+                box_ious, pred_labels, pred_scores, gt_labels, gt_crowdeds, gt_areas))
+            report.update(self._prefixed(coco_report(result, self.label_names)))
+        return self._observation(report)
 
 
-def strip_records(counts, pred_labels, pred_scores, gts):
+def strip_records(counts, pred_labels, pred_scores, gts, box_ious=None):
     """``collect()``'s records without what the host matching never reads: each ground-truth
     tuple keeps its length and its labels (and difficult / crowd / area) but loses the boxes and
-    masks, which are by far the largest part."""
+    masks, which are by far the largest part.  The box IoU records, when present, stay whole."""
     gts = [(None, g[1], None) + tuple(g[3:]) for g in gts]
-    return list(counts), list(pred_labels), list(pred_scores), gts
+    out = (list(counts), list(pred_labels), list(pred_scores), gts)
+    return out if box_ious is None else out + (list(box_ious),)
 
 
 def merge_records(per_rank):
-    """Concatenate the ranks' records (each ``(counts, pred_labels, pred_scores, gts)``) in rank
-    order, which is the test set's order when rank i holds the i-th contiguous shard."""
-    merged = ([], [], [], [])
+    """Concatenate the ranks' records (each ``(counts, pred_labels, pred_scores, gts[,
+    box_ious])``) in rank order, which is the test set's order when rank i holds the i-th
+    contiguous shard."""
+    per_rank = list(per_rank)
+    widths = set(len(r) for r in per_rank)
+    if len(widths) > 1:
+        raise ValueError('records with and without box IoU tables cannot be merged')
+    merged = tuple([] for _ in range(widths.pop() if widths else 4))
     for records in per_rank:
         for out, part in zip(merged, records):
             out.extend(part)

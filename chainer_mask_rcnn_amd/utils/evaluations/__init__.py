@@ -3,3 +3,4 @@ from .eval_instance_segmentation_voc import eval_instseg_voc, calc_instseg_voc_p
 from .eval_instance_segmentation_coco import eval_instseg_coco
 from .masks import mask_iou
 from .matching import calc_detection_voc_ap
+from .eval_detection import eval_detection_voc, eval_detection_coco

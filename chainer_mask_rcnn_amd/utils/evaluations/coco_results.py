@@ -7,12 +7,19 @@ pycocotools' ``COCO.loadRes``.  The segmentations are COCO's compressed RLE, enc
 from the packed masks (rle.py); ``eval_coco_results`` decodes them on the device and scores them
 with the same host matching as the in-memory evaluator, so a file written from a model scores
 exactly what ``InstanceSegmentationCOCOEvaluator.evaluate()`` reports for it.
+
+The detection track's file has the same entries without ``segmentation``: ``results_entries`` /
+``ResultsWriter`` write it when given ``segmentations=None``, and ``eval_coco_results(...,
+iou_type='bbox')`` scores the ``bbox`` fields of either kind of file (device bbIou tables,
+boxes.py; the same matching) to the evaluator's ``bbox/`` keys.
 """
 import json
 from collections import OrderedDict
 
 import numpy as np
 
+from . import boxes as B
+from . import eval_detection as D
 from . import masks as M
 from . import matching
 from . import rle as R
@@ -22,10 +29,16 @@ def results_entries(img_id, bboxes, labels, scores, segmentations, class_id_to_c
     """The results entries of one image: ``bboxes`` (D, 4) (y1, x1, y2, x2) in original-image
     pixels -> ``bbox`` [x1, y1, x2 - x1, y2 - y1]; ``labels`` (D,) class ids -> the dataset's
     ``category_id``; ``scores`` (D,) float32 -> Python floats (exact); ``segmentations`` the
-    compressed RLE dicts.  Entries keep the detections' order."""
+    compressed RLE dicts, or None for bbox-only entries (the detection track's format).  Entries
+    keep the detections' order."""
     bboxes = np.asarray(bboxes, np.float32).reshape(-1, 4)
     labels = np.asarray(labels).ravel()
     scores = np.asarray(scores, np.float32).ravel()
+    if segmentations is None:
+        if not (len(bboxes) == len(labels) == len(scores)):
+            raise ValueError('%d boxes, %d labels and %d scores'
+                             % (len(bboxes), len(labels), len(scores)))
+        segmentations = [None] * len(bboxes)
     if not (len(bboxes) == len(labels) == len(scores) == len(segmentations)):
         raise ValueError('%d boxes, %d labels, %d scores and %d segmentations'
                          % (len(bboxes), len(labels), len(scores), len(segmentations)))
@@ -34,8 +47,10 @@ def results_entries(img_id, bboxes, labels, scores, segmentations, class_id_to_c
                                            segmentations):
         out.append({'image_id': int(img_id), 'category_id': int(class_id_to_cat_id[int(l)]),
                     'bbox': [float(x1), float(y1), float(x2 - x1), float(y2 - y1)],
-                    'score': float(s), 'segmentation': {'size': [int(v) for v in seg['size']],
-                                                        'counts': seg['counts']}})
+                    'score': float(s)})
+        if seg is not None:
+            out[-1]['segmentation'] = {'size': [int(v) for v in seg['size']],
+                                       'counts': seg['counts']}
     return out
 
 
@@ -74,8 +89,19 @@ class ResultsWriter(object):
         self.close()
 
 
-def _load(results, dataset):
+def _check_bbox(k, e):
+    b = e['bbox']
+    if (not isinstance(b, (list, tuple)) or len(b) != 4
+            or not all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in b)):
+        raise ValueError('results entry %d: bbox must be [x, y, w, h] numbers' % k)
+
+
+def _load(results, dataset, iou_type='segm'):
     """load_results with each entry's position in the file: image_id -> [(k, entry), ...]."""
+    if iou_type not in ('segm', 'bbox'):
+        raise ValueError("iou_type must be 'segm' or 'bbox', got %r" % (iou_type,))
+    needed = ('image_id', 'category_id', 'score') + (
+        ('segmentation',) if iou_type == 'segm' else ('bbox',))
     if isinstance(results, str):
         with open(results) as f:
             results = json.load(f)
@@ -86,14 +112,19 @@ def _load(results, dataset):
     for k, e in enumerate(results):
         if not isinstance(e, dict):
             raise ValueError('results entry %d is not an object' % k)
-        for key in ('image_id', 'category_id', 'score', 'segmentation'):
+        for key in needed:
             if key not in e:
                 raise ValueError('results entry %d has no %r' % (k, key))
-        img_id, seg = e['image_id'], e['segmentation']
+        img_id = e['image_id']
         if img_id not in dataset.img_sizes:
             raise ValueError('results entry %d: unknown image_id %r' % (k, img_id))
         if e['category_id'] not in dataset.cat_id_to_class_id:
             raise ValueError('results entry %d: unknown category_id %r' % (k, e['category_id']))
+        if iou_type == 'bbox':                        # the segmentation, if any, is not read
+            _check_bbox(k, e)
+            grouped.setdefault(img_id, []).append((k, e))
+            continue
+        seg = e['segmentation']
         if isinstance(seg, list):
             raise ValueError('results entry %d: polygon segmentations are not supported; '
                              'segm results are RLE {"size", "counts"}' % k)
@@ -113,26 +144,60 @@ def _load(results, dataset):
     return grouped
 
 
-def load_results(results, dataset):
+def load_results(results, dataset, iou_type='segm'):
     """A results file (path) or list of entries -> OrderedDict image_id -> entries, in file
     order, validated against ``dataset`` (a COCOInstanceSegmentationDataset): every image id and
     category id must be the annotation file's, every segmentation a compressed string or a count
     list of the image's size.  ``bbox`` is optional (Detectron's segmentation results have
-    none); polygons are refused, as pycocotools' ``loadRes`` refuses them for segm results."""
-    return OrderedDict((i, [e for _, e in v]) for i, v in _load(results, dataset).items())
+    none); polygons are refused, as pycocotools' ``loadRes`` refuses them for segm results.
+    With ``iou_type='bbox'`` an entry needs ``bbox`` ([x, y, w, h] numbers) instead and need not
+    have a ``segmentation``."""
+    return OrderedDict((i, [e for _, e in v])
+                       for i, v in _load(results, dataset, iou_type).items())
 
 
-def eval_coco_results(results, dataset, limit=None, label_names=None):
+def _eval_bbox_results(grouped, dataset, n, label_names):
+    """eval_coco_results for iou_type 'bbox': one launch makes every image's bbIou table."""
+    from ...extensions.instance_segmentation_evaluators import coco_report
+    pred, gt_boxes, pred_labels, pred_scores, gts = [], [], [], [], []
+    for i in range(n):
+        entries = [e for _, e in grouped.get(dataset.img_ids[i], [])]
+        gt = dataset.get_annotations(i)
+        pred.append(np.array([e['bbox'] for e in entries], np.float64).reshape(-1, 4))
+        gt_boxes.append(B.to_xywh64(gt[0]))
+        pred_labels.append(np.array([dataset.cat_id_to_class_id[e['category_id']]
+                                     for e in entries], np.int32))
+        pred_scores.append(np.array([e['score'] for e in entries], np.float32))
+        gts.append(gt)
+    gt_labels = [g[1] for g in gts]
+    gt_crowdeds = gt_areas = None
+    if gts and len(gts[0]) == 5:                      # as the evaluator: crowds and areas
+        gt_crowdeds = [g[3] for g in gts]
+        gt_areas = [g[4] for g in gts]
+    tables = D.coco_box_tables(pred, gt_boxes, gt_crowdeds)
+    result = matching.coco_results(matching.coco_evaluate_from_ious(
+        tables, pred_labels, pred_scores, gt_labels, gt_crowdeds, gt_areas))
+    return {'validation/main/bbox/%s' % k: v
+            for k, v in coco_report(result, label_names).items()}
+
+
+def eval_coco_results(results, dataset, limit=None, label_names=None, iou_type='segm'):
     """Score a results file (path or list of entries) against ``dataset`` (a
     COCOInstanceSegmentationDataset; its images in order, the first ``limit`` when given; an
     image without entries has no detections).  Each image's segmentations are decoded in one
     device call and intersected with its packed ground truth; the counts feed
     ``matching.coco_evaluate_from_counts``.  Returns the keys of
-    ``InstanceSegmentationCOCOEvaluator.evaluate()`` (``validation/main/map``, ...)."""
+    ``InstanceSegmentationCOCOEvaluator.evaluate()`` (``validation/main/map``, ...).
+
+    ``iou_type='bbox'``: the entries' ``bbox`` fields are scored against the boxes of
+    ``dataset.get_annotations(i)`` (the masks' tight boxes) instead, and the evaluator's
+    ``validation/main/bbox/...`` keys come back; the entries need no ``segmentation``."""
     import torch
     from ...extensions.instance_segmentation_evaluators import coco_report
-    grouped = _load(results, dataset)
+    grouped = _load(results, dataset, iou_type)
     n = len(dataset) if not limit else min(int(limit), len(dataset))
+    if iou_type == 'bbox':
+        return _eval_bbox_results(grouped, dataset, n, label_names)
     dev = M._device()
     counts, pred_labels, pred_scores, gts = [], [], [], []
     for i in range(n):

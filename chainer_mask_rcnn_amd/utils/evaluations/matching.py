@@ -7,6 +7,9 @@ per-image intersection counts.  No masks are touched here — each image is desc
 flags.  The CPU tests feed counts computed with NumPy; everything that decides a number lives
 in this file.
 
+The box entry points (``voc_prec_rec_from_ious``, ``coco_evaluate_from_ious``) take per-image
+IoU tables instead (boxes.py makes them on the device) and run the same loops.
+
 * VOC: ``voc_prec_rec_from_counts`` restates ``calc_instseg_voc_prec_rec``
   (chainer_mask_rcnn/utils/evaluations/eval_instance_segmentation_voc.py) with its order rules.
 * COCO: ``coco_evaluate_from_counts`` restates pycocotools' COCOeval ``evaluate`` /
@@ -26,8 +29,23 @@ def voc_prec_rec_from_counts(counts, pred_labels, pred_scores, gt_labels, gt_dif
                              iou_thresh=0.5):
     """calc_instseg_voc_prec_rec with the masks replaced by per-image counts
     ``(inter, pred_area, gt_area)``."""
+    return _voc_prec_rec(counts, lambda c: iou_from_counts(*c), pred_labels, pred_scores,
+                         gt_labels, gt_difficults, iou_thresh)
+
+
+def voc_prec_rec_from_ious(ious, pred_labels, pred_scores, gt_labels, gt_difficults=None,
+                           iou_thresh=0.5):
+    """chainercv's calc_detection_voc_prec_rec with the boxes replaced by per-image (P, G) IoU
+    tables (``boxes.queue_box_ious(..., 'voc')``: float32, the +1 convention applied).  The
+    matching is the one ``voc_prec_rec_from_counts`` runs."""
+    return _voc_prec_rec(ious, np.asarray, pred_labels, pred_scores, gt_labels, gt_difficults,
+                         iou_thresh)
+
+
+def _voc_prec_rec(tables, iou_of, pred_labels, pred_scores, gt_labels, gt_difficults, iou_thresh):
+    """The VOC matching and accumulation; ``iou_of(tables[i])`` is image i's (P, G) IoU."""
     counts, pred_labels, pred_scores, gt_labels = (
-        list(counts), list(pred_labels), list(pred_scores), list(gt_labels))
+        list(tables), list(pred_labels), list(pred_scores), list(gt_labels))
     n = len(counts)
     gt_difficults = [None] * n if gt_difficults is None else list(gt_difficults)
     if not (len(pred_labels) == len(pred_scores) == len(gt_labels) == len(gt_difficults) == n):
@@ -37,7 +55,7 @@ def voc_prec_rec_from_counts(counts, pred_labels, pred_scores, gt_labels, gt_dif
     score = defaultdict(list)
     match = defaultdict(list)
 
-    for (inter, pred_area, gt_area), pred_label, pred_score, gt_label, gt_difficult in zip(
+    for table, pred_label, pred_score, gt_label, gt_difficult in zip(
             counts, pred_labels, pred_scores, gt_labels, gt_difficults):
         pred_label = np.asarray(pred_label)
         pred_score = np.asarray(pred_score)
@@ -45,7 +63,7 @@ def voc_prec_rec_from_counts(counts, pred_labels, pred_scores, gt_labels, gt_dif
         if gt_difficult is None:
             gt_difficult = np.zeros(len(gt_label), dtype=bool)
         gt_difficult = np.asarray(gt_difficult)
-        iou_all = iou_from_counts(inter, pred_area, gt_area)
+        iou_all = iou_of(table)
 
         for l in np.unique(np.concatenate((pred_label, gt_label)).astype(int)):
             pred_keep_l = pred_label == l
@@ -218,6 +236,28 @@ def _evaluate_img(ious, dt_scores, dt_area, gt_crowd, gt_area, a_rng, max_det, i
             'dtIgnore': dt_ig}
 
 
+def _count_image(table, n_dt, n_gt):
+    """Image record of the count form: ``(ious(d_idx, g_idx, crowd), dt_area, gt_area)``."""
+    inter, pred_area, gt_area_px = table
+    inter = np.asarray(inter, np.int64).reshape(n_dt, n_gt)
+    pred_area = np.asarray(pred_area, np.int64)
+    gt_area_px = np.asarray(gt_area_px, np.int64)
+
+    def ious(d_idx, g_idx, gc):
+        return _coco_ious(inter[d_idx][:, g_idx], pred_area[d_idx], gt_area_px[g_idx], gc[g_idx])
+    return ious, pred_area, gt_area_px
+
+
+def _iou_image(table, n_dt, n_gt):
+    """Image record of the IoU form: the table already holds bbIou with the crowd rule."""
+    iou, dt_area, gt_area = table
+    iou = np.asarray(iou, np.float64).reshape(n_dt, n_gt)
+
+    def ious(d_idx, g_idx, gc):
+        return iou[d_idx][:, g_idx]
+    return ious, np.asarray(dt_area, np.float64).ravel(), np.asarray(gt_area, np.float64).ravel()
+
+
 def coco_evaluate_from_counts(counts, pred_labels, pred_scores, gt_labels, gt_crowdeds=None,
                               gt_areas=None):
     """COCOeval(gt, dt, 'segm').evaluate() + accumulate() as eval_instseg_coco sets them up,
@@ -227,8 +267,27 @@ def coco_evaluate_from_counts(counts, pred_labels, pred_scores, gt_labels, gt_cr
     where undefined, and ``params`` (iouThrs, recThrs, maxDets, areaRng, areaRngLbl, catIds,
     imgIds).  ``gt_areas`` (if given) decides the gt area range, as the annotation's 'area';
     otherwise the pixel count does.  A detection's area is its pixel count."""
+    return _coco_evaluate(counts, _count_image, pred_labels, pred_scores, gt_labels, gt_crowdeds,
+                          gt_areas)
+
+
+def coco_evaluate_from_ious(tables, pred_labels, pred_scores, gt_labels, gt_crowdeds=None,
+                            gt_areas=None):
+    """COCOeval(gt, dt, 'bbox').evaluate() + accumulate() from per-image
+    ``(iou (P,G), dt_area (P,), gt_box_area (G,))``: the float64 bbIou tables with the crowd rule
+    applied (``boxes.queue_box_ious(..., 'coco', crowd_b)``) and the boxes' ``w*h``.  A
+    detection's area is its box's ``w*h`` (what ``loadRes`` sets for bbox results); a ground
+    truth's is ``gt_areas`` if given, else its box's.  Same loops and return value as
+    ``coco_evaluate_from_counts``."""
+    return _coco_evaluate(tables, _iou_image, pred_labels, pred_scores, gt_labels, gt_crowdeds,
+                          gt_areas)
+
+
+def _coco_evaluate(tables, image_of, pred_labels, pred_scores, gt_labels, gt_crowdeds, gt_areas):
+    """COCOeval's evaluate() + accumulate(); ``image_of(tables[i], P, G)`` gives image i's IoU
+    lookup, detection areas and default ground-truth areas."""
     counts, pred_labels, pred_scores, gt_labels = (
-        list(counts), list(pred_labels), list(pred_scores), list(gt_labels))
+        list(tables), list(pred_labels), list(pred_scores), list(gt_labels))
     n_img = len(counts)
     gt_crowdeds = [None] * n_img if gt_crowdeds is None else list(gt_crowdeds)
     gt_areas = [None] * n_img if gt_areas is None else list(gt_areas)
@@ -242,14 +301,12 @@ def coco_evaluate_from_counts(counts, pred_labels, pred_scores, gt_labels, gt_cr
 
     # evalImgs[k][a][i]
     eval_imgs = [[[None] * n_img for _ in range(A)] for _ in range(K)]
-    for i, ((inter, pred_area, gt_area_px), pl, ps, gl, gc, ga) in enumerate(zip(
+    for i, (table, pl, ps, gl, gc, ga) in enumerate(zip(
             counts, pred_labels, pred_scores, gt_labels, gt_crowdeds, gt_areas)):
         pl, ps, gl = np.asarray(pl).ravel(), np.asarray(ps).ravel(), np.asarray(gl).ravel()
-        inter = np.asarray(inter, np.int64).reshape(len(pl), len(gl))
-        pred_area = np.asarray(pred_area, np.int64)
-        gt_area_px = np.asarray(gt_area_px, np.int64)
+        ious_of, pred_area, gt_area_px = image_of(table, len(pl), len(gl))
         gc = np.zeros(len(gl), bool) if gc is None else np.asarray(gc).astype(bool).ravel()
-        # the annotation 'area' of a gt: the given one, else its pixel count
+        # the annotation 'area' of a gt: the given one, else its pixel count (its box's w*h)
         ga = gt_area_px if ga is None else np.asarray(ga).ravel()
         for k, cat in enumerate(cat_ids):
             d_idx = np.flatnonzero(pl == cat)
@@ -259,8 +316,7 @@ def coco_evaluate_from_counts(counts, pred_labels, pred_scores, gt_labels, gt_cr
             # computeIoU: detections by descending score (mergesort), first maxDets[-1]
             d_idx = d_idx[np.argsort(-ps[d_idx], kind='mergesort')][:max_dets[-1]]
             if len(d_idx) and len(g_idx):
-                ious = _coco_ious(inter[d_idx][:, g_idx], pred_area[d_idx], gt_area_px[g_idx],
-                                  gc[g_idx])
+                ious = ious_of(d_idx, g_idx, gc)
             else:
                 ious = np.zeros((0, 0))
             for a, a_rng in enumerate(p['areaRng']):
@@ -356,7 +412,8 @@ def summarize(prec, rec, iou_threshs, area_ranges, max_detection_list, ap=True,
 
 
 def coco_results(coco_eval):
-    """eval_instseg_coco's result dict from a ``coco_evaluate_from_counts`` result."""
+    """eval_instseg_coco's result dict from a ``coco_evaluate_from_counts`` (or ``_from_ious``)
+    result."""
     p = coco_eval['params']
     results = {'coco_eval': coco_eval}
     for key, ap, iou_thresh, area_range, max_detection in COCO_SETTINGS:

@@ -558,6 +558,30 @@ int mrcnn_mask_intersect(const uint64_t *a, const int32_t *ext_a, int P, const u
                          const int32_t *ext_b, int G, int H, int W, int32_t *inter,
                          void *stream);
 
+/* ---- Box IoU for evaluation (csrc/bbox_eval.hip) ---------------------------------------------
+ * The IoU tables of a whole evaluation batch of images in one launch (ragged): boxes_a (n_a,4)
+ * are the images' detections one after another, boxes_b (n_b,4) their ground-truth boxes; image i
+ * owns rows a_off[i] .. a_off[i+1] of boxes_a (P_i of them) and b_off[i] .. b_off[i+1] of boxes_b
+ * (G_i); a_off / b_off are (n_img+1) int32 prefix offsets, out_off (n_img+1) int64 with
+ * out_off[i+1] - out_off[i] = P_i * G_i and total = out_off[n_img] (the host's copy).  Output: iou
+ * (total) flat, image after image, each image's table row-major (P_i, G_i).  All arrays are device
+ * pointers.  One thread per pair; every read is bounded by the offsets and by n_a / n_b (a pair
+ * the offsets do not describe is left unwritten); total == 0 returns at once without a launch. */
+/* VOC convention: (y1, x1, y2, x2) float32; 1 is added to both max corners, then chainercv's
+ * bbox_iou, operation for operation (the per-pair function mrcnn_bbox_iou_argmax uses) —
+ * bit-identical to utils.bbox.bbox_iou(a + [0,0,1,1], b + [0,0,1,1]).  Replaces the per-image,
+ * per-class `bbox[:, 2:] += 1; bbox_iou(...)` of chainercv's calc_detection_voc_prec_rec. */
+int mrcnn_box_iou_voc(const float *boxes_a, const float *boxes_b, const int32_t *a_off,
+                      const int32_t *b_off, const int64_t *out_off, int n_img, int n_a, int n_b,
+                      int64_t total, float *iou, void *stream);
+/* COCO convention: (x, y, w, h) float64, crowd_b (n_b) uint8 or null (no crowds).  pycocotools'
+ * bbIou: w = min(Dx+Dw, Gx+Gw) - max(Dx, Gx), 0 if w <= 0; h likewise; i = w*h; u = crowd ? Dw*Dh
+ * : Dw*Dh + Gw*Gh - i; i / u.  Replaces maskUtils.iou(d, g, iscrowd) of COCOeval.computeIoU for
+ * iouType 'bbox'. */
+int mrcnn_box_iou_coco(const double *boxes_a, const double *boxes_b, const uint8_t *crowd_b,
+                       const int32_t *a_off, const int32_t *b_off, const int64_t *out_off,
+                       int n_img, int n_a, int n_b, int64_t total, double *iou, void *stream);
+
 /* ---- COCO RLE of packed masks (csrc/mask_rle.hip) -----------------------------------------
  * Uncompressed counts: runs over the column-major pixel index p = x * H + y, alternating 0 / 1
  * starting with zeros (the first run may be 0), summing to H * W (pycocotools maskApi.c

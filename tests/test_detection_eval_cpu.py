@@ -1,0 +1,312 @@
+"""The box entry points of utils/evaluations/matching.py on NumPy IoU tables (no device):
+hand-worked cases, and the cross-pin to the mask path — on integer-cornered boxes the box IoU is
+the pixel IoU of the filled rectangles, so the box matching must reproduce the count matching
+array for array."""
+import numpy as np
+import pytest
+
+import detection_eval_ref as R
+from chainer_mask_rcnn_amd.extensions import instance_segmentation_evaluators as E
+from chainer_mask_rcnn_amd.utils.evaluations import matching
+
+ONE = 1.0 / (1.0 + np.spacing(1))     # accumulate's precision of one true positive: tp / (tp + eps)
+
+
+def _coco_tables(pred_xywh, gt_xywh, crowds=None):
+    crowds = [None] * len(gt_xywh) if crowds is None else crowds
+    return [(R.bb_iou(d, g, c), d[:, 2] * d[:, 3], g[:, 2] * g[:, 3])
+            for d, g, c in zip(pred_xywh, gt_xywh, crowds)]
+
+
+def _f32(*v):
+    return np.array(v, np.float32)
+
+
+# ---------------------------------------------------------------------------- hand-worked cases
+def test_one_detection_at_iou_0_6():
+    # gt 10 x 10, detection 10 x 6 inside it: IoU = 60 / 100
+    gt = [np.array([[0., 0., 10., 10.]])]
+    dt = [np.array([[0., 0., 10., 6.]])]
+    tables = _coco_tables(dt, gt)
+    assert tables[0][0][0, 0] == 0.6
+    r = matching.coco_results(matching.coco_evaluate_from_ious(
+        tables, [np.array([2], np.int32)], [_f32(0.9)], [np.array([2], np.int32)]))
+    assert r['map/iou=0.50/area=all/maxDets=100'] == 1.0
+    assert r['map/iou=0.75/area=all/maxDets=100'] == 0.0
+    # matched at exactly the thresholds that do not exceed 0.6
+    thr = r['coco_eval']['params']['iouThrs']
+    per_t = r['coco_eval']['precision'][:, 0, 0, 0, 2]
+    assert np.array_equal(per_t, (thr <= 0.6) * ONE)
+    # VOC: the same pair in the +1 convention, (y1, x1, y2, x2) = 11 x 11 against 11 x 7: 7/11
+    iou = R.voc_iou(_f32(0, 0, 10, 6).reshape(1, 4), _f32(0, 0, 10, 10).reshape(1, 4))
+    assert iou.dtype == np.float32 and iou[0, 0] == np.float32(77.) / np.float32(121.)
+    for thresh, want in ((0.5, 1.0), (0.75, 0.0)):
+        prec, rec = matching.voc_prec_rec_from_ious(
+            [iou], [np.array([2])], [_f32(0.9)], [np.array([2])], iou_thresh=thresh)
+        ap = matching.calc_detection_voc_ap(prec, rec)
+        assert ap[2] == want and np.isnan(ap[:2]).all()
+
+
+def test_crowd_absorbs_two_detections():
+    # one regular gt, matched by the best detection; one crowd gt holding two more detections
+    gt = [np.array([[0., 0., 10., 10.], [20., 20., 20., 20.]])]
+    crowd = [np.array([0, 1])]
+    dt = [np.array([[0., 0., 10., 10.], [21., 21., 5., 5.], [30., 30., 6., 6.]])]
+    tables = _coco_tables(dt, gt, crowd)
+    assert np.array_equal(tables[0][0], [[1., 0.], [0., 1.], [0., 1.]])   # inter / det area
+    labels = [np.zeros(3, np.int32)]
+    scores = [_f32(0.9, 0.8, 0.7)]
+    r = matching.coco_evaluate_from_ious(tables, labels, scores, [np.zeros(2, np.int32)], crowd)
+    # one positive, found first; the two crowd matches are ignored, not false positives
+    assert np.all(r['precision'][:, :, 0, 0, 2] == ONE)
+    assert np.all(r['recall'][:, 0, 0, 2] == 1.0)
+    # without the flag the same two detections match nothing at IoU >= .5 and are false positives
+    plain = _coco_tables(dt, gt)
+    r2 = matching.coco_evaluate_from_ious(plain, labels, scores, [np.zeros(2, np.int32)])
+    assert r2['recall'][0, 0, 0, 2] == 0.5
+
+
+def test_unmatched_detection_outside_the_area_range_is_ignored():
+    # a small gt found by a small detection; a large stray detection scoring higher.  In the
+    # 'small' range the stray one (area 10000 > 32^2) is ignored, in 'all' it is a false positive
+    gt = [np.array([[0., 0., 10., 10.]])]
+    dt = [np.array([[200., 200., 100., 100.], [0., 0., 10., 10.]])]
+    r = matching.coco_evaluate_from_ious(
+        _coco_tables(dt, gt), [np.zeros(2, np.int32)], [_f32(0.9, 0.5)], [np.zeros(1, np.int32)])
+    small, everything = r['precision'][0, :, 0, 1, 2], r['precision'][0, :, 0, 0, 2]
+    assert np.all(small == ONE)
+    assert np.all(everything == 0.5)
+    # the annotation's area, when given, decides the gt's range: 5000 is not small
+    r = matching.coco_evaluate_from_ious(
+        _coco_tables(dt, gt), [np.zeros(2, np.int32)], [_f32(0.9, 0.5)], [np.zeros(1, np.int32)],
+        gt_areas=[_f32(5000.)])
+    assert np.all(r['precision'][0, :, 0, 1, 2] == -1)          # no small gt left
+
+
+def test_absent_class_is_nan_under_its_own_name():
+    gt = [np.array([[0., 0., 10., 10.]])]
+    tables = _coco_tables(gt, gt)
+    result = matching.coco_results(matching.coco_evaluate_from_ious(
+        tables, [np.array([3], np.int32)], [_f32(0.9)], [np.array([3], np.int32)]))
+    report = E.coco_report(result, ['a', 'b', 'c', 'd', 'e'])
+    assert report['ap/d'] == 1.0 and report['map'] == 1.0
+    for name in 'abce':
+        assert np.isnan(report['ap/' + name])
+    iou = R.voc_iou(_f32(0, 0, 9, 9).reshape(1, 4), _f32(0, 0, 9, 9).reshape(1, 4))
+    prec, rec = matching.voc_prec_rec_from_ious([iou], [np.array([3])], [_f32(0.9)],
+                                                [np.array([3])])
+    report = E.voc_report(matching.calc_detection_voc_ap(prec, rec), ['a', 'b', 'c', 'd', 'e'])
+    assert report['ap/d'] == 1.0
+    for name in 'abce':
+        assert np.isnan(report['ap/' + name])
+
+
+# ------------------------------------------------------------------- cross-pins to the mask path
+@pytest.fixture(scope='module')
+def data():
+    # a seed whose boxes keep every +1-convention IoU away from the VOC threshold (an exact 0.5
+    # is common among small rectangles); the VOC cross-pin asserts that from the reference alone
+    return R.integer_dataset(seed=5)
+
+
+@pytest.mark.parametrize('with_areas', [False, True])
+@pytest.mark.parametrize('with_crowds', [False, True])
+def test_coco_box_matching_equals_count_matching_on_rectangles(data, with_areas, with_crowds):
+    """Integer corners: w*h and the pixel counts are the same integers, so bbIou's i / u and the
+    count form's inter / union are the same float64 quotient (0 where nothing overlaps)."""
+    H, W = data['H'], data['W']
+    crowds = data['gt_crowdeds'] if with_crowds else None
+    areas = data['gt_areas'] if with_areas else None
+    counts = R.counts([R.rasters(b, H, W) for b in data['pred_bboxes']],
+                      [R.rasters(b, H, W) for b in data['gt_bboxes']])
+    want = matching.coco_evaluate_from_counts(counts, data['pred_labels'], data['pred_scores'],
+                                              data['gt_labels'], crowds, areas)
+    tables = _coco_tables([R.xywh64(b) for b in data['pred_bboxes']],
+                          [R.xywh64(b) for b in data['gt_bboxes']],
+                          crowds)
+    got = matching.coco_evaluate_from_ious(tables, data['pred_labels'], data['pred_scores'],
+                                           data['gt_labels'], crowds, areas)
+    assert np.array_equal(got['precision'], want['precision'])
+    assert np.array_equal(got['recall'], want['recall'])
+    assert got['params']['catIds'] == want['params']['catIds']
+    assert (want['precision'] > 0).any() and (want['precision'][5:] > 0).any()   # not vacuous
+    a, b = matching.coco_results(got), matching.coco_results(want)
+    for k in b:
+        if k != 'coco_eval':
+            assert np.array_equal(np.asarray(a[k]), np.asarray(b[k]), equal_nan=True), k
+
+
+@pytest.mark.parametrize('with_difficult', [False, True])
+def test_voc_box_matching_equals_count_matching_on_rectangles(data, with_difficult):
+    """The +1 convention's IoU is the pixel IoU of the rectangles [y1:y2+1, x1:x2+1] — the same
+    integer ratio, rounded to float32 on one side and to float64 on the other.  Rounding is
+    monotone and 0.5 is a float32, so the two sides decide alike unless two different ratios fall
+    in one float32 ulp or a ratio lies within rounding of the threshold.  With unions of at most
+    40 * 40 pixels different ratios are >= 1 / 1600^2 = 3.9e-7 apart (a float32 ulp below 1 is
+    6e-8); that no IoU lies within 1e-6 of the threshold is asserted on the inputs."""
+    H, W = data['H'], data['W']
+    ref32 = [R.voc_iou(p, g) for p, g in zip(data['pred_bboxes'], data['gt_bboxes'])]
+    pm = [R.rasters(b, H, W, inclusive=True) for b in data['pred_bboxes']]
+    gm = [R.rasters(b, H, W, inclusive=True) for b in data['gt_bboxes']]
+    counts = R.counts(pm, gm)
+    for t32, (inter, pa, ga) in zip(ref32, counts):
+        union = pa[:, None] + ga[None, :] - inter
+        assert union.size == 0 or (union.min() >= 1 and union.max() <= 1600)
+        assert not (np.abs(inter / np.maximum(union, 1) - 0.5) < 1e-6).any()
+        assert not (np.abs(t32.astype(np.float64) - 0.5) < 1e-6).any()
+    dif = data['gt_difficults'] if with_difficult else None
+    want = matching.voc_prec_rec_from_counts(counts, data['pred_labels'], data['pred_scores'],
+                                             data['gt_labels'], dif)
+    got = matching.voc_prec_rec_from_ious(ref32, data['pred_labels'], data['pred_scores'],
+                                          data['gt_labels'], dif)
+    assert len(got[0]) == len(want[0]) == 4
+    for g, w in zip(got[0] + got[1], want[0] + want[1]):
+        assert (g is None and w is None) or np.array_equal(g, w, equal_nan=True)
+    ap = matching.calc_detection_voc_ap(*got)
+    assert np.array_equal(ap, matching.calc_detection_voc_ap(*want)) and (ap > 0).any()
+
+
+# ----------------------------------------------------------------------------- no-change guards
+def _records(data, n=6, box=None):
+    H, W = data['H'], data['W']
+    counts = R.counts([R.rasters(b, H, W) for b in data['pred_bboxes'][:n]],
+                      [R.rasters(b, H, W) for b in data['gt_bboxes'][:n]])
+    gts = [(b, l, R.rasters(b, H, W), c, a) for b, l, c, a in zip(
+        data['gt_bboxes'][:n], data['gt_labels'][:n], data['gt_crowdeds'][:n],
+        data['gt_areas'][:n])]
+    rec = (counts, data['pred_labels'][:n], data['pred_scores'][:n], gts)
+    if box == 'coco':
+        rec += (_coco_tables([R.xywh64(b) for b in data['pred_bboxes'][:n]],
+                             [R.xywh64(b) for b in data['gt_bboxes'][:n]],
+                             data['gt_crowdeds'][:n]),)
+    return rec
+
+
+def test_strip_and_merge_round_trip_records_with_and_without_the_box_field(data):
+    plain, boxed = _records(data), _records(data, box='coco')
+    s = E.strip_records(*plain)
+    assert isinstance(s, tuple) and len(s) == 4                       # as it always was
+    assert all(g[0] is None and g[2] is None and len(g) == 5 for g in s[3])
+    m = E.merge_records([s, s])
+    assert isinstance(m, tuple) and len(m) == 4 and all(isinstance(x, list) for x in m)
+    assert m[0] == list(plain[0]) * 2 and m[3] == s[3] * 2
+    sb = E.strip_records(*boxed)
+    assert len(sb) == 5 and sb[4] == list(boxed[4]) and sb[:4][3] == s[3]
+    mb = E.merge_records([sb, sb])
+    assert len(mb) == 5 and mb[4] == list(boxed[4]) * 2 and mb[0] == list(boxed[0]) * 2
+    with pytest.raises(ValueError):
+        E.merge_records([s, sb])
+    assert E.merge_records([]) == ([], [], [], [])
+    # the host half: two shards merged score what the whole scores, segm and bbox keys
+    names = ['c%d' % i for i in range(4)]
+    both = E.InstanceSegmentationCOCOEvaluator(None, None, label_names=names,
+                                               iou_types=('segm', 'bbox'))
+    whole = both.evaluate_collected(*boxed)
+    halves = E.merge_records([E.strip_records(*[r[:3] for r in boxed]),
+                              E.strip_records(*[r[3:] for r in boxed])])
+    merged = both.evaluate_collected(*halves)
+    assert sorted(merged) == sorted(whole)
+    for k in whole:
+        assert np.array_equal(np.asarray(whole[k]), np.asarray(merged[k]), equal_nan=True), k
+    assert {'validation/main/bbox/map', 'validation/main/bbox/map@0.5',
+            'validation/main/bbox/map@0.75', 'validation/main/bbox/ap/c0',
+            'validation/main/map'} <= set(whole)
+    # integer corners: the rectangles' mask AP is their box AP
+    for k in ['map', 'map@0.5', 'map@0.75'] + ['ap/' + n for n in names]:
+        assert np.array_equal(np.asarray(whole['validation/main/bbox/' + k]),
+                              np.asarray(whole['validation/main/' + k]), equal_nan=True), k
+    assert whole['validation/main/bbox/map'] > 0
+    with pytest.raises(ValueError, match='box IoU'):
+        both.evaluate_collected(*plain)
+
+
+def test_default_arguments_report_what_they_always_did(data):
+    names = ['c%d' % i for i in range(4)]
+    plain = _records(data)
+    default = E.InstanceSegmentationCOCOEvaluator(None, None, label_names=names)
+    assert default.iou_types == ('segm',)
+    obs = default.evaluate_collected(*plain)
+    result = matching.coco_results(matching.coco_evaluate_from_counts(
+        plain[0], plain[1], plain[2], [g[1] for g in plain[3]], [g[3] for g in plain[3]],
+        [g[4] for g in plain[3]]))
+    want = {'validation/main/' + k: v for k, v in E.coco_report(result, names).items()}
+    assert sorted(obs) == sorted(want) and not any('bbox' in k for k in obs)
+    for k in want:
+        assert np.array_equal(np.asarray(obs[k]), np.asarray(want[k]), equal_nan=True), k
+    both = E.InstanceSegmentationCOCOEvaluator(None, None, label_names=names,
+                                               iou_types=('segm', 'bbox'))
+    obs2 = both.evaluate_collected(*_records(data, box='coco'))
+    for k in want:                                    # asking for boxes changes no segm value
+        assert np.array_equal(np.asarray(obs2[k]), np.asarray(want[k]), equal_nan=True), k
+    only = E.InstanceSegmentationCOCOEvaluator(None, None, label_names=names, iou_types=('bbox',))
+    obs3 = only.evaluate_collected(*_records(data, box='coco'))
+    assert sorted(obs3) == sorted(k for k in obs2 if '/bbox/' in k)
+    for k in obs3:
+        assert np.array_equal(np.asarray(obs3[k]), np.asarray(obs2[k]), equal_nan=True), k
+    voc = E.InstanceSegmentationVOCEvaluator(None, None, use_07_metric=True, label_names=names)
+    gts4 = [g[:3] for g in plain[3]]
+    assert sorted(voc.evaluate_collected(plain[0], plain[1], plain[2], gts4)) == sorted(
+        ['validation/main/map'] + ['validation/main/ap/' + n for n in names])
+    for bad in ((), ('boxes',), ('segm', 'keypoints')):
+        with pytest.raises(ValueError):
+            E.InstanceSegmentationVOCEvaluator(None, None, iou_types=bad)
+
+
+def test_results_entries_without_segmentations_are_the_detection_format():
+    from chainer_mask_rcnn_amd.utils.evaluations import coco_results as CR
+    from chainer_mask_rcnn_amd.utils.evaluations.boxes import to_xywh64
+    bbox = np.array([[1.5, 2.25, 10.125, 20.5], [0.1, 0.2, 0.3, 0.7]], np.float32)
+    seg = [{'size': [30, 40], 'counts': 'abc'}] * 2
+    full = CR.results_entries(7, bbox, [0, 1], _f32(0.5, 0.25), seg, {0: 11, 1: 13})
+    bare = CR.results_entries(7, bbox, [0, 1], _f32(0.5, 0.25), None, {0: 11, 1: 13})
+    assert [sorted(e) for e in bare] == [['bbox', 'category_id', 'image_id', 'score']] * 2
+    assert [dict(e, segmentation=seg[0]) for e in bare] == full
+    assert [list(r) for r in to_xywh64(bbox)] == [e['bbox'] for e in bare]    # the file's numbers
+    assert np.array_equal(to_xywh64(bbox), R.xywh64(bbox))
+
+
+# ---------------------------------------------------------------------------------------- tools
+def _tool(name):
+    import importlib
+    import os
+    import sys
+    tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tools')
+    if tools not in sys.path:
+        sys.path.insert(0, tools)
+    return importlib.import_module(name)
+
+
+def test_summarize_logs_shows_the_bbox_column_only_when_a_log_has_it(tmp_path, capsys):
+    import json
+    import yaml
+    summarize_logs = _tool('summarize_logs')
+    for name, bbox in (('run_a', 0.31), ('run_b', None)):
+        (tmp_path / name).mkdir()
+        with open(str(tmp_path / name / 'params.yaml'), 'w') as f:
+            yaml.safe_dump({'model': 'resnet50', 'lr': 0.01}, f)
+        entry = {'epoch': 1, 'iteration': 20, 'elapsed_time': 10.0, 'validation/main/map': 0.25}
+        if bbox is not None:
+            entry['validation/main/bbox/map'] = bbox
+        with open(str(tmp_path / name / 'log'), 'w') as f:
+            json.dump([entry], f)
+    rows, _ = summarize_logs.summarize_logs(str(tmp_path))
+    out = capsys.readouterr().out
+    assert 'validation/main/bbox/map' in out and '0.310' in out
+    assert [r[-1] for r in rows] == ['<none>< <none>', '0.310< 0.310']       # run_b, run_a
+    assert len(summarize_logs.KEYS) == len(rows[0]) - 1                      # the default is as it was
+    (tmp_path / 'run_a' / 'log').write_text(json.dumps(
+        [{'epoch': 1, 'iteration': 20, 'elapsed_time': 10.0, 'validation/main/map': 0.25}]))
+    rows, _ = summarize_logs.summarize_logs(str(tmp_path))
+    assert 'bbox' not in capsys.readouterr().out and len(rows[0]) == len(summarize_logs.KEYS)
+
+
+def test_tool_switches_default_to_what_the_tools_did():
+    import argparse
+    evaluate, train = _tool('evaluate'), _tool('train')
+    assert evaluate._iou_types('segm,bbox') == ('segm', 'bbox')
+    assert evaluate._iou_types(' bbox ') == ('bbox',)
+    for bad in ('', 'segm,segm', 'boxes', 'segm;bbox'):
+        with pytest.raises(argparse.ArgumentTypeError):
+            evaluate._iou_types(bad)
+    assert train.parse_args([]).eval_bbox is False
+    assert train.parse_args(['--eval-bbox']).eval_bbox is True

@@ -10,6 +10,7 @@ examples/evaluate_common.py + examples/coco/evaluate.py.
     python tools/evaluate.py --coco-root DIR --detectron model.pkl --save-results res.json
     python tools/evaluate.py --coco-root DIR --split test-dev --detectron model.pkl --save-results res.json
     python tools/evaluate.py --coco-root DIR --results res.json   # score a results file (no model)
+    python tools/evaluate.py --synthetic 16 --iou-types segm,bbox   # box AP beside mask AP
 
 Runs the evaluator (predicted masks stay on the device; extensions/), prints the report and
 the seconds per image spent in prediction and in evaluation, and writes the result as YAML (or
@@ -17,6 +18,9 @@ JSON when PyYAML is missing) next to the snapshot as ``<snapshot>.eval_result.ya
 ``--save-results`` also writes the predictions as a COCO results file (masks as compressed RLE,
 encoded on the device); on test-dev, which has no public annotations, it writes the file and
 does not score.  ``--results`` scores such a file against the annotations alone.
+``--iou-types segm,bbox`` adds the box AP block (``validation/main/bbox/...``: the predicted boxes
+against the dataset's boxes, IoU tables from the device); ``--iou-types bbox`` alone skips the mask
+work, and with ``--save-results`` then writes a bbox-only file, the detection track's format.
 """
 import argparse
 import json
@@ -55,6 +59,28 @@ class _TimedTarget(object):
         return out
 
 
+def _iou_types(text):
+    types = tuple(t.strip() for t in text.split(',') if t.strip())
+    if not types or any(t not in ('segm', 'bbox') for t in types) or len(set(types)) != len(types):
+        raise argparse.ArgumentTypeError("a comma-separated subset of 'segm,bbox', got %r" % text)
+    return types
+
+
+def _print_result(result):
+    """The report: one block as it always was; the segm block and the bbox block when box AP was
+    asked for."""
+    bbox = {k: v for k, v in result.items() if '/bbox/' in k}
+    if not bbox:
+        pprint.pprint(result)
+        return
+    segm = {k: v for k, v in result.items() if k not in bbox}
+    if segm:
+        print('segm:')
+        pprint.pprint(segm)
+    print('bbox:')
+    pprint.pprint(bbox)
+
+
 def main():
     ap = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     ap.add_argument('--dataset', default='coco', choices=['coco', 'voc', 'sbd'],
@@ -87,6 +113,9 @@ def main():
     ap.add_argument('--results', default=None, metavar='FILE',
                     help='score a COCO results file against --coco-root / --split (no model, '
                          'no images needed)')
+    ap.add_argument('--iou-types', type=_iou_types, default=('segm',), metavar='segm[,bbox]',
+                    help='what to score: mask AP (segm), box AP (bbox) or both; with --results, '
+                         'each type is scored from the file')
     args = ap.parse_args()
     if args.results:
         if args.coco_root is None:
@@ -161,6 +190,8 @@ def main():
     writer = _results_writer(args, data)
     if writer is not None:
         kw['results_sink'] = writer
+    if args.iou_types != ('segm',):
+        kw['iou_types'] = args.iou_types
     evaluator = cls(batches, target, label_names=class_names, **kw)
     t0 = time.perf_counter()
     if args.split == 'test-dev':
@@ -178,7 +209,7 @@ def main():
     result = {k: float(v) for k, v in result.items()}
     timing = {'images': n, 'predict_s_per_image': target.seconds / n,
               'eval_s_per_image': (total - target.seconds) / n}
-    pprint.pprint(result)
+    _print_result(result)
     print('timing:', json.dumps(timing))
 
     out = args.out or ((weights + '.eval_result.yaml') if weights else
@@ -238,11 +269,14 @@ def score_results(args):
         split, root_dir=args.coco_root, use_crowd=True, return_crowd=True, return_area=True)
     torch.cuda.set_device(0)
     t0 = time.perf_counter()
-    result = eval_coco_results(args.results, data, limit=args.limit or None,
-                               label_names=[str(n) for n in data.class_names])
+    result = {}
+    for iou_type in getattr(args, 'iou_types', ('segm',)):
+        result.update(eval_coco_results(args.results, data, limit=args.limit or None,
+                                        label_names=[str(n) for n in data.class_names],
+                                        iou_type=iou_type))
     seconds = time.perf_counter() - t0
     result = {k: float(v) for k, v in result.items()}
-    pprint.pprint(result)
+    _print_result(result)
     n = len(data) if not args.limit else min(args.limit, len(data))
     timing = {'images': n, 'eval_s_per_image': seconds / max(n, 1)}
     print('timing:', json.dumps(timing))
@@ -312,12 +346,15 @@ def evaluate_log_dir(args):
     writer = _results_writer(args, test_data)
     if writer is not None and evaluator_type != 'coco':
         raise SystemExit('--save-results needs the coco evaluator')
+    kw = {}
+    if getattr(args, 'iou_types', ('segm',)) != ('segm',):
+        kw['iou_types'] = args.iou_types
     if evaluator_type == 'voc':
         evaluator = cmr.extensions.InstanceSegmentationVOCEvaluator(
-            batches, model, use_07_metric=True, label_names=class_names)
+            batches, model, use_07_metric=True, label_names=class_names, **kw)
     else:
         evaluator = cmr.extensions.InstanceSegmentationCOCOEvaluator(
-            batches, model, label_names=class_names, results_sink=writer)
+            batches, model, label_names=class_names, results_sink=writer, **kw)
     result = {k: float(v) for k, v in evaluator.evaluate().items()}
     yaml_file = pretrained_model + '.eval_result.yaml'
     with open(yaml_file, 'w') as f:
@@ -329,7 +366,7 @@ def evaluate_log_dir(args):
             yaml.safe_dump({'results_file': os.path.abspath(writer.path)}, f,
                            default_flow_style=False)
     print('Saved evaluation:', yaml_file)
-    pprint.pprint(result)
+    _print_result(result)
     return result
 
 

@@ -6,7 +6,8 @@
 One row per run directory (params.yaml + log of tools/train.py), newest first: the row of the log
 entry with the best ``validation/main/map``, the run's settings and, when tools/evaluate.py
 --log-dir has been run on it, the map of snapshot_model.npz.eval_result.yaml.  Directories
-without params.yaml are listed as ignored.
+without params.yaml are listed as ignored.  A ``validation/main/bbox/map`` column (box AP, tools/
+train.py --eval-bbox) is shown when some run's log has it.
 """
 import argparse
 import datetime
@@ -16,6 +17,17 @@ import os.path as osp
 
 KEYS = ['name', 'elapsed_time', 'last_time', 'git_hash', 'hostname', 'model', 'initializer', 'lr',
         'epoch', 'iteration', 'eval_result', 'validation/main/map']
+
+
+BBOX_KEY = 'validation/main/bbox/map'
+
+
+def log_has_key(logs_dir, name, key):
+    try:
+        with open(osp.join(logs_dir, name, 'log')) as f:
+            return any(key in entry for entry in json.load(f))
+    except Exception:
+        return False
 
 
 def seconds_to_string(seconds):
@@ -70,7 +82,7 @@ def summarize_log(logs_dir, name, keys, target_key, objective, now=None):
                        '%.3f< %s <%.3f' % (df[key].min(), value, df[key].max()))
         elif key.endswith('/map'):
             min_value = max_value = '<none>'
-            value = '<none>' if dfi is None else '%.3f' % dfi[key]
+            value = '<none>' if dfi is None or key not in dfi else '%.3f' % dfi[key]
             if objective == 'max':
                 if df is not None and key in df:
                     min_value = '%.3f' % df[key].min()
@@ -105,6 +117,9 @@ def summarize_logs(logs_dir, keys=KEYS, target_key='validation/main/map', object
     import tabulate
     assert objective in ('min', 'max')
     assert target_key in keys
+    if BBOX_KEY not in keys and any(log_has_key(logs_dir, name, BBOX_KEY)
+                                    for name in sorted(os.listdir(logs_dir))):
+        keys = list(keys) + [BBOX_KEY]
     rows, ignored = [], []
     for name in sorted(os.listdir(logs_dir)):
         row, _, ignored_dir = summarize_log(logs_dir, name, keys, target_key, objective)

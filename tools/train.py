@@ -77,6 +77,9 @@ def parse_args(argv=None):
     ap.add_argument('--device-masks', action='store_true',
                     help='ground-truth masks cross PCIe as bits and are resized / flipped by a HIP '
                          'kernel (COCO: the dataset also keeps them packed on the host)')
+    ap.add_argument('--eval-bbox', action='store_true',
+                    help='the evaluator also scores the boxes: validation/main/bbox/map joins the '
+                         'log and the printed report (the best snapshot stays on the mask map)')
     ap.add_argument('--logs-dir', default=osp.join(ROOT, 'logs'))
     ap.add_argument('--no-plot', action='store_true', help='do not write loss.png / accuracy.png')
     return ap.parse_args(argv)
@@ -272,24 +275,28 @@ def assemble(args, comm, model, train_data, test_data, evaluator_type, synthetic
     loop = train_loop.TrainLoop(train_loop.SerialIterator(train, args.batch_size_per_gpu),
                                 chain, opt, comm.device)
     test_iter = train_loop.SerialIterator(test, args.batch_size_per_gpu, shuffle=False)
+    eval_bbox = bool(getattr(args, 'eval_bbox', False))
+    kw = {'iou_types': ('segm', 'bbox')} if eval_bbox else {}
     if evaluator_type == 'voc':
         evaluator = cmr.extensions.InstanceSegmentationVOCEvaluator(
-            test_iter, model, use_07_metric=True, label_names=args.class_names)
+            test_iter, model, use_07_metric=True, label_names=args.class_names, **kw)
     else:
         evaluator = cmr.extensions.InstanceSegmentationCOCOEvaluator(
-            test_iter, model, label_names=args.class_names)
+            test_iter, model, label_names=args.class_names, **kw)
     if comm.parallel:
         evaluator = cmr.extensions.create_multi_node_evaluator(evaluator)
 
     args.git_hash = cmr.utils.git_hash(__file__)
     args.hostname = socket.gethostname()
-    params = {k: v for k, v in vars(args).items()}
+    # the switch is recorded only when set: a default run's params.yaml stays as it was
+    params = {k: v for k, v in vars(args).items() if k != 'eval_bbox' or v}
     tr = T.Trainer(loop, (args.max_epoch, 'epoch'), out=args.out if comm.rank == 0 else None)
     T.extend_reference_set(tr, model, evaluator=evaluator, vis_iterator=test_iter,
                            class_names=args.class_names, step_size=args.step_size,
                            params=params, plot=not args.no_plot,
                            print_out=print_out if comm.rank == 0 else None, rank=comm.rank,
-                           gather=comm.gather if comm.parallel else None, **intervals)
+                           gather=comm.gather if comm.parallel else None, eval_bbox=eval_bbox,
+                           **intervals)
     return Run(tr, loop, chain, opt, evaluator, train_data, test_data)
 
 

@@ -678,9 +678,11 @@ def extend_reference_set(trainer, model, evaluator=None, vis_iterator=None, clas
                          step_size=None, params=None, eval_interval=(1, 'epoch'),
                          log_interval=(20, 'iteration'), plot_interval=(0.1, 'epoch'),
                          print_interval=(20, 'iteration'), plot=True, print_out=sys.stdout,
-                         rank=0, gather=None):
+                         rank=0, gather=None, eval_bbox=False):
     """The extensions of examples/train_common.py:251-372 (without dump_graph / ProgressBar)
     with the same triggers and priorities; ``model``: the MaskRCNN (``chain.mask_rcnn``).
+    ``eval_bbox``: the evaluator also reports ``validation/main/bbox/map``, which then joins the
+    printed report (the best snapshot and accuracy.png stay on ``validation/main/map``).
 
     Data parallel (``gather``: the control-plane all-gather, see DictSummary.compute_mean): the lr
     shift, the evaluator (a multi-node one), observe_lr and the summaries of LogReport and the
@@ -712,7 +714,9 @@ def extend_reference_set(trainer, model, evaluator=None, vis_iterator=None, clas
                              gather=gather))
     if print_out is not None:
         extend_lead(PrintReport(['iteration', 'epoch', 'elapsed_time', 'lr'] + LOG_KEYS[:1]
-                                + LOG_KEYS[1:] + ['validation/main/map'], out=print_out),
+                                + LOG_KEYS[1:] + ['validation/main/map']
+                                + (['validation/main/bbox/map'] if eval_bbox else []),
+                                out=print_out),
                     trigger=print_interval)
     if plot:
         trainer.extend(PlotReport(LOG_KEYS, file_name='loss.png', trigger=plot_interval,
