@@ -817,14 +817,16 @@ def _d(arg):
 # name -> the test that compares it bit-exactly or in float64 at realistic sizes (or: a query)
 ALLOWED = {
     'mrcnn_nms_sorted': 'tests/test_gpu_proposal.py (vs the C oracle, exact keep lists)',
-    'mrcnn_nms_sorted_batched': 'tests/test_gpu_inference.py::test_c5_full_size_predict',
+    'mrcnn_nms_sorted_batched': 'tests/test_gpu_proposal.py::test_nms_batched_structure_and_device_counts, '
+                                '::test_nms_workspace_reuse (vs the C oracle, exact keep lists)',
     'mrcnn_topk_desc': 'tests/test_gpu_proposal.py',
     'mrcnn_topk_desc_batched': 'tests/test_gpu_proposal.py',
-    'mrcnn_decode_clip': 'tests/test_gpu_proposal.py',
+    'mrcnn_decode_clip': 'tests/test_gpu_proposal.py::test_decode_clip_min_size_validity, '
+                         '::test_proposal_creator_default_min_size (boxes and valid bytes, bit for bit)',
     'mrcnn_gather_rows': 'tests/test_gpu_proposal.py',
-    'mrcnn_detect_sort': 'tests/test_gpu_inference.py::test_c5_full_size_predict',
-    'mrcnn_detect_compact': 'tests/test_gpu_inference.py::test_c5_full_size_predict',
-    'mrcnn_decode_cls_boxes': 'tests/test_gpu_inference.py',
+    'mrcnn_detect_sort': 'tests/test_gpu_inference.py::test_suppress_edges_match_oracle',
+    'mrcnn_detect_compact': 'tests/test_gpu_inference.py::test_suppress_edges_match_oracle',
+    'mrcnn_decode_cls_boxes': 'tests/test_gpu_inference.py::test_decode_cls_boxes_mean_std_and_stride',
     'mrcnn_observe_accumulate': 'tests/test_gpu_trainer.py (loss observation)',
     'mrcnn_prepare_image': 'tests/test_gpu_inference.py (image preparation)',
     'mrcnn_paste_masks': 'tests/test_gpu_inference.py (mask pasting)',

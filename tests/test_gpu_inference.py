@@ -239,3 +239,96 @@ def test_c5_full_size_predict(dev):
         total += len(b)
     assert total > 0, 'synthetic weights produced no detections: the NMS / mask stages did not run'
     print('C5: proposals/img', counts.tolist(), 'detections/img', [len(b) for b in bboxes])
+
+
+# ---- detection edges: ties, the threshold itself, block edges of R, empty classes -------------
+# Inputs: tests/proposal_cases.py; tests/test_oracle_boxes.py checks on the oracle alone that
+# they hold the cases named here.
+import proposal_cases as PC      # noqa: E402
+
+
+def _bare_model(n_class):
+    model = cmr.models.MaskRCNN(None, None, None, mean=None)
+    model.head = type('H', (), {'n_class': n_class, 'mask_size': 14})()
+    return model
+
+
+@pytest.mark.parametrize('R,n_class,variant', PC.detect_ids())
+def test_suppress_edges_match_oracle(dev, R, n_class, variant):
+    """mrcnn_detect_sort / batched NMS / mrcnn_detect_compact through MaskRCNN._suppress on
+    probabilities in multiples of 1 / 64 (ties inside every class decide the NMS order), entries
+    at the score threshold and its fp32 neighbours, R at the 256-thread block edges and 0, one and
+    80 foreground classes, a first or last class that is empty or collapses to one box: bbox,
+    label and score equal the oracle's, same length, same order."""
+    c = PC.detect_case(R, n_class, variant)
+    model = _bare_model(n_class)
+    cls_bbox, prob = torch.tensor(c['cls_bbox'], device=dev), torch.tensor(c['prob'], device=dev)
+    for score_thresh, nms_thresh in ((None, None), (0.0, 0.3)):
+        if score_thresh is None:
+            ref = np_infer.suppress(c['cls_bbox'], c['prob'], n_class)
+        else:
+            model.score_thresh, model.nms_thresh = score_thresh, nms_thresh
+            ref = np_infer.suppress(c['cls_bbox'], c['prob'], n_class, nms_thresh, score_thresh)
+        got = model._suppress(cls_bbox, prob)
+        for g, r, dtype in zip(got, ref, (np.float32, np.int32, np.float32)):
+            assert g.dtype == dtype and g.shape == r.shape, (score_thresh, g.shape, r.shape)
+        assert np.array_equal(got[1], ref[1]), score_thresh
+        assert np.array_equal(got[2], ref[2]), score_thresh
+        assert np.array_equal(got[0], ref[0]), score_thresh
+
+
+@pytest.mark.parametrize('scale', [1.6, 1333 / 500])
+@pytest.mark.parametrize('R', [1, 257])
+def test_decode_cls_boxes_mean_std_and_stride(dev, R, scale):
+    """mrcnn_decode_cls_boxes with a non-zero loc_normalize_mean (loc * std + mean formed in
+    double and rounded once: an fp32 product and sum differ in the last bit), loc rows inside a
+    wider buffer (ld_loc = 4 n_class + 12), a scale that is no short binary fraction and rows
+    whose dh / dw blow the box up to the clip: bit-equal to the oracle."""
+    import ctypes
+    rng = np.random.RandomState(100 + R)
+    n_class, size = 21, (500, 750)
+    roi, loc, _ = _make(rng, R, n_class, size[0] * scale, size[1] * scale)
+    loc[::5, 2::4] = rng.uniform(20, 60, loc[::5, 2::4].shape)       # large dh
+    loc[::7, 3::4] = rng.uniform(-60, -20, loc[::7, 3::4].shape)     # collapsing dw
+    mean_t, std_t = (0.013, -0.027, 0.11, -0.07), (0.1, 0.15, 0.2, 0.25)
+    ld = 4 * n_class + 12
+    buf = rng.standard_normal((R, ld)).astype(np.float32)
+    buf[:, :4 * n_class] = loc
+    out = torch.empty((R, n_class, 4), device=dev)
+    roi_d, buf_d = torch.tensor(roi, device=dev), torch.tensor(buf, device=dev)
+    mean, std = (ctypes.c_double * 4)(*mean_t), (ctypes.c_double * 4)(*std_t)
+    _lib.call('mrcnn_decode_cls_boxes', _lib.ptr(roi_d), _lib.ptr(buf_d), ld, _lib.ptr(out), R,
+              n_class, float(scale), mean, std, float(size[0]), float(size[1]), _lib.stream_ptr())
+    ref = np_infer.decode_cls_boxes(roi, loc, n_class, scale, size, mean=mean_t, std=std_t)
+    ref = ref.reshape(R, n_class, 4)
+    assert np.isfinite(ref).all()
+    assert np.array_equal(out.cpu().numpy().view(np.uint32), ref.view(np.uint32))
+
+
+def test_to_bboxes_with_an_image_without_rois(dev):
+    """A batch of three whose middle image has no RoI: empty results of the right types for it,
+    the oracle's detections for its neighbours."""
+    rng = np.random.RandomState(21)
+    n_class, (H, W), scales = 21, (300, 400), [1.6, 1.0, 2.0]
+    counts = [130, 0, 70]
+    parts = [_make(rng, n, n_class, H * s, W * s) for n, s in zip(counts, scales)]
+    roi, loc, logits = (np.concatenate([p[k] for p in parts]) for k in range(3))
+    roi_indices = np.repeat(np.asarray([0, 1, 2], np.int32), counts)
+    assert set(roi_indices) == {0, 2}
+    model = _bare_model(n_class)
+    t = lambda a: torch.tensor(a, device=dev)
+    bboxes, labels, scores = model._to_bboxes(t(loc), t(logits), t(roi), t(roi_indices),
+                                              [(H, W)] * 3, scales)
+    assert len(bboxes) == len(labels) == len(scores) == 3
+    assert bboxes[1].shape == (0, 4) and bboxes[1].dtype == np.float32
+    assert labels[1].shape == (0,) and labels[1].dtype == np.int32
+    assert scores[1].shape == (0,) and scores[1].dtype == np.float32
+    prob = cmr.functions.softmax(t(logits)).cpu().numpy()
+    for i in (0, 2):
+        sel = roi_indices == i
+        cls_bbox = np_infer.decode_cls_boxes(roi[sel], loc[sel], n_class, scales[i], (H, W))
+        b, l, s = np_infer.finish(*np_infer.suppress(cls_bbox, prob[sel], n_class))
+        assert len(b) > 0 and len(bboxes[i]) == len(b)
+        assert np.array_equal(labels[i], l)
+        assert np.array_equal(scores[i], s)
+        assert np.array_equal(bboxes[i], b)

@@ -211,3 +211,141 @@ def test_topk_batched_equals_per_row(dev):
         ref = idx[np_ref.stable_argsort_desc(score[g][idx])][:k]
         assert n_out[g] == len(ref)
         assert np.array_equal(order[g, :len(ref)], ref.astype(np.int32))
+
+
+# ---- the proposal layer as shipped (min_size = 16), batched NMS structure, workspace reuse ----
+# Inputs: tests/proposal_cases.py; tests/test_oracle_boxes.py checks on the oracle alone that
+# they hold the cases named here.
+import proposal_cases as PC      # noqa: E402
+from chainer_mask_rcnn_amd.models.utils import ProposalCreator      # noqa: E402
+
+
+def test_decode_clip_min_size_validity(dev):
+    """decode_clip with min_size = 16 * scale: boxes bit for bit and the valid byte equal to
+    np_ref.ProposalCreator's arithmetic (loc2bbox, clip, f32(16 * scale), >=), on random rows and
+    on rows whose side is min_size exactly, one ulp less, one ulp more, reaches it only before the
+    clip, or comes from an exp that overflows or underflows."""
+    d = PC.decode_cases()
+    a, l = torch.tensor(d['anchor'], device=dev), torch.tensor(d['loc'], device=dev)
+    for scale in d['scales']:
+        roi, valid = P.decode_clip(a, l, d['img_size'], 16 * scale)
+        ref_roi, ref_valid = PC.decode_reference(d['anchor'], d['loc'], d['img_size'], scale)
+        valid = valid.cpu().numpy()
+        assert valid.dtype == np.uint8 and np.array_equal(valid, ref_valid.astype(np.uint8)), \
+            (scale, d['tags'][valid != ref_valid])
+        assert np.array_equal(roi.cpu().numpy().view(np.uint32), ref_roi.view(np.uint32)), scale
+
+
+@pytest.fixture(scope='module')
+def creator_refs():
+    """np_ref.ProposalCreator over creator_cases(): {(name, train): (roi, indices)}."""
+    pc = np_ref.ProposalCreator(**PC.CREATOR_PARAMS)
+    return {(c['name'], train): pc(c['loc'], c['score'], PC.anchors(), PC.IMG, c['scale'],
+                                   train=train, return_indices=True)
+            for c in PC.creator_cases() for train in (True, False)}
+
+
+@pytest.mark.parametrize('train', [True, False])
+def test_proposal_creator_default_min_size(dev, creator_refs, train):
+    """The creator as the models build it (min_size left at 16) against the oracle: same RoIs,
+    same anchor indices, also with fewer valid boxes than n_pre_nms and with none."""
+    pc = ProposalCreator(**PC.CREATOR_PARAMS)
+    assert pc.min_size == 16
+    pc.train = train
+    anchor = torch.tensor(PC.anchors(), device=dev)
+    for c in PC.creator_cases():
+        roi, idx = pc(torch.tensor(c['loc'], device=dev), torch.tensor(c['score'], device=dev),
+                      anchor, PC.IMG, c['scale'], return_indices=True)
+        ref_roi, ref_idx = creator_refs[c['name'], train]
+        roi, idx = roi.cpu().numpy(), idx.cpu().numpy()
+        assert roi.shape == ref_roi.shape and roi.dtype == np.float32, (c['name'], roi.shape)
+        if c['name'] == 'all_invalid':
+            assert roi.shape == (0, 4)
+        assert idx.dtype == np.int32 and np.array_equal(idx, ref_idx), c['name']
+        assert np.array_equal(roi, ref_roi), c['name']
+
+
+@pytest.mark.parametrize('train', [True, False])
+def test_proposal_creator_batch_equals_oracle_per_image(dev, creator_refs, train):
+    """batch(), the path the RPN takes: every image with its own scale (its own min_size), one
+    of them ending with no proposal; with and without the host copy."""
+    cases = PC.creator_cases()
+    anchor = torch.tensor(PC.anchors(), device=dev)
+    locs = [torch.tensor(c['loc'], device=dev) for c in cases]
+    scores = [torch.tensor(c['score'], device=dev) for c in cases]
+    scales = [c['scale'] for c in cases]
+    refs = [creator_refs[c['name'], train][0] for c in cases]
+    _check_gather_rows_zeroes_the_rows_after_the_count(dev)
+    for keep_host_copy in (False, True):
+        pc = ProposalCreator(**PC.CREATOR_PARAMS)
+        pc.train = train
+        pc.keep_host_copy = keep_host_copy
+        rois = pc.batch(locs, scores, anchor, PC.IMG, scales)
+        assert len(rois) == len(cases)
+        assert pc.last_counts == [len(r) for r in refs]
+        for i, (roi, ref) in enumerate(zip(rois, refs)):
+            got = roi.cpu().numpy()
+            assert got.shape == ref.shape and np.array_equal(got, ref), cases[i]['name']
+        if keep_host_copy:
+            assert len(pc.last_host_rois) == len(cases)
+            for roi, host in zip(rois, pc.last_host_rois):
+                assert host.dtype == np.float32 and host.shape == tuple(roi.shape)
+                assert np.array_equal(host, roi.cpu().numpy())
+        else:
+            assert pc.last_host_rois is None
+
+
+def _check_gather_rows_zeroes_the_rows_after_the_count(dev):
+    """batch() hands gather_rows' output to the NMS as sorted_rois: rows from n_dev on are zero
+    whatever idx holds there (here: valid indices of non-zero rows)."""
+    rng = np.random.RandomState(15)
+    src = rng.uniform(1, 2, (500, 4)).astype(np.float32)
+    idx = rng.randint(0, 500, 300).astype(np.int32)
+    for n in (0, 1, 255, 256, 299, 300):
+        out = P.gather_rows(torch.tensor(src, device=dev), torch.tensor(idx, device=dev),
+                            torch.tensor([n], dtype=torch.int32, device=dev)).cpu().numpy()
+        assert np.array_equal(out[:n], src[idx[:n]]) and not out[n:].any(), n
+
+
+def _check_batched(bbox, counts, keep, n_keep, thresh, limit):
+    keep, n_keep = keep.cpu().numpy(), n_keep.cpu().numpy()
+    assert keep.dtype == np.int32 and n_keep.dtype == np.int32
+    for g, n in enumerate(counts):
+        ref = oracle.nms_sorted(bbox[g, :n], thresh, limit or -1)
+        assert n_keep[g] == len(ref), (g, n, thresh, limit, n_keep[g], len(ref))
+        assert np.array_equal(keep[g, :n_keep[g]], ref), (g, n, thresh, limit)
+
+
+@pytest.mark.parametrize('case', PC.nms_batched_cases(), ids=lambda c: 'n_max%d' % c['n_max'])
+def test_nms_batched_structure_and_device_counts(dev, case):
+    """The batched call where its structure is not trivial: 17 chunks (256 threads) and 33 (1024
+    threads), twelve groups whose counts sit at the chunk and super-step edges below n_max (mask
+    rows strided by the batch's chunk count, loops bounded by the group's own), long dependency
+    chains, limits reached and not reached, and poison at and after every count."""
+    bbox, counts = case['bbox'], case['counts']
+    b, c = torch.tensor(bbox, device=dev), torch.tensor(counts, device=dev)
+    for thresh in PC.NMS_THRESHOLDS:
+        for limit in PC.NMS_LIMITS:
+            keep, n_keep = P.nms_sorted_batched(b, c, thresh, limit=limit)
+            _check_batched(bbox, counts, keep, n_keep, thresh, limit)
+            keep, n_keep = keep.cpu().numpy(), n_keep.cpu().numpy()
+            for g in range(len(counts)):
+                k1, n1 = P.nms_sorted(b[g], thresh, n_dev=c[g:g + 1], limit=limit)
+                n1 = int(n1.item())
+                assert n1 == n_keep[g] and np.array_equal(k1[:n1].cpu().numpy(), keep[g, :n1]), \
+                    (g, thresh, limit)
+
+
+def test_nms_workspace_reuse(dev):
+    """One cached workspace, three shapes in a row: dense overlap at n_max = 2112, sparse boxes at
+    n_max = 1088 (other row stride, other offset of the column words), dense again.  A mask word or
+    a column word left by the call before must not reach a result."""
+    rng = np.random.RandomState(16)
+    dense = np.stack([PC.dense_boxes(rng, 2112) for _ in range(3)])
+    dense_n = np.asarray([2112, 1500, 2000], np.int32)
+    sparse = np.stack([PC.rand_boxes(rng, 1088, size=4000.) for _ in range(3)])
+    sparse_n = np.asarray([1088, 700, 64], np.int32)
+    for bbox, counts in ((dense, dense_n), (sparse, sparse_n), (dense, dense_n)):
+        keep, n_keep = P.nms_sorted_batched(torch.tensor(bbox, device=dev),
+                                            torch.tensor(counts, device=dev), 0.7)
+        _check_batched(bbox, counts, keep, n_keep, 0.7, 0)

@@ -164,6 +164,112 @@ def test_inference_postprocessing_pinned_to_reference_methods(golden_dir):
         lo += n
 
 
+def test_proposal_cases_meet_their_conditions():
+    """The oracle alone on the builders of tests/proposal_cases.py: the inputs of the GPU tests
+    hold the cases they were built for.  Conditions, not measurements."""
+    import proposal_cases as PC
+    from oracle import np_infer
+    # decode: a real share of the random rows on either side of min_size.  The lower bound is 5 %:
+    # loc ~ 0.3 N(0, 1) on the shipped anchors leaves about 6 % below 16 px at scale 1.0 and the
+    # same loc serves every scale.
+    d = PC.decode_cases()
+    tags, n_random = d['tags'], d['n_random']
+    for scale in d['scales']:
+        roi, valid = PC.decode_reference(d['anchor'], d['loc'], d['img_size'], scale)
+        assert np.isfinite(roi).all()
+        invalid = 1. - valid[:n_random].mean()
+        assert 0.05 <= invalid <= 0.90, (scale, invalid)
+        m = np.float32(PC.MIN_SIZE * scale)
+        below = np.nextafter(m, np.float32(0))
+        hs, ws = roi[:, 2] - roi[:, 0], roi[:, 3] - roi[:, 1]
+        assert scale != 1.5 or m == 24                  # the side of the integer anchors
+        # both outcomes in both axes, at every scale
+        assert (valid & (hs == m) & (tags == 'exact')).any() and (valid & (ws == m) & (tags == 'exact')).any()
+        assert (~valid & (hs == below) & (ws >= m) & (tags == 'in_h')).any()
+        assert (~valid & (ws == below) & (hs >= m) & (tags == 'in_w')).any()
+        assert (valid & (hs > m) & (tags == 'out_h')).any() and (valid & (ws > m) & (tags == 'out_w')).any()
+    roi, valid = PC.decode_reference(d['anchor'], d['loc'], d['img_size'], 1.5)
+    hs, ws = roi[:, 2] - roi[:, 0], roi[:, 3] - roi[:, 1]
+    clipped = tags == 'clipped'
+    assert clipped.sum() == 4 and not valid[clipped].any()
+    assert (np.minimum(hs, ws)[clipped] == 16).all() and (np.maximum(hs, ws)[clipped] == 24).all()
+    e = roi[tags == 'exp']
+    whole = (e[:, 2] - e[:, 0] == 256) | (e[:, 3] - e[:, 1] == 320)
+    flat = (e[:, 2] == e[:, 0]) | (e[:, 3] == e[:, 1])
+    assert (whole | flat).all() and whole.any() and flat.any() and (whole & flat).any()
+
+    # creator
+    pc = np_ref.ProposalCreator(**PC.CREATOR_PARAMS)
+    assert pc.min_size == 16
+    for c in PC.creator_cases():
+        _, valid = PC.decode_reference(PC.anchors(), c['loc'], PC.IMG, c['scale'])
+        for train, n_pre, n_post in ((True, 2112, 300), (False, 1088, 100)):
+            roi = pc(c['loc'], c['score'], PC.anchors(), PC.IMG, c['scale'], train=train)
+            if c['name'] == 'all_invalid':
+                assert roi.shape == (0, 4) and valid.sum() == 0
+            elif c['name'] == 'few_valid':
+                assert 0 < valid.sum() < n_pre and 0 < len(roi)
+            else:
+                assert valid.sum() > n_pre and len(roi) == n_post, (c['name'], train, len(roi))
+
+    # batched NMS
+    for case in PC.nms_batched_cases():
+        n_max, bbox, counts = case['n_max'], case['bbox'], case['counts']
+        assert list(counts) == [0, 1, 63, 64, 65, 511, 512, 513, 1024, 1025, n_max - 1, n_max]
+        for g, n in enumerate(counts):
+            poison = bbox[g, n:]
+            assert np.isnan(poison).all() if g % 2 else len(oracle.nms_sorted(poison, 0.5)) == len(poison)
+        for thresh in PC.NMS_THRESHOLDS:
+            full = [oracle.nms_sorted(bbox[g, :n], thresh) for g, n in enumerate(counts)]
+            for limit in PC.NMS_LIMITS:
+                if limit > 1:
+                    assert any(len(k) > limit for k in full) and any(0 < len(k) < limit for k in full)
+            for g, n in enumerate(counts):
+                if case['kinds'][g] == 'stair' and n >= 513:
+                    kept = np.zeros(n, bool)
+                    kept[full[g]] = True
+                    for side in (kept[448:512], kept[512:576]):     # the chunks at the boundary
+                        assert side.any() and not side.all(), (n_max, g, thresh)
+
+    # detection
+    for c in PC.detect_cases():
+        prob, cls_bbox, n_class = c['prob'], c['cls_bbox'], c['n_class']
+        R = len(prob)
+        assert prob.shape == (R, n_class) and cls_bbox.shape == (R, n_class, 4)
+        if R == 0:
+            continue
+        for name, inside in (('at', False), ('below', False), ('above', True)):
+            v = {'at': PC.SCORE_THRESH, 'below': np.nextafter(PC.SCORE_THRESH, np.float32(0)),
+                 'above': np.nextafter(PC.SCORE_THRESH, np.float32(1))}[name]
+            for r, l in c[name]:
+                assert prob[r, l] == v and bool(prob[r, l] > 0.05) == inside
+        assert n_class == 2 or (c['at'] and c['above'] and c['below'])
+        # the empty class by construction holds nothing above the threshold: where it is the only
+        # class, the conditions are met by the second run of the GPU test (thresholds 0.0 / 0.3)
+        only_empty = n_class == 2 and c['empty'] is not None
+        b, l, s = np_infer.suppress(cls_bbox.reshape(R, -1), prob, n_class)
+        assert len(b) > 0 or only_empty
+        if c['full'] is not None:
+            assert (prob[:, c['full']] > 0.05).all() and (l == c['full'] - 1).sum() == 1
+        if c['empty'] is not None:
+            assert not (prob[:, c['empty']] > 0.05).any() and (prob[:, c['empty']] == PC.SCORE_THRESH).any()
+        for r, cl in c['at'] + c['below']:
+            assert not ((l == cl - 1) & (s == prob[r, cl])).any()
+        if R >= 255:
+            score_thresh = 0.05
+            if only_empty:
+                score_thresh = 0.0
+                b, l, s = np_infer.suppress(cls_bbox.reshape(R, -1), prob, n_class, 0.3, score_thresh)
+            tied, removed = 0., 0.
+            for cl in range(1, n_class):
+                p = prob[:, cl][prob[:, cl] > score_thresh]
+                if len(p):
+                    _, inv, cnt = np.unique(p, return_inverse=True, return_counts=True)
+                    tied = max(tied, (cnt[inv] > 1).mean())
+                    removed = max(removed, 1. - (l == cl - 1).sum() / len(p))
+            assert tied >= 0.2 and removed >= 0.2, (R, n_class, tied, removed)
+
+
 def _segm_fixture(golden_dir):
     import os
     d = np.load(os.path.join(golden_dir, 'segm_results.npz'))
