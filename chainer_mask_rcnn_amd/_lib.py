@@ -113,6 +113,10 @@ SIGNATURES = {
                                       c_vp]),
     'mrcnn_sgd_momentum_wd_ex': (c_int, [c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32,
                                          c_int, c_vp]),
+    'mrcnn_grad_sumsq': (c_int, [c_vp, c_i64, c_vp, c_vp]),
+    'mrcnn_grad_control': (c_int, [c_vp, c_int, c_f32, c_f32, c_int, c_vp, c_vp]),
+    'mrcnn_sgd_momentum_wd_ctl': (c_int, [c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_vp,
+                                          c_int, c_vp]),
     'mrcnn_bbox_iou_argmax': (c_int, [c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'mrcnn_anchor_labels': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_f32, c_f32, c_vp, c_vp]),
     'mrcnn_anchor_targets_finish': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int,

@@ -203,33 +203,134 @@ __global__ void avgpool_bwd_kernel(const float *__restrict__ gy, float *__restri
 }
 
 // ---- MomentumSGD + WeightDecay -----------------------------------
-template <bool ZERO_GRAD>
+// v' = momentum v - lr (g grad_scale + wd p): the one statement of the update, for both kernels
+__device__ __forceinline__ float sgd_velocity(float p, float g, float v, float lr, float momentum,
+                                              float wd, float grad_scale)
+{
+    return momentum * v - lr * (g * grad_scale + wd * p);
+}
+
+// CTL: grad_scale is ctl[MRCNN_CTL_FACTOR] (written by grad_control_kernel earlier on the stream),
+// and with ctl[MRCNN_CTL_SKIPPED] != 0 p and v stay as they are (g is still cleared).
+template <bool ZERO_GRAD, bool CTL>
 __global__ void sgd_kernel(float *__restrict__ p, float *__restrict__ g,
                            float *__restrict__ v, int64_t n, float lr, float momentum, float wd,
-                           float grad_scale)
+                           float grad_scale, const float *__restrict__ ctl)
 {
     const int64_t nv = n / 4;
+    const int64_t tail = nv * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (CTL) {
+        grad_scale = ctl[MRCNN_CTL_FACTOR];
+        if (ctl[MRCNN_CTL_SKIPPED] != 0.f) {
+            if (ZERO_GRAD) {
+                for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv;
+                     i += (int64_t)gridDim.x * blockDim.x)
+                    reinterpret_cast<float4 *>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (tail < n) g[tail] = 0.f;
+            }
+            return;
+        }
+    }
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv;
          i += (int64_t)gridDim.x * blockDim.x) {
         float4 pp = reinterpret_cast<float4 *>(p)[i];
         const float4 gg = reinterpret_cast<const float4 *>(g)[i];
         float4 vv = reinterpret_cast<float4 *>(v)[i];
-        vv.x = momentum * vv.x - lr * (gg.x * grad_scale + wd * pp.x);
-        vv.y = momentum * vv.y - lr * (gg.y * grad_scale + wd * pp.y);
-        vv.z = momentum * vv.z - lr * (gg.z * grad_scale + wd * pp.z);
-        vv.w = momentum * vv.w - lr * (gg.w * grad_scale + wd * pp.w);
+        vv.x = sgd_velocity(pp.x, gg.x, vv.x, lr, momentum, wd, grad_scale);
+        vv.y = sgd_velocity(pp.y, gg.y, vv.y, lr, momentum, wd, grad_scale);
+        vv.z = sgd_velocity(pp.z, gg.z, vv.z, lr, momentum, wd, grad_scale);
+        vv.w = sgd_velocity(pp.w, gg.w, vv.w, lr, momentum, wd, grad_scale);
         pp.x += vv.x; pp.y += vv.y; pp.z += vv.z; pp.w += vv.w;
         reinterpret_cast<float4 *>(v)[i] = vv;
         reinterpret_cast<float4 *>(p)[i] = pp;
         if (ZERO_GRAD) reinterpret_cast<float4 *>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    const int64_t i = nv * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t i = tail;
     if (i < n) {
-        const float vv = momentum * v[i] - lr * (g[i] * grad_scale + wd * p[i]);
+        const float vv = sgd_velocity(p[i], g[i], v[i], lr, momentum, wd, grad_scale);
         v[i] = vv;
         p[i] += vv;
         if (ZERO_GRAD) g[i] = 0.f;
     }
+}
+
+// ---- Global gradient norm + step control word (clipping, non-finite guard) ---------
+// partials[b] = sum of (double)g[i]^2 over chunk b of the slice: MRCNN_SUMSQ_PARTIALS equal runs
+// of whole float4 (the n % 4 tail belongs to the last chunk).  One workgroup per chunk, float64
+// from the square onward, a fixed order (lane-strided, then a tree over the 256 lanes): the same
+// bits on every call and every device.  Every partial is written, empty chunks as 0.
+constexpr int kSumsqThreads = 256;
+
+__global__ void __launch_bounds__(kSumsqThreads)
+grad_sumsq_kernel(const float *__restrict__ g, int64_t n, double *__restrict__ partials)
+{
+    __shared__ double lane_sum[kSumsqThreads];
+    const int64_t nv = n / 4;
+    const int64_t per = (nv + MRCNN_SUMSQ_PARTIALS - 1) / MRCNN_SUMSQ_PARTIALS;
+    const int64_t lo = std::min((int64_t)blockIdx.x * per, nv);
+    const int64_t hi = std::min(lo + per, nv);
+    const float4 *g4 = reinterpret_cast<const float4 *>(g);
+    double a0 = 0., a1 = 0., a2 = 0., a3 = 0.;
+    int64_t i = lo + threadIdx.x;
+    // four 16-byte loads in flight per lane
+    for (; i + 3 * kSumsqThreads < hi; i += 4 * kSumsqThreads) {
+        const float4 x0 = g4[i], x1 = g4[i + kSumsqThreads], x2 = g4[i + 2 * kSumsqThreads],
+                     x3 = g4[i + 3 * kSumsqThreads];
+        a0 += (double)x0.x * (double)x0.x; a1 += (double)x0.y * (double)x0.y;
+        a2 += (double)x0.z * (double)x0.z; a3 += (double)x0.w * (double)x0.w;
+        a0 += (double)x1.x * (double)x1.x; a1 += (double)x1.y * (double)x1.y;
+        a2 += (double)x1.z * (double)x1.z; a3 += (double)x1.w * (double)x1.w;
+        a0 += (double)x2.x * (double)x2.x; a1 += (double)x2.y * (double)x2.y;
+        a2 += (double)x2.z * (double)x2.z; a3 += (double)x2.w * (double)x2.w;
+        a0 += (double)x3.x * (double)x3.x; a1 += (double)x3.y * (double)x3.y;
+        a2 += (double)x3.z * (double)x3.z; a3 += (double)x3.w * (double)x3.w;
+    }
+    for (; i < hi; i += kSumsqThreads) {
+        const float4 x = g4[i];
+        a0 += (double)x.x * (double)x.x; a1 += (double)x.y * (double)x.y;
+        a2 += (double)x.z * (double)x.z; a3 += (double)x.w * (double)x.w;
+    }
+    if (blockIdx.x == MRCNN_SUMSQ_PARTIALS - 1) {
+        const int64_t t = nv * 4 + threadIdx.x;
+        if (t < n) a0 += (double)g[t] * (double)g[t];
+    }
+    lane_sum[threadIdx.x] = (a0 + a1) + (a2 + a3);
+    __syncthreads();
+    for (int s = kSumsqThreads / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) lane_sum[threadIdx.x] += lane_sum[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partials[blockIdx.x] = lane_sum[0];
+}
+
+// One workgroup: the partials summed in index order in float64 by lane 0 (staged through LDS,
+// 1024 at a time), then the control word.
+constexpr int kControlStage = 1024;
+
+__global__ void __launch_bounds__(256)
+grad_control_kernel(const double *__restrict__ partials, int n_partials, float grad_scale,
+                    float clip, int skip_nonfinite, float *__restrict__ ctl)
+{
+    __shared__ double stage[kControlStage];
+    double sum = 0.;
+    for (int base = 0; base < n_partials; base += kControlStage) {
+        const int m = std::min(kControlStage, n_partials - base);
+        for (int k = threadIdx.x; k < m; k += blockDim.x) stage[k] = partials[base + k];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int k = 0; k < m; ++k) sum += stage[k];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    // finite <=> the exponent field is not all ones (decided on the float64 sum, never on the norm)
+    const bool finite = (__double_as_longlong(sum) & 0x7ff0000000000000LL) != 0x7ff0000000000000LL;
+    const double norm = sqrt(sum) * (double)grad_scale;
+    float factor = grad_scale;
+    if (clip > 0.f && norm > (double)clip) factor = (float)((double)grad_scale * (double)clip / norm);
+    ctl[MRCNN_CTL_NORM] = (float)norm;
+    ctl[MRCNN_CTL_FACTOR] = factor;
+    ctl[MRCNN_CTL_SKIPPED] = (skip_nonfinite && !finite) ? 1.f : 0.f;
+    ctl[MRCNN_CTL_NORM_REPORTED] = finite ? (float)norm : 0.f;
 }
 
 inline int grid_for(int64_t work, int threads = 256)
@@ -500,9 +601,10 @@ extern "C" int mrcnn_sparse3x3_scatter(const float *g_patches, const int32_t *lo
     return mrcnn::check_launch("sparse3x3_scatter");
 }
 
-extern "C" int mrcnn_sgd_momentum_wd_ex(float *p, float *g, float *v, int64_t n, float lr,
-                                        float momentum, float wd, float grad_scale, int zero_grad,
-                                        void *stream)
+namespace {
+
+int launch_sgd(float *p, float *g, float *v, int64_t n, float lr, float momentum, float wd,
+               float grad_scale, const float *ctl, int zero_grad, void *stream)
 {
     MRCNN_REQUIRE(n >= 0, "sgd: n < 0");
     if (n == 0) return 0;
@@ -510,13 +612,61 @@ extern "C" int mrcnn_sgd_momentum_wd_ex(float *p, float *g, float *v, int64_t n,
     MRCNN_REQUIRE(aligned16(p) && aligned16(g) && aligned16(v), "sgd: arenas must be 16-byte aligned");
     mrcnn::ProfScope prof(mrcnn::PROF_SGD, 0., (zero_grad ? 24.0 : 20.0) * (double)n,
                           mrcnn::as_stream(stream));
-    if (zero_grad)
-        hipLaunchKernelGGL(sgd_kernel<true>, dim3(grid_for(n / 4 + 1)), dim3(256), 0,
-                           mrcnn::as_stream(stream), p, g, v, n, lr, momentum, wd, grad_scale);
+    const dim3 grid(grid_for(n / 4 + 1)), block(256);
+    hipStream_t s = mrcnn::as_stream(stream);
+    if (ctl && zero_grad)
+        hipLaunchKernelGGL((sgd_kernel<true, true>), grid, block, 0, s, p, g, v, n, lr, momentum, wd,
+                           grad_scale, ctl);
+    else if (ctl)
+        hipLaunchKernelGGL((sgd_kernel<false, true>), grid, block, 0, s, p, g, v, n, lr, momentum, wd,
+                           grad_scale, ctl);
+    else if (zero_grad)
+        hipLaunchKernelGGL((sgd_kernel<true, false>), grid, block, 0, s, p, g, v, n, lr, momentum, wd,
+                           grad_scale, ctl);
     else
-        hipLaunchKernelGGL(sgd_kernel<false>, dim3(grid_for(n / 4 + 1)), dim3(256), 0,
-                           mrcnn::as_stream(stream), p, g, v, n, lr, momentum, wd, grad_scale);
+        hipLaunchKernelGGL((sgd_kernel<false, false>), grid, block, 0, s, p, g, v, n, lr, momentum, wd,
+                           grad_scale, ctl);
     return mrcnn::check_launch("sgd");
+}
+
+}  // namespace
+
+extern "C" int mrcnn_sgd_momentum_wd_ex(float *p, float *g, float *v, int64_t n, float lr,
+                                        float momentum, float wd, float grad_scale, int zero_grad,
+                                        void *stream)
+{
+    return launch_sgd(p, g, v, n, lr, momentum, wd, grad_scale, nullptr, zero_grad, stream);
+}
+
+extern "C" int mrcnn_sgd_momentum_wd_ctl(float *p, float *g, float *v, int64_t n, float lr,
+                                         float momentum, float wd, const float *ctl, int zero_grad,
+                                         void *stream)
+{
+    MRCNN_REQUIRE(ctl, "sgd_ctl: null control word");
+    return launch_sgd(p, g, v, n, lr, momentum, wd, 0.f, ctl, zero_grad, stream);
+}
+
+extern "C" int mrcnn_grad_sumsq(const float *g, int64_t n, double *partials, void *stream)
+{
+    MRCNN_REQUIRE(n >= 0, "grad_sumsq: n < 0");
+    MRCNN_REQUIRE(partials, "grad_sumsq: null partials");
+    MRCNN_REQUIRE(n == 0 || g, "grad_sumsq: null pointer");
+    MRCNN_REQUIRE(aligned16(g), "grad_sumsq: the gradient slice must be 16-byte aligned");
+    mrcnn::ProfScope prof(mrcnn::PROF_ELEMENTWISE, 2.0 * (double)n, 4.0 * (double)n,
+                          mrcnn::as_stream(stream));
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(MRCNN_SUMSQ_PARTIALS), dim3(kSumsqThreads), 0,
+                       mrcnn::as_stream(stream), g, n, partials);
+    return mrcnn::check_launch("grad_sumsq");
+}
+
+extern "C" int mrcnn_grad_control(const double *partials, int n_partials, float grad_scale,
+                                  float clip, int skip_nonfinite, float *ctl, void *stream)
+{
+    MRCNN_REQUIRE(n_partials >= 0, "grad_control: n_partials < 0");
+    MRCNN_REQUIRE(ctl && (n_partials == 0 || partials), "grad_control: null pointer");
+    hipLaunchKernelGGL(grad_control_kernel, dim3(1), dim3(256), 0, mrcnn::as_stream(stream),
+                       partials, n_partials, grad_scale, clip, skip_nonfinite, ctl);
+    return mrcnn::check_launch("grad_control");
 }
 
 extern "C" int mrcnn_sgd_momentum_wd(float *p, const float *g, float *v, int64_t n, float lr,

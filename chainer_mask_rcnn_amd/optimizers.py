@@ -27,7 +27,19 @@ and run on a second stream inside the NEXT step's proposal window (between the R
 and the RoI head, where the GPU is otherwise nearly idle).  The parameters are updated before
 they are read again, so every step computes the same values; ``flush()`` forces pending work
 (called by ``predict``, the serializers and at the end of a timed region).
+
+Gradient-norm hooks (opt-in: ``GradientClipping``, ``SkipNonFiniteUpdate``, ``ObserveGradientNorm``):
+with any of them the step is three kinds of launch on the compute stream and no host round trip —
+``mrcnn_grad_sumsq`` over each run of written parameters (float64 partial sums of squares in a
+fixed order), one ``mrcnn_grad_control`` that turns them into a control word on the device (norm of
+the averaged gradient, the factor the update multiplies the gradient by, the skip flag), and
+``mrcnn_sgd_momentum_wd_ctl``, the same update reading that word.  ``opt.report`` holds views of
+the word for the trainer's log.  Under data parallelism nothing extra is exchanged: every rank
+holds the same all-reduced gradient arena and computes the same word.  Deferred weight gradients do
+not exist yet when the norm is taken, so the two features refuse each other.
 """
+import math
+
 import torch
 
 from . import _lib
@@ -38,6 +50,37 @@ class WeightDecay(object):
 
     def __init__(self, rate):
         self.rate = rate
+
+
+class GradientClipping(object):
+    """chainer.optimizer_hooks.GradientClipping(threshold): with the L2 norm of ALL gradients
+    above ``threshold`` they are scaled by ``threshold / norm``.  The norm is that of the data
+    gradient after the 1/world averaging; weight decay is added afterwards, inside the SGD kernel
+    — chainer's result when GradientClipping is registered before WeightDecay (hooks run in
+    registration order)."""
+
+    def __init__(self, threshold):
+        threshold = float(threshold)
+        if not (math.isfinite(threshold) and threshold > 0):
+            raise ValueError('GradientClipping: threshold must be finite and > 0, got %r'
+                             % (threshold,))
+        self.threshold = threshold
+
+
+class SkipNonFiniteUpdate(object):
+    """A step whose gradients hold a NaN or an infinity changes neither values nor momenta (the
+    gradients are still cleared); ``opt.report['skipped']`` is 1 for it.  Decided on the device,
+    on the float64 sum of squares: finite gradients are never skipped."""
+
+
+class ObserveGradientNorm(object):
+    """Only ``opt.report['grad_norm']``: the update is the plain one, bit for bit."""
+
+
+NORM_HOOKS = (GradientClipping, SkipNonFiniteUpdate, ObserveGradientNorm)
+# slots of the device control word and the partials per run: include/mrcnn_hip.h
+CTL_NORM, CTL_FACTOR, CTL_SKIPPED, CTL_NORM_REPORTED, CTL_SIZE = 0, 1, 2, 3, 4
+SUMSQ_PARTIALS = 1024
 
 
 def disable_update(module):
@@ -140,8 +183,15 @@ class MomentumSGD(object):
 
     def __init__(self, lr=0.01, momentum=0.9):
         self.lr = lr
+        self.lr_scale = 1.0        # warm-up factor: every SGD launch gets lr * lr_scale
         self.momentum = momentum
         self.weight_decay = 0.
+        self.grad_clip = 0.        # GradientClipping threshold (0: off)
+        self.skip_nonfinite = False
+        self.observe_norm = False  # any gradient-norm hook installed: step() takes the ctl path
+        self.report = {}           # 'grad_norm', 'skipped': 1-element views of the control word
+        self._ctl = None           # device float[CTL_SIZE]
+        self._partials = None      # device double[runs * SUMSQ_PARTIALS]
         self.target = None
         self.arena = None
         self.grad_sync = None      # set by parallel.DataParallelGradSync
@@ -157,8 +207,27 @@ class MomentumSGD(object):
     def add_hook(self, hook):
         if isinstance(hook, WeightDecay):
             self.weight_decay = hook.rate
+        elif isinstance(hook, NORM_HOOKS):
+            if self.deferred_params:
+                raise ValueError(
+                    '%s cannot be combined with deferred weight gradients '
+                    '(defer_weight_gradients): their gradients do not exist yet when the norm is '
+                    'taken; build the optimizer without deferral' % type(hook).__name__)
+            if isinstance(hook, GradientClipping):
+                self.grad_clip = hook.threshold
+            elif isinstance(hook, SkipNonFiniteUpdate):
+                self.skip_nonfinite = True
+            self.observe_norm = True
+            if self.arena is not None:
+                self._bind_report()
         else:
             raise TypeError('unsupported optimizer hook: %r' % (hook,))
+
+    def _bind_report(self):
+        if self._ctl is None:
+            self._ctl = torch.zeros(CTL_SIZE, dtype=torch.float32, device=self.arena.values.device)
+            self.report = {'grad_norm': self._ctl[CTL_NORM_REPORTED:CTL_NORM_REPORTED + 1],
+                           'skipped': self._ctl[CTL_SKIPPED:CTL_SKIPPED + 1]}
 
     def defer_weight_gradients(self, params):
         """Hold the weight gradients (and the update) of ``params`` — parameters of the RoI
@@ -166,7 +235,13 @@ class MomentumSGD(object):
         head — back into the next step's proposal window.  Under data parallelism their
         gradient slices are all-reduced there too (call this BEFORE the first update: the
         gradient buckets are planned around them)."""
-        self.deferred_params = list(params)
+        params = list(params)
+        if params and self.observe_norm:
+            raise ValueError(
+                'defer_weight_gradients cannot be combined with a gradient-norm hook '
+                '(GradientClipping / SkipNonFiniteUpdate / ObserveGradientNorm): the deferred '
+                'gradients do not exist yet when the norm is taken')
+        self.deferred_params = params
         if self not in _DEFERRING:
             _DEFERRING.append(self)
 
@@ -233,6 +308,8 @@ class MomentumSGD(object):
             raise ValueError('no trainable parameters')
         params.reverse()           # backward produces gradients in this order
         self.arena = ParamArena(params)
+        if self.observe_norm:
+            self._bind_report()
         if self.grad_sync is not None:
             self.grad_sync.attach(self)
 
@@ -266,7 +343,8 @@ class MomentumSGD(object):
     def step(self, grad_scale=1.0, zero_grads=False, deferred=None):
         """Apply the update rule to every parameter that received a gradient since the last
         step (one launch when that is all of them: the normal case).  ``zero_grads`` clears
-        the gradient arena in the same pass."""
+        the gradient arena in the same pass.  With a gradient-norm hook, ``grad_scale`` goes through
+        the device control word (see the module docstring)."""
         a = self.arena
         a.rebind()
         written = a.written()
@@ -298,15 +376,34 @@ class MomentumSGD(object):
             held = set(i for i, p in enumerate(a.params) if p.grad.data_ptr() in grads)
             self._pending = (deferred.jobs,
                              [a.slice_bounds(f, l) for f, l in _runs([i in held for i in range(len(a.params))])],
-                             self.lr, self.momentum, self.weight_decay, grad_scale)
+                             self.lr * self.lr_scale, self.momentum, self.weight_decay, grad_scale)
         all_written = all(written)
-        runs = _runs([w and i not in held for i, w in enumerate(written)])
-        for first, last in runs:
-            lo, hi = a.slice_bounds(first, last)
-            _lib.call('mrcnn_sgd_momentum_wd_ex', _lib.ptr(a.values[lo:hi]),
-                      _lib.ptr(a.grads[lo:hi]), _lib.ptr(a.momenta[lo:hi]), hi - lo,
-                      float(self.lr), float(self.momentum), float(self.weight_decay),
-                      float(grad_scale), 1 if zero_grads else 0, _lib.stream_ptr())
+        runs = [a.slice_bounds(first, last)
+                for first, last in _runs([w and i not in held for i, w in enumerate(written)])]
+        lr = float(self.lr * self.lr_scale)
+        if self.observe_norm:
+            self._bind_report()
+            P = SUMSQ_PARTIALS
+            if self._partials is None or self._partials.numel() < len(runs) * P:
+                self._partials = torch.zeros(max(1, len(runs)) * P, dtype=torch.float64,
+                                             device=a.values.device)
+            for k, (lo, hi) in enumerate(runs):
+                _lib.call('mrcnn_grad_sumsq', _lib.ptr(a.grads[lo:hi]), hi - lo,
+                          _lib.ptr(self._partials[k * P:(k + 1) * P]), _lib.stream_ptr())
+            _lib.call('mrcnn_grad_control', _lib.ptr(self._partials), len(runs) * P,
+                      float(grad_scale), float(self.grad_clip), 1 if self.skip_nonfinite else 0,
+                      _lib.ptr(self._ctl), _lib.stream_ptr())
+            for lo, hi in runs:
+                _lib.call('mrcnn_sgd_momentum_wd_ctl', _lib.ptr(a.values[lo:hi]),
+                          _lib.ptr(a.grads[lo:hi]), _lib.ptr(a.momenta[lo:hi]), hi - lo,
+                          lr, float(self.momentum), float(self.weight_decay),
+                          _lib.ptr(self._ctl), 1 if zero_grads else 0, _lib.stream_ptr())
+        else:
+            for lo, hi in runs:
+                _lib.call('mrcnn_sgd_momentum_wd_ex', _lib.ptr(a.values[lo:hi]),
+                          _lib.ptr(a.grads[lo:hi]), _lib.ptr(a.momenta[lo:hi]), hi - lo,
+                          lr, float(self.momentum), float(self.weight_decay),
+                          float(grad_scale), 1 if zero_grads else 0, _lib.stream_ptr())
         from .functions import conv
         conv.weights_changed()       # the kernel writes the arena behind torch's version counters
         if zero_grads and not all_written:

@@ -505,6 +505,39 @@ int mrcnn_sgd_momentum_wd_ex(float *p, float *g, float *v, int64_t n, float lr,
                              float momentum, float wd, float grad_scale, int zero_grad,
                              void *stream);
 
+/* ---- Global gradient norm and the step's control word (chainer's GradientClipping rule,
+ * a non-finite guard, the logged norm) — three launches on one stream, no host round trip:
+ * mrcnn_grad_sumsq per arena run, one mrcnn_grad_control, mrcnn_sgd_momentum_wd_ctl per run. */
+/* partials[b], b < MRCNN_SUMSQ_PARTIALS: the sum of (double)g[i]^2 over chunk b of the n floats
+ * (equal contiguous runs of whole 16-byte groups; the n % 4 tail belongs to the last chunk).
+ * float64 from the square onward, a fixed order, no atomics: the same bits on every call,
+ * whatever the device's CU count.  Every partial is written (empty chunks and n == 0: 0).
+ * g: 16-byte aligned. */
+#define MRCNN_SUMSQ_PARTIALS 1024
+int mrcnn_grad_sumsq(const float *g, int64_t n, double *partials, void *stream);
+/* ctl[4] from the partial slabs of one or more runs (n_partials doubles, summed in index order
+ * in float64; sum = that total):
+ *   NORM          (float)(sqrt(sum) * grad_scale): the norm of the averaged gradient; may be
+ *                 inf / NaN, and may saturate to inf in float
+ *   FACTOR        what the SGD launch multiplies g by: grad_scale bit for bit, or, when
+ *                 clip > 0 and norm > clip, grad_scale * clip / norm (float64, rounded once) —
+ *                 chainer's rate = threshold / norm, applied only when rate < 1
+ *   SKIPPED       1.f if skip_nonfinite and the float64 sum is not finite, else 0.f (squares of
+ *                 fp32 values cannot overflow float64: finite gradients are never skipped)
+ *   NORM_REPORTED NORM, or 0 when the sum is not finite (keeps a log window's mean finite) */
+#define MRCNN_CTL_NORM 0
+#define MRCNN_CTL_FACTOR 1
+#define MRCNN_CTL_SKIPPED 2
+#define MRCNN_CTL_NORM_REPORTED 3
+#define MRCNN_CTL_SIZE 4
+int mrcnn_grad_control(const double *partials, int n_partials, float grad_scale, float clip,
+                       int skip_nonfinite, float *ctl, void *stream);
+/* mrcnn_sgd_momentum_wd_ex with grad_scale = ctl[MRCNN_CTL_FACTOR] read on the device (the same
+ * update expression: the same bits for the same factor).  With ctl[MRCNN_CTL_SKIPPED] != 0, p and
+ * v are left untouched; g is still cleared when zero_grad is set. */
+int mrcnn_sgd_momentum_wd_ctl(float *p, float *g, float *v, int64_t n, float lr, float momentum,
+                              float wd, const float *ctl, int zero_grad, void *stream);
+
 /* Per-class `prob > thresh` filter + stable descending sort + gather, all foreground
  * classes in one launch: the first half of MaskRCNN._suppress (models/mask_rcnn.py:178-202).
  * prob (R, n_class), cls_bbox (R, n_class, 4) -> sorted_boxes (n_class-1, R, 4),

@@ -80,6 +80,18 @@ def parse_args(argv=None):
     ap.add_argument('--eval-bbox', action='store_true',
                     help='the evaluator also scores the boxes: validation/main/bbox/map joins the '
                          'log and the printed report (the best snapshot stays on the mask map)')
+    ap.add_argument('--grad-clip', type=float, default=0.,
+                    help='clip the global L2 norm of the averaged gradient at T '
+                         '(optimizers.GradientClipping; 0: off).  Like --skip-nonfinite it turns '
+                         'the deferred weight gradients off')
+    ap.add_argument('--skip-nonfinite', action='store_true',
+                    help='an update whose gradients hold a NaN or an infinity is skipped '
+                         '(optimizers.SkipNonFiniteUpdate); a log window of nothing but skipped '
+                         'updates ends the run')
+    ap.add_argument('--warmup-iters', type=int, default=0,
+                    help="Detectron's linear lr warm-up over the first N updates (0: off)")
+    ap.add_argument('--warmup-factor', type=float, default=1. / 3.,
+                    help='lr factor of update 0 with --warmup-iters')
     ap.add_argument('--logs-dir', default=osp.join(ROOT, 'logs'))
     ap.add_argument('--no-plot', action='store_true', help='do not write loss.png / accuracy.png')
     return ap.parse_args(argv)
@@ -244,6 +256,18 @@ def build_model(args, weights, **kwargs):
         imagenet_weights=weights, **kwargs)
 
 
+# switches recorded in params.yaml only when set: a default run's file stays as it was
+OPTIONAL_PARAMS = ('eval_bbox', 'grad_clip', 'skip_nonfinite', 'warmup_iters')
+
+
+def recorded_params(args):
+    """vars(args) as params.yaml records them."""
+    params = {k: v for k, v in vars(args).items() if k not in OPTIONAL_PARAMS or v}
+    if not params.get('warmup_iters'):
+        params.pop('warmup_factor', None)
+    return params
+
+
 Run = collections.namedtuple('Run', 'trainer loop chain optimizer evaluator train test')
 
 
@@ -260,9 +284,13 @@ def assemble(args, comm, model, train_data, test_data, evaluator_type, synthetic
 
         def make_sync(opt):
             return parallel.DataParallelGradSync(opt)
+    hooks = train_loop.norm_hooks(getattr(args, 'grad_clip', 0.),
+                                  getattr(args, 'skip_nonfinite', False))
+    # a gradient-norm hook needs every gradient in the arena at the step: no deferral
     chain, opt = train_loop.setup_training(model, comm.device, args.batch_size,
                                            synthetic_weights=synthetic_weights,
-                                           make_sync=make_sync)
+                                           make_sync=make_sync, hooks=hooks,
+                                           **({'defer': 0} if hooks else {}))
 
     # examples/train_common.py:200-205: scattered train / test data
     train_data = cmr.datasets.scatter_dataset(train_data, comm.rank, comm.world, shuffle=True,
@@ -288,15 +316,17 @@ def assemble(args, comm, model, train_data, test_data, evaluator_type, synthetic
 
     args.git_hash = cmr.utils.git_hash(__file__)
     args.hostname = socket.gethostname()
-    # the switch is recorded only when set: a default run's params.yaml stays as it was
-    params = {k: v for k, v in vars(args).items() if k != 'eval_bbox' or v}
+    params = recorded_params(args)
+    warmup_iters = getattr(args, 'warmup_iters', 0)
+    warmup = T.LinearWarmup(warmup_iters, getattr(args, 'warmup_factor', 1. / 3.)) \
+        if warmup_iters else None
     tr = T.Trainer(loop, (args.max_epoch, 'epoch'), out=args.out if comm.rank == 0 else None)
     T.extend_reference_set(tr, model, evaluator=evaluator, vis_iterator=test_iter,
                            class_names=args.class_names, step_size=args.step_size,
                            params=params, plot=not args.no_plot,
                            print_out=print_out if comm.rank == 0 else None, rank=comm.rank,
                            gather=comm.gather if comm.parallel else None, eval_bbox=eval_bbox,
-                           **intervals)
+                           warmup=warmup, grad_report=bool(hooks), **intervals)
     return Run(tr, loop, chain, opt, evaluator, train_data, test_data)
 
 

@@ -275,13 +275,15 @@ def build_voc_trainer(n_layers, device, lr_batch, defer=5):
     return model, chain, opt, None
 
 
-def setup_training(model, device, lr_batch, defer=5, synthetic_weights=True, make_sync=None):
+def setup_training(model, device, lr_batch, defer=5, synthetic_weights=True, make_sync=None,
+                   hooks=()):
     """Train chain and optimizer of examples/train_common.py:171-190 for ``model``: MomentumSGD
     (lr 0.00125 * batch, momentum 0.9) + WeightDecay(1e-4), conv1 / bn1 / res2 and every
     AffineChannel2D frozen; ``synthetic_weights``: bench.stabilise_synthetic_weights (random
     init); ``defer``: the res5 weight gradients held back into the next step (optimizers.py);
     ``make_sync(opt)``: data parallel, creates the gradient sync (parallel.DataParallelGradSync)
-    before the deferred parameters are chosen, as bench.build_trainer does."""
+    before the deferred parameters are chosen, as bench.build_trainer does; ``hooks``: further
+    optimizer hooks (the gradient-norm hooks of optimizers.py need ``defer=0``)."""
     import bench
     import chainer_mask_rcnn_amd as cmr
     from chainer_mask_rcnn_amd import optimizers
@@ -291,6 +293,8 @@ def setup_training(model, device, lr_batch, defer=5, synthetic_weights=True, mak
     opt = optimizers.MomentumSGD(lr=0.00125 * lr_batch, momentum=0.9)
     opt.setup(chain)
     opt.add_hook(optimizers.WeightDecay(rate=0.0001))
+    for hook in hooks:
+        opt.add_hook(hook)
     for link in (model.extractor.conv1, model.extractor.bn1, model.extractor.res2):
         optimizers.disable_update(link)
     for m in chain.modules():
@@ -306,6 +310,17 @@ def setup_training(model, device, lr_batch, defer=5, synthetic_weights=True, mak
                                     b2.conv2.W, b2.conv1.W, b2.conv3.W, a.conv1.W,
                                     a.conv4.W][:defer])
     return chain, opt
+
+
+def norm_hooks(grad_clip=0., skip_nonfinite=False):
+    """The optimizer hooks of --grad-clip T / --skip-nonfinite (tools/train.py, this file)."""
+    from chainer_mask_rcnn_amd import optimizers
+    hooks = []
+    if grad_clip:
+        hooks.append(optimizers.GradientClipping(grad_clip))
+    if skip_nonfinite:
+        hooks.append(optimizers.SkipNonFiniteUpdate())
+    return hooks
 
 
 def build(dataset, n_layers=50, device='cuda:0', batch_size=2, seed=0, defer=5, prefetch=True,
@@ -360,6 +375,12 @@ def main():
     ap.add_argument('--device-masks', action='store_true',
                     help='ground-truth masks cross PCIe as bits and are resized / flipped by a HIP '
                          'kernel (COCO: the dataset also keeps them packed on the host)')
+    ap.add_argument('--defer', type=int, default=5,
+                    help='res5 weight gradients held back into the next step (0: none)')
+    ap.add_argument('--grad-clip', type=float, default=0.,
+                    help='optimizers.GradientClipping threshold (0: off; needs --defer 0)')
+    ap.add_argument('--skip-nonfinite', action='store_true',
+                    help='optimizers.SkipNonFiniteUpdate (needs --defer 0)')
     args = ap.parse_args()
     import chainer_mask_rcnn_amd as cmr
     if os.environ.get('TORCH_THREADS'):
@@ -379,8 +400,11 @@ def main():
                                                             root_dir=args.coco_root,
                                                             packed_masks=args.device_masks)
     loop, model, chain, opt = build(data, args.layers, 'cuda:0', args.batch, args.seed,
-                                    prefetch=not args.no_prefetch, pooling_func=args.pooling_func,
-                                    model_settings=settings, device_masks=args.device_masks)
+                                    defer=args.defer, prefetch=not args.no_prefetch,
+                                    pooling_func=args.pooling_func, model_settings=settings,
+                                    device_masks=args.device_masks)
+    for hook in norm_hooks(args.grad_clip, args.skip_nonfinite):
+        opt.add_hook(hook)            # (refused with deferred weight gradients: --defer 0)
     for _ in range(int(os.environ.get('WARMUP', 3))):
         loop.step()
     opt.flush()

@@ -363,6 +363,9 @@ class Trainer(object):
                 self.observation = {}
                 self.updater.update()
                 self.observation.update(('main/' + k, v) for k, v in chain.report.items())
+                # the optimizer's device scalars (grad_norm, skipped) beside the chain's, if any
+                opt_report = getattr(getattr(self.loop, 'optimizer', None), 'report', None) or {}
+                self.observation.update(('main/' + k, v) for k, v in opt_report.items())
                 for e in entries:
                     if e.trigger(self):
                         e.extension(self)
@@ -442,7 +445,61 @@ class observe_lr(object):
     name = 'observe_lr'
 
     def __call__(self, trainer):
-        trainer.observation['lr'] = trainer.updater.get_optimizer('main').lr
+        opt = trainer.updater.get_optimizer('main')
+        # the rate the SGD launch got: the schedule's value times the warm-up factor (1.0: the same)
+        trainer.observation['lr'] = opt.lr * getattr(opt, 'lr_scale', 1.0)
+
+
+class LinearWarmup(object):
+    """Detectron's linear warm-up: update number i (0-based) runs at ``lr * (factor + (1 - factor)
+    * i / iters)`` for i < iters and at exactly ``lr`` afterwards.  It sets the optimizer's
+    ``lr_scale`` for the next update and leaves ``lr`` to the schedule, so ExponentialShift
+    composes; register it for every iteration."""
+
+    priority = PRIORITY_READER
+    trigger = (1, 'iteration')
+
+    def __init__(self, iters, factor=1. / 3.):
+        iters = int(iters)
+        if iters < 0 or not 0. <= factor <= 1.:
+            raise ValueError('LinearWarmup: iters >= 0 and 0 <= factor <= 1, got %r, %r'
+                             % (iters, factor))
+        self.iters, self.factor = iters, float(factor)
+
+    def scale(self, i):
+        if i >= self.iters:
+            return 1.0
+        return self.factor + (1. - self.factor) * i / self.iters
+
+    def initialize(self, trainer):
+        self(trainer)
+
+    def __call__(self, trainer):
+        trainer.updater.get_optimizer('main').lr_scale = self.scale(trainer.updater.iteration)
+
+
+class StopWhenEverythingSkipped(object):
+    """With optimizers.SkipNonFiniteUpdate: a run whose every update of a log window was skipped
+    has diverged and would skip for ever, so it ends with an error.  Runs at the log trigger,
+    after the LogReport, on its newest entry."""
+
+    priority = PRIORITY_READER
+
+    def __init__(self, log_report='LogReport', key='main/skipped'):
+        self._log_report, self._key = log_report, key
+        self._seen = 0
+
+    def __call__(self, trainer):
+        log = trainer.get_extension(self._log_report).log
+        if len(log) == self._seen:
+            return
+        self._seen = len(log)
+        entry = log[-1]
+        if entry.get(self._key) == 1.0:
+            raise RuntimeError(
+                'every update up to iteration %d of the last log window was skipped for '
+                'non-finite gradients (%s = 1): training has diverged'
+                % (entry.get('iteration', trainer.updater.iteration), self._key))
 
 
 class ExponentialShift(object):
@@ -672,17 +729,23 @@ def _plain(v):
 
 LOG_KEYS = ['main/loss', 'main/roi_loc_loss', 'main/roi_cls_loss', 'main/roi_mask_loss',
             'main/rpn_loc_loss', 'main/rpn_cls_loss']
+# the optimizer's report with a gradient-norm hook (optimizers.py).  6 + 2 device scalars per
+# summary: exactly MRCNN_MAX_OBSERVED (DeviceSums), so a further one needs a larger bound there
+GRAD_KEYS = ['main/grad_norm', 'main/skipped']
 
 
 def extend_reference_set(trainer, model, evaluator=None, vis_iterator=None, class_names=None,
                          step_size=None, params=None, eval_interval=(1, 'epoch'),
                          log_interval=(20, 'iteration'), plot_interval=(0.1, 'epoch'),
                          print_interval=(20, 'iteration'), plot=True, print_out=sys.stdout,
-                         rank=0, gather=None, eval_bbox=False):
+                         rank=0, gather=None, eval_bbox=False, warmup=None, grad_report=False):
     """The extensions of examples/train_common.py:251-372 (without dump_graph / ProgressBar)
     with the same triggers and priorities; ``model``: the MaskRCNN (``chain.mask_rcnn``).
     ``eval_bbox``: the evaluator also reports ``validation/main/bbox/map``, which then joins the
     printed report (the best snapshot and accuracy.png stay on ``validation/main/map``).
+    ``warmup``: a LinearWarmup, run every iteration on every rank.  ``grad_report``: the optimizer
+    has a gradient-norm hook: ``main/grad_norm`` and ``main/skipped`` join the printed report and
+    StopWhenEverythingSkipped ends a run whose whole log window was skipped.
 
     Data parallel (``gather``: the control-plane all-gather, see DictSummary.compute_mean): the lr
     shift, the evaluator (a multi-node one), observe_lr and the summaries of LogReport and the
@@ -699,6 +762,8 @@ def extend_reference_set(trainer, model, evaluator=None, vis_iterator=None, clas
     if step_size is not None:
         trainer.extend(ExponentialShift('lr', 0.1),
                        trigger=ManualScheduleTrigger(step_size, 'epoch'))
+    if warmup is not None:
+        trainer.extend(warmup, trigger=(1, 'iteration'))
     if evaluator is not None:
         trainer.extend(Evaluator(evaluator), trigger=eval_interval)
         extend_lead(snapshot_object(model, 'snapshot_model.npz'), reads_params=True,
@@ -712,9 +777,12 @@ def extend_reference_set(trainer, model, evaluator=None, vis_iterator=None, clas
     trainer.extend(observe_lr(), trigger=log_interval)
     trainer.extend(LogReport(trigger=log_interval, log_name='log' if lead else None,
                              gather=gather))
+    if grad_report:
+        trainer.extend(StopWhenEverythingSkipped(), trigger=log_interval)
     if print_out is not None:
         extend_lead(PrintReport(['iteration', 'epoch', 'elapsed_time', 'lr'] + LOG_KEYS[:1]
-                                + LOG_KEYS[1:] + ['validation/main/map']
+                                + LOG_KEYS[1:] + (GRAD_KEYS if grad_report else [])
+                                + ['validation/main/map']
                                 + (['validation/main/bbox/map'] if eval_bbox else []),
                                 out=print_out),
                     trigger=print_interval)
