@@ -127,6 +127,7 @@ SIGNATURES = {
     'mrcnn_mask_targets': (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int,
                                    c_vp, c_vp]),
     'mrcnn_mask_resize_nearest': (c_int, [c_vp] + [c_int] * 3 + [c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
+    'mrcnn_mask_resize_crop': (c_int, [c_vp] + [c_int] * 3 + [c_vp, c_vp, c_int] + [c_vp] * 5),
     'mrcnn_allreduce_unique_id': (c_int, [c_vp]),
     'mrcnn_allreduce_init': (c_int, [c_vp, c_int, c_int, ctypes.POINTER(c_vp)]),
     'mrcnn_allreduce_destroy': (c_int, [c_vp]),
@@ -142,6 +143,8 @@ SIGNATURES = {
     'mrcnn_prepare_image': (c_int, [c_vp, c_int, c_int, c_int, c_int, ctypes.c_double,
                                     ctypes.POINTER(c_f32), c_vp, c_int, c_int, c_int, c_int, c_int,
                                     c_int, c_vp]),
+    'mrcnn_prepare_image_crop': (c_int, [c_vp, c_int, c_int, c_int, c_int, ctypes.c_double,
+                                         ctypes.POINTER(c_f32), c_vp] + [c_int] * 8 + [c_vp]),
     'mrcnn_paste_masks': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     'mrcnn_mask_pack': (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mrcnn_paste_masks_packed': (c_int, [c_vp, c_vp, c_vp] + [c_int] * 5 + [c_vp] * 4),

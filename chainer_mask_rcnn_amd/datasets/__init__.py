@@ -3,6 +3,7 @@
 ``datasets/concat_examples.py`` (the image half on the device)."""
 from .transforms import MaskRCNNTransform  # NOQA
 from .transforms import resize_bbox, flip_bbox, resize_nearest, flip  # NOQA
+from .transforms import draw_scale_jitter  # NOQA
 from .packed_masks import PackedMasks  # NOQA
 from .concat_examples import concat_examples  # NOQA
 from .coco import COCOInstanceSegmentationDataset  # NOQA

@@ -8,6 +8,11 @@ consume them run on the host (``MaskRCNNTrainChain``).  ``device_masks=True`` mo
 they are uploaded as bits and resized / flipped by ``mrcnn_mask_resize_nearest``.  The random flip consumes one
 ``random.choice([True, False])`` from Python's global generator, exactly what
 ``chainercv.transforms.random_flip(img, x_random=True)`` draws.
+
+``scale_jitter=(lo, hi)`` (not in the reference) turns on large-scale jitter:
+the example is resized by a random factor and cropped or zero-padded to one fixed square, by
+``mrcnn_prepare_image_crop`` and ``mrcnn_mask_resize_crop``.  Its draws follow the flip's, three
+per attempt (``draw_scale_jitter``).
 """
 import random
 
@@ -92,6 +97,32 @@ def flip(img, y_flip=False, x_flip=False):
     return img
 
 
+SCALE_JITTER_ATTEMPTS = 8
+
+
+def _resized_size(in_size, scale):
+    # the rounding of MaskRCNN.prepare
+    return (max(1, int(np.round(in_size[0] * scale))), max(1, int(np.round(in_size[1] * scale))))
+
+
+def draw_scale_jitter(in_size, crop_size, scale_range):
+    """One large-scale-jitter geometry for an (H, W) example on an S x S canvas:
+    ``(scale, (rH, rW), (oy, ox))``.  Exactly three draws from Python's global ``random``, in this
+    order: ``r = uniform(lo, hi)`` — the longer side becomes r * S, ``scale = min(r*S/H, r*S/W)``,
+    the resized size rounded as ``MaskRCNN.prepare`` rounds it — then ``random()`` for the row
+    offset and ``random()`` for the column offset of the crop window, each uniform over
+    ``0 .. max(resized - S, 0)``.  A resized side shorter than S is padded at the bottom / right."""
+    H, W = in_size
+    S = crop_size
+    lo, hi = scale_range
+    r = random.uniform(lo, hi)
+    scale = min(r * S / H, r * S / W)
+    rH, rW = _resized_size((H, W), scale)
+    oy = int(np.floor(random.random() * (max(rH - S, 0) + 1)))
+    ox = int(np.floor(random.random() * (max(rW - S, 0) + 1)))
+    return scale, (rH, rW), (oy, ox)
+
+
 class MaskRCNNTransform(object):
     """``MaskRCNNTransform(mask_rcnn, train=True)(in_data)`` with ``in_data`` =
     ``(img HWC, bbox, label, mask)`` or the 6-tuple that also carries ``crowd, area``.
@@ -102,12 +133,38 @@ class MaskRCNNTransform(object):
     masks cross PCIe as bits — a dense stack is packed on the host first — and the returned mask
     is the (G, o_H, o_W) uint8 device tensor that ``mrcnn_mask_resize_nearest`` builds on the
     image's stream; the draw from ``random``, boxes, labels, image and scale are the same.
-    Otherwise a ``PackedMasks`` is unpacked and takes the host path."""
+    Otherwise a ``PackedMasks`` is unpacked and takes the host path.
 
-    def __init__(self, mask_rcnn, train=True, device_masks=False):
+    ``scale_jitter=(lo, hi)`` (training mode with ``device_masks=True`` only): large-scale jitter
+    onto a ``crop_size`` square.  After the flip, up to ``SCALE_JITTER_ATTEMPTS`` geometries are
+    drawn (``draw_scale_jitter``); the first that leaves an instance with at least one pixel on
+    the canvas is taken.  Instances left with no pixel are dropped from masks, labels and boxes,
+    and ``bbox`` is the tight box of each cropped mask (the dataset's ``mask_to_bbox``
+    convention), float32.  When no attempt leaves anything, or there are no instances (then
+    nothing is drawn), the example is resized by ``min(S/H, S/W)`` at offset 0 and every instance
+    is kept with its given box resized and flipped: the plain path on an S x S canvas.  The image
+    is (3, S, S), the masks (G', S, S), ``scale`` the resize scale.  With ``scale_jitter=None``
+    nothing changes."""
+
+    def __init__(self, mask_rcnn, train=True, device_masks=False, scale_jitter=None,
+                 crop_size=1024):
         self.mask_rcnn = mask_rcnn
         self.train = train
         self.device_masks = device_masks
+        if scale_jitter is not None:
+            if not (train and device_masks):
+                raise ValueError('MaskRCNNTransform: scale_jitter requires train=True and '
+                                 'device_masks=True (the crop is built on the device)')
+            lo, hi = (float(v) for v in scale_jitter)
+            if not 0 < lo <= hi:
+                raise ValueError('MaskRCNNTransform: scale_jitter=(lo, hi) needs 0 < lo <= hi, '
+                                 'got %r' % (tuple(scale_jitter),))
+            if int(crop_size) != crop_size or crop_size <= 0:
+                raise ValueError('MaskRCNNTransform: crop_size must be a positive integer, got %r'
+                                 % (crop_size,))
+            scale_jitter, crop_size = (lo, hi), int(crop_size)
+        self.scale_jitter = scale_jitter
+        self.crop_size = crop_size
 
     def __call__(self, in_data):
         if len(in_data) not in (4, 6):
@@ -122,6 +179,8 @@ class MaskRCNNTransform(object):
         # touches an RNG, so drawing first leaves the random stream identical
         x_flip = random.choice([True, False])
         in_size = chw.shape[1:]
+        if self.scale_jitter is not None:
+            return self._scale_jitter(chw, bbox, label, mask, x_flip)
         imgs, _, scales = self.mask_rcnn.prepare([chw], x_flips=[x_flip])
         x = imgs[0]                        # device tensor (3, o_H, o_W), channels-last memory
         out_size = tuple(x.shape[1:])
@@ -152,3 +211,39 @@ class MaskRCNNTransform(object):
         out = gt_masks.resize_masks_nearest(gt_masks.upload_packed_masks(mask, device), out_size,
                                             x_flip=x_flip)
         return out[0] if flat else out
+
+    def _scale_jitter(self, chw, bbox, label, mask, x_flip):
+        """The jittered example (class docstring); the flip has been drawn."""
+        import torch
+        from ..functions import gt_masks, scale_jitter as SJ
+        model, S = self.mask_rcnn, self.crop_size
+        dev = next(model.parameters()).device
+        in_size = tuple(chw.shape[1:])
+        flat = not isinstance(mask, PackedMasks) and mask.ndim == 2
+        if not isinstance(mask, PackedMasks):
+            mask = PackedMasks.from_dense(mask[None] if flat else mask)
+        G = len(mask)
+        packed = gt_masks.upload_packed_masks(mask, dev)
+        masks = None
+        for _ in range(SCALE_JITTER_ATTEMPTS if G > 0 else 0):
+            scale, resized, offset = draw_scale_jitter(in_size, S, self.scale_jitter)
+            cropped, meta = SJ.resize_crop_masks_meta(packed, resized, offset, S, x_flip)
+            meta = meta.cpu().numpy()                  # boxes and areas: the one read-back
+            keep = meta[4 * G:] >= 1
+            if keep.any():
+                masks = cropped
+                break
+        if masks is not None:
+            if not keep.all():
+                masks = masks[torch.from_numpy(np.flatnonzero(keep)).to(dev)]
+                label = label[keep]
+            bbox = meta[:4 * G].reshape(G, 4)[keep].astype(np.float32)
+        else:
+            scale = min(float(S) / in_size[0], float(S) / in_size[1])
+            resized, offset = _resized_size(in_size, scale), (0, 0)
+            masks = SJ.resize_crop_masks(packed, resized, offset, S, x_flip)[0]
+            if len(bbox) > 0:
+                bbox = resize_bbox(bbox, in_size, resized)
+            bbox = flip_bbox(bbox, resized, x_flip=x_flip)
+        x = SJ.prepare_image_crop(model.mean, chw, scale, resized, offset, S, x_flip, dev)
+        return x, bbox, label, (masks[0] if flat else masks), scale

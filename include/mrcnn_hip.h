@@ -557,6 +557,18 @@ int mrcnn_detect_sort(const float *prob, const float *cls_bbox, int R, int n_cla
 int mrcnn_prepare_image(const void *src_chw, int src_is_u8, int C, int H, int W, double scale,
                         const float *mean_host, float *dst_nhwc, int dstH, int dstW,
                         int outH, int outW, int n, int flip_x, void *stream);
+/* Large-scale jitter: mrcnn_prepare_image's arguments, with (rH,rW) the
+ * rounded scaled size, plus a crop window.  Image n of dst (N,dstH,dstW,3) NHWC is the canvas:
+ * canvas pixel (y,x) = pixel (y+oy, x+ox) of the (rH,rW) image mrcnn_prepare_image would write
+ * with the same flip_x, and 0 where that lies beyond it; the whole slot is written, so the caller
+ * need not zero it.  The pixel function is mrcnn_prepare_image's own (csrc/prepare_pixel.h), so
+ * the result equals a slice of its output bit for bit, and the resized image (4 x the canvas at
+ * twice the canvas size) never exists.  0 <= oy < rH, 0 <= ox < rW, dstH <= 65535.  The reference
+ * has no scale augmentation (chainer_mask_rcnn/datasets/transforms.py:10-51 resizes to one
+ * fixed scale); this extends the kernel that replaces its resize. */
+int mrcnn_prepare_image_crop(const void *src_chw, int src_is_u8, int C, int H, int W, double scale,
+                             const float *mean_host, float *dst_nhwc, int dstH, int dstW,
+                             int rH, int rW, int oy, int ox, int n, int flip_x, void *stream);
 /* segm_results / expand_boxes (models/mask_rcnn.py:44-107): mask_logits (D,M,M,Kc) NHWC head
  * outputs, label (D) foreground class per detection, bbox (D,4) yx in image coordinates ->
  * out (D,im_h,im_w) uint8 {0,1}: sigmoid, 1-pixel zero pad, box expanded by (M+2)/M and
@@ -802,6 +814,20 @@ int mrcnn_mask_targets(const uint8_t *masks, int G, int H, int W, const float *s
  * LDS). */
 int mrcnn_mask_resize_nearest(const uint64_t *packed, int G, int H, int W, const int32_t *ys,
                               const int32_t *xs, int outH, int outW, uint8_t *out, void *stream);
+/* The same for the S x S canvas of large-scale jitter: ys / xs (S) device
+ * tables in which a NEGATIVE entry means "outside the resized mask" (the canvas is padded there:
+ * 0 is written); entries >= 0 are clamped to H-1 / W-1 as above, so no read leaves the buffers
+ * whatever the tables hold.  out (G,S,S) uint8 {0,1}; box (G,4) int32 (y_lo, x_lo, y_hi, x_hi),
+ * half-open and tight around the pixels of out[g], (0,0,0,0) for an empty mask; area (G) int32
+ * pixel counts.  row_stats: (G,S,3) int32 of workspace (per-row x_lo, x_hi, count, reduced per
+ * instance by a second launch on the same stream: integers, in a fixed order).  Replaces the
+ * host resize and flip of datasets/transforms.py:resize_nearest followed by a crop / zero pad
+ * and utils.mask_to_bbox of the result (the reference's
+ * chainer_mask_rcnn/datasets/transforms.py:36-49 has the resize and flip only).  G = 0 is a no-op.
+ * H * W < 2^31, G * S * S < 2^31, W <= 524288. */
+int mrcnn_mask_resize_crop(const uint64_t *packed, int G, int H, int W, const int32_t *ys,
+                           const int32_t *xs, int S, uint8_t *out, int32_t *box, int32_t *area,
+                           int32_t *row_stats, void *stream);
 
 /* ---- Gradient exchange over RCCL / xGMI ---------------------------------------------- */
 /* Replaces ChainerMN's communicator as the reference uses it

@@ -77,6 +77,7 @@ def parse_args(argv=None):
     ap.add_argument('--device-masks', action='store_true',
                     help='ground-truth masks cross PCIe as bits and are resized / flipped by a HIP '
                          'kernel (COCO: the dataset also keeps them packed on the host)')
+    train_loop.add_scale_jitter_arguments(ap)
     ap.add_argument('--eval-bbox', action='store_true',
                     help='the evaluator also scores the boxes: validation/main/bbox/map joins the '
                          'log and the printed report (the best snapshot stays on the mask map)')
@@ -94,7 +95,9 @@ def parse_args(argv=None):
                     help='lr factor of update 0 with --warmup-iters')
     ap.add_argument('--logs-dir', default=osp.join(ROOT, 'logs'))
     ap.add_argument('--no-plot', action='store_true', help='do not write loss.png / accuracy.png')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    train_loop.scale_jitter_options(ap, args)
+    return args
 
 
 OMPI_TO_TORCH = (('OMPI_COMM_WORLD_RANK', 'RANK'), ('OMPI_COMM_WORLD_SIZE', 'WORLD_SIZE'),
@@ -265,6 +268,8 @@ def recorded_params(args):
     params = {k: v for k, v in vars(args).items() if k not in OPTIONAL_PARAMS or v}
     if not params.get('warmup_iters'):
         params.pop('warmup_factor', None)
+    if 'scale_jitter' in params:                      # (present only when given, with crop_size)
+        params['scale_jitter'] = [float(v) for v in params['scale_jitter']]
     return params
 
 
@@ -298,7 +303,8 @@ def assemble(args, comm, model, train_data, test_data, evaluator_type, synthetic
     test_data = cmr.datasets.scatter_dataset(test_data, comm.rank, comm.world,
                                              force_equal_length=False)
     train = train_loop.TransformDataset(train_data, cmr.datasets.MaskRCNNTransform(
-        model, device_masks=getattr(args, 'device_masks', False)))
+        model, device_masks=getattr(args, 'device_masks', False),
+        scale_jitter=getattr(args, 'scale_jitter', None), crop_size=getattr(args, 'crop_size', 1024)))
     test = train_loop.TransformDataset(test_data, cmr.datasets.MaskRCNNTransform(model, train=False))
     loop = train_loop.TrainLoop(train_loop.SerialIterator(train, args.batch_size_per_gpu),
                                 chain, opt, comm.device)

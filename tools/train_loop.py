@@ -26,6 +26,7 @@ gives bit-identical losses (tests/test_gpu_train_loop.py).
     python tools/train_loop.py --synthetic 64 --iterations 20        # in-memory synthetic examples
     python tools/train_loop.py --dataset sbd --sbd-root DIR --split train   # VOC settings (20 classes)
     python tools/train_loop.py --synthetic 64 --device-masks        # masks as bits, resized on the device
+    python tools/train_loop.py --synthetic 64 --device-masks --scale-jitter 0.1,2.0   # 1024 x 1024 crops
 """
 import functools
 import os
@@ -323,12 +324,53 @@ def norm_hooks(grad_clip=0., skip_nonfinite=False):
     return hooks
 
 
+def scale_jitter_range(text):
+    """``--scale-jitter LO,HI`` -> (lo, hi)."""
+    import argparse
+    try:
+        lo, hi = (float(v) for v in text.split(','))
+    except ValueError:
+        raise argparse.ArgumentTypeError('expected LO,HI (two numbers), got %r' % (text,))
+    if not 0 < lo <= hi:
+        raise argparse.ArgumentTypeError('needs 0 < LO <= HI, got %r' % (text,))
+    return lo, hi
+
+
+def add_scale_jitter_arguments(ap):
+    """--scale-jitter / --crop-size of this tool and tools/train.py.  Neither has an attribute
+    when it is not given (a default run's recorded arguments stay as they were): read them with
+    ``scale_jitter_options``."""
+    import argparse
+    ap.add_argument('--scale-jitter', type=scale_jitter_range, default=argparse.SUPPRESS,
+                    metavar='LO,HI',
+                    help='large-scale jitter: resize the longer side to r * crop size, r uniform in '
+                         '[LO, HI], then crop or zero-pad to the square (needs --device-masks; '
+                         'evaluation keeps min_size / max_size; off by default)')
+    ap.add_argument('--crop-size', type=int, default=argparse.SUPPRESS,
+                    help='side of the square training canvas of --scale-jitter (1024)')
+
+
+def scale_jitter_options(ap, args):
+    """(scale_jitter or None, crop_size) of the parsed ``args``; misuse ends in ``ap.error``.  With
+    jitter on, ``args`` carries both values afterwards."""
+    jitter, crop = getattr(args, 'scale_jitter', None), getattr(args, 'crop_size', 1024)
+    if jitter is not None and not args.device_masks:
+        ap.error('--scale-jitter needs --device-masks: the crops are built on the device')
+    if crop <= 0:
+        ap.error('--crop-size must be positive')
+    if jitter is not None:
+        args.crop_size = crop
+    return jitter, crop
+
+
 def build(dataset, n_layers=50, device='cuda:0', batch_size=2, seed=0, defer=5, prefetch=True,
-          world=1, pooling_func='align', model_settings='coco', device_masks=False):
+          world=1, pooling_func='align', model_settings='coco', device_masks=False,
+          scale_jitter=None, crop_size=1024):
     """Model, optimizer and loop as examples/train_common.py:135-231 builds them (COCO settings of
     examples/coco/train.py:36-38, or with ``model_settings='voc'`` those of
     examples/voc/train.py); ``pooling_func`` one of POOLING_FUNCS; ``device_masks``: the
-    ground-truth masks travel as bits and are resized on the device (MaskRCNNTransform)."""
+    ground-truth masks travel as bits and are resized on the device (MaskRCNNTransform);
+    ``scale_jitter`` = (lo, hi) with ``crop_size``: its large-scale jitter."""
     import bench
     import chainer_mask_rcnn_amd as cmr
     random.seed(seed)                                   # :135-136
@@ -348,7 +390,7 @@ def build(dataset, n_layers=50, device='cuda:0', batch_size=2, seed=0, defer=5, 
         raise ValueError('model_settings must be coco or voc, got %r' % (model_settings,))
     model.head.pooling_func = getattr(cmr.functions, POOLING_FUNCS[pooling_func])
     train_data = TransformDataset(dataset, cmr.datasets.MaskRCNNTransform(
-        model, device_masks=device_masks))
+        model, device_masks=device_masks, scale_jitter=scale_jitter, crop_size=crop_size))
     it = SerialIterator(train_data, batch_size)
     return TrainLoop(it, chain, opt, device, prefetch=prefetch), model, chain, opt
 
@@ -375,6 +417,7 @@ def main():
     ap.add_argument('--device-masks', action='store_true',
                     help='ground-truth masks cross PCIe as bits and are resized / flipped by a HIP '
                          'kernel (COCO: the dataset also keeps them packed on the host)')
+    add_scale_jitter_arguments(ap)
     ap.add_argument('--defer', type=int, default=5,
                     help='res5 weight gradients held back into the next step (0: none)')
     ap.add_argument('--grad-clip', type=float, default=0.,
@@ -382,6 +425,7 @@ def main():
     ap.add_argument('--skip-nonfinite', action='store_true',
                     help='optimizers.SkipNonFiniteUpdate (needs --defer 0)')
     args = ap.parse_args()
+    scale_jitter, crop_size = scale_jitter_options(ap, args)
     import chainer_mask_rcnn_amd as cmr
     if os.environ.get('TORCH_THREADS'):
         torch.set_num_threads(int(os.environ['TORCH_THREADS']))
@@ -402,7 +446,8 @@ def main():
     loop, model, chain, opt = build(data, args.layers, 'cuda:0', args.batch, args.seed,
                                     defer=args.defer, prefetch=not args.no_prefetch,
                                     pooling_func=args.pooling_func, model_settings=settings,
-                                    device_masks=args.device_masks)
+                                    device_masks=args.device_masks,
+                                    scale_jitter=scale_jitter, crop_size=crop_size)
     for hook in norm_hooks(args.grad_clip, args.skip_nonfinite):
         opt.add_hook(hook)            # (refused with deferred weight gradients: --defer 0)
     for _ in range(int(os.environ.get('WARMUP', 3))):
