@@ -13,6 +13,7 @@
 // arithmetic only, deterministic, no scratch.
 // Built with -ffp-contract=off.
 #include "common.h"
+#include "mask_box.h"
 #include "prepare_pixel.h"
 
 namespace {
@@ -41,22 +42,6 @@ __global__ void prepare_crop_kernel(const T *__restrict__ src, int C, int H, int
     }
 }
 
-__device__ __forceinline__ int wave_min(int v)
-{
-    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off));
-    return v;
-}
-__device__ __forceinline__ int wave_max(int v)
-{
-    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
-    return v;
-}
-__device__ __forceinline__ int wave_sum(int v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // One workgroup per `rows` consecutive output rows of one instance.  The source rows they read
 // are staged in LDS together (a padded row, ys[y] < 0, stages nothing); then every wave builds
 // whole output rows, four bytes per lane and step, stored as one dword.  As in gt_masks.hip the
@@ -64,6 +49,7 @@ __device__ __forceinline__ int wave_sum(int v)
 // ends are written as single bytes.  In-range table entries are clamped, so every read stays
 // inside the buffers.  Lane 0 of the wave leaves the row's (x_lo, x_hi, count) in row_stats
 // (x_hi half-open; an empty row has count 0): integer min / max / sum, the same for any order.
+// mask_box.h's mask_box_kernel, shared with copy_paste.hip, reduces them per instance.
 __global__ void __launch_bounds__(kThreads)
 mask_resize_crop_kernel(const uint64_t *__restrict__ packed, int H, int W, int Wq,
                         const int32_t *__restrict__ ys, const int32_t *__restrict__ xs, int S,
@@ -134,54 +120,6 @@ mask_resize_crop_kernel(const uint64_t *__restrict__ packed, int H, int W, int W
     }
 }
 
-// One workgroup per instance: its S row records -> box (y_lo, x_lo, y_hi, x_hi) and area.
-__global__ void __launch_bounds__(kThreads)
-mask_box_kernel(const int32_t *__restrict__ row_stats, int S, int32_t *__restrict__ box,
-                int32_t *__restrict__ area)
-{
-    __shared__ int s_part[kWaves][5];
-    const int g = blockIdx.x;
-    const int32_t *st = row_stats + (int64_t)g * S * 3;
-    int y_lo = S, x_lo = S, y_hi = 0, x_hi = 0, sum = 0;
-    for (int y = threadIdx.x; y < S; y += kThreads) {
-        const int count = st[3 * y + 2];
-        if (count > 0) {
-            y_lo = min(y_lo, y);
-            y_hi = y + 1;                             // y grows within a thread
-            x_lo = min(x_lo, st[3 * y]);
-            x_hi = max(x_hi, st[3 * y + 1]);
-            sum += count;
-        }
-    }
-    y_lo = wave_min(y_lo);
-    x_lo = wave_min(x_lo);
-    y_hi = wave_max(y_hi);
-    x_hi = wave_max(x_hi);
-    sum = wave_sum(sum);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        s_part[wave][0] = y_lo; s_part[wave][1] = x_lo; s_part[wave][2] = y_hi;
-        s_part[wave][3] = x_hi; s_part[wave][4] = sum;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kWaves; ++w) {
-            y_lo = min(y_lo, s_part[w][0]);
-            x_lo = min(x_lo, s_part[w][1]);
-            y_hi = max(y_hi, s_part[w][2]);
-            x_hi = max(x_hi, s_part[w][3]);
-            sum += s_part[w][4];
-        }
-        int32_t *b = box + 4 * g;
-        const bool any = sum > 0;
-        b[0] = any ? y_lo : 0;
-        b[1] = any ? x_lo : 0;
-        b[2] = any ? y_hi : 0;
-        b[3] = any ? x_hi : 0;
-        area[g] = sum;
-    }
-}
-
 }  // namespace
 
 extern "C" int mrcnn_prepare_image_crop(const void *src_chw, int src_is_u8, int C, int H, int W,
@@ -232,7 +170,7 @@ extern "C" int mrcnn_mask_resize_crop(const uint64_t *packed, int G, int H, int 
     hipLaunchKernelGGL(mask_resize_crop_kernel, dim3((unsigned)(G * groups)), dim3(kThreads),
                        (size_t)rows * Wq * 8, s, packed, H, W, Wq, ys, xs, S, rows, groups, out,
                        row_stats);
-    hipLaunchKernelGGL(mask_box_kernel, dim3((unsigned)G), dim3(kThreads), 0, s, row_stats, S, box,
-                       area);
+    hipLaunchKernelGGL(mask_box_kernel, dim3((unsigned)G), dim3(kMaskBoxThreads), 0, s, row_stats, S,
+                       box, area);
     return mrcnn::check_launch("mask_resize_crop");
 }

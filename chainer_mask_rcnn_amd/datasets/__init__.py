@@ -12,3 +12,4 @@ from .voc import VOC2012InstanceSeg, SBDInstanceSeg  # NOQA
 from .mask_rcnn import MaskRcnnDataset  # NOQA
 from .indexing_dataset import IndexingDataset  # NOQA
 from .scatter import scatter_dataset, SubDataset  # NOQA
+from .copy_paste import CopyPasteDataset, draw_paste_selection  # NOQA

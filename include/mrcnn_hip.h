@@ -828,6 +828,27 @@ int mrcnn_mask_resize_nearest(const uint64_t *packed, int G, int H, int W, const
 int mrcnn_mask_resize_crop(const uint64_t *packed, int G, int H, int W, const int32_t *ys,
                            const int32_t *xs, int S, uint8_t *out, int32_t *box, int32_t *area,
                            int32_t *row_stats, void *stream);
+/* Simple Copy-Paste (Ghiasi et al., 2021) on that canvas: the K instances
+ * idx[0..K) of a source example pasted onto a target example.  img_t, img_s, img_out: (S,S,3)
+ * NHWC fp32; masks_t (Gt,S,S), masks_s (Gs,S,S) uint8, a byte other than 0 counts as set; idx (K)
+ * int32, clamped to [0, Gs) on the device, so no read leaves masks_s whatever it holds.
+ *   alpha             = OR over k of masks_s[idx[k]]
+ *   img_out           = alpha ? img_s : img_t      a select of 32-bit patterns, never a blend:
+ *                                                  nothing of the unselected image reaches the output
+ *   masks_out[g]      = masks_t[g] & ~alpha        g < Gt
+ *   masks_out[Gt + k] = masks_s[idx[k]]            k < K, written as {0,1}
+ * box (Gt+K,4) / area (Gt+K) int32: mrcnn_mask_resize_crop's convention for masks_out.  Every
+ * byte of img_out, masks_out, box and area is written.  Workspace: row_stats (Gt+K,S,3) int32.
+ * Two launches on the stream (masks and image, each workgroup with the alpha of its own rows one
+ * bit per pixel in LDS; boxes), integers only on the mask side, no atomics.  K = 0, Gt = 0 and
+ * Gt + K = 0 are legal (the image is still written); a pointer may be null only where its count
+ * is 0.  K <= Gs, (Gt+K)*S*S < 2^31, and no output or workspace may overlap an input or another
+ * output (img_out == img_t is refused).  The reference has no copy-paste augmentation
+ * (chainer_mask_rcnn/datasets/transforms.py:10-51 transforms one example at a time). */
+int mrcnn_copy_paste(const float *img_t, const float *img_s, const uint8_t *masks_t, int Gt,
+                     const uint8_t *masks_s, int Gs, const int32_t *idx, int K, int S,
+                     float *img_out, uint8_t *masks_out, int32_t *box, int32_t *area,
+                     int32_t *row_stats, void *stream);
 
 /* ---- Gradient exchange over RCCL / xGMI ---------------------------------------------- */
 /* Replaces ChainerMN's communicator as the reference uses it

@@ -78,6 +78,7 @@ def parse_args(argv=None):
                     help='ground-truth masks cross PCIe as bits and are resized / flipped by a HIP '
                          'kernel (COCO: the dataset also keeps them packed on the host)')
     train_loop.add_scale_jitter_arguments(ap)
+    train_loop.add_copy_paste_argument(ap)
     ap.add_argument('--eval-bbox', action='store_true',
                     help='the evaluator also scores the boxes: validation/main/bbox/map joins the '
                          'log and the printed report (the best snapshot stays on the mask map)')
@@ -97,6 +98,7 @@ def parse_args(argv=None):
     ap.add_argument('--no-plot', action='store_true', help='do not write loss.png / accuracy.png')
     args = ap.parse_args(argv)
     train_loop.scale_jitter_options(ap, args)
+    train_loop.copy_paste_option(ap, args)
     return args
 
 
@@ -305,6 +307,8 @@ def assemble(args, comm, model, train_data, test_data, evaluator_type, synthetic
     train = train_loop.TransformDataset(train_data, cmr.datasets.MaskRCNNTransform(
         model, device_masks=getattr(args, 'device_masks', False),
         scale_jitter=getattr(args, 'scale_jitter', None), crop_size=getattr(args, 'crop_size', 1024)))
+    if getattr(args, 'copy_paste', None) is not None:   # the partner comes from the rank's own shard
+        train = cmr.datasets.CopyPasteDataset(train, args.copy_paste)
     test = train_loop.TransformDataset(test_data, cmr.datasets.MaskRCNNTransform(model, train=False))
     loop = train_loop.TrainLoop(train_loop.SerialIterator(train, args.batch_size_per_gpu),
                                 chain, opt, comm.device)

@@ -363,14 +363,46 @@ def scale_jitter_options(ap, args):
     return jitter, crop
 
 
+def copy_paste_probability(text):
+    """``--copy-paste P`` -> P."""
+    import argparse
+    try:
+        p = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('expected a probability, got %r' % (text,))
+    if not 0 < p <= 1:
+        raise argparse.ArgumentTypeError('needs 0 < P <= 1, got %r' % (text,))
+    return p
+
+
+def add_copy_paste_argument(ap):
+    """--copy-paste of this tool and tools/train.py; no attribute when it is not given, like
+    --scale-jitter: read it with ``copy_paste_option``."""
+    import argparse
+    ap.add_argument('--copy-paste', type=copy_paste_probability, default=argparse.SUPPRESS,
+                    metavar='P',
+                    help='copy-paste augmentation: with probability P, instances of another training '
+                         'example are pasted onto the example on the device (needs --scale-jitter: '
+                         'both examples lie on its square; training data only; off by default)')
+
+
+def copy_paste_option(ap, args):
+    """The probability of the parsed ``args`` or None; misuse ends in ``ap.error``."""
+    prob = getattr(args, 'copy_paste', None)
+    if prob is not None and getattr(args, 'scale_jitter', None) is None:
+        ap.error('--copy-paste needs --scale-jitter: examples are pasted on its fixed-size canvas')
+    return prob
+
+
 def build(dataset, n_layers=50, device='cuda:0', batch_size=2, seed=0, defer=5, prefetch=True,
           world=1, pooling_func='align', model_settings='coco', device_masks=False,
-          scale_jitter=None, crop_size=1024):
+          scale_jitter=None, crop_size=1024, copy_paste=None):
     """Model, optimizer and loop as examples/train_common.py:135-231 builds them (COCO settings of
     examples/coco/train.py:36-38, or with ``model_settings='voc'`` those of
     examples/voc/train.py); ``pooling_func`` one of POOLING_FUNCS; ``device_masks``: the
     ground-truth masks travel as bits and are resized on the device (MaskRCNNTransform);
-    ``scale_jitter`` = (lo, hi) with ``crop_size``: its large-scale jitter."""
+    ``scale_jitter`` = (lo, hi) with ``crop_size``: its large-scale jitter; ``copy_paste`` = P: the
+    jittered examples go through ``datasets.CopyPasteDataset(prob=P)``."""
     import bench
     import chainer_mask_rcnn_amd as cmr
     random.seed(seed)                                   # :135-136
@@ -391,6 +423,8 @@ def build(dataset, n_layers=50, device='cuda:0', batch_size=2, seed=0, defer=5, 
     model.head.pooling_func = getattr(cmr.functions, POOLING_FUNCS[pooling_func])
     train_data = TransformDataset(dataset, cmr.datasets.MaskRCNNTransform(
         model, device_masks=device_masks, scale_jitter=scale_jitter, crop_size=crop_size))
+    if copy_paste is not None:
+        train_data = cmr.datasets.CopyPasteDataset(train_data, copy_paste)
     it = SerialIterator(train_data, batch_size)
     return TrainLoop(it, chain, opt, device, prefetch=prefetch), model, chain, opt
 
@@ -418,6 +452,7 @@ def main():
                     help='ground-truth masks cross PCIe as bits and are resized / flipped by a HIP '
                          'kernel (COCO: the dataset also keeps them packed on the host)')
     add_scale_jitter_arguments(ap)
+    add_copy_paste_argument(ap)
     ap.add_argument('--defer', type=int, default=5,
                     help='res5 weight gradients held back into the next step (0: none)')
     ap.add_argument('--grad-clip', type=float, default=0.,
@@ -426,6 +461,7 @@ def main():
                     help='optimizers.SkipNonFiniteUpdate (needs --defer 0)')
     args = ap.parse_args()
     scale_jitter, crop_size = scale_jitter_options(ap, args)
+    copy_paste = copy_paste_option(ap, args)
     import chainer_mask_rcnn_amd as cmr
     if os.environ.get('TORCH_THREADS'):
         torch.set_num_threads(int(os.environ['TORCH_THREADS']))
@@ -447,7 +483,8 @@ def main():
                                     defer=args.defer, prefetch=not args.no_prefetch,
                                     pooling_func=args.pooling_func, model_settings=settings,
                                     device_masks=args.device_masks,
-                                    scale_jitter=scale_jitter, crop_size=crop_size)
+                                    scale_jitter=scale_jitter, crop_size=crop_size,
+                                    copy_paste=copy_paste)
     for hook in norm_hooks(args.grad_clip, args.skip_nonfinite):
         opt.add_hook(hook)            # (refused with deferred weight gradients: --defer 0)
     for _ in range(int(os.environ.get('WARMUP', 3))):
