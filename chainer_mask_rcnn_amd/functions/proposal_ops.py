@@ -99,6 +99,68 @@ def nms_sorted_batched(bbox, n_dev, thresh, limit=0):
     return keep, n_keep
 
 
+SOFT_NMS_METHODS = {'hard': 0, 'linear': 1, 'gaussian': 2}      # MRCNN_SOFT_NMS_*
+
+
+def soft_nms_method(method):
+    """'hard' / 'linear' / 'gaussian' (or the MRCNN_SOFT_NMS_* integer) -> the integer."""
+    if method in SOFT_NMS_METHODS:
+        return SOFT_NMS_METHODS[method]
+    if isinstance(method, int) and not isinstance(method, bool) and method in SOFT_NMS_METHODS.values():
+        return method
+    raise ValueError("soft_nms: method must be one of %s, got %r"
+                     % (sorted(SOFT_NMS_METHODS), method))
+
+
+def _require_array(name, t, dtype, shape):
+    """The C ABI reads raw pointers: a wrong dtype or shape would read out of bounds."""
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise ValueError('%s must be %s of shape %s, got %s %s'
+                         % (name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
+    return t.contiguous()
+
+
+def soft_nms_sorted_batched(bbox, prob, n_dev, method, overlap_thresh=0.3, sigma=0.5,
+                            min_score=0.001, limit=0):
+    """Soft-NMS (Detectron's cpu_soft_nms) over boxes sorted per group: bbox (G, n_max, 4), prob
+    (G, n_max), n_dev (G,) int32.  Returns keep (G, n_max) = rows in emission order, n_keep (G,)
+    and soft_prob (G, n_max) = the decayed score of every row."""
+    _lib.require_device(bbox, prob, n_dev)
+    method = soft_nms_method(method)
+    if bbox.dim() != 3 or bbox.shape[2] != 4:
+        raise ValueError('bbox must be (G, n_max, 4), got %s' % (tuple(bbox.shape),))
+    G, n_max = bbox.shape[0], bbox.shape[1]
+    bbox = _require_array('bbox', bbox, torch.float32, (G, n_max, 4))
+    prob = _require_array('prob', prob, torch.float32, (G, n_max))
+    n_dev = _require_array('n_dev', n_dev, torch.int32, (G,))
+    keep = torch.empty((G, max(n_max, 1)), dtype=torch.int32, device=bbox.device)
+    n_keep = torch.empty((G,), dtype=torch.int32, device=bbox.device)
+    soft_prob = torch.empty((G, max(n_max, 1)), dtype=torch.float32, device=bbox.device)
+    _lib.call('mrcnn_soft_nms_sorted_batched', _lib.ptr(bbox), _lib.ptr(prob), _lib.ptr(n_dev), G,
+              n_max, method, float(overlap_thresh), float(sigma), float(min_score), int(limit or 0),
+              _lib.ptr(keep), _lib.ptr(n_keep), _lib.ptr(soft_prob), _lib.stream_ptr())
+    return keep, n_keep, soft_prob
+
+
+def box_vote(bbox, prob, n_dev, keep, n_keep, vote_thresh=0.8):
+    """Bounding-box voting (Detectron's box_voting, scoring method ID): every kept row becomes the
+    mean, weighted by the undecayed ``prob``, of its group's boxes with IoU >= vote_thresh.
+    Returns voted (G, n_max, 4), written at the kept rows only."""
+    _lib.require_device(bbox, prob, n_dev, keep, n_keep)
+    if bbox.dim() != 3 or bbox.shape[2] != 4:
+        raise ValueError('bbox must be (G, n_max, 4), got %s' % (tuple(bbox.shape),))
+    G, n_max = bbox.shape[0], bbox.shape[1]
+    bbox = _require_array('bbox', bbox, torch.float32, (G, n_max, 4))
+    prob = _require_array('prob', prob, torch.float32, (G, n_max))
+    n_dev = _require_array('n_dev', n_dev, torch.int32, (G,))
+    keep = _require_array('keep', keep, torch.int32, (G, max(n_max, 1)))
+    n_keep = _require_array('n_keep', n_keep, torch.int32, (G,))
+    voted = torch.empty((G, max(n_max, 1), 4), dtype=torch.float32, device=bbox.device)
+    _lib.call('mrcnn_box_vote', _lib.ptr(bbox), _lib.ptr(prob), _lib.ptr(n_dev), _lib.ptr(keep),
+              _lib.ptr(n_keep), G, n_max, float(vote_thresh), _lib.ptr(voted), _lib.stream_ptr())
+    return voted
+
+
 def non_maximum_suppression(bbox, thresh, score=None, limit=None):
     """Suppress bounding boxes according to their IoUs (chainercv semantics).
 
@@ -118,3 +180,34 @@ def non_maximum_suppression(bbox, thresh, score=None, limit=None):
     if order is not None:
         keep = order[keep.long()]
     return keep
+
+
+def soft_nms(bbox, score, method='linear', overlap_thresh=0.3, sigma=0.5, min_score=0.001,
+             limit=None):
+    """Soft-NMS of one set of boxes (Detectron's ``soft_nms``; Bodla et al. 2017).
+
+    bbox: (R, 4) float32 device tensor (y_min, x_min, y_max, x_max), score: (R,) finite and
+    non-negative.  Returns (indices, new_scores): int32 indices into the caller's order, in
+    emission order (non-increasing decayed score; ties: lower index first), and their decayed
+    float32 scores.
+    """
+    _lib.require_device(bbox, score)
+    method = soft_nms_method(method)
+    if bbox.dim() != 2 or bbox.shape[1] != 4 or tuple(score.shape) != (bbox.shape[0],):
+        raise ValueError('bbox must be (R, 4) and score (R,), got %s and %s'
+                         % (tuple(bbox.shape), tuple(score.shape)))
+    R = bbox.shape[0]
+    if R == 0:
+        return (torch.zeros((0,), dtype=torch.int32, device=bbox.device),
+                torch.zeros((0,), dtype=torch.float32, device=bbox.device))
+    # the kernels read float32: other floating types are converted, not reinterpreted
+    bbox, score = bbox.to(torch.float32), score.to(torch.float32)
+    order, _ = topk_desc(score, R)
+    sorted_bbox = gather_rows(bbox, order)
+    sorted_score = gather_rows(score.reshape(R, 1), order).reshape(R)
+    n_dev = torch.full((1,), R, dtype=torch.int32, device=bbox.device)
+    keep, n_keep, soft_prob = soft_nms_sorted_batched(
+        sorted_bbox[None], sorted_score[None], n_dev, method, overlap_thresh, sigma, min_score,
+        limit or 0)
+    keep = keep[0, :int(n_keep.item())].long()
+    return order[keep], soft_prob[0][keep]

@@ -35,6 +35,13 @@ class MaskRCNN(torch.nn.Module):
 
         self.nms_thresh = 0.5
         self.score_thresh = 0.05
+        # Detectron's test-time options (TEST.SOFT_NMS, TEST.BBOX_VOTE), off by default: set
+        # after construction like nms_thresh and score_thresh
+        self.soft_nms = None                # None, 'linear' or 'gaussian' (at most 4096 RoIs per image)
+        self.soft_nms_thresh = 0.3          # linear: the IoU from which scores decay
+        self.soft_nms_sigma = 0.5           # gaussian
+        self.soft_nms_min_score = 0.001     # rows decayed below it are dropped
+        self.bbox_vote_thresh = None        # None, or the IoU of a vote (Detectron: 0.8)
 
         self._detections_per_im = detections_per_im
 
@@ -54,8 +61,17 @@ class MaskRCNN(torch.nn.Module):
     def _suppress_queue(self, cls_bbox, prob):
         """Device half of the per-class score threshold + NMS (:178-202) for one image, all
         classes batched: queues the kernels and returns the device results without
-        synchronising.  cls_bbox (R, n_class, 4), prob (R, n_class) device tensors."""
+        synchronising.  cls_bbox (R, n_class, 4), prob (R, n_class) device tensors.
+        With ``soft_nms`` set the Soft-NMS launch stands in the place of the NMS launch, with
+        ``bbox_vote_thresh`` set the vote launch follows either; with both off (the default) the
+        launches are the reference's rule and nothing else."""
+        if self.soft_nms is not None and self.soft_nms not in ('linear', 'gaussian'):
+            raise ValueError("soft_nms must be None, 'linear' or 'gaussian', got %r"
+                             % (self.soft_nms,))
         R = cls_bbox.shape[0]
+        if self.soft_nms is not None and R > 4096:
+            raise ValueError('soft_nms handles at most 4096 RoIs per image (mrcnn_soft_nms_sorted_'
+                             'batched keeps a class in one workgroup), got %d' % R)
         n_fg = self.n_class - 1
         dev = cls_bbox.device
         sorted_boxes = torch.empty((n_fg, max(R, 1), 4), dtype=torch.float32, device=dev)
@@ -67,7 +83,19 @@ class MaskRCNN(torch.nn.Module):
         _lib.call('mrcnn_detect_sort', _lib.ptr(prob), _lib.ptr(cls_bbox),
                   R, self.n_class, float(self.score_thresh), _lib.ptr(sorted_boxes),
                   _lib.ptr(sorted_prob), _lib.ptr(counts), _lib.ptr(ws), _lib.stream_ptr())
-        keep, n_keep = P.nms_sorted_batched(sorted_boxes, counts, self.nms_thresh)
+        undecayed = sorted_prob
+        if self.soft_nms is None:
+            keep, n_keep = P.nms_sorted_batched(sorted_boxes, counts, self.nms_thresh)
+        else:
+            # scores decay instead of rows being deleted; the decayed scores go to compact
+            keep, n_keep, sorted_prob = P.soft_nms_sorted_batched(
+                sorted_boxes, undecayed, counts, self.soft_nms, self.soft_nms_thresh,
+                self.soft_nms_sigma, self.soft_nms_min_score)
+        if self.bbox_vote_thresh is not None:
+            # every kept box becomes the mean of the candidates that overlap it, weighted by
+            # their undecayed scores; compact reads the kept rows only
+            sorted_boxes = P.box_vote(sorted_boxes, undecayed, counts, keep, n_keep,
+                                      self.bbox_vote_thresh)
         # pack the kept rows of all classes on the device: the host then reads one count and
         # D rows instead of four (n_fg, R) arrays
         cap = n_fg * max(R, 1)

@@ -547,6 +547,44 @@ int mrcnn_detect_sort(const float *prob, const float *cls_bbox, int R, int n_cla
                       float thresh, float *sorted_boxes, float *sorted_prob,
                       int32_t *counts, void *ws, void *stream);
 
+/* Soft-NMS (Bodla et al. 2017) in the place of mrcnn_nms_sorted_batched: replaces Detectron's
+ * utils/cython_nms.pyx:cpu_soft_nms (TEST.SOFT_NMS), all classes in one launch.  sorted_boxes
+ * (groups, n_max, 4), sorted_prob (groups, n_max) and counts (groups) as mrcnn_detect_sort writes
+ * them.  Per group, with s an fp32 copy of the first counts[g] scores and every row alive:
+ *   repeat: i = the alive row with the largest s (ties: the lowest row); stop if no row is alive,
+ *           or not (s[i] >= min_score), or `limit` (> 0) picks were made; emit i, alive[i] = false;
+ *           for every alive j: s[j] = s[j] * w(iou(box_i, box_j))        (one fp32 multiply)
+ *   w hard:     iou >= overlap_thresh ? 0 : 1
+ *   w linear:   iou >= overlap_thresh ? 1 - iou : 1                      (fp32)
+ *   w gaussian: iou > 0 ? (float)exp(-((double)iou * (double)iou) / (double)sigma) : 1
+ * iou is the fp32 expression of mrcnn_nms_sorted (a NaN IoU, from zero-area boxes, gives weight 1),
+ * so method hard emits the rows mrcnn_nms_sorted_batched keeps.  cpu_soft_nms swaps the maximum to
+ * the front and prunes rows below min_score after every pick; scores only fall, so this rule emits
+ * the same rows in the same order with the same scores, and fixes the order of equal scores.
+ * Writes keep (groups, n_max) = rows in emission order, n_keep (groups) and soft_prob
+ * (groups, n_max) = the score every row had when it was emitted or, if it never was, when the loop
+ * ended (rows >= counts[g] are not written); mrcnn_detect_compact takes soft_prob as its
+ * sorted_prob.  Input contract: scores finite and non-negative (mrcnn_detect_sort's
+ * `prob > thresh`), sigma > 0 for the gaussian method (unused by the others), n_max <= 4096. */
+#define MRCNN_SOFT_NMS_HARD     0
+#define MRCNN_SOFT_NMS_LINEAR   1
+#define MRCNN_SOFT_NMS_GAUSSIAN 2
+int mrcnn_soft_nms_sorted_batched(const float *sorted_boxes, const float *sorted_prob,
+                                  const int32_t *counts, int groups, int n_max, int method,
+                                  float overlap_thresh, float sigma, float min_score, int limit,
+                                  int32_t *keep, int32_t *n_keep, float *soft_prob, void *stream);
+/* Bounding-box voting behind either suppression: replaces Detectron's utils/boxes.py:box_voting
+ * with scoring method ID (TEST.BBOX_VOTE; scores are not changed).  For every kept row
+ * k = keep[g][q], q < n_keep[g]: over j = 0 .. counts[g] - 1 in row order, every j with
+ * iou(box_k, box_j) >= vote_thresh adds w = (double)sorted_prob[g][j] (the undecayed score) to wsum
+ * and w * (double)box_j[c] to acc[c]; voted_boxes[g][k][c] = (float)(acc[c] / wsum), or box_k
+ * unchanged when wsum == 0 (a zero-area box overlaps nothing, itself included).  Only the kept rows
+ * of voted_boxes (groups, n_max, 4) are written; mrcnn_detect_compact takes it as its
+ * sorted_boxes. */
+int mrcnn_box_vote(const float *sorted_boxes, const float *sorted_prob, const int32_t *counts,
+                   const int32_t *keep, const int32_t *n_keep, int groups, int n_max,
+                   float vote_thresh, float *voted_boxes, void *stream);
+
 /* ---- Image I/O at both ends of predict (device restatement of the reference's cv2 calls) ---- */
 /* MaskRCNN.prepare (models/mask_rcnn.py:152-176) for one image + its slot in the zero-padded
  * batch (datasets/concat_examples.py:20-26): bilinear resize by `scale` (OpenCV INTER_LINEAR

@@ -17,6 +17,10 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tools'))
+
+from evaluate import (add_postprocessing_flags, apply_postprocessing_flags,  # noqa: E402
+                      check_postprocessing_flags)
 
 POOLING_FUNCS = {'align': 'roi_align_2d', 'pooling': 'roi_pooling_2d', 'resize': 'crop_and_resize'}
 
@@ -34,7 +38,9 @@ def main():
                     help='text file with one foreground class name per line (default: the VOC '
                          'names for --dataset voc, class0..class79 for coco)')
     ap.add_argument('--out', default='demo_out', help='output directory')
+    add_postprocessing_flags(ap)
     args = ap.parse_args()
+    check_postprocessing_flags(ap, args)
     if not (args.snapshot or args.detectron):
         ap.error('--snapshot or --detectron is required')
 
@@ -62,6 +68,7 @@ def main():
     else:
         serializers.load_detectron(args.detectron, model, n_layers=args.layers)
     model.eval()
+    apply_postprocessing_flags(model, args)
     os.makedirs(args.out, exist_ok=True)
 
     for img_file in args.img:

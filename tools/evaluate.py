@@ -11,6 +11,7 @@ examples/evaluate_common.py + examples/coco/evaluate.py.
     python tools/evaluate.py --coco-root DIR --split test-dev --detectron model.pkl --save-results res.json
     python tools/evaluate.py --coco-root DIR --results res.json   # score a results file (no model)
     python tools/evaluate.py --synthetic 16 --iou-types segm,bbox   # box AP beside mask AP
+    python tools/evaluate.py --coco-root DIR --detectron model.pkl --soft-nms linear --bbox-vote 0.8
 
 Runs the evaluator (predicted masks stay on the device; extensions/), prints the report and
 the seconds per image spent in prediction and in evaluation, and writes the result as YAML (or
@@ -21,6 +22,9 @@ does not score.  ``--results`` scores such a file against the annotations alone.
 ``--iou-types segm,bbox`` adds the box AP block (``validation/main/bbox/...``: the predicted boxes
 against the dataset's boxes, IoU tables from the device); ``--iou-types bbox`` alone skips the mask
 work, and with ``--save-results`` then writes a bbox-only file, the detection track's format.
+``--soft-nms {linear,gaussian}`` and ``--bbox-vote THRESH`` turn on Detectron's test-time options
+(TEST.SOFT_NMS, TEST.BBOX_VOTE; both decided on the device); the values
+used are written into the result file as ``postprocessing``.
 """
 import argparse
 import json
@@ -64,6 +68,62 @@ def _iou_types(text):
     if not types or any(t not in ('segm', 'bbox') for t in types) or len(set(types)) != len(types):
         raise argparse.ArgumentTypeError("a comma-separated subset of 'segm,bbox', got %r" % text)
     return types
+
+
+def add_postprocessing_flags(ap):
+    """Detectron's test-time options of MaskRCNN (soft_nms, bbox_vote_thresh): off by default."""
+    ap.add_argument('--soft-nms', default=None, choices=['linear', 'gaussian'],
+                    help='Soft-NMS in the place of the hard per-class NMS (Detectron TEST.SOFT_NMS): '
+                         'scores of overlapping boxes decay instead of the boxes being deleted')
+    ap.add_argument('--soft-nms-thresh', type=float, default=None, metavar='IOU',
+                    help='linear Soft-NMS: the IoU from which a score decays (model default 0.3); '
+                         'needs --soft-nms linear')
+    ap.add_argument('--soft-nms-sigma', type=float, default=None, metavar='SIGMA',
+                    help='gaussian Soft-NMS sigma (model default 0.5); needs --soft-nms gaussian')
+    ap.add_argument('--soft-nms-min-score', type=float, default=None, metavar='SCORE',
+                    help='Soft-NMS drops a box once its score has decayed below this (model '
+                         'default 0.001); needs --soft-nms')
+    ap.add_argument('--bbox-vote', type=float, default=None, metavar='THRESH',
+                    help='bounding-box voting (Detectron TEST.BBOX_VOTE, 0.8 there): each kept box '
+                         'becomes the score-weighted mean of the candidates with IoU >= THRESH')
+
+
+def check_postprocessing_flags(ap, args, no_model=False):
+    """A flag that would be ignored is an error, not a silent no-op."""
+    given = [flag for flag, value in (('--soft-nms', args.soft_nms),
+                                      ('--soft-nms-thresh', args.soft_nms_thresh),
+                                      ('--soft-nms-sigma', args.soft_nms_sigma),
+                                      ('--soft-nms-min-score', args.soft_nms_min_score),
+                                      ('--bbox-vote', args.bbox_vote)) if value is not None]
+    if no_model and given:
+        ap.error('%s: nothing is predicted when a results file is scored' % ', '.join(given))
+    if args.soft_nms is None and given and given != ['--bbox-vote']:
+        ap.error('%s given without --soft-nms' % ', '.join(f for f in given if f != '--bbox-vote'))
+    if args.soft_nms_thresh is not None and args.soft_nms != 'linear':
+        ap.error('--soft-nms-thresh is the linear method\'s (got --soft-nms %s)' % args.soft_nms)
+    if args.soft_nms_sigma is not None and args.soft_nms != 'gaussian':
+        ap.error('--soft-nms-sigma is the gaussian method\'s (got --soft-nms %s)' % args.soft_nms)
+    if args.soft_nms_sigma is not None and not args.soft_nms_sigma > 0:
+        ap.error('--soft-nms-sigma must be positive')
+
+
+def apply_postprocessing_flags(model, args):
+    """Set the model's attributes from the flags; returns what is in force, for the result file."""
+    if getattr(args, 'soft_nms', None):
+        model.soft_nms = args.soft_nms
+        for flag, attr in (('soft_nms_thresh', 'soft_nms_thresh'), ('soft_nms_sigma', 'soft_nms_sigma'),
+                           ('soft_nms_min_score', 'soft_nms_min_score')):
+            if getattr(args, flag, None) is not None:
+                setattr(model, attr, float(getattr(args, flag)))
+    if getattr(args, 'bbox_vote', None) is not None:
+        model.bbox_vote_thresh = float(args.bbox_vote)
+    used = {'nms_thresh': float(model.nms_thresh), 'score_thresh': float(model.score_thresh),
+            'soft_nms': model.soft_nms, 'bbox_vote_thresh': model.bbox_vote_thresh}
+    if model.soft_nms:
+        used.update(soft_nms_thresh=float(model.soft_nms_thresh),
+                    soft_nms_sigma=float(model.soft_nms_sigma),
+                    soft_nms_min_score=float(model.soft_nms_min_score))
+    return used
 
 
 def _print_result(result):
@@ -116,7 +176,9 @@ def main():
     ap.add_argument('--iou-types', type=_iou_types, default=('segm',), metavar='segm[,bbox]',
                     help='what to score: mask AP (segm), box AP (bbox) or both; with --results, '
                          'each type is scored from the file')
+    add_postprocessing_flags(ap)
     args = ap.parse_args()
+    check_postprocessing_flags(ap, args, no_model=bool(args.results))
     if args.results:
         if args.coco_root is None:
             ap.error('--results needs --coco-root')
@@ -177,6 +239,7 @@ def main():
             n_class = len(class_names) + 1
             model.head.cls_loc_score.W[4 * n_class:5 * n_class] *= 60.
     model.eval()
+    postprocessing = apply_postprocessing_flags(model, args)
 
     transform = cmr.datasets.MaskRCNNTransform(model, train=False)
     n = len(data) if not args.limit else min(args.limit, len(data))
@@ -215,7 +278,8 @@ def main():
     out = args.out or ((weights + '.eval_result.yaml') if weights else
                        'synthetic.eval_result.yaml')
     payload = {'result': result, 'timing': timing, 'evaluator': args.evaluator,
-               'weights': weights, 'split': None if args.synthetic else args.split}
+               'weights': weights, 'split': None if args.synthetic else args.split,
+               'postprocessing': postprocessing}
     if args.save_results:
         payload['results_file'] = os.path.abspath(args.save_results)
     try:
@@ -325,6 +389,7 @@ def evaluate_log_dir(args):
         min_size=params['min_size'], max_size=params['max_size'],
         roi_size=params['roi_size']).to(dev)
     model.eval()
+    postprocessing = apply_postprocessing_flags(model, args)
     transform = cmr.datasets.MaskRCNNTransform(model, train=False)
 
     class DummyTrainer(object):
@@ -357,14 +422,16 @@ def evaluate_log_dir(args):
             batches, model, label_names=class_names, results_sink=writer, **kw)
     result = {k: float(v) for k, v in evaluator.evaluate().items()}
     yaml_file = pretrained_model + '.eval_result.yaml'
-    with open(yaml_file, 'w') as f:
-        yaml.safe_dump(result, f, default_flow_style=False)
+    # one dump: the metrics as they always were, then whatever else describes the run
+    payload = dict(result)
+    if postprocessing['soft_nms'] or postprocessing['bbox_vote_thresh'] is not None:
+        payload['postprocessing'] = postprocessing
     if writer is not None:
         writer.close()
         print('Saved results: %s (%d entries)' % (writer.path, writer.n_entries))
-        with open(yaml_file, 'a') as f:
-            yaml.safe_dump({'results_file': os.path.abspath(writer.path)}, f,
-                           default_flow_style=False)
+        payload['results_file'] = os.path.abspath(writer.path)
+    with open(yaml_file, 'w') as f:
+        yaml.safe_dump(payload, f, default_flow_style=False)
     print('Saved evaluation:', yaml_file)
     _print_result(result)
     return result
