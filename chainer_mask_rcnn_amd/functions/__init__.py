@@ -7,6 +7,7 @@ from .affine_channel_2d import AffineChannel2DFunction
 from .roi_align_2d import roi_align_2d
 from .roi_align_2d import ROIAlign2D
 from .roi_align_2d import spatial_order as roi_spatial_order
+from .roi_align_2d import RoiHints
 
 from .roi_pooling_2d import roi_pooling_2d
 from .roi_pooling_2d import ROIPooling2D

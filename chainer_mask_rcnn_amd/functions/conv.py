@@ -927,10 +927,10 @@ class _StageFn(torch.autograd.Function):
 
     # inputs of forward in front of *params (x .. records_graph): a change of the signature below
     # changes this number, and nothing else
-    FIXED_INPUTS = 7
+    FIXED_INPUTS = 8
 
     @staticmethod
-    def forward(ctx, x, strides, proj, poll, tail_rows, roi, records_graph, *params):
+    def forward(ctx, x, strides, proj, poll, tail_rows, tail_slot, roi, records_graph, *params):
         """``roi`` (a ``RoiSpec`` or None): with it ``x`` is the FEATURE MAP and block 0 (which must
         have a projection shortcut) runs its two 1x1 convolutions on the map and pools their outputs
         (projected pooling, see above) — the stage then equals ``stage(roi_align(x, roi))``.
@@ -941,7 +941,8 @@ class _StageFn(torch.autograd.Function):
         the node then returns ``(average_pooling(y) (N,C,1,1), y[tail_rows])`` instead of the
         stage output y (the RoI head's two consumers of res5, models/mask_rcnn_resnet.py:186-195),
         and its backward forms the gradient entering the last block from both in ONE pass,
-        ReLU mask included (``mrcnn_head_tail_bwd``); ``records_graph``: torch.is_grad_enabled()
+        ReLU mask included (``mrcnn_head_tail_bwd``); ``tail_slot``: the int32 table row -> position
+        among ``tail_rows`` (-1 elsewhere), None = built here; ``records_graph``: torch.is_grad_enabled()
         at the call (in here grad mode is always off and ctx.needs_input_grad reports the inputs'
         requires_grad flags even under torch.no_grad()); ``params``: per block
         W1,s1,b1,W2,s2,b2,W3,s3,b3 (+ W4,s4,b4 when proj[i])."""
@@ -1014,11 +1015,10 @@ class _StageFn(torch.autograd.Function):
             _lib.call('mrcnn_avgpool_fwd', _lib.ptr(h), _lib.ptr(pooled), R_, h.shape[2] * h.shape[3],
                       C_, _lib.stream_ptr())
             sub = h.permute(0, 2, 3, 1).index_select(0, tail_rows).permute(0, 3, 1, 2)
-            slot = getattr(tail_rows, '_mrcnn_slot', None)     # built on the host by the caller
-            if slot is None:
-                slot = torch.full((R_,), -1, dtype=torch.int32, device=h.device)
-                slot[tail_rows] = torch.arange(tail_rows.numel(), dtype=torch.int32, device=h.device)
-            ctx.tail_slot = slot
+            if tail_slot is None:
+                tail_slot = torch.full((R_,), -1, dtype=torch.int32, device=h.device)
+                tail_slot[tail_rows] = torch.arange(tail_rows.numel(), dtype=torch.int32, device=h.device)
+            ctx.tail_slot = tail_slot
         if ctx.tail:
             return pooled.reshape(R_, C_, 1, 1), sub
         return h
@@ -1114,11 +1114,11 @@ class _StageFn(torch.autograd.Function):
         return tuple(grads)
 
 
-def building_block(x, blocks, first_stride=None, poll=None, tail_rows=None, roi=None):
+def building_block(x, blocks, first_stride=None, poll=None, tail_rows=None, roi=None, tail_slot=None):
     """A chain of Bottleneck links (chainer BuildingBlock) as one fused autograd node.  With
     ``tail_rows`` (int64 row indices) it returns ``(average_pooling_2d(y, map size), y[tail_rows])``
-    instead of y — see _StageFn.forward.  With ``roi`` (a ``RoiSpec``) ``x`` is the feature map and
-    the result is ``building_block(roi_align(x, roi), ...)`` (projected pooling)."""
+    instead of y (``tail_slot``: their optional slot table) — see _StageFn.forward.  With ``roi``
+    (a ``RoiSpec``) ``x`` is the feature map and the result is ``building_block(roi_align(x, roi), ...)`` (projected pooling)."""
     strides, proj, params = [], [], []
     for i, b in enumerate(blocks):
         strides.append(b.conv1.stride if not (i == 0 and first_stride is not None) else first_stride)
@@ -1127,5 +1127,5 @@ def building_block(x, blocks, first_stride=None, poll=None, tail_rows=None, roi=
                    b.conv3.W, b.bn3.W, b.bn3.b]
         if b.projection:
             params += [b.conv4.W, b.bn4.W, b.bn4.b]
-    return _StageFn.apply(x, tuple(strides), tuple(proj), poll, tail_rows, roi,
+    return _StageFn.apply(x, tuple(strides), tuple(proj), poll, tail_rows, tail_slot, roi,
                           torch.is_grad_enabled(), *params)

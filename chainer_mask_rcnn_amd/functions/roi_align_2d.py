@@ -6,6 +6,8 @@ Same names, argument meaning and error behaviour; tensors are PyTorch-ROCm
 tensors with the reference's logical NCHW shapes (physically channels-last),
 arithmetic is the hand-written HIP kernel behind ``mrcnn_roi_align_fwd/bwd``.
 """
+import collections
+
 from . import _roi_extractor as _re
 
 
@@ -63,6 +65,11 @@ class ROIAlign2D(object):
         return _ROIAlign2DFn.apply(x, rois, self.outh, self.outw,
                                    self.spatial_scale, self.sampling_ratio, self.bin_stride,
                                    self.order)
+
+
+# ``ResNetRoIHead.forward(hints=)``, device tensors: (R, 5) float32 rows (batch, x1, y1, x2, y2), (R,) int32
+# processing order (``spatial_order``), (R,) int32 row -> position among ``mask_rows`` (-1 elsewhere)
+RoiHints = collections.namedtuple('RoiHints', 'rois5 order mask_slot', defaults=(None, None, None))
 
 
 def spatial_order(rois_yx, roi_indices, spatial_scale, band=6.0):

@@ -312,17 +312,14 @@ class MaskRCNN(torch.nn.Module):
         try:
             with torch.no_grad():
                 h = self.extractor(x)
-                rpn_locs, rpn_scores, rois, roi_indices, anchor = self.rpn(
-                    h, x.shape[2:], scales)
+                proposals = self.rpn.propose(h, x.shape[2:], scales)
+                rois, roi_indices = proposals.rois, proposals.roi_indices
                 # one image's proposals at a time: keeps every activation below the 2 GiB
                 # buffer-addressing limit of the conv kernels (8 x 1000 RoIs would not fit)
-                # (rois are grouped by image in order: one host read of the index column gives
-                # the slice bounds; a boolean mask per image would synchronise eight times and
-                # leave the GPU idle while the host queues the next head)
-                counts = getattr(self.rpn, 'last_counts', None)   # host ints of THIS rpn call
-                if counts is None or len(counts) != x.shape[0]:
-                    counts = np.bincount(roi_indices.cpu().numpy(), minlength=x.shape[0])
-                bounds = np.concatenate([[0], np.cumsum(counts)])
+                # (rois are grouped by image in order and the RPN call knows their counts on the
+                # host: a boolean mask per image would synchronise eight times and leave the GPU
+                # idle while the host queues the next head)
+                bounds = np.concatenate([[0], np.cumsum(proposals.counts)])
                 locs, scs = [], []
                 for i in range(x.shape[0]):
                     lo, hi = int(bounds[i]), int(bounds[i + 1])

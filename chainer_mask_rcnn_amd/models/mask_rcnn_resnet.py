@@ -63,6 +63,18 @@ def _mask_std(initialW, chainer_shape):
     return float(initialW)
 
 
+def _check_hints(hints, rois, mask_rows):
+    """ValueError naming the field of ``hints`` (a ``functions.RoiHints``) that does not fit ``rois``."""
+    R = rois.shape[0]
+    for t, name, dtype, shape in zip(hints, hints._fields, (torch.float32, torch.int32, torch.int32),
+                                     ((R, 5), (R,), (R,))):
+        if t is not None and (t.dtype != dtype or tuple(t.shape) != shape or t.device != rois.device):
+            raise ValueError('hints.%s must be a %s tensor of shape %s on %s, got %s %s on %s'
+                             % (name, dtype, shape, rois.device, t.dtype, tuple(t.shape), t.device))
+    if hints.mask_slot is not None and mask_rows is None:
+        raise ValueError('hints.mask_slot is the slot table of mask_rows, which was not given')
+
+
 class ResNetRoIHead(torch.nn.Module):
 
     mask_size = 14  # Size of the predicted mask.
@@ -97,11 +109,14 @@ class ResNetRoIHead(torch.nn.Module):
         # pixels instead of the pooled ones).  None = follow functions.conv.PROJECTED_POOLING.
         self.projected_pooling = None
 
-    def forward(self, x, rois, roi_indices, pred_bbox=True, pred_mask=True, mask_rows=None):
+    def forward(self, x, rois, roi_indices, pred_bbox=True, pred_mask=True, mask_rows=None, hints=None):
         """Reference: models/mask_rcnn_resnet.py:168-196.
 
         ``mask_rows`` (extension): int64 index tensor of the RoI rows the mask branch is run
-        for; ``roi_masks`` then has ``len(mask_rows)`` rows.  ``None`` = all rows."""
+        for; ``roi_masks`` then has ``len(mask_rows)`` rows.  ``None`` = all rows.
+        ``hints`` (extension): a ``functions.RoiHints`` the caller built with the RoIs; same results."""
+        hints = hints if hints is not None else functions.RoiHints()
+        _check_hints(hints, rois, mask_rows)
         from .. import optimizers
         optimizers.join_pending_all()      # deferred updates of the head's parameters (if any)
         if rois.shape[0] == 0:
@@ -109,10 +124,7 @@ class ResNetRoIHead(torch.nn.Module):
             z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=x.device)
             return (z(0, 4 * self.n_class) if pred_bbox else None, z(0, self.n_class) if pred_bbox else None,
                     z(0, self.n_class - 1, self.mask_size, self.mask_size) if pred_mask else None)
-        # (batch, x1, y1, x2, y2) rows when the caller built them with the RoIs (MaskRCNNTrainChain)
-        rois5 = getattr(rois, '_mrcnn_rois5', None)
-        if rois5 is not None and tuple(rois5.shape) != (rois.shape[0], 5):
-            rois5 = None
+        rois5, order = hints.rois5, hints.order
         indices_and_rois = None
         if rois5 is None:
             roi_indices = roi_indices.to(torch.float32)
@@ -121,7 +133,7 @@ class ResNetRoIHead(torch.nn.Module):
         # Both consumers of res5 wanted and the mask branch on a row subset (training): the fused
         # stage hands back (pool5, res5[mask_rows]) and combines their gradients in one pass
         fused_tail = pred_bbox and pred_mask and mask_rows is not None and self.fused_tail
-        kw = dict(tail_rows=mask_rows) if fused_tail else {}
+        kw = dict(tail_rows=mask_rows, tail_slot=hints.mask_slot) if fused_tail else {}
         from ..functions import conv as _conv
         projected = self.projected_pooling if self.projected_pooling is not None else _conv.PROJECTED_POOLING
         projected = projected and self.pooling_func is functions.roi_align_2d and rois.shape[0] > 0
@@ -130,7 +142,6 @@ class ResNetRoIHead(torch.nn.Module):
         if projected:
             # the stage node pools inside block a: conv1 / conv4 (1x1, stride s) read only the bins
             # (s*i, s*j) of the pooled map, and they commute with ROIAlign
-            order = getattr(rois, '_mrcnn_order', None)
             # without a graph (predict: one head call per image and per mask group on ONE map) the
             # two projections of the map are computed once and kept until the map or the weights change
             pre = None
@@ -145,8 +156,7 @@ class ResNetRoIHead(torch.nn.Module):
             # the shortcut conv4), i.e. only the bins (s*i, s*j): pool just those and run the
             # block with stride 1 — same values, a quarter of the ROIAlign work and traffic.
             # a spatially sorted processing order, when the caller sampled the RoIs on the host
-            # and attached one (MaskRCNNTrainChain): same values, fewer feature-map re-reads
-            order = getattr(rois, '_mrcnn_order', None)
+            # and passed one (MaskRCNNTrainChain): same values, fewer feature-map re-reads
             okw = dict(order=order) if order is not None else {}
             pool = self.pooling_func(
                 x, indices_and_rois, outh=self.roi_size, outw=self.roi_size,

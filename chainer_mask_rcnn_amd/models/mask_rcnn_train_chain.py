@@ -5,12 +5,15 @@ forward(imgs, bboxes, labels, masks, scales) -> scalar loss (sum of the five los
 the six reported scalars are kept in ``self.report`` (device tensors, no sync) as the
 reference reports them through chainer.reporter (:182-188).
 """
+import collections
 import time
 
 import numpy as np
 import torch
 
 from .. import functions as F
+from ..functions.conv import SparseRows
+from ..functions.roi_align_2d import spatial_order
 from .utils import AnchorTargetCreator
 from .utils import ProposalTargetCreator
 
@@ -128,6 +131,12 @@ def _upload_many(arrays, dtypes, dev):
     return [flat[o:o + n].view(dt).reshape(shape) for o, n, shape, dt in spans]
 
 
+# what either target path hands ``forward`` (n_fg: a host count; roi_hints: the head's, or None)
+StepTargets = collections.namedtuple('StepTargets', (
+    'rpn_locs rpn_scores sample_rois sample_roi_indices gt_roi_locs gt_roi_labels gt_roi_masks '
+    'gt_rpn_locs gt_rpn_labels roi_cls_locs roi_scores roi_masks mask_rows n_fg roi_hints'))
+
+
 class MaskRCNNTrainChain(torch.nn.Module):
 
     def __init__(self, mask_rcnn, rpn_sigma=3., roi_sigma=1.,
@@ -198,35 +207,28 @@ class MaskRCNNTrainChain(torch.nn.Module):
         anchor_h = self.mask_rcnn.rpn.host_anchor(features.shape[2], features.shape[3], dev)
         atc = self.anchor_target_creator
         ptc = self.proposal_target_creator
-        if self.device_targets and dev.type == 'cuda' and hasattr(ptc, 'sample_device') \
-                and hasattr(atc, 'prepare_device'):
-            (rpn_locs, rpn_scores, sample_rois, sample_roi_indices, gt_roi_locs, gt_roi_labels,
-             gt_roi_masks, gt_rpn_locs, gt_rpn_labels, roi_cls_locs, roi_scores, roi_masks,
-             mask_rows) = self._forward_device_targets(
-                features, img_size, scales, bboxes, labels, masks, anchor_h, mark)
-        else:
-            (rpn_locs, rpn_scores, sample_rois, sample_roi_indices, gt_roi_locs, gt_roi_labels,
-             gt_roi_masks, gt_rpn_locs, gt_rpn_labels, roi_cls_locs, roi_scores, roi_masks,
-             mask_rows) = self._forward_host_targets(
-                features, img_size, scales, bboxes, labels, masks, anchor_h, mark)
-        rpn_locs = rpn_locs.reshape(-1, 4)
-        rpn_scores = rpn_scores.reshape(-1)
-        rpn_loc_loss = F.fast_rcnn_loc_loss(rpn_locs, gt_rpn_locs, gt_rpn_labels, self.rpn_sigma)
-        rpn_cls_loss = F.sigmoid_cross_entropy(rpn_scores, gt_rpn_labels)
+        device_path = self.device_targets and dev.type == 'cuda' and hasattr(ptc, 'sample_device') \
+            and hasattr(atc, 'prepare_device')
+        t = (self._forward_device_targets if device_path else self._forward_host_targets)(
+            features, img_size, scales, bboxes, labels, masks, anchor_h, mark)
+        rpn_locs = t.rpn_locs.reshape(-1, 4)
+        rpn_scores = t.rpn_scores.reshape(-1)
+        rpn_loc_loss = F.fast_rcnn_loc_loss(rpn_locs, t.gt_rpn_locs, t.gt_rpn_labels, self.rpn_sigma)
+        rpn_cls_loss = F.sigmoid_cross_entropy(rpn_scores, t.gt_rpn_labels)
 
         # Losses for outputs of the head: the class-specific 4-vector is selected inside
         # the kernel (roi_cls_locs[arange(n), gt_roi_labels], :168-170).
         roi_loc_loss = F.fast_rcnn_loc_loss(
-            roi_cls_locs, gt_roi_locs, gt_roi_labels, self.roi_sigma, cls=gt_roi_labels)
-        roi_cls_loss = F.softmax_cross_entropy(roi_scores, gt_roi_labels)
+            t.roi_cls_locs, t.gt_roi_locs, t.gt_roi_labels, self.roi_sigma, cls=t.gt_roi_labels)
+        roi_cls_loss = F.softmax_cross_entropy(t.roi_scores, t.gt_roi_labels)
 
         # Losses for outputs of mask branch (:176-178)
-        if mask_rows is not None:
+        if t.mask_rows is not None:
             roi_mask_loss = F.mask_sigmoid_cross_entropy(
-                roi_masks, gt_roi_labels.index_select(0, mask_rows),
-                gt_roi_masks.index_select(0, mask_rows))
+                t.roi_masks, t.gt_roi_labels.index_select(0, t.mask_rows),
+                t.gt_roi_masks.index_select(0, t.mask_rows))
         else:
-            roi_mask_loss = F.mask_sigmoid_cross_entropy(roi_masks, gt_roi_labels, gt_roi_masks)
+            roi_mask_loss = F.mask_sigmoid_cross_entropy(t.roi_masks, t.gt_roi_labels, t.gt_roi_masks)
 
         loss = rpn_loc_loss + rpn_cls_loss + roi_loc_loss + roi_cls_loss + roi_mask_loss
         self.report = {'rpn_loc_loss': rpn_loc_loss.detach(),
@@ -236,50 +238,35 @@ class MaskRCNNTrainChain(torch.nn.Module):
                        'roi_mask_loss': roi_mask_loss.detach(),
                        'loss': loss.detach()}
         mark('losses queued')
-        self.last_targets = {'sample_rois': sample_rois, 'sample_roi_indices': sample_roi_indices,
-                             'feature_shape': tuple(features.shape), 'gt_roi_labels': gt_roi_labels,
-                             'gt_roi_masks': gt_roi_masks, 'gt_rpn_labels': gt_rpn_labels,
-                             'n_rois': int(sample_rois.shape[0]),
-                             'n_fg': getattr(self, '_last_n_fg', None)}   # host count, no read-back
+        self.last_targets = {'sample_rois': t.sample_rois, 'sample_roi_indices': t.sample_roi_indices,
+                             'feature_shape': tuple(features.shape), 'gt_roi_labels': t.gt_roi_labels,
+                             'gt_roi_masks': t.gt_roi_masks, 'gt_rpn_labels': t.gt_rpn_labels,
+                             'n_rois': int(t.sample_rois.shape[0]), 'roi_hints': t.roi_hints,
+                             'n_fg': t.n_fg}                  # host count, no read-back
+        if t.roi_hints is not None:
+            # read by the benchmark's isolated ROIAlign measurement only, never by this package
+            t.sample_rois._mrcnn_order = t.roi_hints.order
         return loss
 
     def _forward_host_targets(self, features, img_size, scales, bboxes, labels, masks, anchor_h, mark):
         """RPN, host target creators (the reference's arrangement, :126-158) and the RoI head."""
         dev = features.device
-        batch_size = features.shape[0]
         to_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
         atc = self.anchor_target_creator
         atc_jobs = None
         if hasattr(atc, 'prepare') and hasattr(atc, 'finish'):
             atc_jobs = [_pool().submit(atc.prepare, bbox, anchor_h, img_size) for bbox in bboxes]
-        pc = getattr(self.mask_rcnn.rpn, 'proposal_layer', None)
-        has_flag = pc is not None and hasattr(pc, 'keep_host_copy')
-        prev_flag = pc.keep_host_copy if has_flag else None
-        try:
-            if has_flag:
-                pc.keep_host_copy = True   # proposals also as host arrays, same synchronisation
-            rpn_locs, rpn_scores, rois, roi_indices, anchor = self.mask_rcnn.rpn(
-                features, img_size, scales)
-        finally:
-            if has_flag:                   # predict() / eval calls keep their single D2H read
-                pc.keep_host_copy = prev_flag
-
+        # (proposals also as host arrays, in the synchronisation that reads their counts)
+        proposals = self.mask_rcnn.rpn.propose(features, img_size, scales, host_copy=True)
         # proposal targets: host-side sampling, exactly as the reference (:126-146)
         mark('extractor+rpn queued')
-        host_rois = getattr(pc, 'last_host_rois', None) if pc is not None else None
-        if host_rois is not None:
-            pc.last_host_rois = None       # consumed
-        if host_rois is None:
-            rois_h = rois.cpu().numpy()
-            roi_indices_h = roi_indices.cpu().numpy()
-            host_rois = [rois_h[roi_indices_h == i] for i in range(batch_size)]
         mark('rois on host')
         ptc = self.proposal_target_creator
         split = hasattr(ptc, 'sample') and hasattr(ptc, 'mask_targets')
         sample_rois, sample_roi_indices = [], []
         gt_roi_locs, gt_roi_labels, gt_roi_masks, mask_jobs = [], [], [], []
         for batch_index, (bbox, label, mask) in enumerate(zip(bboxes, labels, masks)):
-            roi = host_rois[batch_index]
+            roi = proposals.host_rois[batch_index]
             if split:
                 sample_roi, gt_roi_loc, gt_roi_label, job = ptc.sample(roi, bbox, label)
                 mask_jobs.append((job, mask, sample_roi))
@@ -294,14 +281,13 @@ class MaskRCNNTrainChain(torch.nn.Module):
             gt_roi_labels.append(gt_roi_label)
         up = lambda parts, dt: _upload(np.concatenate(parts, axis=0), dt, dev)
         gt_roi_labels_h = np.concatenate(gt_roi_labels, axis=0)
-        self._last_n_fg = int((gt_roi_labels_h > 0).sum())
+        n_fg = int((gt_roi_labels_h > 0).sum())
         fg_rows = np.flatnonzero(gt_roi_labels_h > 0) if self.mask_branch_fg_only else np.zeros(0)
         cat = lambda parts: np.concatenate(parts, axis=0)
         # row -> position among the foreground rows (-1: background), for the fused res5 tail
         fg_slot = np.full((len(gt_roi_labels_h),), -1, np.int32)
         fg_slot[fg_rows.astype(np.int64)] = np.arange(len(fg_rows), dtype=np.int32)
         # processing order of the RoIs for the ROIAlign forward (same values in any order)
-        from ..functions.roi_align_2d import spatial_order
         roi_order = spatial_order(cat(sample_rois), cat(sample_roi_indices), self.mask_rcnn.head.spatial_scale)
         # the (batch index, x1, y1, x2, y2) rows ROIAlign reads, built here instead of by three small
         # device launches (cat, cast, column permutation) in front of the head
@@ -313,9 +299,6 @@ class MaskRCNNTrainChain(torch.nn.Module):
              roi_order, rois5_h],
             [torch.float32, torch.int32, torch.float32, torch.int32, torch.int64, torch.int32,
              torch.int32, torch.float32], dev)
-        fg_rows_d._mrcnn_slot = fg_slot_d
-        sample_rois._mrcnn_order = roi_order_d
-        sample_rois._mrcnn_rois5 = rois5_d
 
         # The reference runs the mask branch on every sampled RoI (:147-148) although
         # background rows carry all-ignored (-1) mask targets and therefore contribute
@@ -326,8 +309,9 @@ class MaskRCNNTrainChain(torch.nn.Module):
         mask_rows = None
         if self.mask_branch_fg_only and len(fg_rows) > 0:
             mask_rows = fg_rows_d
+        hints = F.RoiHints(rois5_d, roi_order_d, fg_slot_d if mask_rows is not None else None)
         roi_cls_locs, roi_scores, roi_masks = self.mask_rcnn.head(
-            features, sample_rois, sample_roi_indices, mask_rows=mask_rows)
+            features, sample_rois, sample_roi_indices, mask_rows=mask_rows, hints=hints)
 
         mark('head queued')
         # the head is now queued on the GPU: build the 14x14 mask targets on the host meanwhile
@@ -364,13 +348,10 @@ class MaskRCNNTrainChain(torch.nn.Module):
         # those positions to its backward (functions/conv.py: SparseRows; anchor index =
         # position * A + a, utils/bbox.py enumerate_shifted_anchor)
         extra, extra_dt = [], []
-        rpn = self.mask_rcnn.rpn
-        hint = getattr(rpn, 'grad_rows', None)
         n_rows = 0
-        if hint is not None and self.sparse_rpn_backward:
-            from ..functions.conv import SparseRows
+        if self.sparse_rpn_backward:
             hw = int(features.shape[2] * features.shape[3])
-            pos = [np.flatnonzero(np.asarray(lab) >= 0) // rpn.n_anchor + i * hw
+            pos = [np.flatnonzero(np.asarray(lab) >= 0) // self.mask_rcnn.rpn.n_anchor + i * hw
                    for i, lab in enumerate(gt_rpn_labels)]
             rows_h, lookup_h = SparseRows.host_tables(np.concatenate(pos), hw * len(gt_rpn_labels))
             n_rows = len(rows_h)
@@ -380,10 +361,11 @@ class MaskRCNNTrainChain(torch.nn.Module):
             [torch.float32, torch.int32] + extra_dt, dev)
         gt_rpn_locs, gt_rpn_labels = up_all[0], up_all[1]
         if n_rows > 0:
-            hint.set(up_all[2], up_all[3], n_rows)
+            proposals.grad_rows.set(up_all[2], up_all[3], n_rows)
         mark('rpn targets')
-        return (rpn_locs, rpn_scores, sample_rois, sample_roi_indices, gt_roi_locs, gt_roi_labels,
-                gt_roi_masks, gt_rpn_locs, gt_rpn_labels, roi_cls_locs, roi_scores, roi_masks, mask_rows)
+        return StepTargets(proposals.rpn_locs, proposals.rpn_scores, sample_rois, sample_roi_indices,
+                           gt_roi_locs, gt_roi_labels, gt_roi_masks, gt_rpn_locs, gt_rpn_labels,
+                           roi_cls_locs, roi_scores, roi_masks, mask_rows, n_fg, hints)
 
     def _mask_targets_of_device_mask(self, job, mask, sample_roi, dev):
         """(n, M, M) int32 mask targets of one image of the host-target path whose ground-truth
@@ -406,24 +388,19 @@ class MaskRCNNTrainChain(torch.nn.Module):
         np.random call order is the reference's: every ProposalTargetCreator draw (foreground,
         background, image by image), then every AnchorTargetCreator draw."""
         dev = features.device
-        batch_size = features.shape[0]
         atc, ptc = self.anchor_target_creator, self.proposal_target_creator
         anchor_d = self.mask_rcnn.rpn._anchor(features.shape[2], features.shape[3], dev)[1]
         # RPN label rule: needs only the ground truth -> queued ahead of the RPN itself; the
         # labels travel to pinned host memory asynchronously
         atc_states = [atc.prepare_device(bbox, anchor_d, anchor_h, img_size, upload=_upload)
                       for bbox in bboxes]
-        rpn_locs, rpn_scores, rois, roi_indices, anchor = self.mask_rcnn.rpn(
-            features, img_size, scales)
+        proposals = self.mask_rcnn.rpn.propose(features, img_size, scales)
         mark('extractor+rpn queued')
-        counts = getattr(self.mask_rcnn.rpn, 'last_counts', None)
-        if counts is None:
-            counts = np.bincount(roi_indices.cpu().numpy(), minlength=batch_size).tolist()
-        bounds = np.concatenate([[0], np.cumsum(counts)]).astype(int)
+        bounds = np.concatenate([[0], np.cumsum(proposals.counts)]).astype(int)
         mark('rois on host')
         s_rois, s_idx, g_locs, g_labels, jobs = [], [], [], [], []
         for i, (bbox, label) in enumerate(zip(bboxes, labels)):
-            roi_i = rois[int(bounds[i]):int(bounds[i + 1])]
+            roi_i = proposals.rois[int(bounds[i]):int(bounds[i + 1])]
             sample_roi, gt_roi_loc, gt_roi_label, job = ptc.sample_device(roi_i, bbox, label,
                                                                           upload=_upload)
             mark('ptc.sample')
@@ -435,7 +412,7 @@ class MaskRCNNTrainChain(torch.nn.Module):
         sample_rois, sample_roi_indices = torch.cat(s_rois, 0), torch.cat(s_idx, 0)
         gt_roi_locs, gt_roi_labels = torch.cat(g_locs, 0), torch.cat(g_labels, 0)
         offs = np.concatenate([[0], np.cumsum([j['n'] for j in jobs])]).astype(int)
-        self._last_n_fg = int(sum(j['n_fg'] for j in jobs))
+        n_fg = int(sum(j['n_fg'] for j in jobs))
         fg_rows = np.concatenate([np.arange(offs[i], offs[i] + j['n_fg']) for i, j in enumerate(jobs)]) \
             if self.mask_branch_fg_only else np.zeros(0, np.int64)
         # ground-truth masks that live on the host: their 14x14 targets are built there (as in
@@ -470,5 +447,6 @@ class MaskRCNNTrainChain(torch.nn.Module):
         g_rl, g_rlab = zip(*[atc.finish_device(st) for st in atc_states])
         gt_rpn_locs, gt_rpn_labels = torch.cat(g_rl, 0), torch.cat(g_rlab, 0)
         mark('rpn targets')
-        return (rpn_locs, rpn_scores, sample_rois, sample_roi_indices, gt_roi_locs, gt_roi_labels,
-                gt_roi_masks, gt_rpn_locs, gt_rpn_labels, roi_cls_locs, roi_scores, roi_masks, mask_rows)
+        return StepTargets(proposals.rpn_locs, proposals.rpn_scores, sample_rois, sample_roi_indices,
+                           gt_roi_locs, gt_roi_labels, gt_roi_masks, gt_rpn_locs, gt_rpn_labels,
+                           roi_cls_locs, roi_scores, roi_masks, mask_rows, n_fg, None)

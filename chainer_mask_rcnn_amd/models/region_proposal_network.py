@@ -6,6 +6,8 @@
 over a fused (4A + A, padded to a multiple of 4) filter; ``loc.W`` / ``score.W`` are
 views of that filter with the reference's shapes.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -30,6 +32,11 @@ class _ConvView(object):
         return self._owner.b[self._lo:self._hi]
 
 
+# propose(): forward's five values, then what else the call knows (counts, host_rois: ProposalBatch)
+Proposals = collections.namedtuple(
+    'Proposals', 'rpn_locs rpn_scores rois roi_indices anchor counts host_rois grad_rows')
+
+
 class RegionProposalNetwork(torch.nn.Module):
 
     def __init__(self, in_channels=512, mid_channels=512, ratios=[0.5, 1, 2],
@@ -50,12 +57,6 @@ class RegionProposalNetwork(torch.nn.Module):
         self.loc = _ConvView(self.loc_score, 0, 4 * A)
         self.score = _ConvView(self.loc_score, 4 * A, 5 * A)
         self._anchor_cache = {}
-        # map positions outside which the gradient of conv1's output is exactly zero (the sampled
-        # anchors of the RPN losses): filled by MaskRCNNTrainChain where the anchor targets are
-        # built, consumed by conv1's backward (functions/conv.py: SparseRows).  A NEW object per
-        # forward: each graph's conv1 node keeps the hint of ITS forward, so two forwards before a
-        # backward (gradient accumulation) never see each other's rows
-        self.grad_rows = None
 
     def _anchor(self, hh, ww, device):
         key = (hh, ww, str(device))
@@ -67,12 +68,20 @@ class RegionProposalNetwork(torch.nn.Module):
     def forward(self, x, img_size, scales):
         """x (N,C,H,W) -> rpn_locs (N,HWA,4), rpn_scores (N,HWA), rois (R',4),
         roi_indices (R',) int32, anchor (HWA,4)."""
+        return self.propose(x, img_size, scales)[:5]
+
+    def propose(self, x, img_size, scales, host_copy=False):
+        """``forward`` as a ``Proposals`` record; ``host_copy``: see ``ProposalCreator.batch``."""
         n, _, hh, ww = x.shape
         A = self.n_anchor
         _, anchor = self._anchor(hh, ww, x.device)
         from ..functions.conv import SparseRows, sparse_output_grad
-        self.grad_rows = SparseRows()
-        with sparse_output_grad(self.grad_rows):
+        # map positions outside which the gradient of conv1's output is exactly zero (the sampled
+        # anchors of the RPN losses): filled by MaskRCNNTrainChain where the anchor targets are built,
+        # consumed by conv1's backward (functions/conv.py: SparseRows).  A NEW object per call: each
+        # graph's conv1 node keeps ITS hint, so two forwards before a backward never share rows
+        grad_rows = SparseRows()
+        with sparse_output_grad(grad_rows):
             h = self.conv1(x, relu=True)
         out = self.loc_score(h)                               # (N, 5A(+pad), H, W), NHWC
         nhwc = out.permute(0, 2, 3, 1)
@@ -85,19 +94,14 @@ class RegionProposalNetwork(torch.nn.Module):
         if optimizers.DEFER_LAUNCH_AT == 'window-open':
             optimizers.launch_pending_all()
         self.proposal_layer.train = self.training
-        if hasattr(self.proposal_layer, 'batch'):
-            rois = self.proposal_layer.batch(rpn_locs, rpn_scores, anchor, img_size, scales)
-        else:
-            rois = [self.proposal_layer(rpn_locs[i], rpn_scores[i], anchor, img_size,
-                                        scale=float(scales[i])) for i in range(n)]
+        rois, counts, host_rois = self.proposal_layer.batch(rpn_locs, rpn_scores, anchor, img_size,
+                                                            scales, host_copy=host_copy)
         if optimizers.DEFER_LAUNCH_AT != 'window-open':
             optimizers.launch_pending_all()    # the proposal read-back has returned: GPU idle
-        self.last_counts = [int(len(roi)) for roi in rois]     # host-known: no read-back
-        roi_indices = [torch.full((len(roi),), i, dtype=torch.int32, device=x.device)
-                       for i, roi in enumerate(rois)]
+        roi_indices = [torch.full((c,), i, dtype=torch.int32, device=x.device) for i, c in enumerate(counts)]
         rois = torch.cat(rois, dim=0)
         roi_indices = torch.cat(roi_indices, dim=0)
-        return rpn_locs, rpn_scores, rois, roi_indices, anchor
+        return Proposals(rpn_locs, rpn_scores, rois, roi_indices, anchor, counts, host_rois, grad_rows)
 
     def host_anchor(self, hh, ww, device):
         return self._anchor(hh, ww, device)[0]

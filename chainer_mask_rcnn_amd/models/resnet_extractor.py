@@ -93,14 +93,14 @@ class BuildingBlock(torch.nn.Module):
         # block): parallel.DataParallelGradSync launches completed gradient buckets from it
         self.grad_poll = None
 
-    def forward(self, x, first_stride=None, tail_rows=None, roi=None):
+    def forward(self, x, first_stride=None, tail_rows=None, roi=None, tail_slot=None):
         """``first_stride`` overrides the stride of block ``a`` (used by the RoI head when the
         stride-2 subsampling has already been done by the pooling op).  ``tail_rows``: return
-        ``(average_pooling_2d(y), y[tail_rows])`` instead of y.  ``roi`` (a
-        ``functions.conv.RoiSpec``): ``x`` is the feature map and the stage pools inside block
-        ``a``, behind its 1x1 projections (functions/conv.py "projected pooling")."""
-        return F.building_block(x, [getattr(self, n) for n in self._names], first_stride,
-                                poll=self.grad_poll, tail_rows=tail_rows, roi=roi)
+        ``(average_pooling_2d(y), y[tail_rows])`` instead of y (``tail_slot``: see
+        ``F.building_block``).  ``roi`` (a ``functions.conv.RoiSpec``): ``x`` is the feature map and the
+        stage pools inside block ``a``, behind its 1x1 projections (functions/conv.py "projected pooling")."""
+        return F.building_block(x, [getattr(self, n) for n in self._names], first_stride, poll=self.grad_poll,
+                                tail_rows=tail_rows, roi=roi, tail_slot=tail_slot)
 
 
 def pad_image_nhwc4(x):

@@ -4,9 +4,15 @@ parameters of models/mask_rcnn_resnet.py:48-52, per-image call :135-138; algorit
 SURVEY.md Appendix A.4).  Upstream copies loc/score/anchor to the host, sorts with
 NumPy and scans the NMS bit-mask in Python; here every step is a HIP kernel and the
 only host round trip is the final kept-count."""
+import collections
+
 import torch
 
 from ...functions import proposal_ops as P
+
+
+# batch(): per image the proposals (device tensors), their counts (host ints), host arrays or None
+ProposalBatch = collections.namedtuple('ProposalBatch', 'rois counts host_rois')
 
 
 class ProposalCreator(object):
@@ -21,9 +27,6 @@ class ProposalCreator(object):
         self.force_cpu_nms = force_cpu_nms   # accepted for interface parity; no CPU path exists
         self.min_size = min_size
         self.train = True                    # chainer.config.train
-        self.keep_host_copy = False          # set by MaskRCNNTrainChain (see batch())
-        self.last_host_rois = None
-        self.last_counts = None              # per-image proposal counts of the last batch()
 
     def __call__(self, loc, score, anchor, img_size, scale=1., return_indices=False):
         """loc (S,4), score (S,), anchor (S,4) device tensors -> roi (R,4) device tensor."""
@@ -45,11 +48,12 @@ class ProposalCreator(object):
             return out, order[keep.long()]
         return out
 
-    def batch(self, locs, scores, anchor, img_size, scales):
+    def batch(self, locs, scores, anchor, img_size, scales, host_copy=False):
         """All images of a batch at once: per-image decode / top-k / gather are queued
         without synchronising, the NMS of every image runs in ONE batched launch (one
         workgroup scans each image's mask concurrently) and the kept counts come back in a
-        single host read.  Same results as calling the object once per image."""
+        single host read (``host_copy``: the proposals with them).  Same results as calling the
+        object once per image."""
         if self.train:
             n_pre, n_post = self.n_train_pre_nms, self.n_train_post_nms
         else:
@@ -72,17 +76,16 @@ class ProposalCreator(object):
             sorted_rois[i] = P.gather_rows(roi_all[i], order[i], counts[i:i + 1])
         keep, n_keep = P.nms_sorted_batched(sorted_rois, counts, self.nms_thresh,
                                             limit=n_post if n_post > 0 else 0)
-        if self.keep_host_copy:
+        host_rois = None
+        if host_copy:
             # one synchronisation brings the counts AND the data the host needs to form its
             # own copy of the proposals (the train chain samples RoIs on the host): the
             # device gather below then runs without a second device-to-host round trip
             n_keep_h, keep_h, sorted_h = n_keep.cpu(), keep.cpu(), sorted_rois.cpu()
             n_keep = n_keep_h.tolist()
             keep_np, sorted_np = keep_h.numpy(), sorted_h.numpy()
-            self.last_host_rois = [sorted_np[i][keep_np[i, :n_keep[i]]] for i in range(n)]
+            host_rois = [sorted_np[i][keep_np[i, :n_keep[i]]] for i in range(n)]
         else:
             n_keep = n_keep.cpu().tolist()       # the one host synchronisation
-            self.last_host_rois = None
-        self.last_counts = list(n_keep)
-        return [P.gather_rows(sorted_rois[i], keep[i, :n_keep[i]].contiguous())
-                for i in range(n)]
+        rois = [P.gather_rows(sorted_rois[i], keep[i, :n_keep[i]].contiguous()) for i in range(n)]
+        return ProposalBatch(rois, n_keep, host_rois)

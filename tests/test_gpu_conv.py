@@ -281,8 +281,9 @@ def test_row_sparse_hint_is_per_forward(dev):
         rpn.zero_grad(set_to_none=True)
         outs, hints = [], []
         for x in xs:
-            outs.append(rpn(x, (H * 16, W * 16), [1.0])[1])
-            hints.append(rpn.grad_rows)
+            p = rpn.propose(x, (H * 16, W * 16), [1.0])
+            outs.append(p.rpn_scores)
+            hints.append(p.grad_rows)
         assert hints[0] is not hints[1]
         if sparse:
             for h, p in zip(hints, pos):

@@ -492,8 +492,7 @@ def test_optimizer_ownership_rules(dev):
     assert float(snap_v.abs().max()) > 0
     feat = model.extractor(x)
     t = chain.last_targets
-    idx = torch.zeros(len(t['sample_rois']), dtype=torch.int32, device=dev)
-    cls_locs, scores, _ = model.head(feat, t['sample_rois'], idx, pred_mask=False)
+    cls_locs, scores, _ = model.head(feat, t['sample_rois'], t['sample_roi_indices'], pred_mask=False)
     (cls_locs.sum() * 1e-4 + scores.sum() * 1e-4).backward()
     join_wgrad_stream()
     written = dict(zip([id(p) for p in arena.params], arena.written()))

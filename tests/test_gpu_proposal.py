@@ -276,23 +276,23 @@ def test_proposal_creator_batch_equals_oracle_per_image(dev, creator_refs, train
     scales = [c['scale'] for c in cases]
     refs = [creator_refs[c['name'], train][0] for c in cases]
     _check_gather_rows_zeroes_the_rows_after_the_count(dev)
-    for keep_host_copy in (False, True):
-        pc = ProposalCreator(**PC.CREATOR_PARAMS)
-        pc.train = train
-        pc.keep_host_copy = keep_host_copy
-        rois = pc.batch(locs, scores, anchor, PC.IMG, scales)
+    pc = ProposalCreator(**PC.CREATOR_PARAMS)
+    pc.train = train
+    for host_copy in (False, True, False):      # the last: a call without the copy after one with it
+        out = pc.batch(locs, scores, anchor, PC.IMG, scales, host_copy=host_copy)
+        rois = out.rois
         assert len(rois) == len(cases)
-        assert pc.last_counts == [len(r) for r in refs]
+        assert out.counts == [len(r) for r in refs]
         for i, (roi, ref) in enumerate(zip(rois, refs)):
             got = roi.cpu().numpy()
             assert got.shape == ref.shape and np.array_equal(got, ref), cases[i]['name']
-        if keep_host_copy:
-            assert len(pc.last_host_rois) == len(cases)
-            for roi, host in zip(rois, pc.last_host_rois):
+        if host_copy:
+            assert len(out.host_rois) == len(cases)
+            for roi, host in zip(rois, out.host_rois):
                 assert host.dtype == np.float32 and host.shape == tuple(roi.shape)
                 assert np.array_equal(host, roi.cpu().numpy())
         else:
-            assert pc.last_host_rois is None
+            assert out.host_rois is None
 
 
 def _check_gather_rows_zeroes_the_rows_after_the_count(dev):

@@ -32,7 +32,8 @@ def main():
         ev.record()
         marks.append((label, ev))
 
-    ext_fwd, rpn_fwd, head_fwd = model.extractor.forward, model.rpn.forward, model.head.forward
+    # (the train chain calls the RPN through ``propose``, of which ``forward`` is the first five values)
+    ext_fwd, rpn_fwd, head_fwd = model.extractor.forward, model.rpn.propose, model.head.forward
     conv1_fwd = model.rpn.loc_score.forward
 
     def ext(x):
@@ -59,7 +60,7 @@ def main():
         mark('head fwd')
         return out
 
-    model.extractor.forward, model.rpn.forward, model.head.forward = ext, rpn, head
+    model.extractor.forward, model.rpn.propose, model.head.forward = ext, rpn, head
     model.rpn.loc_score.forward = loc_score
     chain_fwd = chain.forward
 
