@@ -17,6 +17,7 @@ import torch
 
 from .. import _lib
 from .._lib import ConvDesc, EPI_BIAS, EPI_AFFINE, EPI_RESIDUAL, EPI_RELU, EPI_ACCUM, EPI_EXACT_SIGNS
+from ..streams import join_wgrad_stream, wgrad_stream
 from ._layout import nhwc, empty_nhwc
 from ._roi_extractor import out_size
 from .roi_align_2d import roi_align_backward
@@ -147,25 +148,23 @@ class SparseRows(object):
         return rows, lookup
 
 
-_SPARSE_HINT = None
-
-
-class sparse_output_grad(object):
-    """``with sparse_output_grad(hint): y = conv2d(...)`` — the 3x3 / stride 1 / pad 1 convolutions
-    recorded inside may take their backward from ``hint`` (a ``SparseRows`` filled before backward)."""
-
-    def __init__(self, hint):
-        self.hint = hint
-
-    def __enter__(self):
-        global _SPARSE_HINT
-        self.prev, _SPARSE_HINT = _SPARSE_HINT, self.hint
-        return self.hint
-
-    def __exit__(self, *exc):
-        global _SPARSE_HINT
-        _SPARSE_HINT = self.prev
-        return False
+def _check_grad_rows(d, stride, pad, scale, residual):
+    """A convolution given ``grad_rows`` must be able to use it: 3x3 / stride 1 / pad 1, no affine,
+    no residual (the row-sparse backward is the 1x1 problem on gathered 3x3 patches)."""
+    if (d.R, d.S) != (3, 3):
+        why = 'the filter is %dx%d, not 3x3' % (d.R, d.S)
+    elif stride != 1:
+        why = 'stride is %d, not 1' % stride
+    elif pad != 1:
+        why = 'pad is %d, not 1' % pad
+    elif scale is not None:
+        why = 'it has an affine scale'
+    elif residual is not None:
+        why = 'it has a residual'
+    else:
+        return
+    raise ValueError('conv2d: grad_rows needs a 3x3 / stride 1 / pad 1 convolution without scale '
+                     'or residual, but %s' % why)
 
 
 def _sparse3x3_backward(ctx, d, x, Wc, g, hint, need_x, need_w, need_b):
@@ -194,13 +193,15 @@ class _Conv2dFn(torch.autograd.Function):
     """y = relu?( affine?( conv(x, W) + b? ) + residual? )"""
 
     @staticmethod
-    def forward(ctx, x, W, b, scale, shift, residual, stride, pad, relu, records_graph):
+    def forward(ctx, x, W, b, scale, shift, residual, stride, pad, relu, records_graph, grad_rows):
         # ``records_graph``: torch.is_grad_enabled() at the call (in here grad mode is always off and
         # ctx.needs_input_grad reports the inputs' requires_grad flags even under torch.no_grad())
         _lib.require_device(x, W)
         x = nhwc(x)
         Wc = nhwc(W) if W.dim() == 4 else W.contiguous()
         d = make_desc(x.shape, W.shape, stride, pad)
+        if grad_rows is not None:
+            _check_grad_rows(d, stride, pad, scale, residual)
         flags = 0
         if b is not None:
             flags |= EPI_BIAS
@@ -225,8 +226,7 @@ class _Conv2dFn(torch.autograd.Function):
         ctx.relu = relu
         ctx.has_bias = b is not None
         ctx.has_res = residual is not None
-        ctx.sparse_hint = _SPARSE_HINT if (d.R == 3 and d.S == 3 and stride == 1 and pad == 1 and
-                                           scale is None and residual is None) else None
+        ctx.sparse_hint = grad_rows
         ctx.W_param = W
         ctx.b_param = b
         ctx.save_for_backward(x, Wc, scale, y if relu else None)
@@ -249,7 +249,7 @@ class _Conv2dFn(torch.autograd.Function):
         if hint is not None and SPARSE_CONV_BACKWARD and hint.valid_for(d, gy.device):
             gx, gW, gb = _sparse3x3_backward(ctx, d, x, Wc, g, hint, need_x, need_w, need_b)
             hint.clear()
-            return gx, gW, gb, None, None, None, None, None, None, None
+            return gx, gW, gb, None, None, None, None, None, None, None, None
         if need_w:
             if ctx.wino:
                 gW = _wgrad(d, x, g, ctx.W_param, wino=True)
@@ -263,18 +263,21 @@ class _Conv2dFn(torch.autograd.Function):
         if need_b:
             gb = _bias_grad(ctx.b_param, g, d.N * d.P * d.Q)
         gres = gr if ctx.has_res and ctx.needs_input_grad[5] else None
-        return gx, gW, gb, None, None, gres, None, None, None, None
+        return gx, gW, gb, None, None, gres, None, None, None, None, None
 
 
-def conv2d(x, W, b=None, stride=1, pad=0, scale=None, shift=None, residual=None, relu=False):
+def conv2d(x, W, b=None, stride=1, pad=0, scale=None, shift=None, residual=None, relu=False,
+           grad_rows=None):
     """Fused convolution: ``relu(affine(conv(x,W)+b) + residual)`` with each stage optional.
 
     ``scale``/``shift`` are the AffineChannel2D ``W``/``b`` (frozen: no gradient is
     produced for them — the reference computes but never uses it,
-    examples/train_common.py:188-190).
+    examples/train_common.py:188-190).  ``grad_rows``: a ``SparseRows`` (filled before backward) the
+    backward of a 3x3 / stride 1 / pad 1 convolution may take its rows from; ValueError for a
+    convolution that cannot use it.
     """
     return _Conv2dFn.apply(x, W, b, scale, shift, residual, stride, pad, relu,
-                           torch.is_grad_enabled())
+                           torch.is_grad_enabled(), grad_rows)
 
 
 class _StemFn(torch.autograd.Function):
@@ -521,8 +524,8 @@ def _wino_forward(kind, training):
     return WINOGRAD_TRAIN_FORWARD in (True, kind) or not training
 
 
-def _wino_ws(d, device, tag='wino'):
-    return _lib.workspace(_lib.load().mrcnn_conv3x3_wino_workspace_bytes(ctx_desc(d)), device, tag)
+def _wino_ws(d, device):
+    return _lib.workspace(_lib.load().mrcnn_conv3x3_wino_workspace_bytes(ctx_desc(d)), device, 'wino')
 
 
 # Transformed filters of inference calls, keyed by the filter tensor: valid while the tensor has
@@ -641,11 +644,11 @@ def wino_dgrad(d, g, Wc, fold_scale=None, out_scale=None, out_mask_y=None):
     return gx
 
 
-def wino_wgrad_into(d, x, v, g, gW, row_scale=None, tag='wino'):
+def wino_wgrad_into(d, x, v, g, gW, row_scale=None):
     """gW = backward-filter from ``g`` and exactly one of ``x`` (raw input) / ``v`` (the
     transformed input a forward with ``keep_v`` returned)."""
     _lib.call('mrcnn_conv3x3_wino_wgrad', ctx_desc(d), _lib.ptr(x), _lib.ptr(v), _lib.ptr(g),
-              _lib.ptr(gW), _lib.ptr(row_scale), _lib.ptr(_wino_ws(d, g.device, tag)),
+              _lib.ptr(gW), _lib.ptr(row_scale), _lib.ptr(_wino_ws(d, g.device)),
               _lib.stream_ptr())
 
 
@@ -654,27 +657,7 @@ def wino_wgrad_into(d, x, v, g, gW, row_scale=None, tag='wino'):
 # launches of a bottleneck go to a second HIP stream so that their workgroups fill the CUs
 # that the tail round of the concurrently running dgrad leaves idle (and vice versa): with
 # 128x128 tiles and 512 resident workgroups a single kernel wastes up to a round at its end.
-_side_streams = {}
-
-
-def wgrad_stream(device):
-    key = str(device)
-    if key not in _side_streams:
-        _side_streams[key] = torch.cuda.Stream(device=device)
-    return _side_streams[key]
-
-
-def wgrad_stream_if_used(device):
-    """The weight-gradient side stream of ``device`` if one has been created, else None."""
-    return _side_streams.get(str(device))
-
-
-def join_wgrad_stream(device=None):
-    """Make the current stream wait for every weight gradient queued on the side stream
-    (call before reading gradients: optimizer step, all-reduce)."""
-    for key, st in _side_streams.items():
-        if device is None or key == str(device):
-            torch.cuda.current_stream(st.device).wait_stream(st)
+# (The stream itself: streams.wgrad_stream.)
 
 
 # ---- weight gradients deferred into the next step's proposal window --------------------------
@@ -694,14 +677,13 @@ class WgradJob(object):
         self.d, self.x, self.g, self.gW = d, x, g, gW
         self.row_scale, self.wino, self.v = row_scale, wino, v
 
-    def launch(self, stream_tag=''):
-        """On the current stream; ``stream_tag`` ('', '-side', '-defer') names the scratch, which
-        two streams must not share."""
+    def launch(self):
+        """On the current stream (``_lib.workspace`` keys the scratch on it: two streams never
+        share a buffer)."""
         if self.wino:
-            wino_wgrad_into(self.d, self.x, self.v, self.g, self.gW, self.row_scale,
-                            tag='wino' + stream_tag)
+            wino_wgrad_into(self.d, self.x, self.v, self.g, self.gW, self.row_scale)
         else:
-            _launch_wgrad(self.d, self.x, self.g, self.gW, self.row_scale, 'wgrad' + stream_tag)
+            _launch_wgrad(self.d, self.x, self.g, self.gW, self.row_scale)
 
     def tensors(self):
         """The operands a held-back job keeps alive."""
@@ -709,7 +691,8 @@ class WgradJob(object):
 
 
 class DeferQueue(object):
-    """``jobs``: one ``WgradJob`` per held-back weight gradient of the parameters ``params``."""
+    """``jobs``: one ``WgradJob`` per held-back weight gradient of the parameters ``params``.
+    MomentumSGD.update hangs one on the parameter arena (``ParamArena.defer``) around backward."""
 
     def __init__(self, params):
         self.ids = set(id(p) for p in params)
@@ -720,27 +703,16 @@ class DeferQueue(object):
         return set(j.gW.data_ptr() for j in self.jobs)
 
 
-_DEFER = None          # set by MomentumSGD.update around backward
-_defer_streams = {}
-
-
-def defer_stream(device):
-    key = str(device)
-    if key not in _defer_streams:
-        _defer_streams[key] = torch.cuda.Stream(device=device)
-    return _defer_streams[key]
-
-
 def run_deferred_wgrads(jobs):
     """Launch the held-back weight gradients on the current stream (the caller selects it)."""
     for job in jobs:
-        job.launch('-defer')
+        job.launch()
 
 
-def _launch_wgrad(d, x, g, gW, row_scale=None, tag='wgrad', ex=True):
+def _launch_wgrad(d, x, g, gW, row_scale=None, ex=True):
     """The implicit-GEMM weight gradient into the buffer ``gW``, on the current stream.  ``ex``
     False: the plain entry point (no ``row_scale``)."""
-    ws = _lib.workspace(_lib.load().mrcnn_conv2d_wgrad_workspace_bytes(ctx_desc(d)), g.device, tag)
+    ws = _lib.workspace(_lib.load().mrcnn_conv2d_wgrad_workspace_bytes(ctx_desc(d)), g.device, 'wgrad')
     tail = (_lib.ptr(row_scale), _lib.stream_ptr()) if ex else (_lib.stream_ptr(),)
     _lib.call('mrcnn_conv2d_wgrad_ex' if ex else 'mrcnn_conv2d_wgrad', ctx_desc(d), _lib.ptr(x),
               _lib.ptr(g), _lib.ptr(gW), _lib.ptr(ws), *tail)
@@ -754,14 +726,16 @@ def _wgrad(d, x, g, W, side=None, row_scale=None, wino=False, v=None):
     gW, result = _grad_target(W)
     job = WgradJob(d, x, g, gW, row_scale, wino, v)
     direct = result is None
-    if direct and _DEFER is not None and id(W) in _DEFER.ids:
-        _DEFER.jobs.append(job)
+    # (direct: the arena slot was claimed, so the arena exists and answers the rest of the question)
+    defer = W._arena.defer if direct else None
+    if defer is not None and id(W) in defer.ids:
+        defer.jobs.append(job)
     elif direct and side is not None:
         side.wait_stream(torch.cuda.current_stream(g.device))
         for t in (x, g):
             t.record_stream(side)
         with torch.cuda.stream(side):
-            job.launch('-side')
+            job.launch()
     else:
         job.launch()
     return result

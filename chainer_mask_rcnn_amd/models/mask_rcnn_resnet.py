@@ -103,7 +103,6 @@ class ResNetRoIHead(torch.nn.Module):
         self.roi_size = roi_size
         self.spatial_scale = spatial_scale
         self.pooling_func = pooling_func
-        self.fused_tail = True      # developer switch: res5's two consumers inside the stage node
         # Pool BEHIND res5.a's 1x1 projections instead of in front of them (functions/conv.py
         # "projected pooling": the same values up to fp32 rounding, the two projections on the map's
         # pixels instead of the pooled ones).  None = follow functions.conv.PROJECTED_POOLING.
@@ -132,8 +131,8 @@ class ResNetRoIHead(torch.nn.Module):
         res5_stride = self.roi_size // 7
         # Both consumers of res5 wanted and the mask branch on a row subset (training): the fused
         # stage hands back (pool5, res5[mask_rows]) and combines their gradients in one pass
-        fused_tail = pred_bbox and pred_mask and mask_rows is not None and self.fused_tail
-        kw = dict(tail_rows=mask_rows, tail_slot=hints.mask_slot) if fused_tail else {}
+        two_output_tail = pred_bbox and pred_mask and mask_rows is not None
+        kw = dict(tail_rows=mask_rows, tail_slot=hints.mask_slot) if two_output_tail else {}
         from ..functions import conv as _conv
         projected = self.projected_pooling if self.projected_pooling is not None else _conv.PROJECTED_POOLING
         projected = projected and self.pooling_func is functions.roi_align_2d and rois.shape[0] > 0
@@ -169,22 +168,16 @@ class ResNetRoIHead(torch.nn.Module):
             res5 = self.res5(pool, **kw)
 
         roi_cls_locs = roi_scores = roi_masks = None
-        res5_fg = None
-        pool5 = None
-        if fused_tail:
-            pool5, res5_fg = res5
-        elif pred_bbox and pred_mask and mask_rows is not None:
-            res5, res5_fg = F.fanout_rows(res5, mask_rows)
+        if two_output_tail:
+            pool5, res5 = res5                  # res5: the mask rows only
+        elif pred_bbox:
+            pool5 = F.average_pooling_2d(res5, 7, stride=7)
         if pred_bbox:
-            if pool5 is None:
-                pool5 = F.average_pooling_2d(res5, 7, stride=7)
             fc = F.linear(pool5, self.cls_loc_score.W, self.cls_loc_score.b)
             roi_cls_locs = fc[:, :4 * self.n_class]
             roi_scores = fc[:, 4 * self.n_class:5 * self.n_class]
         if pred_mask:
-            if res5_fg is not None:
-                res5 = res5_fg
-            elif mask_rows is not None:
+            if mask_rows is not None and not two_output_tail:
                 res5 = res5.index_select(0, mask_rows)
             deconv6 = F.deconv2x2s2(res5, self.deconv6.W, self.deconv6.b, relu=True)
             roi_masks = self.mask(deconv6)

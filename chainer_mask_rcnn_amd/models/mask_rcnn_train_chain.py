@@ -14,24 +14,12 @@ import torch
 from .. import functions as F
 from ..functions.conv import SparseRows
 from ..functions.roi_align_2d import spatial_order
+from ..streams import copy_stream      # (the benchmark imports it from here)
 from .utils import AnchorTargetCreator
 from .utils import ProposalTargetCreator
 
 
 _POOL = None
-_COPY_STREAMS = {}
-
-
-def copy_stream(dev):
-    """The host-to-device copy stream of ``dev`` (one per device for the whole process: input
-    pipelines should upload on it rather than create their own — the step uses four HIP streams
-    (compute, copy, weight gradients, deferred work) and a GPU has four hardware queues by default;
-    a fifth stream shares a queue with one of them and serialises work that was meant to overlap)."""
-    key = str(dev)
-    if key not in _COPY_STREAMS:
-        _COPY_STREAMS[key] = torch.cuda.Stream(device=dev)
-    return _COPY_STREAMS[key]
-
 
 _NP_OF = {torch.float32: np.float32, torch.int32: np.int32, torch.int64: np.int64,
           torch.uint8: np.uint8}

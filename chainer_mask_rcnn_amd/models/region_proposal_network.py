@@ -75,29 +75,29 @@ class RegionProposalNetwork(torch.nn.Module):
         n, _, hh, ww = x.shape
         A = self.n_anchor
         _, anchor = self._anchor(hh, ww, x.device)
-        from ..functions.conv import SparseRows, sparse_output_grad
+        from ..functions.conv import SparseRows
         # map positions outside which the gradient of conv1's output is exactly zero (the sampled
         # anchors of the RPN losses): filled by MaskRCNNTrainChain where the anchor targets are built,
         # consumed by conv1's backward (functions/conv.py: SparseRows).  A NEW object per call: each
         # graph's conv1 node keeps ITS hint, so two forwards before a backward never share rows
         grad_rows = SparseRows()
-        with sparse_output_grad(grad_rows):
-            h = self.conv1(x, relu=True)
+        h = self.conv1(x, relu=True, grad_rows=grad_rows)
         out = self.loc_score(h)                               # (N, 5A(+pad), H, W), NHWC
         nhwc = out.permute(0, 2, 3, 1)
         rpn_locs = nhwc[..., :4 * A].reshape(n, -1, 4)
         rpn_scores = nhwc[..., 4 * A:5 * A].reshape(n, -1)
 
         # the proposal window opens (top-k / NMS + the host's RoI sampling: the GPU is nearly
-        # idle): weight gradients the optimizer held back from the previous step run here
+        # idle): weight gradients the optimizer held back from the previous step run here, right
+        # behind the RPN convolutions and beside the top-k / NMS kernels.  Measured best: 49.6-50.0 ms
+        # per step, against 50.0-50.6 when launched once the proposal read-back has returned and
+        # 50.6-51.2 without deferral.  The proposal kernels on a separate high-priority stream next
+        # to the deferred work were measured and dropped (64 ms per step).
         from .. import optimizers
-        if optimizers.DEFER_LAUNCH_AT == 'window-open':
-            optimizers.launch_pending_all()
+        optimizers.launch_pending_all()
         self.proposal_layer.train = self.training
         rois, counts, host_rois = self.proposal_layer.batch(rpn_locs, rpn_scores, anchor, img_size,
                                                             scales, host_copy=host_copy)
-        if optimizers.DEFER_LAUNCH_AT != 'window-open':
-            optimizers.launch_pending_all()    # the proposal read-back has returned: GPU idle
         roi_indices = [torch.full((c,), i, dtype=torch.int32, device=x.device) for i, c in enumerate(counts)]
         rois = torch.cat(rois, dim=0)
         roi_indices = torch.cat(roi_indices, dim=0)

@@ -40,12 +40,12 @@ class Convolution2D(torch.nn.Module):
         self.b = None if nobias else torch.nn.Parameter(torch.zeros(out_ch))
         self.stride, self.pad = stride, pad
 
-    def forward(self, x, affine=None, residual=None, relu=False):
+    def forward(self, x, affine=None, residual=None, relu=False, grad_rows=None):
         scale = shift = None
         if affine is not None:
             scale, shift = affine.W, affine.b
         return F.conv2d(x, self.W, self.b, self.stride, self.pad, scale=scale, shift=shift,
-                        residual=residual, relu=relu)
+                        residual=residual, relu=relu, grad_rows=grad_rows)
 
 
 class Bottleneck(torch.nn.Module):
@@ -194,11 +194,9 @@ class ResNetExtractorBase(torch.nn.Module):
         if self._prefetched is not None and self._prefetched[0] == self._prefetch_key(x):
             return
         dev = x.device
-        # the stream the deferred weight gradients use (idle between two proposal windows), NOT a
-        # stream of its own: a fifth stream changes which HIP streams share a hardware queue
-        # (GPU_MAX_HW_QUEUES = 4) and the proposal chain then queues behind the deferred weight
-        # gradients — measured +2.4 ms under data parallelism, +6 ms with 5..8 queues (profiles/HISTORY.md 7a)
-        from ..functions.conv import defer_stream, no_filter_cache
+        # on the deferred-work stream, idle between two proposal windows (streams.py: why not its own)
+        from ..functions.conv import no_filter_cache
+        from ..streams import defer_stream
         side, main = defer_stream(dev), torch.cuda.current_stream(dev)
         side.wait_stream(main)
         # (the transformed-filter cache is ordered on the main stream only: bypassed here)

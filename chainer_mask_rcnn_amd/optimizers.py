@@ -42,7 +42,7 @@ import math
 
 import torch
 
-from . import _lib
+from . import _lib, streams
 
 
 class WeightDecay(object):
@@ -110,6 +110,9 @@ class ParamArena(object):
         self.grads = torch.zeros(total, dtype=torch.float32, device=dev)
         self.momenta = torch.zeros(total, dtype=torch.float32, device=dev)
         self.epoch = 1            # bumped by every optimizer step
+        # None, or the conv.DeferQueue of the backward in progress: a weight gradient that claimed
+        # its slot and whose parameter the queue names is held back instead of launched (conv._wgrad)
+        self.defer = None
         with torch.no_grad():
             for i, (p, off) in enumerate(zip(self.params, offs)):
                 size, stride = tuple(p.shape), p.stride()
@@ -256,7 +259,7 @@ class MomentumSGD(object):
         self._pending = None
         a = self.arena
         dev = a.values.device
-        side, main = conv.defer_stream(dev), torch.cuda.current_stream(dev)
+        side, main = streams.defer_stream(dev), torch.cuda.current_stream(dev)
         side.wait_stream(main)
         with torch.cuda.stream(side):
             conv.run_deferred_wgrads(jobs)
@@ -327,13 +330,12 @@ class MomentumSGD(object):
             from .functions import conv
             if self.deferred_params and (self.grad_sync is None or
                                          getattr(self.grad_sync, 'supports_deferred', False)):
-                defer = conv._DEFER = conv.DeferQueue(self.deferred_params)
+                defer = self.arena.defer = conv.DeferQueue(self.deferred_params)
             try:
                 loss.backward()
             finally:
-                conv._DEFER = None
-        from .functions.conv import join_wgrad_stream
-        join_wgrad_stream()            # weight gradients queued on the side stream
+                self.arena.defer = None
+        streams.join_wgrad_stream()    # weight gradients queued on the side stream
         scale = 1.0
         if self.grad_sync is not None:
             scale = self.grad_sync.finish()
@@ -413,13 +415,6 @@ class MomentumSGD(object):
 
 
 _DEFERRING = []       # optimizers that may hold deferred work (see defer_weight_gradients)
-# where the held-back work is queued: 'window-open' = right behind the RPN convolutions, beside
-# the top-k / NMS kernels (measured best: 49.6-50.0 vs 50.6-51.2 ms per step without deferral);
-# 'after-proposals' = once the proposal read-back has returned (50.0-50.6).  Running the proposal
-# kernels on a separate high-priority stream next to the deferred work was measured and dropped
-# (64 ms per step).
-import os as _os
-DEFER_LAUNCH_AT = _os.environ.get('MRCNN_DEFER_AT', 'window-open')
 
 
 def launch_pending_all():

@@ -52,7 +52,7 @@ class TorchDistExchange(object):
     def allreduce_async(self, tensor, bucket_id=0):
         if tensor.is_cuda:
             # weight gradients queued on the side stream must be ordered before the collective
-            from .functions.conv import join_wgrad_stream
+            from .streams import join_wgrad_stream
             join_wgrad_stream(tensor.device)
         self._works.append(dist.all_reduce(tensor, op=dist.ReduceOp.SUM, group=self.group,
                                            async_op=True))
@@ -118,7 +118,7 @@ class RcclExchange(object):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _side_stream(self):
-        from .functions.conv import wgrad_stream_if_used
+        from .streams import wgrad_stream_if_used
         st = wgrad_stream_if_used(self.device)
         return ctypes.c_void_p(st.cuda_stream) if st is not None else None
 

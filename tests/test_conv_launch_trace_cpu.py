@@ -206,10 +206,9 @@ def _head_arena(rec, mp):
     arena = optimizers.ParamArena(params[::-1])
     held = [blocks[0].conv1.W, blocks[0].conv2.W, blocks[0].conv4.W, blocks[1].conv3.W, blocks[2].conv2.W]
     x = _input(rec, (2, 32, 6, 8), False)
-    queue = C.DeferQueue(held)
-    mp.setattr(C, '_DEFER', queue)
+    queue = arena.defer = C.DeferQueue(held)
     _head_backward(rec, blocks, x, rois, order, tail)
-    mp.setattr(C, '_DEFER', None)
+    arena.defer = None
     assert len(queue.jobs) == len(held)
     rec.mark('deferred')
     C.run_deferred_wgrads(queue.jobs)
@@ -230,8 +229,7 @@ def _conv2d_sparse(rec, mp, filled):
     W, b = _conv_layer(rec, 8, 16, 3)
     x = _input(rec, (2, 8, 5, 6), True)
     hint = C.SparseRows()
-    with C.sparse_output_grad(hint):
-        y = F.conv2d(x, W, b, stride=1, pad=1, relu=True)
+    y = F.conv2d(x, W, b, stride=1, pad=1, relu=True, grad_rows=hint)
     if filled:
         import numpy as np
         rows, lookup = C.SparseRows.host_tables([3, 17, 40, 41], 2 * 5 * 6)
@@ -275,15 +273,14 @@ def _conv2d_arena(rec, mp, winograd):
         mp.setattr(C, 'WINOGRAD_MIN_CHANNELS', 8)
         mp.setattr(C, 'WINOGRAD_MIN_WORK', 0)
     W, b = _conv_layer(rec, 8, 16, 3)
-    optimizers.ParamArena([b, W])
+    arena = optimizers.ParamArena([b, W])
     x = _input(rec, (2, 8, 5, 6), False)
-    queue = C.DeferQueue([W])
-    mp.setattr(C, '_DEFER', queue)
+    queue = arena.defer = C.DeferQueue([W])
     for _ in range(2):
         y = F.conv2d(x, W, b, stride=1, pad=1, relu=True)
         rec.mark('backward')
         y.backward(torch.ones_like(y))
-    mp.setattr(C, '_DEFER', None)
+    arena.defer = None
     assert len(queue.jobs) == int(winograd)
     rec.mark('deferred')
     C.run_deferred_wgrads(queue.jobs)

@@ -240,8 +240,7 @@ def test_row_sparse_3x3_backward_equals_dense(dev, shape):
     def run(sparse):
         xt, wt, bt = (t.clone().requires_grad_(True) for t in (x, Wt, b))
         hint = conv_mod.SparseRows()
-        with conv_mod.sparse_output_grad(hint):
-            y = F.conv2d(xt, wt, bt, 1, 1, relu=True)
+        y = F.conv2d(xt, wt, bt, 1, 1, relu=True, grad_rows=hint)
         if sparse:
             hint.set(torch.tensor(rows_h, device=dev), torch.tensor(lookup_h, device=dev), len(rows_h))
         y.backward(gy)
@@ -305,8 +304,7 @@ def test_row_sparse_hint_is_per_forward(dev):
     # a hint for a different map: rejected by the backward's guard, result = dense
     xt = xs[0].clone().requires_grad_(True)
     hint = conv_mod.SparseRows()
-    with conv_mod.sparse_output_grad(hint):
-        y = F.conv2d(xt, rpn.conv1.W, rpn.conv1.b, 1, 1, relu=True)
+    y = F.conv2d(xt, rpn.conv1.W, rpn.conv1.b, 1, 1, relu=True, grad_rows=hint)
     r, l = conv_mod.SparseRows.host_tables(np.array([1, 2]), N * H * W + 7)
     hint.set(torch.tensor(r, device=dev), torch.tensor(l, device=dev), len(r))
     assert not hint.valid_for(conv_mod.make_desc(xt.shape, rpn.conv1.W.shape, 1, 1), xt.device)

@@ -16,7 +16,7 @@ import torch
 
 import chainer_mask_rcnn_amd as cmr
 import grad_control_ref as R
-from chainer_mask_rcnn_amd import optimizers
+from chainer_mask_rcnn_amd import optimizers, streams
 from chainer_mask_rcnn_amd.functions import conv
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -84,7 +84,7 @@ def backward_by_hand(chain, opt, inputs, seed):
     np.random.seed(seed)
     loss = chain(*inputs)
     loss.backward()
-    conv.join_wgrad_stream()
+    streams.join_wgrad_stream()
     torch.cuda.synchronize()
     return loss
 

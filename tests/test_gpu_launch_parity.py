@@ -21,7 +21,7 @@ import torch
 
 import bench
 import launch_ref
-from chainer_mask_rcnn_amd import _lib
+from chainer_mask_rcnn_amd import _lib, streams
 from chainer_mask_rcnn_amd.functions import conv
 
 pytestmark = pytest.mark.gpu
@@ -183,7 +183,7 @@ def _run_block(blk, x, seed=5):
     g = torch.randn(y.shape, generator=torch.Generator(device=y.device).manual_seed(seed),
                     device=y.device).contiguous(memory_format=torch.channels_last)
     y.backward(g)
-    conv.join_wgrad_stream(x.device)
+    streams.join_wgrad_stream(x.device)
     torch.cuda.synchronize()
     out = [y.detach().clone(), xt.grad.clone()] + [p.grad.clone() for p in blk.parameters() if p.grad is not None]
     for p in blk.parameters():

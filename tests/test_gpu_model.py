@@ -389,7 +389,7 @@ def test_optimizer_arena_step(dev, setup):
     a = opt.arena
     loss = chain(torch.tensor(imgs, device=dev), bboxes, labels, masks, [1., 1.])
     loss.backward()
-    from chainer_mask_rcnn_amd.functions.conv import join_wgrad_stream
+    from chainer_mask_rcnn_amd.streams import join_wgrad_stream
     join_wgrad_stream()
     assert all(a.written()), 'every arena parameter received a gradient'
     p0, v0 = a.values.clone(), a.momenta.clone()
@@ -462,7 +462,7 @@ def test_optimizer_ownership_rules(dev):
     raises; layers below freeze_at are never updated even if left enabled; a parameter without
     a gradient in a step is skipped entirely; a dropped .grad is re-bound; two backward passes
     before one step accumulate."""
-    from chainer_mask_rcnn_amd.functions.conv import join_wgrad_stream
+    from chainer_mask_rcnn_amd.streams import join_wgrad_stream
     model, chain, imgs, bboxes, labels, masks = _build(dev)
     opt = optimizers.MomentumSGD(lr=1e-4, momentum=0.9)
     opt.setup(chain)

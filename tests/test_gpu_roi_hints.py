@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from chainer_mask_rcnn_amd.functions import RoiHints, roi_spatial_order
-from chainer_mask_rcnn_amd.functions.conv import join_wgrad_stream
+from chainer_mask_rcnn_amd.streams import join_wgrad_stream
 from chainer_mask_rcnn_amd.models.mask_rcnn_resnet import ResNetRoIHead
 from chainer_mask_rcnn_amd.models.mask_rcnn_train_chain import _upload_many
 from test_gpu_projected_pooling import _rois

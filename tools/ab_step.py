@@ -1,19 +1,14 @@
 """Developer tool: A/B a switch on the same box, alternating blocks of train steps.
-usage: python tools/ab_step.py <toggle> [rounds] [steps]   toggles: fanout, upload, wside_all, posmajor"""
+usage: python tools/ab_step.py <toggle> [rounds] [steps]   toggles: upload, wside_all, posmajor"""
 import os, sys, time
 import numpy as np
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
-import chainer_mask_rcnn_amd.functions as F
 from chainer_mask_rcnn_amd.models import mask_rcnn_train_chain
 
 
 def toggles(name):
-    if name == 'fanout':
-        orig = F.fanout_rows
-        plain = lambda x, rows: (x, x.index_select(0, rows))
-        return (lambda: setattr(F, 'fanout_rows', orig)), (lambda: setattr(F, 'fanout_rows', plain))
     if name == 'upload':
         orig = mask_rcnn_train_chain._upload
         plain = lambda a, dt, dev: torch.tensor(a, dtype=dt, device=dev)
