@@ -1,0 +1,379 @@
+"""The case lists and the policy restatement of tests/gemm_edge_cases.py, without a device:
+coverage of the launch policy's branches and of the kernel instantiations, the float64 references
+of tests/launch_ref.py at the degenerate geometries of the lists, the comparison of
+tests/test_gpu_gemm_edges.py on emulated kernels (right, and wrong the way each edge goes wrong),
+and the size caps."""
+import collections
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as TF
+
+import gemm_edge_cases as G
+import launch_ref as L
+from oracle import np_ref
+
+F64 = torch.float64
+
+
+def _t(a):
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64)))
+
+
+def _calls():
+    return list(G.all_calls())
+
+
+# ---- coverage -----------------------------------------------------------------------------------
+
+# label -> why no accepted shape reaches it in that mode (none so far: every label is reached)
+UNREACHABLE_FWD = {}
+UNREACHABLE_DGRAD = {}
+
+
+def test_every_policy_label_is_reached():
+    seen = collections.defaultdict(set)
+    for fam, i, entry, d, ws, kn in _calls():
+        r = G.route(entry, d, 0, ws, kn)
+        p = None if 'wgrad' in entry else G.gemm_problem(entry, d, ws, dict(G.DEFAULT_KNOBS, **kn))
+        mode = 'wgrad' if p is None else p.mode
+        arith = 'fp32' if kn.get('split_bf16', 3) == 0 else 'split'
+        seen[(mode, arith)].add(r.label)
+        assert r.label != 'w8', i                  # out of scope, and never by accident
+        assert sum(r.record.values()) == len(r.launches) >= 1
+    assert seen[(G.FWD, 'split')] | set(UNREACHABLE_FWD) == set(G.FWD_LABELS)
+    assert seen[(G.FWD, 'fp32')] | set(UNREACHABLE_FWD) == set(G.FWD_LABELS)
+    assert seen[(G.DGRAD, 'split')] | set(UNREACHABLE_DGRAD) == set(G.FWD_LABELS)
+    assert seen[('wgrad', 'split')] >= set(G.WGRAD_LABELS)
+    assert seen[('wgrad', 'split')] - set(G.WGRAD_LABELS) <= set(G.OTHER_LABELS)
+
+
+def test_every_instantiation_appears():
+    tags = collections.Counter()
+    per_mode = collections.defaultdict(set)
+    for fam, i, entry, d, ws, kn in _calls():
+        for kind, t in G.route(entry, d, 0, ws, kn).launches:
+            tags.update(t)
+            per_mode[t[0]].add(t[1:])
+    for want in ('PW', 'K3', 'general', 'perm', 'stem', G.OUT_STRIDED, G.OUT_DECONV, 'WPERM', 'split', 'fp32',
+                 '64x64', '128x128'):
+        assert tags[want] > 0, want
+    # both tile sizes of the three modes; the strided scatter and the pixel shuffle in both forms
+    for mode in (G.FWD, G.DGRAD, G.WGRAD):
+        assert {t[0] for t in per_mode[mode]} == {'64x64', '128x128'}, mode
+    for out in (G.OUT_STRIDED, G.OUT_DECONV):
+        assert any(t[1] == out for t in per_mode[G.FWD]) and any(t[1] == out for t in per_mode[G.DGRAD]), out
+    # PW and K3 on both tile sizes, the position-major order on the general instantiation only
+    for inst in ('PW', 'K3'):
+        assert {t[0] for t in per_mode[G.FWD] if inst in t} == {'64x64', '128x128'}, inst
+
+
+def test_expected_labels_of_the_lists():
+    for i, d, kn, label in G.WGRAD_WPERM:
+        assert G.route('conv2d_wgrad_ex', d, 0, True, kn).label == label, i
+    for i, entry, d, kn, label in G.policy_cases():
+        assert G.route(entry, d, 0, True, kn).label == label, i
+        rows, cols = d.W, (d.K if entry == 'conv2d_fwd' else d.C)
+        assert cols % 64 == 4 and rows % 64 != 0 and rows % 128 != 0, i       # ragged in both
+    assert G.route('conv2d_dgrad_ex', G.DGRAD_TINY_SPLIT[1]).label == 'small/tiny_split'
+    assert G.route('conv2d_dgrad', G.DGRAD_TINY_SPLIT[1], 0, False).label == 'small/plain'
+    for i, (R, Cin, Cout) in G.LINEAR:
+        if R == 1 and Cin == 2048:
+            assert G.route('conv2d_fwd', G.desc(R, Cin, 1, 1, Cout)).label == 'small/tiny_split', i
+    # the thresholds of choose_perm: 63 / 64 images, 256 / 272 positions, the knob
+    on = dict(G.DEFAULT_KNOBS)
+    assert G.choose_perm(63, 7, 7, 3, 3, 1, 1, on) == 0 and G.choose_perm(64, 7, 7, 3, 3, 1, 1, on) == 64
+    assert G.choose_perm(64, 16, 16, 3, 3, 1, 1, on) == 64 and G.choose_perm(64, 16, 17, 3, 3, 1, 1, on) == 0
+    assert G.choose_perm(64, 7, 7, 3, 3, 1, 0, on) == 0 and G.choose_perm(64, 7, 7, 1, 1, 1, 1, on) == 0
+    assert G.choose_perm(64, 7, 7, 3, 3, 1, 1, dict(on, position_major_rows=0)) == 0
+    perm = [G.gemm_problem('conv2d_fwd', d, True, on) for _, d in G.PERM_POSITIONS]
+    assert perm[0].perm_n == 64 and perm[0].M == 128 * 256 and perm[1].perm_n == 0
+    # 129 images: two blocks of kPermBlock, 127 padding rows per position in the last
+    p = G.gemm_problem('conv2d_fwd', G.desc(129, 4, 2, 2, 4, 3, 3, 1, 1), True, on)
+    assert p.perm_n == 129 and p.M == 256 * 4
+
+
+def test_policy_cases_are_the_smallest_that_reach_their_label():
+    """One tile row fewer (rows - 64, still ragged) at the same columns and depth takes another branch."""
+    for i, entry, d, kn, label in G.policy_cases():
+        if d.W <= 64:
+            continue
+        fewer = d._replace(W=d.W - 64)
+        assert G.route(entry, fewer, 0, True, kn).label != label, i
+
+
+def test_fit_ws_clamp_is_unreachable_at_the_default_knobs():
+    """The arithmetic of the comment above gemm_edge_cases.fit_ws, at its worst cases."""
+    ws = G.SPLIT_WS_BYTES
+    assert 512 * 128 * 128 * 4 <= ws                    # one-round rule: T fit <= 512
+    assert 383 * 128 * 128 * 8 * 4 <= ws                # big_split_k > 0 under big_min_tiles = 384
+    assert 128 * 64 * 64 * 16 * 4 <= ws                 # tiny split
+    assert 154 * 64 * 64 * 16 * 4 <= ws                 # 64x64 fused tail
+    assert 1024 * 128 * 128 * 4 <= ws                   # 128x128 fused tail: tiles x slabs < 1024
+    for fam, i, entry, d, ws_, kn in _calls():
+        if 'wgrad' in entry:
+            continue
+        p = G.gemm_problem(entry, d, ws_, dict(G.DEFAULT_KNOBS, **kn))
+        assert G.fit_ws(16, p.M, p.N) == 16 or p.M * p.N * 4 > (ws >> 4), i
+
+
+# ---- size caps ------------------------------------------------------------------------------------
+
+def test_size_caps():
+    over = set()
+    for fam, i, entry, d, ws, kn in _calls():
+        b = G.moved_bytes(entry, d)
+        assert b <= 256 << 20, i
+        if b > 16 << 20:
+            assert fam == 'policy', i
+            over.add(i)
+    by_id = {i: label for i, _, _, _, label in G.policy_cases()}
+    for i in over:
+        assert by_id[i] in G.POLICY_SIZE_REASON and 'size forced by ' + by_id[i] in i, i
+    for N, C, H, W, K in G.WINOGRAD:
+        assert 4 * N * H * W * (C + K) <= 16 << 20
+
+
+def test_operands_have_no_zeros_and_no_repeats():
+    for d in (G.pw_desc(129, 132, 100), G.desc(65, 36, 2, 2, 40, 3, 3, 1, 1), G.desc(1, 4, 1, 1, 4)):
+        x, w, gy = G.operands(d)
+        for a in (x.transpose(0, 2, 3, 1).reshape(-1, d.C), w.reshape(d.K, -1), gy.transpose(0, 2, 3, 1).reshape(-1, d.K)):
+            assert np.all(a != 0)
+            assert len(np.unique(a, axis=0)) == a.shape[0] and len(np.unique(a.T, axis=0)) == a.shape[1]
+        x2, _, _ = G.operands(d)
+        assert np.array_equal(x, x2)                 # seeded
+
+
+# ---- the references at the degenerate geometries ---------------------------------------------------
+
+def _close64(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    assert a.shape == b.shape
+    assert np.abs(a - b).max() <= 1e-12 * max(1., np.abs(b).max())
+
+
+def _geometries():
+    out = []
+    for what, R, S, pad, H, W in G.SMALL_MAP_GEOMS:
+        out += [G.desc(N, 4, H, W, 8, R, S, 1, pad) for N in (1, 3)]
+    out += [d._replace(C=4, K=8) for _, d in G.STRIDED if d.N == 1]
+    out += [G.desc(1, 4, 1, 1, 4), G.desc(1, 8, 1, 5, 4)]                  # one pixel, one image / one row
+    out += [G.desc(N, 3, H, W, 4, 7, 7, 2, 3) for _, (N, H, W, K, aff) in G.STEM[::4]]    # the stem's geometry
+    return out
+
+
+@pytest.mark.parametrize('d', _geometries(), ids=lambda d: 'N%d %dx%d R%dS%d s%d p%d' % (
+    d.N, d.H, d.W, d.R, d.S, d.stride, d.pad))
+def test_conv_references_at_degenerate_geometries(d):
+    """launch_ref.conv_fwd / conv_dgrad / conv_wgrad against the NumPy oracle (square filters) and
+    torch.nn.functional in float64 (every filter) where H < R, on odd and 1x1 maps under stride 2, for
+    a non-square filter, one pixel, one image."""
+    x, w, gy = (a.astype(np.float64) for a in G.operands(d))
+    y = L.conv_fwd(_t(x), _t(w), d.stride, d.pad)
+    gx = L.conv_dgrad(_t(gy), _t(w), d.H, d.W, d.stride, d.pad)
+    gw = L.conv_wgrad(_t(x), _t(gy), d.R, d.S, d.stride, d.pad)
+    assert tuple(y.shape) == (d.N, d.K, d.P, d.Q)
+    xt, wt = _t(x).requires_grad_(True), _t(w).requires_grad_(True)
+    yt = TF.conv2d(xt, wt, None, d.stride, d.pad)
+    yt.backward(_t(gy))
+    _close64(y, yt.detach())
+    _close64(gx, xt.grad)
+    _close64(gw, wt.grad)
+    if d.R == d.S:
+        _close64(y, np_ref.conv2d_fwd(x, w, None, d.stride, d.pad))
+        ogx, ogw, _ = np_ref.conv2d_bwd(x, w, gy, d.stride, d.pad)
+        _close64(gx, ogx)
+        _close64(gw, ogw)
+
+
+def test_stem_reference_through_the_packed_layout():
+    """The stem reference of the checker reads x4 (N,H,W,4) and w784 (K,7,8,4): the same slicing on the
+    tiny images, against the oracle."""
+    for i, (N, H, W, K, aff) in G.STEM[::2]:
+        rng = np.random.RandomState(G.seed_of(N, H, W, K))
+        x = rng.standard_normal((N, 3, H, W))
+        w = rng.standard_normal((K, 3, 7, 7)) / 12.
+        b, sc, sh = rng.standard_normal(K), rng.uniform(.5, 1.5, K), rng.standard_normal(K)
+        x4 = np.zeros((N, H, W, 4))
+        x4[..., :3] = x.transpose(0, 2, 3, 1)
+        w784 = np.zeros((K, 7, 8, 4))
+        w784[:, :, :7, :3] = w.transpose(0, 2, 3, 1)
+        X = _t(x4)[..., :3].permute(0, 3, 1, 2)
+        Wt = _t(w784)[:, :, :7, :3].permute(0, 3, 1, 2)
+        flags = L.EPI_RELU | L.EPI_BIAS | (L.EPI_AFFINE if aff else 0)
+        got = L.fwd_epilogue(L.conv_fwd(X, Wt, 2, 3), flags, _t(b), _t(sc), _t(sh))
+        ref = np_ref.conv2d_fwd(x, w, b, 2, 3)
+        if aff:
+            ref = np_ref.affine_channel_2d_fwd(ref, sc, sh)
+        _close64(got, np.maximum(ref, 0))
+
+
+def test_deconv_references_at_the_list_shapes():
+    for i, d in G.DECONV:
+        if d.C == 64:
+            continue
+        rng = np.random.RandomState(G.seed_of(*d))
+        x = rng.standard_normal((d.N, d.C, d.H, d.W))
+        w = rng.standard_normal((d.C, d.K, 2, 2)) / np.sqrt(d.C)
+        gy = rng.standard_normal((d.N, d.K, 2 * d.H, 2 * d.W))
+        xt, wt = _t(x).requires_grad_(True), _t(w).requires_grad_(True)
+        yt = TF.conv_transpose2d(xt, wt, None, 2)
+        yt.backward(_t(gy))
+        y, gx, gw = L.deconv_fwd(_t(x), _t(w)), L.deconv_dgrad(_t(gy), _t(w)), L.deconv_wgrad(_t(x), _t(gy))
+        _close64(y, yt.detach())
+        _close64(gx, xt.grad)
+        _close64(gw, wt.grad)
+        # the oracle rounds its deconvolution results to fp32: 2^-24 relative
+        ogx, ogw, _ = np_ref.deconv2x2s2_bwd(x, w, gy)
+        for got, ref in ((y, np_ref.deconv2x2s2_fwd(x, w, None)), (gx, ogx), (gw, ogw)):
+            assert got.shape == ref.shape
+            assert np.all(np.abs(got.numpy() - ref) <= 2. ** -23 * np.abs(got.numpy()) + 1e-30), i
+
+
+@pytest.mark.parametrize('variant', G.DGRAD_VARIANTS)
+def test_dgrad_epilogue_reference_on_one_pixel_and_tiny_maps(variant):
+    for d in (G.desc(1, 4, 1, 1, 4), G.desc(3, 36, 2, 2, 40, 3, 3, 1, 1)):
+        rng = np.random.RandomState(3)
+        acc = rng.standard_normal((d.N, d.C, d.H, d.W))
+        flags, rg, ry, mk, sc, prev = G.dgrad_flags_operands(variant, d, rng)
+        ref = acc * (1. if sc is None else sc.astype(np.float64)[None, :, None, None])
+        if rg is not None:
+            ref = ref + (rg if ry is None else rg * (ry > 0))
+        if prev is not None:
+            ref = ref + prev
+        if mk is not None:
+            ref = ref * (mk > 0)
+        got = L.dgrad_epilogue(_t(acc), flags, *(None if a is None else _t(a) for a in (prev, rg, ry, mk, sc)))
+        _close64(got, ref)
+        assert (variant in ('accum', 'all')) == bool(flags & L.EPI_ACCUM)
+
+
+# ---- the detector catches what it is for ---------------------------------------------------------
+
+def _f32(t):
+    """What a correct fp32 kernel may return: the float64 result rounded to fp32."""
+    return t.to(torch.float32)
+
+
+def _accepts(got, ref):
+    return L.ratio(got, ref) <= 1.
+
+
+def _gemm(d):
+    """(x rows (M, Kc), w (N, Kc)) float64 of a 1x1 problem and its product."""
+    x, w, _ = G.operands(d)
+    X = _t(x)[0, :, 0, :].t().contiguous()
+    Wm = _t(w)[:, :, 0, 0]
+    return X, Wm, X @ Wm.t()
+
+
+RAGGED = [G.pw_desc(*c) for c in ((65, 68, 36), (129, 132, 100), (1, 4, 4), (63, 60, 28), (200, 132, 100))]
+
+
+@pytest.mark.parametrize('d', RAGGED, ids=lambda d: G.pw_id(d.W, d.K, d.C))
+def test_detector_ragged_k_rows_and_columns(d):
+    X, Wm, ref = _gemm(d)
+    assert _accepts(_f32(ref), ref)
+    if d.C % 32:
+        assert not _accepts(_f32(X[:, :-1] @ Wm[:, :-1].t()), ref), 'last K element dropped'
+    for what, bad in (('last row dropped', lambda y: y[-1].zero_()),
+                      ('last column dropped', lambda y: y[:, -1].zero_()),
+                      ('last row taken from its neighbour', lambda y: y[-1].copy_(y[-2] if len(y) > 1 else -y[-1])),
+                      ('last column taken from its neighbour', lambda y: y[:, -1].copy_(y[:, -2]))):
+        y = _f32(ref).clone()
+        bad(y)
+        assert not _accepts(y, ref), what
+
+
+@pytest.mark.parametrize('geom', G.SMALL_MAP_GEOMS[:6], ids=lambda g: g[0])
+def test_detector_padding_tap_wrapped(geom):
+    what, R, S, pad, H, W = geom
+    d = G.desc(3, 4, H, W, 8, R, S, 1, pad)
+    x, w, _ = G.operands(d)
+    ref = L.conv_fwd(_t(x), _t(w), 1, pad)
+    assert _accepts(_f32(ref), ref)
+    wrapped = TF.conv2d(TF.pad(_t(x), (pad,) * 4, mode='circular'), _t(w))
+    assert not _accepts(_f32(wrapped), ref), 'padding taps read the opposite border'
+
+
+def test_detector_skipped_k_split_slab():
+    cases = [(e, d) for _, e, d, kn, label in G.policy_cases() if label == 'small/tiny_split'] + \
+        [('conv2d_dgrad_ex', G.DGRAD_TINY_SPLIT[1])]
+    for entry, d in cases:
+        depth = d.C if entry == 'conv2d_fwd' else d.K
+        rng = np.random.RandomState(5)
+        A = _t(rng.standard_normal((d.W, depth)))
+        B = _t(rng.standard_normal((68, depth)) / np.sqrt(depth))
+        ref = A @ B.t()
+        assert _accepts(_f32(ref), ref)
+        slices = G.ceil_div(depth, G.BK)
+        splits = min(16, slices // 8, 512)
+        slab = G.ceil_div(slices, splits) * G.BK
+        for s in (0, splits - 1):
+            keep = torch.ones(depth, dtype=F64)
+            keep[s * slab:(s + 1) * slab] = 0
+            assert not _accepts(_f32((A * keep) @ B.t()), ref), 'slab %d of %d skipped' % (s, splits)
+
+
+def test_detector_deconv_column_groups_shifted():
+    for i, d in G.DECONV:
+        if (4 * d.K) % 64 == 0 or d.C == 64:
+            continue
+        rng = np.random.RandomState(G.seed_of(*d))
+        x = _t(rng.standard_normal((d.N, d.C, d.H, d.W)))
+        w = _t(rng.standard_normal((d.C, d.K, 2, 2)) / np.sqrt(d.C))
+        ref = L.deconv_fwd(x, w)
+        assert _accepts(_f32(ref), ref), i
+        # columns are (a, b, o): the map shifted by one group sends group (a, b) to the next output pixel
+        shifted = L.deconv_fwd(x, w.reshape(d.C, d.K, 4).roll(1, 2).reshape(d.C, d.K, 2, 2))
+        assert not _accepts(_f32(shifted), ref), i
+
+
+def test_detector_guard_bands_and_prefill():
+    d = G.desc(129, 4, 2, 2, 8, 3, 3, 1, 1)
+    x, w, _ = G.operands(d)
+    ref = L.conv_fwd(_t(x), _t(w), 1, 1).permute(0, 2, 3, 1).contiguous()          # NHWC, as the kernels write
+    n = ref.numel()
+
+    def fresh():
+        g = G.Guarded(n, 'cpu')
+        g.out.copy_(_f32(ref).reshape(-1))
+        return g
+
+    g = fresh()
+    assert g.check() is None and _accepts(g.out.view(ref.shape), ref)
+    # a padding row of the last kPermBlock block (image 129 of 256) written: it lands behind the output
+    g = fresh()
+    g.buf[G.GUARD + n:G.GUARD + n + d.K] = 0
+    assert 'guard' in g.check()
+    # one element written past the end / before the start
+    for at in (G.GUARD + n, G.GUARD - 1, n + 2 * G.GUARD - 1):
+        g = fresh()
+        g.buf[at] = 0x3f800000
+        assert 'guard' in g.check()
+    # one output element left unwritten: the NaN prefill stays, ratio() is inf and check() names it
+    g = fresh()
+    g.buf[G.GUARD + n // 2] = G.NAN_BITS
+    assert 'never written' in g.check() and not _accepts(g.out.view(ref.shape), ref)
+    # ... unless the operation defines no value there
+    defined = torch.ones(n, dtype=torch.bool)
+    defined[n // 2] = False
+    assert g.check(defined) is None
+    # the prefill is a NaN with a payload no kernel produces
+    assert torch.isnan(G.Guarded(4, 'cpu').out).all()
+
+
+def test_detector_strided_scatter_needs_exact_zeros():
+    """OUT_STRIDED without ACCUM: the positions between the strided pixels are exact zeros; a stale
+    value below the bound's floor still fails the exact check the device test makes."""
+    d = G.desc(1, 4, 5, 4, 8, 1, 1, 2, 0)
+    x, w, gy = G.operands(d)
+    ref = L.conv_dgrad(_t(gy), _t(w), d.H, d.W, 2, 0)
+    between = torch.ones_like(ref, dtype=torch.bool)
+    between[:, :, ::2, ::2] = False
+    assert bool((ref[between] == 0).all())
+    got = _f32(ref)
+    assert _accepts(got, ref) and bool((got[between] == 0).all())
+    got[0, 0, 1, 1] = 1e-7 * float(ref.abs().max())
+    assert _accepts(got, ref) and not bool((got[between] == 0).all())

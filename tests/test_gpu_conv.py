@@ -534,8 +534,7 @@ def test_position_major_wgrad(dev, case):
         lib.mrcnn_set_tuning(b'position_major_rows', 1)
     _, gW, _ = np_ref.conv2d_bwd(*_64(x, np.zeros((K, C, 3, 3), np.float32), gy), 1, 1, need_gx=False)
     _close(outs[0].cpu().numpy(), gW)
-    _close(outs[1].cpu().numpy(), gW)
-    assert not torch.equal(outs[0], outs[1]) or True     # orders differ; values agree to 1e-4
+    _close(outs[1].cpu().numpy(), gW)       # the claim: both pixel orders within the bound of float64
 
 
 @pytest.mark.parametrize('rois', [1024, 1000])
