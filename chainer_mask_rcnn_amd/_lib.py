@@ -25,6 +25,16 @@ class ConvDesc(ctypes.Structure):
 _DP = ctypes.POINTER(ConvDesc)
 
 
+class TestAugView(ctypes.Structure):
+    """mrcnn_test_aug_view: one view of an image for mrcnn_decode_cls_boxes_views."""
+    _fields_ = [('roi', c_vp), ('cls_loc', c_vp), ('ld_loc', ctypes.c_int32), ('R', ctypes.c_int32),
+                ('scale', c_f32), ('flip_x', ctypes.c_int32)]
+
+
+TEST_AUG_MAX_VIEWS = 8
+MASK_AUG_HEURS = {'soft_avg': 0, 'soft_max': 1, 'logit_avg': 2}     # MRCNN_MASK_AUG_*
+
+
 # name -> (restype, argtypes); every symbol declared in include/mrcnn_hip.h
 SIGNATURES = {
     'mrcnn_last_error': (ctypes.c_char_p, []),
@@ -169,6 +179,12 @@ SIGNATURES = {
     'mrcnn_decode_cls_boxes': (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_f32,
                                        ctypes.POINTER(ctypes.c_double),
                                        ctypes.POINTER(ctypes.c_double), c_f32, c_f32, c_vp]),
+    'mrcnn_decode_cls_boxes_views': (c_int, [ctypes.POINTER(TestAugView), c_int, c_int,
+                                             ctypes.POINTER(ctypes.c_double),
+                                             ctypes.POINTER(ctypes.c_double), c_f32, c_f32, c_vp,
+                                             c_vp]),
+    'mrcnn_mask_aug_combine': (c_int, [ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_int32), c_int,
+                                       c_int, c_int, c_int, c_int, c_vp, c_vp]),
 }
 
 _lib = None

@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "decode_cls_box.h"
 
 namespace {
 
@@ -187,7 +188,7 @@ __global__ void gather_rows_kernel(const float *__restrict__ src, const int32_t 
     dst[e] = r < n ? src[(int64_t)idx[r] * cols + c] : 0.f;
 }
 
-struct Norm4 { double v[4]; };
+using mrcnn::Norm4;
 
 __global__ void decode_cls_boxes_kernel(const float4 *__restrict__ roi,
                                         const float *__restrict__ cls_loc, int ld_loc,
@@ -198,28 +199,8 @@ __global__ void decode_cls_boxes_kernel(const float4 *__restrict__ roi,
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= R * n_class) return;
     const int r = e / n_class, l = e % n_class;
-    float4 a = roi[r];
-    // rois[keep] / scale  (models/mask_rcnn.py:220)
-    if (use_div) { a.x = a.x / scale; a.y = a.y / scale; a.z = a.z / scale; a.w = a.w / scale; }
-    else { a.x *= inv_scale; a.y *= inv_scale; a.z *= inv_scale; a.w *= inv_scale; }
-    const float *lp = cls_loc + (int64_t)r * ld_loc + 4 * l;
-    // (roi_cls_loc * std + mean).astype(float32) (:225-229): mean / std come from Python tuples,
-    // i.e. float64 arrays — the product and sum are formed in double and rounded once
-    const float dy = (float)((double)lp[0] * stdv.v[0] + mean.v[0]);
-    const float dx = (float)((double)lp[1] * stdv.v[1] + mean.v[1]);
-    const float dh = (float)((double)lp[2] * stdv.v[2] + mean.v[2]);
-    const float dw = (float)((double)lp[3] * stdv.v[3] + mean.v[3]);
-    const float h = a.z - a.x, w = a.w - a.y;
-    const float cy = a.x + 0.5f * h, cx = a.y + 0.5f * w;
-    const float ncy = dy * h + cy, ncx = dx * w + cx;
-    const float nh = (float)exp((double)dh) * h;
-    const float nw = (float)exp((double)dw) * w;
-    float4 o;
-    o.x = fminf(fmaxf(ncy - 0.5f * nh, 0.f), size_h);
-    o.y = fminf(fmaxf(ncx - 0.5f * nw, 0.f), size_w);
-    o.z = fminf(fmaxf(ncy + 0.5f * nh, 0.f), size_h);
-    o.w = fminf(fmaxf(ncx + 0.5f * nw, 0.f), size_w);
-    cls_bbox[e] = o;
+    cls_bbox[e] = mrcnn::decode_cls_box(roi[r], cls_loc + (int64_t)r * ld_loc + 4 * l, inv_scale,
+                                        mean, stdv, size_h, size_w, use_div, scale);
 }
 
 }  // namespace

@@ -3,9 +3,10 @@ chainer_mask_rcnn/extensions/instance_segmentation_{voc,coco}_evaluator.py.
 
 ``evaluate()`` returns the observation dict chainer's reporter builds for ``name='validation'``
 (``validation/main/map``, ...).  Predicted masks never leave the device: per batch,
-``prepare`` -> ``predict_prepared(masks_to_host=False)`` -> packed paste -> intersections
+``predict_images(masks_to_host=False)`` -> packed paste -> intersections
 against the uploaded and packed ground truth, all queued before one read-back of the counts
-and areas.  Boxes, labels and scores come back as ``predict_prepared`` returns them.  Matching
+and areas.  Boxes, labels and scores come back as ``predict_images`` returns them (with the
+model's test-time augmentation, if it has any configured).  Matching
 and accumulation run on the host from those counts (utils/evaluations/matching.py).
 
 ``iou_types=('segm', 'bbox')`` adds box AP under ``validation/main/bbox/...``: the batch's box IoU
@@ -102,10 +103,9 @@ class _InstanceSegmentationEvaluator(object):
                 if len(ex) not in (4, 5, 6):
                     raise ValueError('expected (img, bbox, label, mask[, difficult | crowd, area]) '
                                      'examples, got a %d-tuple' % len(ex))
-            x, sizes, scales = target.prepare([ex[0] for ex in batch])
-            bboxes, roi_masks, labels, scores = target.predict_prepared(
-                x, scales, sizes, masks_to_host=False)
-            dev = x.device
+            bboxes, roi_masks, labels, scores, sizes = target.predict_images(
+                [ex[0] for ex in batch], masks_to_host=False)
+            dev = roi_masks[0].device
             queued, encodes = [], []
             for j, ex in enumerate(batch if segm else ()):
                 gt_mask = ex[3]

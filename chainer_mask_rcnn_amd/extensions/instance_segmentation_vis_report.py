@@ -5,7 +5,7 @@ Per image, the ground truth and the predictions with a score of at least 0.7 are
 the image (utils.draw_instance_bboxes, labels + 1 with '__background__' prepended to the
 names), the two panels are stacked, and the panels of the first rows * cols images are tiled
 into one mosaic (utils.get_tile_image) that is written as a JPEG.  Everything up to the mosaic
-stays on the device: ``prepare`` -> ``predict_prepared(masks_to_host=False)`` -> packed paste
+stays on the device: ``predict_images(masks_to_host=False)`` -> packed paste
 of the kept detections -> drawing in place -> tiling; the mosaic is the only large copy back to
 the host.  Prediction stops once rows * cols images are drawn.
 """
@@ -45,10 +45,9 @@ class InstanceSegmentationVisReport(object):
             batch = list(batch)
             if not batch:
                 continue
-            x, sizes, scales = target.prepare([ex[0] for ex in batch])
-            bboxes, roi_masks, labels, scores = target.predict_prepared(
-                x, scales, sizes, masks_to_host=False)
-            dev = x.device
+            bboxes, roi_masks, labels, scores, sizes = target.predict_images(
+                [ex[0] for ex in batch], masks_to_host=False)
+            dev = roi_masks[0].device
             for j, ex in enumerate(batch[:n_max - len(vizs)]):
                 img, gt_bbox, gt_label, gt_mask = ex[:4]
                 img = np.asarray(img).transpose(1, 2, 0)          # CHW -> HWC

@@ -21,6 +21,7 @@ from .loss import (sigmoid_cross_entropy, softmax_cross_entropy, fast_rcnn_loc_l
                    mask_sigmoid_cross_entropy, softmax)
 from .proposal_ops import non_maximum_suppression
 from .proposal_ops import soft_nms
+from .aug_merge import decode_cls_boxes_views, mask_aug_combine
 from .gt_masks import resize_masks_nearest, upload_packed_masks
 from .scale_jitter import prepare_image_crop, resize_crop_masks
 from .copy_paste import copy_paste, copy_paste_meta

@@ -42,6 +42,13 @@ class MaskRCNN(torch.nn.Module):
         self.soft_nms_sigma = 0.5           # gaussian
         self.soft_nms_min_score = 0.001     # rows decayed below it are dropped
         self.bbox_vote_thresh = None        # None, or the IoU of a vote (Detectron: 0.8)
+        # Detectron's test-time augmentation (TEST.BBOX_AUG / TEST.MASK_AUG), off by default: see
+        # test_aug_views() and predict_images()
+        self.test_aug_h_flip = False        # also run the mirrored image
+        self.test_aug_scales = ()           # extra min_size values
+        self.test_aug_max_size = None       # the extra scales' max_size; None: the model's
+        self.test_aug_scale_h_flip = False  # also run every extra scale mirrored
+        self.mask_aug_heur = 'soft_avg'     # 'soft_avg', 'soft_max' or 'logit_avg' (MASK_AUG.HEUR)
 
         self._detections_per_im = detections_per_im
 
@@ -58,20 +65,23 @@ class MaskRCNN(torch.nn.Module):
         return roi_cls_locs, roi_scores, rois, roi_indices, roi_masks
 
     # ------------------------------------------------------------------ inference
-    def _suppress_queue(self, cls_bbox, prob):
+    def _suppress_queue(self, cls_bbox, prob, n_views=1):
         """Device half of the per-class score threshold + NMS (:178-202) for one image, all
         classes batched: queues the kernels and returns the device results without
         synchronising.  cls_bbox (R, n_class, 4), prob (R, n_class) device tensors.
         With ``soft_nms`` set the Soft-NMS launch stands in the place of the NMS launch, with
         ``bbox_vote_thresh`` set the vote launch follows either; with both off (the default) the
-        launches are the reference's rule and nothing else."""
+        launches are the reference's rule and nothing else.  ``n_views``: how many test-time
+        augmentation views the rows are the union of (for the error message only)."""
         if self.soft_nms is not None and self.soft_nms not in ('linear', 'gaussian'):
             raise ValueError("soft_nms must be None, 'linear' or 'gaussian', got %r"
                              % (self.soft_nms,))
         R = cls_bbox.shape[0]
         if self.soft_nms is not None and R > 4096:
             raise ValueError('soft_nms handles at most 4096 RoIs per image (mrcnn_soft_nms_sorted_'
-                             'batched keeps a class in one workgroup), got %d' % R)
+                             'batched keeps a class in one workgroup), got %d%s'
+                             % (R, ' as the union of %d test-time augmentation views' % n_views
+                                if n_views > 1 else ''))
         n_fg = self.n_class - 1
         dev = cls_bbox.device
         sorted_boxes = torch.empty((n_fg, max(R, 1), 4), dtype=torch.float32, device=dev)
@@ -224,22 +234,25 @@ class MaskRCNN(torch.nn.Module):
         return [roi_masks[roi_indices == i] for i in range(batch_size)]
 
     # ------------------------------------------------------------------ image I/O on device
-    def prepare(self, imgs, x_flips=None):
+    def prepare(self, imgs, x_flips=None, min_size=None, max_size=None):
         """models/mask_rcnn.py:152-176 + concat_examples(padding=0): a list of CHW RGB images
         (uint8 or float) -> zero-padded device batch x (N,3,H,W) channels-last, original
         sizes and scales.  The bilinear resize (cv2 INTER_LINEAR rule) and the mean
         subtraction run in one HIP kernel per image; uint8 images are uploaded as they are.
         ``x_flips`` (extension, used by datasets.MaskRCNNTransform): per-image booleans, mirror
-        the resized image left-right in the same pass."""
+        the resized image left-right in the same pass.  ``min_size`` / ``max_size`` (extension, used
+        by the test-time augmentation views): in the place of the model's."""
+        min_size = self.min_size if min_size is None else min_size
+        max_size = self.max_size if max_size is None else max_size
         dev = next(self.parameters()).device
         sizes, scales, outs = [], [], []
         for img in imgs:
             _, H, W = img.shape
             scale = 1.
-            if self.min_size:
-                scale = self.min_size / min(H, W)
-            if self.max_size and scale * max(H, W) > self.max_size:
-                scale = self.max_size / max(H, W)
+            if min_size:
+                scale = min_size / min(H, W)
+            if max_size and scale * max(H, W) > max_size:
+                scale = max_size / max(H, W)
             sizes.append((H, W))
             scales.append(scale)
             outs.append((int(np.round(H * scale)), int(np.round(W * scale))))
@@ -291,11 +304,150 @@ class MaskRCNN(torch.nn.Module):
     def predict(self, imgs):
         """Detect objects in a list of CHW RGB images (models/mask_rcnn.py:307-337):
         returns (bboxes, masks, labels, scores), per-image lists as the reference."""
-        x, sizes, scales = self.prepare(imgs)
-        bboxes, roi_masks, labels, scores = self.predict_prepared(
-            x, scales, sizes, masks_to_host=False)
+        bboxes, roi_masks, labels, scores, sizes = self.predict_images(imgs, masks_to_host=False)
         masks = self._to_masks(bboxes, labels, scores, roi_masks, sizes)
         return bboxes, masks, labels, scores
+
+    # ------------------------------------------------------------------ test-time augmentation
+    def test_aug_views(self):
+        """The views an image is run through, as (min_size, max_size, flip) in Detectron's order
+        (core/test.py:im_detect_bbox_aug): the identity; its mirror with ``test_aug_h_flip``;
+        then every extra ``test_aug_scales`` entry (with ``test_aug_max_size``, or the model's
+        ``max_size`` if that is None), each followed by its mirror with ``test_aug_scale_h_flip``.
+        With nothing configured that is the identity alone, and nothing is augmented.
+
+        Every view has its own proposals, so there is one rule for merging the views' boxes and
+        scores, Detectron's UNION heuristic: all candidates of all views go into the one per-class
+        suppression (SCORE_HEUR / COORD_HEUR other than UNION need the same boxes in every view,
+        which an RPN does not give).  Masks are computed on the final boxes in every view and
+        combined by ``mask_aug_heur``.  Aspect-ratio views are not offered.
+
+        Raises ValueError for more than 8 views, a non-positive scale or max size, an unknown
+        ``mask_aug_heur``, and ``test_aug_scale_h_flip`` without ``test_aug_scales``."""
+        scales = tuple(self.test_aug_scales or ())
+        if self.mask_aug_heur not in _lib.MASK_AUG_HEURS:
+            raise ValueError('mask_aug_heur must be one of %s, got %r'
+                             % (sorted(_lib.MASK_AUG_HEURS), self.mask_aug_heur))
+        if any(not s > 0 for s in scales):
+            raise ValueError('test_aug_scales must be positive, got %r' % (scales,))
+        if self.test_aug_max_size is not None and not self.test_aug_max_size > 0:
+            raise ValueError('test_aug_max_size must be positive or None, got %r'
+                             % (self.test_aug_max_size,))
+        if self.test_aug_scale_h_flip and not scales:
+            raise ValueError('test_aug_scale_h_flip needs test_aug_scales')
+        views = [(self.min_size, self.max_size, False)]
+        if self.test_aug_h_flip:
+            views.append((self.min_size, self.max_size, True))
+        max_size = self.max_size if self.test_aug_max_size is None else self.test_aug_max_size
+        for s in scales:
+            views.append((s, max_size, False))
+            if self.test_aug_scale_h_flip:
+                views.append((s, max_size, True))
+        if len(views) > _lib.TEST_AUG_MAX_VIEWS:
+            raise ValueError('at most %d test-time augmentation views (mrcnn_decode_cls_boxes_views,'
+                             ' mrcnn_mask_aug_combine), got %d' % (_lib.TEST_AUG_MAX_VIEWS, len(views)))
+        return views
+
+    def predict_images(self, imgs, masks_to_host=True):
+        """``prepare`` + ``predict_prepared`` for a list of CHW RGB images: returns (bboxes,
+        roi_mask_logits, labels, scores, sizes), the first four as ``predict_prepared`` returns
+        them.  With no test-time augmentation configured (``test_aug_views()`` is the identity)
+        that is all it does.  Otherwise every view is prepared and run through the extractor, the
+        RPN and the box heads; per image the views' candidates are decoded into one union in the
+        image frame (mrcnn_decode_cls_boxes_views) which the usual suppression decides, Soft-NMS
+        and box voting included; the mask head then runs on the final boxes in every view and the
+        views' maps are combined by ``mask_aug_heur`` (mrcnn_mask_aug_combine)."""
+        views = self.test_aug_views()
+        if len(views) == 1:
+            x, sizes, scales = self.prepare(imgs)
+            return self.predict_prepared(x, scales, sizes, masks_to_host=masks_to_host) + (sizes,)
+        from .. import optimizers
+        from ..datasets.transforms import flip_bbox
+        from ..functions import aug_merge
+        optimizers.flush_all()
+        was_training = self.training
+        self.eval()
+        try:
+            n_img, n_views = len(imgs), len(views)
+            flips = [flip for _, _, flip in views]
+            passes = []
+            with torch.no_grad():
+                for min_size, max_size, flip in views:
+                    x, sizes, scales = self.prepare(imgs, x_flips=[flip] * n_img,
+                                                    min_size=min_size, max_size=max_size)
+                    h, rois, _, bounds, locs, roi_scores = self._box_heads(x, scales)
+                    if locs.stride(1) != 1:
+                        locs = locs.contiguous()
+                    passes.append((h, scales, rois, bounds, locs, F.softmax(roi_scores)))
+            queued = []
+            for i in range(n_img):
+                recs, probs = [], []
+                for (_, scales, rois, bounds, locs, prob), flip in zip(passes, flips):
+                    lo, hi = int(bounds[i]), int(bounds[i + 1])
+                    recs.append((rois[lo:hi], locs[lo:hi], scales[i], flip))
+                    probs.append(prob[lo:hi])
+                cls_bbox = aug_merge.decode_cls_boxes_views(
+                    recs, self.n_class, self.loc_normalize_mean, self.loc_normalize_std, sizes[i])
+                queued.append(self._suppress_queue(cls_bbox, torch.cat(probs, dim=0),
+                                                   n_views=n_views))
+            # the groups of predict_prepared: a group's boxes are made final, then its mask passes
+            # (one head launch per view) and the combine of each of its images are queued
+            n_groups = 2 if n_img >= 4 else 1
+            per = -(-n_img // n_groups)
+            bboxes, labels, scores, roi_masks = [], [], [], []
+            for g0 in range(0, n_img, per):
+                ids = list(range(g0, min(g0 + per, n_img)))
+                for i in ids:
+                    b, l, s = self._finish_detections(queued[i])
+                    bboxes.append(b)
+                    labels.append(l)
+                    scores.append(s)
+                per_view = []
+                for (h, scales, _, _, _, _), flip in zip(passes, flips):
+                    # the final boxes in the view's frame: mirrored about the original width, then
+                    # scaled by _roi_masks_group as in the plain path
+                    boxes = [flip_bbox(bboxes[i], sizes[i], x_flip=True) if flip else bboxes[i]
+                             for i in ids]
+                    per_view.append(self._roi_masks_group(h, boxes, ids, scales))
+                for k in range(len(ids)):
+                    roi_masks.append(aug_merge.mask_aug_combine([m[k] for m in per_view], flips,
+                                                                self.mask_aug_heur))
+            if masks_to_host:
+                roi_masks = self._masks_to_host(roi_masks, h.device)
+        finally:
+            self.train(was_training)
+        return bboxes, roi_masks, labels, scores, sizes
+
+    def _box_heads(self, x, scales):
+        """The first half of prediction on a prepared batch: extractor -> rpn.propose -> the box
+        heads, one image's proposals at a time.  Returns (h, rois, roi_indices, bounds,
+        roi_cls_locs, roi_scores); bounds: the per-image row bounds of rois, on the host."""
+        h = self.extractor(x)
+        proposals = self.rpn.propose(h, x.shape[2:], scales)
+        rois, roi_indices = proposals.rois, proposals.roi_indices
+        # one image's proposals at a time: keeps every activation below the 2 GiB
+        # buffer-addressing limit of the conv kernels (8 x 1000 RoIs would not fit)
+        # (rois are grouped by image in order and the RPN call knows their counts on the
+        # host: a boolean mask per image would synchronise eight times and leave the GPU
+        # idle while the host queues the next head)
+        bounds = np.concatenate([[0], np.cumsum(proposals.counts)])
+        locs, scs = [], []
+        for i in range(x.shape[0]):
+            lo, hi = int(bounds[i]), int(bounds[i + 1])
+            l_i, s_i, _ = self.head(h, rois[lo:hi], roi_indices[lo:hi], pred_mask=False)
+            locs.append(l_i)
+            scs.append(s_i)
+        return h, rois, roi_indices, bounds, torch.cat(locs, dim=0), torch.cat(scs, dim=0)
+
+    @staticmethod
+    def _masks_to_host(roi_masks, device):
+        """(N x <=100 x 80 x 14 x 14 floats: ~50 MB for a batch of 8) through pinned host memory,
+        all copies queued before the one synchronisation."""
+        host = [torch.empty(m.shape, dtype=m.dtype, pin_memory=True) for m in roi_masks]
+        for h_, m in zip(host, roi_masks):
+            h_.copy_(m, non_blocking=True)
+        torch.cuda.current_stream(device).synchronize()
+        return [h_.numpy() for h_ in host]
 
     def predict_prepared(self, x, scales, sizes, masks_to_host=True, return_intermediates=False):
         """The device part of ``predict`` (:311-335) on an already prepared, zero-padded
@@ -311,23 +463,7 @@ class MaskRCNN(torch.nn.Module):
         self.eval()
         try:
             with torch.no_grad():
-                h = self.extractor(x)
-                proposals = self.rpn.propose(h, x.shape[2:], scales)
-                rois, roi_indices = proposals.rois, proposals.roi_indices
-                # one image's proposals at a time: keeps every activation below the 2 GiB
-                # buffer-addressing limit of the conv kernels (8 x 1000 RoIs would not fit)
-                # (rois are grouped by image in order and the RPN call knows their counts on the
-                # host: a boolean mask per image would synchronise eight times and leave the GPU
-                # idle while the host queues the next head)
-                bounds = np.concatenate([[0], np.cumsum(proposals.counts)])
-                locs, scs = [], []
-                for i in range(x.shape[0]):
-                    lo, hi = int(bounds[i]), int(bounds[i + 1])
-                    l_i, s_i, _ = self.head(h, rois[lo:hi], roi_indices[lo:hi], pred_mask=False)
-                    locs.append(l_i)
-                    scs.append(s_i)
-                roi_cls_locs = torch.cat(locs, dim=0)
-                roi_scores = torch.cat(scs, dim=0)
+                h, rois, roi_indices, bounds, roi_cls_locs, roi_scores = self._box_heads(x, scales)
             # Detections: every image's device work is queued first; the host halves then run
             # group by group and each group's mask-head pass is launched as soon as its
             # boxes are final, so the GPU computes masks while the host finishes the next
@@ -349,13 +485,7 @@ class MaskRCNN(torch.nn.Module):
                     scores.append(s)
                 roi_masks += self._roi_masks_group(h, [bboxes[i] for i in ids], ids, scales)
             if masks_to_host:
-                # (N x <=100 x 80 x 14 x 14 floats: ~50 MB for a batch of 8) through pinned
-                # host memory, all copies queued before the one synchronisation
-                host = [torch.empty(m.shape, dtype=m.dtype, pin_memory=True) for m in roi_masks]
-                for h_, m in zip(host, roi_masks):
-                    h_.copy_(m, non_blocking=True)
-                torch.cuda.current_stream(x.device).synchronize()
-                roi_masks = [h_.numpy() for h_ in host]
+                roi_masks = self._masks_to_host(roi_masks, x.device)
         finally:
             self.train(was_training)
         if return_intermediates:

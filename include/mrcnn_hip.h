@@ -802,6 +802,62 @@ int mrcnn_decode_cls_boxes(const float *roi, const float *cls_loc, int ld_loc,
                            const double *mean4, const double *std4, float size_h,
                            float size_w, void *stream);
 
+/* ---- Test-time augmentation (csrc/test_aug.hip; Detectron TEST.BBOX_AUG / TEST.MASK_AUG) ----
+ * An image is run through the network as up to MRCNN_TEST_AUG_MAX_VIEWS views (mirrored, other
+ * scales); these two launches map the views' results back into the image frame and merge them. */
+#define MRCNN_TEST_AUG_MAX_VIEWS 8
+typedef struct {
+    const float *roi;       /* (R,4) device: the view's RoIs (y_min, x_min, y_max, x_max) in the
+                             * view's own (scaled, possibly mirrored) frame; 16-byte aligned */
+    const float *cls_loc;   /* (R, >= 4*n_class) device: the head's regression outputs */
+    int32_t ld_loc;         /* floats from one row of cls_loc to the next, >= 4*n_class */
+    int32_t R;              /* rows of this view; 0 is legal (the pointers are then not read) */
+    float scale;            /* the view's scale, as mrcnn_decode_cls_boxes takes it */
+    int32_t flip_x;         /* != 0: the view saw the image mirrored left-right */
+} mrcnn_test_aug_view;      /* 32 bytes */
+/* One image's union of candidates over its views in one launch.  views: HOST array of n_views
+ * records (0 <= n_views <= MRCNN_TEST_AUG_MAX_VIEWS), copied into the launch by value; mean4 / std4
+ * HOST pointers to 4 doubles; cls_bbox (sum R_v, n_class, 4) device, 16-byte aligned.  The rows of
+ * view v start at row sum_{u<v} R_u and keep the view's own row order.  Every row is
+ *   1. the expression of mrcnn_decode_cls_boxes with the view's scale and (size_h, size_w) (one
+ *      shared device function, csrc/decode_cls_box.h), then
+ *   2. for a view with flip_x != 0, in fp32:  x_min' = size_w - x_max,  x_max' = size_w - x_min
+ *      (boxes are (y_min, x_min, y_max, x_max): chainercv's flip_bbox about the original width,
+ *      datasets/transforms.py:flip_bbox; clipped boxes stay inside [0, size_w]).
+ * For an unmirrored view the rows equal mrcnn_decode_cls_boxes on that view bit for bit.  As in
+ * Detectron the mirror is taken about the ORIGINAL width size_w: the view was mirrored about its
+ * resized width round(size_w * scale), so its frame maps back to a width of
+ * round(size_w * scale) / scale, and the difference to size_w (at most half a resized pixel,
+ * 0.5 / scale) is ignored.  n_views == 0 or sum R_v == 0 launches nothing;
+ * (sum R_v) * n_class < 2^31. */
+int mrcnn_decode_cls_boxes_views(const mrcnn_test_aug_view *views, int n_views, int n_class,
+                                 const double *mean4, const double *std4, float size_h,
+                                 float size_w, float *cls_bbox, void *stream);
+/* The views' mask-head outputs for the same D boxes combined into one map (Detectron
+ * MASK_AUG.HEUR).  maps: HOST array of n_views device pointers to (D,M,M,Kc) fp32 NHWC logits, the
+ * layout mrcnn_paste_masks reads; flip_x: HOST array of n_views flags; out (D,M,M,Kc) logits, so
+ * mrcnn_paste_masks / mrcnn_paste_masks_packed take it as they take one view's map.  With
+ * l_v = maps[v][d, y, flip_x[v] ? M-1-x : x, k], v = 0 .. n_views-1 in order, out[d,y,x,k] is
+ *   LOGIT_AVG: (float)((l_0 + l_1 + ... ) / n_views)     sum in double in view order, one division
+ *   SOFT_MAX:  the largest l_v (fp32; sigmoid is monotone, so the largest probability); of equal
+ *              values the first view's (matters for -0 / +0 only)
+ *   SOFT_AVG:  the logit of the mean probability, in double: e_v = exp(-|l_v|),
+ *              p_v = sigmoid(l_v) and q_v = sigmoid(-l_v) taken as 1 / (1 + e_v) and e_v / (1 + e_v)
+ *              (which is which by the sign of l_v), P = (sum p_v) / n_views, Q = (sum q_v) / n_views,
+ *              out = (float)(log(P) - log(Q)); 1 - P is never formed, so the result stays accurate
+ *              where the maps saturate (all views at -300 give -300, not -inf).
+ * Input contract: finite logits, 1 <= n_views <= MRCNN_TEST_AUG_MAX_VIEWS, no map aliases out,
+ * D * M * M * Kc < 2^31.  SOFT_AVG beyond the range of double: where every view's logit is below
+ * about -745 (exp(-|l|) underflows to 0; it is subnormal from about -708), P is 0 and out is
+ * -infinity, and likewise +infinity above +745; mrcnn_paste_masks' sigmoid reads them as 0 and 1.
+ * D == 0 launches nothing.  16-byte loads and stores are used where Kc % 4 == 0 and every pointer
+ * is 16-byte aligned, scalar ones otherwise; the result is the same. */
+#define MRCNN_MASK_AUG_SOFT_AVG  0
+#define MRCNN_MASK_AUG_SOFT_MAX  1
+#define MRCNN_MASK_AUG_LOGIT_AVG 2
+int mrcnn_mask_aug_combine(const float *const *maps, const int32_t *flip_x, int n_views, int D,
+                           int M, int Kc, int heuristic, float *out, void *stream);
+
 /* ---- Target creators: the device half ------------------------- */
 /* The deterministic arithmetic of ProposalTargetCreator.__call__
  * (models/utils/proposal_target_creator.py:121-177) and chainercv's AnchorTargetCreator

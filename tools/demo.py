@@ -73,9 +73,8 @@ def main():
 
     for img_file in args.img:
         img = np.asarray(Image.open(img_file).convert('RGB'))
-        x, sizes, scales = model.prepare([img.transpose(2, 0, 1)])
-        bboxes, roi_masks, labels, scores = model.predict_prepared(x, scales, sizes,
-                                                                   masks_to_host=False)
+        bboxes, roi_masks, labels, scores, sizes = model.predict_images(
+            [img.transpose(2, 0, 1)], masks_to_host=False)
         bbox, label, score = bboxes[0], labels[0], scores[0]
         k = np.flatnonzero(score >= 0.7)
         k = k[np.argsort(score[k], kind='stable')]

@@ -12,6 +12,8 @@ examples/evaluate_common.py + examples/coco/evaluate.py.
     python tools/evaluate.py --coco-root DIR --results res.json   # score a results file (no model)
     python tools/evaluate.py --synthetic 16 --iou-types segm,bbox   # box AP beside mask AP
     python tools/evaluate.py --coco-root DIR --detectron model.pkl --soft-nms linear --bbox-vote 0.8
+    python tools/evaluate.py --coco-root DIR --detectron model.pkl --test-aug-h-flip \
+        --test-aug-scales 500,1000 --test-aug-scale-h-flip --soft-nms linear --bbox-vote 0.8
 
 Runs the evaluator (predicted masks stay on the device; extensions/), prints the report and
 the seconds per image spent in prediction and in evaluation, and writes the result as YAML (or
@@ -25,6 +27,9 @@ work, and with ``--save-results`` then writes a bbox-only file, the detection tr
 ``--soft-nms {linear,gaussian}`` and ``--bbox-vote THRESH`` turn on Detectron's test-time options
 (TEST.SOFT_NMS, TEST.BBOX_VOTE; both decided on the device); the values
 used are written into the result file as ``postprocessing``.
+``--test-aug-h-flip``, ``--test-aug-scales`` (with ``--test-aug-max-size``, ``--test-aug-scale-h-flip``)
+and ``--mask-aug-heur`` turn on Detectron's test-time augmentation (TEST.BBOX_AUG / TEST.MASK_AUG;
+the views merged on the device); the views run are recorded there too.
 """
 import argparse
 import json
@@ -44,20 +49,14 @@ POOLING_FUNCS = {'align': 'roi_align_2d', 'pooling': 'roi_pooling_2d', 'resize':
 
 
 class _TimedTarget(object):
-    """The model, with the seconds spent in prepare + predict_prepared counted."""
+    """The model, with the seconds spent in predict_images counted."""
 
     def __init__(self, model):
         self.model, self.seconds = model, 0.
 
-    def prepare(self, imgs):
+    def predict_images(self, *a, **k):
         t0 = time.perf_counter()
-        out = self.model.prepare(imgs)
-        self.seconds += time.perf_counter() - t0
-        return out
-
-    def predict_prepared(self, *a, **k):
-        t0 = time.perf_counter()
-        out = self.model.predict_prepared(*a, **k)
+        out = self.model.predict_images(*a, **k)
         torch.cuda.synchronize()
         self.seconds += time.perf_counter() - t0
         return out
@@ -70,8 +69,19 @@ def _iou_types(text):
     return types
 
 
+def _scale_list(text):
+    try:
+        scales = tuple(int(t) for t in text.split(',') if t.strip())
+    except ValueError:
+        scales = ()
+    if not scales or any(s <= 0 for s in scales):
+        raise argparse.ArgumentTypeError('a comma-separated list of positive integers, got %r' % text)
+    return scales
+
+
 def add_postprocessing_flags(ap):
-    """Detectron's test-time options of MaskRCNN (soft_nms, bbox_vote_thresh): off by default."""
+    """Detectron's test-time options of MaskRCNN (soft_nms, bbox_vote_thresh, test-time
+    augmentation): off by default."""
     ap.add_argument('--soft-nms', default=None, choices=['linear', 'gaussian'],
                     help='Soft-NMS in the place of the hard per-class NMS (Detectron TEST.SOFT_NMS): '
                          'scores of overlapping boxes decay instead of the boxes being deleted')
@@ -86,6 +96,20 @@ def add_postprocessing_flags(ap):
     ap.add_argument('--bbox-vote', type=float, default=None, metavar='THRESH',
                     help='bounding-box voting (Detectron TEST.BBOX_VOTE, 0.8 there): each kept box '
                          'becomes the score-weighted mean of the candidates with IoU >= THRESH')
+    ap.add_argument('--test-aug-h-flip', action='store_true',
+                    help='test-time augmentation (Detectron TEST.BBOX_AUG / MASK_AUG): also run the '
+                         'mirrored image and pool both views\' candidates into the one suppression')
+    ap.add_argument('--test-aug-scales', type=_scale_list, default=None, metavar='S[,S...]',
+                    help='test-time augmentation: also run the image at these min sizes '
+                         '(e.g. 500,1000)')
+    ap.add_argument('--test-aug-max-size', type=int, default=None, metavar='N',
+                    help='the max size of the extra scales (default: the model\'s); needs '
+                         '--test-aug-scales')
+    ap.add_argument('--test-aug-scale-h-flip', action='store_true',
+                    help='also run every extra scale mirrored; needs --test-aug-scales')
+    ap.add_argument('--mask-aug-heur', default=None, choices=['soft_avg', 'soft_max', 'logit_avg'],
+                    help='how the views\' mask maps are combined (Detectron MASK_AUG.HEUR; model '
+                         'default soft_avg); needs --test-aug-h-flip or --test-aug-scales')
 
 
 def check_postprocessing_flags(ap, args, no_model=False):
@@ -95,8 +119,26 @@ def check_postprocessing_flags(ap, args, no_model=False):
                                       ('--soft-nms-sigma', args.soft_nms_sigma),
                                       ('--soft-nms-min-score', args.soft_nms_min_score),
                                       ('--bbox-vote', args.bbox_vote)) if value is not None]
-    if no_model and given:
-        ap.error('%s: nothing is predicted when a results file is scored' % ', '.join(given))
+    aug = [flag for flag, on in (('--test-aug-h-flip', args.test_aug_h_flip),
+                                 ('--test-aug-scales', args.test_aug_scales is not None),
+                                 ('--test-aug-max-size', args.test_aug_max_size is not None),
+                                 ('--test-aug-scale-h-flip', args.test_aug_scale_h_flip),
+                                 ('--mask-aug-heur', args.mask_aug_heur is not None)) if on]
+    if no_model and (given or aug):
+        ap.error('%s: nothing is predicted when a results file is scored' % ', '.join(given + aug))
+    if args.test_aug_scales is None:
+        for flag in ('--test-aug-max-size', '--test-aug-scale-h-flip'):
+            if flag in aug:
+                ap.error('%s given without --test-aug-scales' % flag)
+    if args.test_aug_max_size is not None and args.test_aug_max_size <= 0:
+        ap.error('--test-aug-max-size must be positive')
+    if args.mask_aug_heur is not None and not (args.test_aug_h_flip or args.test_aug_scales):
+        ap.error('--mask-aug-heur given without --test-aug-h-flip or --test-aug-scales: one view '
+                 'has nothing to combine')
+    n_views = (1 + bool(args.test_aug_h_flip)
+               + len(args.test_aug_scales or ()) * (1 + bool(args.test_aug_scale_h_flip)))
+    if n_views > 8:
+        ap.error('%d test-time augmentation views asked for, at most 8 are handled' % n_views)
     if args.soft_nms is None and given and given != ['--bbox-vote']:
         ap.error('%s given without --soft-nms' % ', '.join(f for f in given if f != '--bbox-vote'))
     if args.soft_nms_thresh is not None and args.soft_nms != 'linear':
@@ -123,6 +165,19 @@ def apply_postprocessing_flags(model, args):
         used.update(soft_nms_thresh=float(model.soft_nms_thresh),
                     soft_nms_sigma=float(model.soft_nms_sigma),
                     soft_nms_min_score=float(model.soft_nms_min_score))
+    if getattr(args, 'test_aug_h_flip', False):
+        model.test_aug_h_flip = True
+    if getattr(args, 'test_aug_scales', None):
+        model.test_aug_scales = tuple(args.test_aug_scales)
+        model.test_aug_scale_h_flip = bool(getattr(args, 'test_aug_scale_h_flip', False))
+        if getattr(args, 'test_aug_max_size', None) is not None:
+            model.test_aug_max_size = int(args.test_aug_max_size)
+    if getattr(args, 'mask_aug_heur', None):
+        model.mask_aug_heur = args.mask_aug_heur
+    views = model.test_aug_views()
+    if len(views) > 1:          # (without augmentation the dict is as it always was)
+        used.update(test_aug_views=[[int(lo), int(hi), bool(flip)] for lo, hi, flip in views],
+                    mask_aug_heur=model.mask_aug_heur)
     return used
 
 
@@ -424,7 +479,8 @@ def evaluate_log_dir(args):
     yaml_file = pretrained_model + '.eval_result.yaml'
     # one dump: the metrics as they always were, then whatever else describes the run
     payload = dict(result)
-    if postprocessing['soft_nms'] or postprocessing['bbox_vote_thresh'] is not None:
+    if (postprocessing['soft_nms'] or postprocessing['bbox_vote_thresh'] is not None
+            or 'test_aug_views' in postprocessing):
         payload['postprocessing'] = postprocessing
     if writer is not None:
         writer.close()
