@@ -106,6 +106,7 @@ SIGNATURES = {
     'mrcnn_deconv2x2s2_dgrad': (c_int, [c_vp] * 3 + [c_int] * 5 + [c_vp]),
     'mrcnn_deconv2x2s2_wgrad_workspace_bytes': (c_i64, [c_int] * 5),
     'mrcnn_deconv2x2s2_wgrad': (c_int, [c_vp] * 3 + [c_int] * 5 + [c_vp, c_vp]),
+    'mrcnn_conv_gemm_plan': (c_int, [ctypes.c_char_p, _DP, c_int, ctypes.c_char_p, c_int]),
     'mrcnn_epilogue_bwd': (c_int, [c_vp] * 4 + [c_i64, c_int, c_vp]),
     'mrcnn_colsum': (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     'mrcnn_maxpool3x3s2p1_fwd': (c_int, [c_vp, c_vp] + [c_int] * 6 + [c_vp]),

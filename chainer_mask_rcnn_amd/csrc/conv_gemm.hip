@@ -35,22 +35,14 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv_gemm_plan.h"
 
 namespace {
 
+using namespace mrcnn::gemm;   // the launch policy, its constants (BK, Mode, OutMode, ...) and the knobs
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int BK = 32;
-// The forward-form kernel fits 168 registers, so it runs with ONE LDS stage (37 KB) and three
-// workgroups per CU: a wave spends ~40 % of a K slice issuing MFMAs and ~60 % staging (measured
-// with s_memtime), so three interleaved waves per SIMD keep the pipe fuller than two (res5 3x3:
-// 129 vs 122 TFLOP/s).  The K-strided DGRAD gather would spill at 168 and keeps two stages / two
-// workgroups per CU.
-constexpr bool single_buffered(int tm, int mode)
-{
-    if (tm == 1) return mode == 0;
-    return tm >= 2 && (mode == 0 || mode == 2);
-}
 // minimum workgroups per CU the register allocation must allow (256-thread workgroups: one
 // wave per SIMD each)
 constexpr int min_blocks(int tm, int mode)
@@ -60,11 +52,7 @@ constexpr int min_blocks(int tm, int mode)
 }
 constexpr int KPAD = 4;  // K-contiguous LDS rows are 36 floats (conflict-free b128)
 
-// The stride-1 dgrad is also run in FWD mode: a forward convolution of gy with the flipped,
-// transposed filter (both operands K-contiguous).
-enum Mode { FWD = 0, DGRAD = 1, WGRAD = 2 };
 constexpr bool is_fwd(int m) { return m == FWD; }
-enum OutMode { OUT_PLAIN = 0, OUT_STRIDED = 1, OUT_DECONV = 2 };
 
 struct GemmParams {
     const float *A;      // FWD: x      DGRAD: gy      WGRAD: gy
@@ -124,7 +112,6 @@ struct GemmParams {
 };
 
 // GEMM row -> (image, position) under the block-position-major order of GemmParams::perm_n
-constexpr int kPermBlock = 128;
 struct PermRow { int n, pos; };
 __host__ __device__ __forceinline__ PermRow perm_row(int m, int pq)
 {
@@ -456,7 +443,7 @@ conv_gemm_kernel(const GemmParams p)
 
     const int adv_x = BK % p.gq, adv_y = (BK / p.gq) % p.gp, adv_n = BK / (p.gp * p.gq);
     const int cprs = (MODE == WGRAD) ? 1 : (p.Kc + BK - 1) / BK;  // K slices per (r,s)
-    // FWD/DGRAD split-K (leftover rows of a small-M problem, see launch()): this workgroup
+    // FWD/DGRAD split-K (leftover rows of a small-M problem, see plan_gemm()): this workgroup
     // runs slices [kt0, kt0 + nslices) and writes raw partial sums into its slab
     // position-major rows: the taps that are inside the map for at least one position of this
     // tile, as 4-bit indices packed into a word (wave-uniform)
@@ -1276,38 +1263,23 @@ __global__ void splitk_reduce_kernel(const float *__restrict__ ws, int splits, i
     }
 }
 
-// Workgroups resident at once: 128x128 tiles run 2 per CU (73 KB LDS), 64x64 tiles 4 per CU.
-constexpr int64_t kSlotsBig = 512, kSlotsSmall = 1024;
+GemmKnobs g_knobs;     // mrcnn_set_tuning
 
-int g_split_bf16 = 3;  // mrcnn_set_tuning("split_bf16"): bit 0 = 128x128 kernels, bit 1 = 64x64 forward form on the
-                       // split-operand arithmetic (see SPLIT; the default since round 4), 0 = fp32 MFMA everywhere
-int g_big_split_k = -1; // mrcnn_set_tuning("big_split_k"): small-M problems as 128x128 tiles cut along K.
-                      // -1 (default since round 6) = the one-round rule in launch(), 0 = off (64x64 tiles),
-                      // k > 0 = aim at k workgroups
-int g_big_split_min_slices = 16;   // mrcnn_set_tuning("big_split_min_slices"): fewest K slices per slab of the one-round rule
-int g_w8_min_k = 256; // mrcnn_set_tuning("w8_min_k"): shallowest K (input channels) a W8 launch takes
-int g_w8 = 1;         // mrcnn_set_tuning("w8", 0/1): 256x128 tiles on 512-thread workgroups (W8) for the large
-                      // pointwise forward-form launches of the split-operand arithmetic
-
-int g_pw = 3;         // mrcnn_set_tuning("pw"): bit 0 = the PW instantiations for pointwise forward-form launches,
-                      // bit 1 = the K3 instantiations for the 3x3 / stride 1 / pad 1 ones
-
-// PW's launch rule (see the note above conv_gemm_kernel)
-inline bool pw_plain(const GemmParams &p)
+// what the policy reads of a problem run in `mode`
+inline GemmShape gemm_shape(const GemmParams &p, int mode, bool has_ws)
 {
-    return p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0 && p.perm_n == 0 && !p.stem && p.gp == p.sh &&
-           p.gq == p.sw && p.out_mode == OUT_PLAIN;
-}
-
-// K3's launch rule
-inline bool k3_plain(const GemmParams &p)
-{
-    return p.R == 3 && p.S == 3 && p.stride == 1 && p.pad == 1 && p.perm_n == 0 && !p.stem &&
-           p.out_mode == OUT_PLAIN;
+    GemmShape g = {};
+    g.mode = mode;
+    g.M = p.M; g.N = p.N; g.Kc = p.Kc;
+    g.R = p.R; g.S = p.S; g.stride = p.stride; g.pad = p.pad;
+    g.gp = p.gp; g.gq = p.gq; g.sh = p.sh; g.sw = p.sw;
+    g.ldc = p.ldc; g.out_mode = p.out_mode; g.stem = p.stem; g.perm_n = p.perm_n;
+    g.has_ws = has_ws;
+    return g;
 }
 
 template <int TM, int TN, int MODE>
-void launch_kernel(const GemmParams &p, int64_t tiles, int splits, hipStream_t s, int batch = 1)
+void launch_kernel(const GemmParams &p, GemmInst inst, int64_t tiles, int splits, hipStream_t s, int batch = 1)
 {
     hipEvent_t ev0, ev1;          // kernel-only timing (ProfKernelScope of the caller), usually null
     mrcnn::prof_take(&ev0, &ev1);
@@ -1315,44 +1287,29 @@ void launch_kernel(const GemmParams &p, int64_t tiles, int splits, hipStream_t s
         hipExtLaunchKernelGGL(kernel, dim3((unsigned)tiles, splits, batch), dim3(256), 0, s, ev0, ev1, 0, p);
     };
     if constexpr (MODE == WGRAD && TM == 2 && TN == 2) {
-        if ((g_split_bf16 & 1) && p.perm_n == 0) return go(conv_gemm_kernel<TM, TN, MODE, false, true>);
+        if (inst.split) return go(conv_gemm_kernel<TM, TN, MODE, false, true>);
     }
     if constexpr (MODE == WGRAD) {
-        if (p.perm_n > 0) return go(conv_gemm_kernel<TM, TN, MODE, true>);
+        if (inst.variant == INST_WPERM) return go(conv_gemm_kernel<TM, TN, MODE, true>);
     }
     if constexpr (MODE == FWD && TM == TN && (TM == 1 || TM == 2)) {
-        if (g_split_bf16 & (TM == 2 ? 1 : 2)) {
-            if ((g_pw & 1) && pw_plain(p)) return go(conv_gemm_kernel<TM, TN, MODE, false, true, false, true>);
-            if ((g_pw & 2) && k3_plain(p))
-                return go(conv_gemm_kernel<TM, TN, MODE, false, true, false, false, true>);
+        if (inst.split) {
+            if (inst.variant == INST_PW) return go(conv_gemm_kernel<TM, TN, MODE, false, true, false, true>);
+            if (inst.variant == INST_K3) return go(conv_gemm_kernel<TM, TN, MODE, false, true, false, false, true>);
             return go(conv_gemm_kernel<TM, TN, MODE, false, true>);
         }
     }
     go(conv_gemm_kernel<TM, TN, MODE>);
 }
 
+// the same on the instantiation the policy picks for p (the batched launches of conv_winograd.h)
+template <int TM, int TN, int MODE>
+void launch_kernel(const GemmParams &p, int64_t tiles, int splits, hipStream_t s, int batch = 1)
+{
+    launch_kernel<TM, TN, MODE>(p, pick_inst(gemm_shape(p, MODE, false), TM, g_knobs), tiles, splits, s, batch);
+}
+
 // ---- W8 launches (see the note above conv_gemm_kernel) -------------------------------------------
-constexpr int kW8BM = 256, kW8BN = 128;
-
-inline bool w8_pointwise(const GemmParams &p)
-{
-    return p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0 && p.perm_n == 0 && !p.stem &&
-           p.gp == p.sh && p.gq == p.sw;
-}
-
-// a forward-form launch qualifies: split-operand arithmetic, plain output rows,
-// 1x1 / stride 1 gather, K >= 8 slices, at least three rounds of 256 tiles, rows that fill their tiles
-inline bool w8_ok(const GemmParams &p, int batch = 1)
-{
-    if (!g_w8 || !(g_split_bf16 & 1) || p.out_mode != OUT_PLAIN || !w8_pointwise(p) ||
-        p.split_len != 0 || p.m_lo != 0)
-        return false;
-    const int64_t tm = mrcnn::ceil_div(p.M, kW8BM), tn = mrcnn::ceil_div(p.N, kW8BN);
-    // (measured, profiles/r06b_w8_shapes.txt: the RoI head's 1x1 layers and their transposed-filter data
-    // gradients gain 4 - 7 %; the batch-2 backbone's 270 - 530-tile, 2 - 8-slice launches lose 5 - 20 %)
-    return p.N >= kW8BN && p.Kc >= g_w8_min_k && tm * tn * batch >= 768 && (p.M % kW8BM == 0 || p.M >= 16 * kW8BM);
-}
-
 void launch_w8_kernel(const GemmParams &p, int64_t wgs, int batch, hipStream_t s)
 {
     hipEvent_t ev0, ev1;
@@ -1361,40 +1318,26 @@ void launch_w8_kernel(const GemmParams &p, int64_t wgs, int batch, hipStream_t s
                           dim3((unsigned)wgs, 1, batch), dim3(512), 0, s, ev0, ev1, 0, p);
 }
 
-// Profiler record of a forward-form / DGRAD launch over `rows` GEMM rows: the operation and byte
-// estimate of the problem, and the bucket of the kernel SYMBOL (what rocprofv3 reports): the
-// forward-form instantiation runs forward convolutions and the transposed-filter dgrads alike
-template <int TM, int MODE>
-mrcnn::ProfKernelScope gemm_prof(const GemmParams &p, int64_t rows, bool w8 = false)
+// Profiler record of launch l of a problem: the operation and byte estimate of its rows, and the
+// bucket of the kernel SYMBOL (what rocprofv3 reports): the forward-form instantiation runs forward
+// convolutions and the transposed-filter dgrads alike
+template <int MODE>
+mrcnn::ProfKernelScope gemm_prof(const GemmParams &p, const GemmLaunch &l)
 {
+    const int small = l.tile >= 128 ? 0 : 1;
+    if (MODE == WGRAD)
+        return mrcnn::ProfKernelScope(mrcnn::PROF_CONV_WGRAD_128 + small, 2.0 * p.M * p.N * (double)p.Kc,
+                                      4.0 * ((double)p.M * p.N + (double)p.Kc * (p.M + (double)p.cin)));
+    const int64_t rows = l.m_hi - l.m_lo;
     const double kdepth = (double)p.R * p.S * (p.stem ? 21.0 : (double)p.Kc);
     const double flops = 2.0 * rows * p.N * kdepth;
     const double bytes = 4.0 * ((double)rows * p.N + (double)rows * p.Kc + (double)p.N * kdepth);
-    const int kind = w8 ? mrcnn::PROF_CONV_FWD_W8
-                        : (MODE == FWD ? mrcnn::PROF_CONV_FWD_128 : mrcnn::PROF_CONV_DGRAD_128) + (TM >= 2 ? 0 : 1);
+    const int kind = l.tile == kW8BM ? mrcnn::PROF_CONV_FWD_W8
+                                     : (MODE == FWD ? mrcnn::PROF_CONV_FWD_128 : mrcnn::PROF_CONV_DGRAD_128) + small;
     return mrcnn::ProfKernelScope(kind, flops, bytes);
 }
 
-template <int TM, int TN, int MODE>
-void launch_tiles(GemmParams p, int m_lo, int m_hi, int splits, hipStream_t s)
-{
-    constexpr int BM = 64 * TM, BN = 64 * TN;
-    p.m_lo = m_lo;
-    p.M = m_hi;
-    const int64_t blocks = mrcnn::ceil_div(m_hi - m_lo, BM) * mrcnn::ceil_div(p.N, BN);
-    if (blocks <= 0) return;
-    const auto prof = gemm_prof<TM, MODE>(p, m_hi - m_lo);
-    launch_kernel<TM, TN, MODE>(p, blocks, splits, s);
-}
-
-// ---- split-K for the leftover rows of a small-M forward / dgrad ----------------------------
-// 64x64 tiles are all resident at once, so a launch of T tiles costs ceil(T / 256) tile-times
-// on the busiest CU (T = 536 -> 3, although the average CU has 2.09).  The rows of the whole
-// multiples of 256 tiles run as usual; the leftover rows (< 154 tiles) are cut along K into
-// `splits` short workgroups that spread over all CUs, write raw partial sums into slabs, and
-// a small kernel sums the slabs in order and applies the epilogue (deterministic).
-constexpr int64_t kSplitWsBytes = 192ll << 20;   // >= 154 leftover tiles x 16 slabs; whole small-M outputs x splits
-
+// ---- the ordered slab sum of the split-K launches (conv_gemm_plan.h) ------------------------
 struct FixParams {
     const float *ws;
     float *C;
@@ -1438,30 +1381,6 @@ __global__ void __launch_bounds__(256) splitk_epilogue_kernel(const FixParams f)
     *reinterpret_cast<float4 *>(f.C + off) = make_float4(v[0], v[1], v[2], v[3]);
 }
 
-template <int MODE>
-bool can_split_rows(const GemmParams &p)
-{
-    return p.split_ws && MODE != WGRAD && p.out_mode == OUT_PLAIN && !p.stem && p.N % 4 == 0 &&
-           p.ldc == p.N;
-}
-
-// fewer slabs while `splits` slabs of a rows x N output overflow the split-K workspace
-int64_t fit_ws(int64_t splits, int64_t rows, int N)
-{
-    while (splits > 1 && rows * N * splits * 4 > kSplitWsBytes) --splits;
-    return splits;
-}
-
-// K-split count of a split launch over `tiles` tiles of a rows x N output: about target_wgs
-// workgroups, at most `cap` slabs, each at least depth_div K slices deep, within the workspace
-int64_t k_splits(int total_slices, int depth_div, int64_t target_wgs, int64_t tiles, int64_t rows, int N,
-                 int64_t cap)
-{
-    return fit_ws(std::min<int64_t>(std::min<int64_t>(cap, total_slices / depth_div),
-                                    mrcnn::ceil_div(target_wgs, tiles)),
-                  rows, N);
-}
-
 // The ordered sum of the `splits` slabs of p.split_ws that hold rows [rows_lo, p.M), with p's
 // epilogue, into p.C
 template <int MODE>
@@ -1479,221 +1398,72 @@ void slab_sum(const GemmParams &p, int rows_lo, int splits, hipStream_t s)
     hipLaunchKernelGGL(splitk_epilogue_kernel, dim3((unsigned)mrcnn::ceil_div(n, 256)), dim3(256), 0, s, f);
 }
 
-// rows [rows_lo, p.M) as 64 TM x 64 TM tiles cut along K into `splits` slabs + the ordered slab sum
-template <int MODE, int TM = 1>
-void launch_split_rows(const GemmParams &p, int rows_lo, int splits, int total_slices, hipStream_t s)
-{
-    GemmParams q = p;
-    q.C = p.split_ws;
-    q.flags = 0;
-    q.bias = q.scale = q.shift = q.residual = q.res_g = q.res_y = q.out_mask_y = nullptr;
-    q.split_len = (int)mrcnn::ceil_div(total_slices, splits);
-    splits = (int)mrcnn::ceil_div(total_slices, q.split_len);
-    q.split_stride = (int64_t)(p.M - rows_lo) * p.N;
-    q.out_row0 = rows_lo;
-    q.c_bytes = (unsigned)(q.split_stride * 4);
-    launch_tiles<TM, TM, MODE>(q, rows_lo, p.M, splits, s);
-    slab_sum<MODE>(p, rows_lo, splits, s);
-}
-
-// Rows [rows_main, p.M) as the K-split pieces of a fused launch (GemmParams::tail_*) behind its
-// first tail_first workgroups; returns the pieces per tile, re-derived from the slab depth.
-int set_tail(GemmParams &p, int rows_main, int64_t tail_first, int total_slices, int64_t splits)
-{
-    p.tail_split_len = (int)mrcnn::ceil_div(total_slices, splits);
-    p.tail_splits = (int)mrcnn::ceil_div(total_slices, p.tail_split_len);
-    p.tail_first = (int)tail_first;
-    p.tail_row0 = rows_main;
-    p.tail_ws = p.split_ws;
-    p.tail_stride = (int64_t)(p.M - rows_main) * p.N;
-    p.tail_bytes = (unsigned)(p.tail_stride * 4);
-    p.m_lo = 0;
-    return p.tail_splits;
-}
-
-int g_fused_tail = 512;            // mrcnn_set_tuning("fused_tail", 0 = off, else target number of tail pieces)
-
-// Rows [0, rows_main) as whole TMxTN tiles and rows [rows_main, p.M) as K-split pieces of the
-// same tile shape in ONE launch (GemmParams::tail_*), then the ordered slab sum.  Returns false
-// (nothing launched) when the problem does not qualify.
-template <int TM, int TN, int MODE>
-bool launch_fused_tail(GemmParams p, int rows_main, hipStream_t s)
-{
-    constexpr int BM = 64 * TM, BN = 64 * TN;
-    if (!g_fused_tail || !can_split_rows<MODE>(p) || p.split_len != 0 || rows_main <= 0 ||
-        rows_main % BM != 0 || rows_main >= p.M)
-        return false;
-    const int64_t ntn = mrcnn::ceil_div(p.N, BN);
-    const int64_t main_tiles = (rows_main / BM) * ntn;
-    const int64_t tail_tiles = mrcnn::ceil_div(p.M - rows_main, BM) * ntn;
-    const int total_slices = p.R * p.S * (int)mrcnn::ceil_div(p.Kc, BK);
-    const int64_t splits = k_splits(total_slices, 4, g_fused_tail, tail_tiles, p.M - rows_main, p.N, 16);
-    if (splits < 2) return false;
-    const int pieces = set_tail(p, rows_main, main_tiles, total_slices, splits);
-    {
-        const auto prof = gemm_prof<TM, MODE>(p, p.M);
-        launch_kernel<TM, TN, MODE>(p, main_tiles + tail_tiles * pieces, 1, s);
-    }
-    slab_sum<MODE>(p, rows_main, pieces, s);
-    return true;
-}
-
-// The 64x64-tile remainder of a 128x128-tile launch (rows [rows_lo, M)) runs alone on the GPU
-// after the main launch: few workgroups, each walking the whole K.  Cut along K so that about
-// two workgroups per CU share the work.
+// Runs `plan` on problem p (p.M = all rows, p.split_ws = the workspace the plan was made with; WGRAD:
+// p.C = gw): per launch the row range, the slab or tail fields and the profiler record, then the
+// ordered slab sum.
 template <int MODE>
-void launch_remainder(const GemmParams &p, int rows_lo, hipStream_t s)
+int run_plan(const GemmParams &p, const GemmPlan &plan, hipStream_t s)
 {
-    const int64_t left_tiles = mrcnn::ceil_div(p.M - rows_lo, 64) * mrcnn::ceil_div(p.N, 64);
-    const int total_slices = p.R * p.S * (int)mrcnn::ceil_div(p.Kc, BK);
-    const int64_t splits = k_splits(total_slices, 8, 512, left_tiles, p.M - rows_lo, p.N, 16);
-    if (!can_split_rows<MODE>(p) || splits < 2) {
-        launch_tiles<1, 1, MODE>(p, rows_lo, p.M, 1, s);
-        return;
-    }
-    launch_split_rows<MODE>(p, rows_lo, (int)splits, total_slices, s);
-}
-
-// One W8 launch for the whole problem: whole rounds of 256 tiles (one 512-thread workgroup per CU)
-// and, when the last round would be less than ~60 % full, its rows as K-split pieces appended to
-// the same grid + the ordered slab sum (the fused-tail scheme of launch_fused_tail, with its own
-// K partition: the W8 and the 128x128 tail pieces of a problem are not bit-identical).
-void launch_w8(GemmParams p, hipStream_t s)
-{
-    const int64_t tm = mrcnn::ceil_div(p.M, kW8BM), tn = mrcnn::ceil_div(p.N, kW8BN);
-    const int64_t T = tm * tn, full = T / 256, rem = T - full * 256;
-    const int total_slices = (int)mrcnn::ceil_div(p.Kc, BK);
-    int64_t main_rows_tiles = tm;
-    if (rem > 0 && rem < 154 && full >= 1 && g_fused_tail && p.split_ws && p.N % 4 == 0 && p.ldc == p.N)
-        main_rows_tiles = (full * 256) / tn;
-    const int rows_main = (int)std::min<int64_t>(p.M, main_rows_tiles * kW8BM);
-    const int64_t tail_tiles = mrcnn::ceil_div(p.M - rows_main, kW8BM) * tn;
-    const int64_t splits =
-        rows_main < p.M ? k_splits(total_slices, 4, 256, tail_tiles, p.M - rows_main, p.N, 16) : 1;
-    const auto prof = gemm_prof<2, FWD>(p, p.M, true);
-    if (splits < 2) {
-        p.m_lo = 0;
-        launch_w8_kernel(p, T, 1, s);
-        return;
-    }
-    const int pieces = set_tail(p, rows_main, main_rows_tiles * tn, total_slices, splits);
-    launch_w8_kernel(p, p.tail_first + tail_tiles * pieces, 1, s);
-    slab_sum<FWD>(p, rows_main, pieces, s);
-}
-
-extern float g_wino_ambiguity;
-int g_big_min_tiles = 384;        // mrcnn_set_tuning("big_min_tiles"): fewest 128x128 tiles that get 128x128 tiles
-int g_small_m_split = 0;          // mrcnn_set_tuning("small_m_split", target workgroups per CU)
-int g_tiny_split = 1;             // mrcnn_set_tuning("tiny_split", 0/1): K-split of launches with <= 128 tiles and >= 32 slices
-
-template <int MODE>
-void launch_small(const GemmParams &p, hipStream_t s)
-{
-    const int64_t tm = mrcnn::ceil_div(p.M, 64), tn = mrcnn::ceil_div(p.N, 64);
-    const int64_t T = tm * tn, whole = (T / 256) * 256, rem = T - whole;
-    const int total_slices = p.R * p.S * (int)mrcnn::ceil_div(p.Kc, BK);
-    // Occupancy-driven split-K: a wave of the 64x64 kernel spends only about a quarter of a K
-    // slice issuing MFMAs, so a SIMD needs ~4 co-resident waves to keep its matrix pipe busy.
-    // A small-M problem has only T / 256 workgroups per CU; cutting every tile along K into
-    // `splits` slabs multiplies the resident waves (each at least 8 slices deep) at the price
-    // of the ordered slab sum.
-    // Tiny launches that are K-deep (the head's fused cls_loc / score layer: 1024 x 408 x 2048 = 112
-    // tiles of 64 slices each on 112 of 256 CUs, 80 us of pure K-loop latency): cut along K so that
-    // ~512 workgroups share the walk, ordered slab sum as for the leftover rows.
-    if (g_tiny_split && can_split_rows<MODE>(p) && T <= 128 && total_slices >= 32) {
-        const int64_t splits = k_splits(total_slices, 8, 512, T, p.M, p.N, 16);
-        if (splits >= 2) {
-            launch_split_rows<MODE>(p, 0, (int)splits, total_slices, s);
-            return;
+    for (int i = 0; i < plan.n; ++i) {
+        const GemmLaunch &l = plan.launch[i];
+        GemmParams q = p;
+        q.m_lo = l.m_lo;
+        q.M = l.m_hi;
+        if constexpr (MODE == WGRAD) {
+            q.perm_n = plan.perm_n;
+            q.split_len = l.split_len;
+            q.split_stride = (int64_t)p.M * p.N;
+            q.C = plan.sum_splits ? p.split_ws : p.C;
+            q.split_ws = nullptr;
+        } else if (l.split_len) {      // raw partial sums into slabs of the workspace
+            q.C = p.split_ws;
+            q.flags = 0;
+            q.bias = q.scale = q.shift = q.residual = q.res_g = q.res_y = q.out_mask_y = nullptr;
+            q.split_len = l.split_len;
+            q.split_stride = (int64_t)(l.m_hi - l.m_lo) * p.N;
+            q.out_row0 = l.m_lo;
+            q.c_bytes = (unsigned)(q.split_stride * 4);
         }
-    }
-    if (g_small_m_split > 0 && can_split_rows<MODE>(p) && T < 256ll * g_small_m_split &&
-        total_slices >= 16) {
-        const int64_t splits = k_splits(total_slices, 8, 256ll * g_small_m_split, T, p.M, p.N, 16);
-        if (splits >= 2) {
-            launch_split_rows<MODE>(p, 0, (int)splits, total_slices, s);
-            return;
+        if (l.tail_splits) {
+            q.tail_first = l.tail_first;
+            q.tail_row0 = l.tail_row0;
+            q.tail_splits = l.tail_splits;
+            q.tail_split_len = l.tail_split_len;
+            q.tail_ws = p.split_ws;
+            q.tail_stride = (int64_t)(l.m_hi - l.tail_row0) * p.N;
+            q.tail_bytes = (unsigned)(q.tail_stride * 4);
         }
-    }
-    const bool can_split = can_split_rows<MODE>(p) && whole > 0 && whole <= 1024 && rem > 0 &&
-                           rem < 154 && total_slices >= 8;   // beyond 4 tile-times per CU the
-                                                             // two extra launches cost more than
-                                                             // the imbalance
-    const int rows_main = can_split ? (int)std::min<int64_t>(p.M, (whole / tn) * 64) : p.M;
-    const int64_t left_tiles = mrcnn::ceil_div(p.M - rows_main, 64) * tn;
-    int splits = 1;
-    // (two or more slabs need left_tiles < 256, so splits x left_tiles < 512 tiles of 16 KB: the
-    // workspace clamp of k_splits never applies here)
-    if (can_split && rows_main < p.M)
-        splits = (int)k_splits(total_slices, 4, 256, left_tiles, p.M - rows_main, p.N, 16);
-    if (splits < 2) {
-        launch_tiles<1, 1, MODE>(p, 0, p.M, 1, s);
-        return;
-    }
-    if (launch_fused_tail<1, 1, MODE>(p, rows_main, s)) return;
-    launch_tiles<1, 1, MODE>(p, 0, rows_main, 1, s);
-    launch_split_rows<MODE>(p, rows_main, splits, total_slices, s);
-}
-
-// FWD / DGRAD launch policy.  With T 128x128 tiles and 512 resident workgroups a launch
-// takes ceil(T/512) "rounds"; when the last round would be mostly empty (e.g. T = 536 or
-// 1568) the rows of the full rounds run as 128x128 tiles and the leftover rows as a second,
-// short launch of 64x64 tiles, instead of one nearly idle round of big tiles.
-template <int MODE>
-int launch(const GemmParams &p0, int splits, hipStream_t s)
-{
-    GemmParams p = p0;
-    const int64_t tm = mrcnn::ceil_div(p.M, 128), tn = mrcnn::ceil_div(p.N, 128);
-    const int64_t T = tm * tn;
-    const bool big_ok = p.N > 64 && p.M > 64;
-    // Small-M, K-deep problems (the batch-2 backbone's 3x3 layers on res4: M = 8568, N = 256,
-    // 72 K slices): 64x64 tiles load twice the operand bytes per MFMA of 128x128 tiles and reach
-    // ~100 TFLOP/s whatever their occupancy (profiles/r05f_small_m.txt: K splits of the 64x64 tiles are
-    // flat), while the 134 tiles of 128x128 fill half the CUs once.  When a K split puts those tiles
-    // into ONE round of the 512 resident workgroups at >= 75 % fill with >= 16 slices each, the
-    // 128x128 kernel plus the ordered slab sum is faster in isolation (98 -> 83 us forward, 97 -> 80 us
-    // data gradient, profiles/r05d_big_split_k.txt); other counts land in a nearly empty second round
-    // and lose.  In the R-50 train step the rule is worth 0.05 - 0.1 ms (12 launches), in the R-101
-    // step (46 launches: 23 res4 blocks) 0.39 ms of 32.1 (same-box A/B, profiles/r06e_ab_big_split_k.txt):
-    // the default since round 6 ("big_split_k" = 0 restores the 64x64 tiles).
-    const int total_slices_ = p.R * p.S * (int)mrcnn::ceil_div(p.Kc, BK);
-    int64_t ksplits = 1;
-    if (g_big_split_k != 0 && big_ok && T < g_big_min_tiles && splits == 1 && can_split_rows<MODE>(p)) {
-        if (g_big_split_k > 0) {
-            ksplits = k_splits(total_slices_, 8, g_big_split_k, T, p.M, p.N, 8);
+        const auto prof = gemm_prof<MODE>(p, l);
+        if (l.tile == kW8BM) {
+            if constexpr (MODE == FWD) launch_w8_kernel(q, l.grid_x, 1, s);
+        } else if (l.tile == 128) {
+            launch_kernel<2, 2, MODE>(q, l.inst, l.grid_x, l.grid_y, s);
         } else {
-            const int64_t fit = kSlotsBig / T;                 // splits that still make one round
-            if (fit >= 2 && fit <= 8 && T * fit >= kSlotsBig * 3 / 4 && total_slices_ / fit >= g_big_split_min_slices)
-                ksplits = fit_ws(fit, p.M, p.N);
+            launch_kernel<1, 1, MODE>(q, l.inst, l.grid_x, l.grid_y, s);
         }
     }
-    if (MODE == FWD && splits == 1 && w8_ok(p)) {
-        launch_w8(p, s);
-    } else if (ksplits >= 2) {
-        launch_split_rows<MODE, 2>(p, 0, (int)ksplits, total_slices_, s);
-    } else if (!big_ok || T < g_big_min_tiles) {
-        launch_small<MODE>(p, s);
+    if constexpr (MODE == WGRAD) {
+        // (Summing the slabs in the last-arriving workgroup of each tile instead was measured 4 ms per
+        // train step slower: the agent-scope release every workgroup needs before it signals writes
+        // back its XCD's whole dirty L2.)
+        if (plan.sum_splits) {
+            const int64_t gwsz = (int64_t)p.M * p.N;
+            const int64_t blocks = mrcnn::ceil_div(gwsz / 4, 256);   // one float4 per thread
+            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
+                               (const float *)p.split_ws, plan.sum_splits, gwsz, gwsz, p.C);
+        }
+        return mrcnn::check_launch("conv_wgrad");
     } else {
-        // whole "rounds" of k workgroups per CU (k = 3, 2, 1): pick the round size that leaves
-        // the smallest leftover, run the leftover rows as 64x64 tiles
-        // resident 128x128 workgroups per CU: 3 single-buffered fp32, 2 otherwise (and split-operand)
-        const bool split_fwd = MODE == FWD && (g_split_bf16 & 1);
-        const int64_t max_per_cu = !split_fwd && single_buffered(2, MODE) ? 3 : 2;
-        int64_t main_tiles_m = tm, best_rem = T;
-        for (int64_t k = max_per_cu; k >= 1; --k) {
-            const int64_t slots = 256 * k, full = T / slots, rem = T - full * slots;
-            if (full >= 1 && rem < best_rem) {
-                best_rem = rem;
-                main_tiles_m = rem > 0 && rem < 154 ? (full * slots) / tn : tm;
-            }
-        }
-        const int rows_main = (int)std::min<int64_t>(p.M, main_tiles_m * 128);
-        if (!(splits == 1 && launch_fused_tail<2, 2, MODE>(p, rows_main, s))) {
-            launch_tiles<2, 2, MODE>(p, 0, rows_main, splits, s);
-            if (rows_main < p.M) launch_remainder<MODE>(p, rows_main, s);
-        }
+        if (plan.sum_splits) slab_sum<MODE>(p, plan.sum_row0, plan.sum_splits, s);
+        return mrcnn::check_launch("conv_gemm");
     }
-    return mrcnn::check_launch("conv_gemm");
+}
+
+// a forward-form / DGRAD problem under the policy of conv_gemm_plan.h
+template <int MODE>
+int launch(const GemmParams &p, hipStream_t s)
+{
+    return run_plan<MODE>(p, plan_gemm(gemm_shape(p, MODE, p.split_ws != nullptr), g_knobs), s);
 }
 
 int check_desc(const mrcnn_conv_desc *d)
@@ -1716,18 +1486,6 @@ int check_desc(const mrcnn_conv_desc *d)
 
 inline bool aligned16(const void *p) { return ((uintptr_t)p % 16) == 0; }
 
-int g_position_major_rows = 1;    // mrcnn_set_tuning("position_major_rows", 0/1)
-
-// Position-major row order (GemmParams::perm_n) pays when many small maps are convolved with
-// a padded filter: n_img maps of gp x gq output positions, pad_eff = padding of the gathered
-// tensor as the forward-form kernel sees it.
-inline int choose_perm(int n_img, int gp, int gq, int R, int S, int stride, int pad_eff)
-{
-    if (!g_position_major_rows || R * S <= 1 || R * S > 16 || stride != 1 || pad_eff <= 0) return 0;
-    if (gp * gq > 256 || n_img < 64) return 0;
-    return n_img;
-}
-
 // buffer extents in floats -> bytes; 32-bit buffer offsets need every tensor < 2 GiB
 int set_extents(GemmParams &p, int64_t a_floats, int64_t b_floats, int64_t c_floats)
 {
@@ -1741,21 +1499,161 @@ int set_extents(GemmParams &p, int64_t a_floats, int64_t b_floats, int64_t c_flo
     return 0;
 }
 
-int wgrad_splits(int64_t tiles, int64_t pixels, int64_t slots)
+// ---- descriptor -> problem ------------------------------------------------------------------------
+// The shape half of every entry point: the descriptor checks and every field of a zero-initialised
+// GemmParams but the pointers and the epilogue flags, which the entry point checks and sets before it
+// launches.  mrcnn_conv_gemm_plan plans the same problems without a pointer.
+
+int fwd_problem(const mrcnn_conv_desc *d, GemmParams &p)
 {
-    // Pick the split count whose tiles*splits workgroups fill whole rounds of `slots`
-    // resident workgroups best, each split at least 8 K slices deep, at most ~3 rounds.
-    const int64_t maxs = std::min<int64_t>(64, std::max<int64_t>(1, pixels / (8 * BK)));
-    int best = 1;
-    double best_u = -1.;
-    for (int64_t sp = 1; sp <= maxs; ++sp) {
-        const int64_t blocks = tiles * sp;
-        if (blocks > 3 * slots && sp > 1) break;
-        const double u = (double)blocks / (double)(mrcnn::ceil_div(blocks, slots) * slots);
-        if (u > best_u + 1e-9) { best_u = u; best = (int)sp; }
-    }
-    return best;
+    if (int rc = check_desc(d)) return rc;
+    p.M = d->N * d->P * d->Q; p.N = d->K; p.Kc = d->C;
+    p.gp = d->P; p.gq = d->Q; p.sh = d->H; p.sw = d->W;
+    p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad = d->pad;
+    p.lda = d->C; p.ldb = d->R * d->S * d->C; p.ldc = d->K;
+    p.out_mode = OUT_PLAIN;
+    p.perm_n = choose_perm(g_knobs, d->N, d->P, d->Q, d->R, d->S, d->stride, d->pad);
+    if (p.perm_n) p.M = (int)(mrcnn::ceil_div(d->N, kPermBlock) * kPermBlock) * d->P * d->Q;
+    return set_extents(p, (int64_t)d->N * d->H * d->W * d->C, (int64_t)d->K * d->R * d->S * d->C,
+                       (int64_t)d->N * d->P * d->Q * d->K);
 }
+
+// Stem: conv1 7x7/2 pad 3 of chainer ResNet50Layers (SURVEY.md A.1) on an input
+// padded to 4 channels; filter given as (K, 7, 8, 4) with zeros at s=7 / c=3.
+int stem_problem(int N, int H, int W, int K, GemmParams &p)
+{
+    MRCNN_REQUIRE(N > 0 && H > 0 && W > 0 && K > 0 && K % 4 == 0, "conv_stem: bad shape");
+    const int P = (H + 6 - 7) / 2 + 1, Q = (W + 6 - 7) / 2 + 1;
+    p.M = N * P * Q; p.N = K; p.Kc = 32;
+    p.gp = P; p.gq = Q; p.sh = H; p.sw = W;
+    p.R = 7; p.S = 1; p.stride = 2; p.pad = 3;
+    p.lda = 4; p.ldb = 7 * 32; p.ldc = K;
+    p.out_mode = OUT_PLAIN; p.stem = 1;
+    return set_extents(p, (int64_t)N * H * W * 4, (int64_t)K * 7 * 32, (int64_t)N * P * Q * K);
+}
+
+// K-strided data gradient; fused_grad: the call has a residual gradient or an output mask
+int dgrad_problem(const mrcnn_conv_desc *d, bool fused_grad, GemmParams &p)
+{
+    if (int rc = check_desc(d)) return rc;
+    MRCNN_REQUIRE(!fused_grad || d->stride == 1,
+                  "conv2d_dgrad: residual gradient / output mask need stride 1");
+    p.N = d->C; p.Kc = d->K; p.cin = d->C;
+    p.R = d->R; p.S = d->S; p.pad = d->pad;
+    p.lda = d->K; p.ldb = d->R * d->S * d->C; p.ldc = d->C;
+    p.sh = d->P; p.sw = d->Q;
+    if (d->stride == 1) {
+        p.M = d->N * d->H * d->W; p.gp = d->H; p.gq = d->W; p.stride = 1;
+        p.out_mode = OUT_PLAIN;
+    } else {
+        MRCNN_REQUIRE(d->R == 1 && d->S == 1 && d->pad == 0,
+                      "conv2d_dgrad: stride>1 is implemented for 1x1/pad0 (the only strided "
+                      "trainable convs of ResNet-C4) and the 2x2/2 adjoint (deconv entry points)");
+        p.M = d->N * d->P * d->Q; p.gp = d->P; p.gq = d->Q; p.stride = d->stride;
+        p.out_mode = OUT_STRIDED; p.oh = d->H; p.ow = d->W;
+    }
+    return set_extents(p, (int64_t)d->N * d->P * d->Q * d->K, (int64_t)d->K * d->R * d->S * d->C,
+                       (int64_t)d->N * d->H * d->W * d->C);
+}
+
+// Data gradient as a forward-form convolution of gy with wT = flip-transpose(w) (C,R,S,K): both
+// operands are K-contiguous (ds_read_b128 fragments, coalesced filter rows).
+// 1x1 / pad 0 strided convolution: every output pixel of the convolution sends its gradient to ONE
+// input pixel — the same forward-form GEMM on the transposed filter, its rows (the convolution's
+// output pixels) scattered to the strided positions of a zero-filled gx (OUT_STRIDED in the
+// per-element epilogue).
+int dgrad_wt_problem(const mrcnn_conv_desc *d, bool fused_grad, GemmParams &p)
+{
+    if (int rc = check_desc(d)) return rc;
+    const bool strided = d->stride > 1;
+    MRCNN_REQUIRE(!strided || (d->R == 1 && d->S == 1 && d->pad == 0),
+                  "conv2d_dgrad_wt: stride > 1 is implemented for 1x1 / pad 0 filters");
+    MRCNN_REQUIRE(!strided || !fused_grad, "conv2d_dgrad_wt: residual gradient / output mask need stride 1");
+    p.N = d->C; p.Kc = d->K;
+    p.sh = d->P; p.sw = d->Q;
+    p.R = d->R; p.S = d->S; p.stride = 1; p.pad = d->R - 1 - d->pad;
+    p.lda = d->K; p.ldb = d->R * d->S * d->K; p.ldc = d->C;
+    if (strided) {
+        p.gp = d->P; p.gq = d->Q; p.ostride = d->stride;
+        p.out_mode = OUT_STRIDED; p.oh = d->H; p.ow = d->W;
+    } else {
+        p.gp = d->H; p.gq = d->W;
+        p.out_mode = OUT_PLAIN;
+        p.perm_n = choose_perm(g_knobs, d->N, d->H, d->W, d->R, d->S, 1, p.pad);
+    }
+    p.M = d->N * p.gp * p.gq;
+    if (p.perm_n) p.M = (int)(mrcnn::ceil_div(d->N, kPermBlock) * kPermBlock) * d->H * d->W;
+    MRCNN_REQUIRE(d->S - 1 - d->pad == p.pad, "conv2d_dgrad_wt: square filters / symmetric padding only");
+    return set_extents(p, (int64_t)d->N * d->P * d->Q * d->K, (int64_t)d->K * d->R * d->S * d->C,
+                       (int64_t)d->N * d->H * d->W * d->C);
+}
+
+// Weight gradient gw[k, rsc] = sum over the pixels: M = K rows, N = R S C columns.  `shape` gets what
+// plan_wgrad() reads beside the GemmParams fields.
+int wgrad_problem(const mrcnn_conv_desc *d, GemmParams &p, GemmShape &shape)
+{
+    const int64_t pixels = (int64_t)d->N * d->P * d->Q;
+    p.M = d->K; p.N = d->R * d->S * d->C; p.Kc = (int)pixels;
+    p.gp = d->P; p.gq = d->Q; p.sh = d->H; p.sw = d->W;
+    p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad = d->pad;
+    p.lda = d->C; p.ldg = d->K; p.cin = d->C; p.ldc = d->R * d->S * d->C;
+    shape = gemm_shape(p, WGRAD, false);
+    shape.pixels = pixels; shape.n_img = d->N; shape.C = d->C;
+    return set_extents(p, pixels * d->K, (int64_t)d->N * d->H * d->W * d->C, (int64_t)d->K * d->R * d->S * d->C);
+}
+
+// ---- Deconvolution 2x2 stride 2 (= adjoint of a 2x2/2 convolution g: (N,2H,2W,K) -> (N,H,W,C)
+//      with KRSC filter w (C,2,2,K)) -----------------------------------------------------------
+inline mrcnn_conv_desc deconv_adjoint_desc(int N, int H, int W, int C, int K)
+{
+    return {N, 2 * H, 2 * W, K, C, 2, 2, 2, 0, H, W};
+}
+
+// The deconvolution forward as a 1x1 GEMM whose output columns (a, b, o) are scattered by the
+// pixel-shuffle map of the epilogue: y[n, 2y + a, 2x + b, o] = sum_c x[n, y, x, c] w[c; (a, b, o)].
+// wt = false: filter w (C, 4K), the K-strided DGRAD form (fp32 MFMA); wt = true: FORWARD form on the
+// transposed filter wT (4K, C) — both operands K-contiguous, i.e. the split-operand kernels.
+int deconv_problem(bool wt, int N, int H, int W, int C, int K, GemmParams &p)
+{
+    MRCNN_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && C % 4 == 0 && K % 4 == 0,
+                  "%s: bad shape", wt ? "deconv_fwd_wt" : "deconv_fwd");
+    p.M = N * H * W; p.N = 4 * K; p.Kc = C; p.cin = wt ? 0 : 4 * K;
+    p.gp = H; p.gq = W; p.sh = H; p.sw = W;
+    p.R = 1; p.S = 1; p.stride = 1; p.pad = 0;
+    p.lda = C; p.ldb = wt ? C : 4 * K; p.ldc = K;
+    p.out_mode = OUT_DECONV; p.ko = K;
+    return set_extents(p, (int64_t)N * H * W * C, (int64_t)C * 4 * K, (int64_t)N * 4 * H * W * K);
+}
+
+int deconv_fwd(bool wt, const float *x, const float *w, const float *bias, float *y, int N, int H, int W,
+               int C, int K, int epi_flags, void *stream)
+{
+    const char *who = wt ? "deconv_fwd_wt" : "deconv_fwd";
+    GemmParams p = {};
+    if (int rc = deconv_problem(wt, N, H, W, C, K, p)) return rc;
+    MRCNN_REQUIRE(x && w && y, "%s: null pointer", who);
+    MRCNN_REQUIRE(aligned16(x) && aligned16(w), "%s: x/%s must be 16-byte aligned", who, wt ? "wT" : "w");
+    MRCNN_REQUIRE((epi_flags & ~(MRCNN_EPI_BIAS | MRCNN_EPI_RELU)) == 0, "%s: bad flags", who);
+    MRCNN_REQUIRE(!(epi_flags & MRCNN_EPI_BIAS) || bias, "%s: bias flag without bias", who);
+    p.A = x; p.B = w; p.C = y; p.bias = bias;
+    p.flags = epi_flags;
+    return wt ? launch<FWD>(p, mrcnn::as_stream(stream)) : launch<DGRAD>(p, mrcnn::as_stream(stream));
+}
+
+int wgrad_run(const mrcnn_conv_desc *d, const float *gy, const float *x, float *gw, void *ws,
+              const float *out_row_scale, void *stream)
+{
+    GemmParams p = {};
+    GemmShape shape;
+    if (int rc = wgrad_problem(d, p, shape)) return rc;
+    p.A = gy; p.B = x; p.C = gw;
+    p.scale = out_row_scale;
+    p.split_ws = (float *)ws;
+    shape.has_ws = ws != nullptr;
+    return run_plan<WGRAD>(p, plan_wgrad(shape, g_knobs), mrcnn::as_stream(stream));
+}
+
+extern float g_wino_ambiguity;
 
 }  // namespace
 
@@ -1764,52 +1662,9 @@ extern "C" int64_t mrcnn_conv2d_split_workspace_bytes(void) { return kSplitWsByt
 extern "C" int mrcnn_set_tuning(const char *name, int value)
 {
     MRCNN_REQUIRE(name != nullptr, "set_tuning: null name");
-    if (strcmp(name, "position_major_rows") == 0) {
-        g_position_major_rows = value != 0;
-        return 0;
-    }
-    if (strcmp(name, "fused_tail") == 0) {
-        g_fused_tail = value == 1 ? 512 : value;
-        return 0;
-    }
+    if (set_knob(g_knobs, name, value)) return 0;
     if (strcmp(name, "wino_ambiguity_ppb") == 0) {
         g_wino_ambiguity = 1e-9f * (float)value;
-        return 0;
-    }
-    if (strcmp(name, "big_min_tiles") == 0) {
-        g_big_min_tiles = value;
-        return 0;
-    }
-    if (strcmp(name, "small_m_split") == 0) {
-        g_small_m_split = value;
-        return 0;
-    }
-    if (strcmp(name, "split_bf16") == 0) {
-        g_split_bf16 = value;          // bit 0: 128x128 kernels, bit 1: 64x64 forward form
-        return 0;
-    }
-    if (strcmp(name, "big_split_k") == 0) {
-        g_big_split_k = value;
-        return 0;
-    }
-    if (strcmp(name, "big_split_min_slices") == 0) {
-        g_big_split_min_slices = value;
-        return 0;
-    }
-    if (strcmp(name, "w8") == 0) {
-        g_w8 = value;
-        return 0;
-    }
-    if (strcmp(name, "w8_min_k") == 0) {
-        g_w8_min_k = value;
-        return 0;
-    }
-    if (strcmp(name, "pw") == 0) {
-        g_pw = value;
-        return 0;
-    }
-    if (strcmp(name, "tiny_split") == 0) {
-        g_tiny_split = value;
         return 0;
     }
     if (int rc = mrcnn::roi_align_set_tuning(name, value); rc >= 0) return rc;   // roi_fwd_lanes / roi_bwd_lanes
@@ -1822,56 +1677,54 @@ extern "C" int mrcnn_conv2d_fwd(const mrcnn_conv_desc *d, const float *x, const 
                                 const float *residual, float *y, int epi_flags, void *split_ws,
                                 void *stream)
 {
-    if (int rc = check_desc(d)) return rc;
+    GemmParams p = {};
+    if (int rc = fwd_problem(d, p)) return rc;
     MRCNN_REQUIRE(x && w && y, "conv2d_fwd: null pointer");
     MRCNN_REQUIRE(aligned16(x) && aligned16(w), "conv2d_fwd: x/w must be 16-byte aligned");
     MRCNN_REQUIRE(!(epi_flags & MRCNN_EPI_BIAS) || bias, "conv2d_fwd: bias flag without bias");
     MRCNN_REQUIRE(!(epi_flags & MRCNN_EPI_AFFINE) || (scale && shift), "conv2d_fwd: affine flag without scale/shift");
     MRCNN_REQUIRE(!(epi_flags & MRCNN_EPI_RESIDUAL) || residual, "conv2d_fwd: residual flag without residual");
-    GemmParams p = {};
     p.A = x; p.B = w; p.C = y;
     p.bias = bias; p.scale = scale; p.shift = shift; p.residual = residual;
-    p.M = d->N * d->P * d->Q; p.N = d->K; p.Kc = d->C;
-    p.gp = d->P; p.gq = d->Q; p.sh = d->H; p.sw = d->W;
-    p.R = d->R; p.S = d->S; p.stride = d->stride; p.pad = d->pad;
-    p.lda = d->C; p.ldb = d->R * d->S * d->C; p.ldc = d->K;
-    p.flags = epi_flags; p.out_mode = OUT_PLAIN;
+    p.flags = epi_flags;
     p.split_ws = (float *)split_ws;
-    p.perm_n = choose_perm(d->N, d->P, d->Q, d->R, d->S, d->stride, d->pad);
-    if (p.perm_n) p.M = (int)(mrcnn::ceil_div(d->N, kPermBlock) * kPermBlock) * d->P * d->Q;
-    if (int rc = set_extents(p, (int64_t)d->N * d->H * d->W * d->C, (int64_t)d->K * d->R * d->S * d->C,
-                             (int64_t)d->N * d->P * d->Q * d->K))
-        return rc;
-    return launch<FWD>(p, 1, mrcnn::as_stream(stream));
+    return launch<FWD>(p, mrcnn::as_stream(stream));
 }
 
-// Stem: conv1 7x7/2 pad 3 of chainer ResNet50Layers (SURVEY.md A.1) on an input
-// padded to 4 channels; filter given as (K, 7, 8, 4) with zeros at s=7 / c=3.
 extern "C" int mrcnn_conv_stem_fwd(const float *x4, const float *w784, const float *bias,
                                    const float *scale, const float *shift, float *y, int N, int H,
                                    int W, int K, int epi_flags, void *stream)
 {
-    MRCNN_REQUIRE(x4 && w784 && y, "conv_stem: null pointer");
-    MRCNN_REQUIRE(N > 0 && H > 0 && W > 0 && K > 0 && K % 4 == 0, "conv_stem: bad shape");
-    MRCNN_REQUIRE(aligned16(x4) && aligned16(w784), "conv_stem: pointers must be 16-byte aligned");
-    const int P = (H + 6 - 7) / 2 + 1, Q = (W + 6 - 7) / 2 + 1;
     GemmParams p = {};
+    if (int rc = stem_problem(N, H, W, K, p)) return rc;
+    MRCNN_REQUIRE(x4 && w784 && y, "conv_stem: null pointer");
+    MRCNN_REQUIRE(aligned16(x4) && aligned16(w784), "conv_stem: pointers must be 16-byte aligned");
     p.A = x4; p.B = w784; p.C = y;
     p.bias = bias; p.scale = scale; p.shift = shift;
-    p.M = N * P * Q; p.N = K; p.Kc = 32;
-    p.gp = P; p.gq = Q; p.sh = H; p.sw = W;
-    p.R = 7; p.S = 1; p.stride = 2; p.pad = 3;
-    p.lda = 4; p.ldb = 7 * 32; p.ldc = K;
-    p.flags = epi_flags; p.out_mode = OUT_PLAIN; p.stem = 1;
-    if (int rc = set_extents(p, (int64_t)N * H * W * 4, (int64_t)K * 7 * 32, (int64_t)N * P * Q * K))
-        return rc;
-    return launch<FWD>(p, 1, mrcnn::as_stream(stream));
+    p.flags = epi_flags;
+    return launch<FWD>(p, mrcnn::as_stream(stream));
 }
 
 extern "C" int mrcnn_conv2d_dgrad_ex(const mrcnn_conv_desc *d, const float *gy, const float *w,
                                      float *gx, int epi_flags, const float *res_g,
                                      const float *res_y, const float *out_mask_y,
-                                     const float *out_scale, void *split_ws, void *stream);
+                                     const float *out_scale, void *split_ws, void *stream)
+{
+    GemmParams p = {};
+    if (int rc = dgrad_problem(d, res_g || out_mask_y, p)) return rc;
+    MRCNN_REQUIRE(!res_y || res_g, "conv2d_dgrad: res_y without res_g");
+    MRCNN_REQUIRE(gy && w && gx, "conv2d_dgrad: null pointer");
+    MRCNN_REQUIRE(aligned16(gy) && aligned16(w), "conv2d_dgrad: gy/w must be 16-byte aligned");
+    MRCNN_REQUIRE((epi_flags & ~MRCNN_EPI_ACCUM) == 0, "conv2d_dgrad: only MRCNN_EPI_ACCUM is valid");
+    hipStream_t s = mrcnn::as_stream(stream);
+    p.A = gy; p.B = w; p.C = gx;
+    p.res_g = res_g; p.res_y = res_y; p.out_mask_y = out_mask_y; p.scale = out_scale;
+    p.flags = epi_flags | (out_scale ? MRCNN_EPI_AFFINE : 0);
+    p.split_ws = (float *)split_ws;
+    if (p.out_mode == OUT_STRIDED && !(epi_flags & MRCNN_EPI_ACCUM))
+        MRCNN_HIP_TRY(hipMemsetAsync(gx, 0, sizeof(float) * (size_t)d->N * d->H * d->W * d->C, s));
+    return launch<DGRAD>(p, s);
+}
 
 extern "C" int mrcnn_conv2d_dgrad(const mrcnn_conv_desc *d, const float *gy, const float *w,
                                   float *gx, int epi_flags, void *stream)
@@ -1880,46 +1733,6 @@ extern "C" int mrcnn_conv2d_dgrad(const mrcnn_conv_desc *d, const float *gy, con
                                  stream);
 }
 
-extern "C" int mrcnn_conv2d_dgrad_ex(const mrcnn_conv_desc *d, const float *gy, const float *w,
-                                     float *gx, int epi_flags, const float *res_g,
-                                     const float *res_y, const float *out_mask_y,
-                                     const float *out_scale, void *split_ws, void *stream)
-{
-    if (int rc = check_desc(d)) return rc;
-    MRCNN_REQUIRE(!res_y || res_g, "conv2d_dgrad: res_y without res_g");
-    MRCNN_REQUIRE((!res_g && !out_mask_y) || d->stride == 1,
-                  "conv2d_dgrad: residual gradient / output mask need stride 1");
-    MRCNN_REQUIRE(gy && w && gx, "conv2d_dgrad: null pointer");
-    MRCNN_REQUIRE(aligned16(gy) && aligned16(w), "conv2d_dgrad: gy/w must be 16-byte aligned");
-    MRCNN_REQUIRE((epi_flags & ~MRCNN_EPI_ACCUM) == 0, "conv2d_dgrad: only MRCNN_EPI_ACCUM is valid");
-    hipStream_t s = mrcnn::as_stream(stream);
-    GemmParams p = {};
-    p.A = gy; p.B = w; p.C = gx;
-    p.res_g = res_g; p.res_y = res_y; p.out_mask_y = out_mask_y; p.scale = out_scale;
-    p.N = d->C; p.Kc = d->K; p.cin = d->C;
-    p.R = d->R; p.S = d->S; p.pad = d->pad;
-    p.lda = d->K; p.ldb = d->R * d->S * d->C; p.ldc = d->C;
-    p.flags = epi_flags | (out_scale ? MRCNN_EPI_AFFINE : 0);
-   
-    p.split_ws = (float *)split_ws;
-    if (int rc = set_extents(p, (int64_t)d->N * d->P * d->Q * d->K, (int64_t)d->K * d->R * d->S * d->C,
-                             (int64_t)d->N * d->H * d->W * d->C))
-        return rc;
-    p.sh = d->P; p.sw = d->Q;
-    if (d->stride == 1) {
-        p.M = d->N * d->H * d->W; p.gp = d->H; p.gq = d->W; p.stride = 1;
-        p.out_mode = OUT_PLAIN;
-    } else {
-        MRCNN_REQUIRE(d->R == 1 && d->S == 1 && d->pad == 0,
-                      "conv2d_dgrad: stride>1 is implemented for 1x1/pad0 (the only strided "
-                      "trainable convs of ResNet-C4) and the 2x2/2 adjoint (deconv entry points)");
-        p.M = d->N * d->P * d->Q; p.gp = d->P; p.gq = d->Q; p.stride = d->stride;
-        p.out_mode = OUT_STRIDED; p.oh = d->H; p.ow = d->W;
-        if (!(epi_flags & MRCNN_EPI_ACCUM))
-            MRCNN_HIP_TRY(hipMemsetAsync(gx, 0, sizeof(float) * (size_t)d->N * d->H * d->W * d->C, s));
-    }
-    return launch<DGRAD>(p, 1, s);
-}
 
 namespace {
 // wT[c][R-1-r][S-1-s][k] = w[k][r][s][c] * row_scale[k]
@@ -2025,62 +1838,28 @@ extern "C" int mrcnn_filter_flip_transpose(const float *w, float *wT, int K, int
     return mrcnn::check_launch("filter_flip_transpose");
 }
 
-// Stride-1 dgrad as a forward-form convolution of gy with wT = flip-transpose(w) (C,R,S,K):
-// both operands are K-contiguous (ds_read_b128 fragments, coalesced filter rows).
 extern "C" int mrcnn_conv2d_dgrad_wt(const mrcnn_conv_desc *d, const float *gy, const float *wT,
                                      float *gx, int epi_flags, const float *res_g,
                                      const float *res_y, const float *out_mask_y,
                                      const float *out_scale, void *split_ws, void *stream)
 {
-    if (int rc = check_desc(d)) return rc;
-    if (d->stride > 1) {
-        // 1x1 / pad 0 strided convolution: every output pixel of the convolution sends its gradient
-        // to ONE input pixel — the same forward-form GEMM on the transposed filter, its rows
-        // scattered to the strided positions of a zero-filled gx (OUT_STRIDED in the per-element epilogue)
-        MRCNN_REQUIRE(d->R == 1 && d->S == 1 && d->pad == 0,
-                      "conv2d_dgrad_wt: stride > 1 is implemented for 1x1 / pad 0 filters");
-        MRCNN_REQUIRE(gy && wT && gx, "conv2d_dgrad_wt: null pointer");
-        MRCNN_REQUIRE(aligned16(gy) && aligned16(wT), "conv2d_dgrad_wt: gy/wT must be 16-byte aligned");
-        MRCNN_REQUIRE((epi_flags & ~MRCNN_EPI_ACCUM) == 0, "conv2d_dgrad_wt: only MRCNN_EPI_ACCUM is valid");
-        MRCNN_REQUIRE(!res_g && !res_y && !out_mask_y, "conv2d_dgrad_wt: residual gradient / output mask need stride 1");
-        hipStream_t s = mrcnn::as_stream(stream);
-        GemmParams p = {};
-        p.A = gy; p.B = wT; p.C = gx;
-        p.scale = out_scale;
-        p.M = d->N * d->P * d->Q; p.N = d->C; p.Kc = d->K;
-        p.gp = d->P; p.gq = d->Q; p.sh = d->P; p.sw = d->Q;
-        p.R = 1; p.S = 1; p.stride = 1; p.pad = 0; p.ostride = d->stride;
-        p.lda = d->K; p.ldb = d->K; p.ldc = d->C;
-        p.flags = epi_flags | (out_scale ? MRCNN_EPI_AFFINE : 0);
-        p.out_mode = OUT_STRIDED; p.oh = d->H; p.ow = d->W;
-        if (int rc = set_extents(p, (int64_t)d->N * d->P * d->Q * d->K, (int64_t)d->K * d->C,
-                                 (int64_t)d->N * d->H * d->W * d->C))
-            return rc;
-        if (!(epi_flags & MRCNN_EPI_ACCUM))
-            MRCNN_HIP_TRY(hipMemsetAsync(gx, 0, sizeof(float) * (size_t)d->N * d->H * d->W * d->C, s));
-        return launch<FWD>(p, 1, s);
-    }
+    GemmParams p = {};
+    if (int rc = dgrad_wt_problem(d, res_g || res_y || out_mask_y, p)) return rc;
     MRCNN_REQUIRE(gy && wT && gx, "conv2d_dgrad_wt: null pointer");
     MRCNN_REQUIRE(aligned16(gy) && aligned16(wT), "conv2d_dgrad_wt: gy/wT must be 16-byte aligned");
     MRCNN_REQUIRE((epi_flags & ~MRCNN_EPI_ACCUM) == 0, "conv2d_dgrad_wt: only MRCNN_EPI_ACCUM is valid");
     MRCNN_REQUIRE(!res_y || res_g, "conv2d_dgrad_wt: res_y without res_g");
-    GemmParams p = {};
+    hipStream_t s = mrcnn::as_stream(stream);
     p.A = gy; p.B = wT; p.C = gx;
     p.res_g = res_g; p.res_y = res_y; p.out_mask_y = out_mask_y; p.scale = out_scale;
-   
-    p.split_ws = (float *)split_ws;
-    p.M = d->N * d->H * d->W; p.N = d->C; p.Kc = d->K;
-    p.gp = d->H; p.gq = d->W; p.sh = d->P; p.sw = d->Q;
-    p.R = d->R; p.S = d->S; p.stride = 1; p.pad = d->R - 1 - d->pad;
-    p.lda = d->K; p.ldb = d->R * d->S * d->K; p.ldc = d->C;
-    p.flags = epi_flags | (out_scale ? MRCNN_EPI_AFFINE : 0); p.out_mode = OUT_PLAIN;
-    p.perm_n = choose_perm(d->N, d->H, d->W, d->R, d->S, 1, p.pad);
-    if (p.perm_n) p.M = (int)(mrcnn::ceil_div(d->N, kPermBlock) * kPermBlock) * d->H * d->W;
-    MRCNN_REQUIRE(d->S - 1 - d->pad == p.pad, "conv2d_dgrad_wt: square filters / symmetric padding only");
-    if (int rc = set_extents(p, (int64_t)d->N * d->P * d->Q * d->K, (int64_t)d->K * d->R * d->S * d->C,
-                             (int64_t)d->N * d->H * d->W * d->C))
-        return rc;
-    return launch<FWD>(p, 1, mrcnn::as_stream(stream));
+    p.flags = epi_flags | (out_scale ? MRCNN_EPI_AFFINE : 0);
+    if (p.out_mode == OUT_STRIDED) {       // (the scattered rows are never cut along K: no workspace)
+        if (!(epi_flags & MRCNN_EPI_ACCUM))
+            MRCNN_HIP_TRY(hipMemsetAsync(gx, 0, sizeof(float) * (size_t)d->N * d->H * d->W * d->C, s));
+    } else {
+        p.split_ws = (float *)split_ws;
+    }
+    return launch<FWD>(p, s);
 }
 
 extern "C" int64_t mrcnn_conv2d_wgrad_workspace_bytes(const mrcnn_conv_desc *d)
@@ -2088,61 +1867,6 @@ extern "C" int64_t mrcnn_conv2d_wgrad_workspace_bytes(const mrcnn_conv_desc *d)
     if (!d) return 0;
     const int64_t gwsz = (int64_t)d->K * d->R * d->S * d->C;
     return 64 * gwsz * 4;  // 64 split slabs
-}
-
-static int wgrad_impl(const float *gy, int ldg, const float *x, float *gw, int Kout, int64_t pixels,
-                      int N_, int H, int W, int C, int P, int Q, int R, int S, int stride, int pad,
-                      void *ws, hipStream_t s, const float *out_row_scale = nullptr)
-{
-    GemmParams p = {};
-    p.A = gy; p.B = x;
-    p.scale = out_row_scale;
-    p.M = Kout; p.N = R * S * C; p.Kc = (int)pixels;
-    p.gp = P; p.gq = Q; p.sh = H; p.sw = W;
-    p.R = R; p.S = S; p.stride = stride; p.pad = pad;
-    p.lda = C; p.ldg = ldg; p.cin = C; p.ldc = R * S * C;
-    const int64_t gwsz = (int64_t)Kout * R * S * C;
-    const int64_t big = mrcnn::ceil_div(p.M, 128) * mrcnn::ceil_div(p.N, 128);
-    // The pixel (K) dimension supplies the parallelism through split-K, so 128x128 tiles are
-    // used whenever tiles x achievable splits fills at least half of the resident slots and
-    // the problem is at least one tile wide; otherwise 64x64 tiles.
-    const int64_t small = mrcnn::ceil_div(p.M, 64) * mrcnn::ceil_div(p.N, 64);
-    const int64_t max_splits = std::min<int64_t>(64, std::max<int64_t>(1, pixels / (8 * BK)));
-    const bool use_big = p.N > 64 && p.M > 64 && (big * max_splits * 2 >= kSlotsBig || g_big_min_tiles <= 1);
-    const int64_t tiles = use_big ? big : small;
-    // block-position-major pixel order (WPERM kernel): border taps skip the positions where
-    // they fall into the padding; the reduction then runs over whole blocks of BK images
-    if (C % (use_big ? 128 : 64) == 0 && N_ >= BK)
-        p.perm_n = choose_perm(N_, P, Q, R, S, stride, pad);
-    const int64_t k_extent = p.perm_n ? mrcnn::ceil_div(N_, BK) * BK * P * Q : pixels;
-    // resident 128x128 workgroups: 3 per CU single-buffered, 2 otherwise (and for the split-operand kernel)
-    const bool split_kernel = (g_split_bf16 & 1) && p.perm_n == 0;
-    const int64_t slots_big = !split_kernel && single_buffered(2, WGRAD) ? 768 : kSlotsBig;
-    int splits = wgrad_splits(tiles, pixels, use_big ? slots_big : kSlotsSmall);
-    if (!ws) splits = 1;
-    p.split_len = (int)(mrcnn::ceil_div(mrcnn::ceil_div(k_extent, splits), BK) * BK);
-    splits = (int)mrcnn::ceil_div(k_extent, p.split_len);
-    p.split_stride = gwsz;
-    if (int rc = set_extents(p, pixels * ldg, (int64_t)N_ * H * W * C, gwsz)) return rc;
-    p.C = splits > 1 ? (float *)ws : gw;
-    {
-        mrcnn::ProfKernelScope prof(use_big ? mrcnn::PROF_CONV_WGRAD_128 : mrcnn::PROF_CONV_WGRAD_64,
-                                    2.0 * p.M * p.N * (double)pixels,
-                                    4.0 * ((double)p.M * p.N + (double)pixels * (p.M + (double)C)));
-        if (use_big)
-            launch_kernel<2, 2, WGRAD>(p, big, splits, s);
-        else
-            launch_kernel<1, 1, WGRAD>(p, tiles, splits, s);
-    }
-    // (Summing the slabs in the last-arriving workgroup of each tile instead was measured 4 ms per
-    // train step slower: the agent-scope release every workgroup needs before it signals writes
-    // back its XCD's whole dirty L2.)
-    if (splits > 1) {
-        const int64_t blocks = mrcnn::ceil_div(gwsz / 4, 256);   // one float4 per thread
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
-                           (const float *)ws, splits, gwsz, gwsz, gw);
-    }
-    return mrcnn::check_launch("conv_wgrad");
 }
 
 extern "C" int mrcnn_conv2d_wgrad_ex(const mrcnn_conv_desc *d, const float *x, const float *gy,
@@ -2153,9 +1877,7 @@ extern "C" int mrcnn_conv2d_wgrad_ex(const mrcnn_conv_desc *d, const float *x, c
     MRCNN_REQUIRE(x && gy && gw, "conv2d_wgrad: null pointer");
     MRCNN_REQUIRE(aligned16(x) && aligned16(gy) && aligned16(gw) && (!ws || aligned16(ws)),
                   "conv2d_wgrad: pointers must be 16-byte aligned");
-    return wgrad_impl(gy, d->K, x, gw, d->K, (int64_t)d->N * d->P * d->Q, d->N, d->H, d->W, d->C,
-                      d->P, d->Q, d->R, d->S, d->stride, d->pad, ws, mrcnn::as_stream(stream),
-                      out_row_scale);
+    return wgrad_run(d, gy, x, gw, ws, out_row_scale, stream);
 }
 
 extern "C" int mrcnn_conv2d_wgrad(const mrcnn_conv_desc *d, const float *x, const float *gy,
@@ -2164,61 +1886,25 @@ extern "C" int mrcnn_conv2d_wgrad(const mrcnn_conv_desc *d, const float *x, cons
     return mrcnn_conv2d_wgrad_ex(d, x, gy, gw, ws, nullptr, stream);
 }
 
-// ---- Deconvolution 2x2 stride 2 (= adjoint of a 2x2/2 convolution g: (N,2H,2W,K) -> (N,H,W,C)
-//      with KRSC filter w (C,2,2,K)) -----------------------------------------------------------
 extern "C" int mrcnn_deconv2x2s2_fwd(const float *x, const float *w, const float *bias, float *y,
                                      int N, int H, int W, int C, int K, int epi_flags,
                                      void *stream)
 {
-    MRCNN_REQUIRE(x && w && y, "deconv_fwd: null pointer");
-    MRCNN_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && C % 4 == 0 && K % 4 == 0,
-                  "deconv_fwd: bad shape");
-    MRCNN_REQUIRE(aligned16(x) && aligned16(w), "deconv_fwd: x/w must be 16-byte aligned");
-    MRCNN_REQUIRE((epi_flags & ~(MRCNN_EPI_BIAS | MRCNN_EPI_RELU)) == 0, "deconv_fwd: bad flags");
-    MRCNN_REQUIRE(!(epi_flags & MRCNN_EPI_BIAS) || bias, "deconv_fwd: bias flag without bias");
-    GemmParams p = {};
-    p.A = x; p.B = w; p.C = y; p.bias = bias;
-    p.M = N * H * W; p.N = 4 * K; p.Kc = C; p.cin = 4 * K;
-    p.gp = H; p.gq = W; p.sh = H; p.sw = W;
-    p.R = 1; p.S = 1; p.stride = 1; p.pad = 0;
-    p.lda = C; p.ldb = 4 * K; p.ldc = K;
-    p.flags = epi_flags; p.out_mode = OUT_DECONV; p.ko = K;
-    if (int rc = set_extents(p, (int64_t)N * H * W * C, (int64_t)C * 4 * K, (int64_t)N * 4 * H * W * K))
-        return rc;
-    return launch<DGRAD>(p, 1, mrcnn::as_stream(stream));
+    return deconv_fwd(false, x, w, bias, y, N, H, W, C, K, epi_flags, stream);
 }
 
-// The same deconvolution in FORWARD form on the transposed filter wT (4K, C) = (a, b, o; c) — both
-// operands K-contiguous, i.e. the split-operand kernels (the K-strided DGRAD form above runs on fp32
-// MFMA): y[n, 2y + a, 2x + b, o] = sum_c x[n, y, x, c] wT[(a, b, o), c], a 1x1 convolution whose
-// output columns are scattered by the pixel-shuffle map of the epilogue.
 extern "C" int mrcnn_deconv2x2s2_fwd_wt(const float *x, const float *wT, const float *bias, float *y,
                                         int N, int H, int W, int C, int K, int epi_flags,
                                         void *stream)
 {
-    MRCNN_REQUIRE(x && wT && y, "deconv_fwd_wt: null pointer");
-    MRCNN_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && C % 4 == 0 && K % 4 == 0,
-                  "deconv_fwd_wt: bad shape");
-    MRCNN_REQUIRE(aligned16(x) && aligned16(wT), "deconv_fwd_wt: x/wT must be 16-byte aligned");
-    MRCNN_REQUIRE((epi_flags & ~(MRCNN_EPI_BIAS | MRCNN_EPI_RELU)) == 0, "deconv_fwd_wt: bad flags");
-    MRCNN_REQUIRE(!(epi_flags & MRCNN_EPI_BIAS) || bias, "deconv_fwd_wt: bias flag without bias");
-    GemmParams p = {};
-    p.A = x; p.B = wT; p.C = y; p.bias = bias;
-    p.M = N * H * W; p.N = 4 * K; p.Kc = C;
-    p.gp = H; p.gq = W; p.sh = H; p.sw = W;
-    p.R = 1; p.S = 1; p.stride = 1; p.pad = 0;
-    p.lda = C; p.ldb = C; p.ldc = K;
-    p.flags = epi_flags; p.out_mode = OUT_DECONV; p.ko = K;
-    if (int rc = set_extents(p, (int64_t)N * H * W * C, (int64_t)C * 4 * K, (int64_t)N * 4 * H * W * K))
-        return rc;
-    return launch<FWD>(p, 1, mrcnn::as_stream(stream));
+    return deconv_fwd(true, x, wT, bias, y, N, H, W, C, K, epi_flags, stream);
 }
 
 extern "C" int mrcnn_deconv2x2s2_dgrad(const float *gy, const float *w, float *gx, int N, int H,
                                        int W, int C, int K, void *stream)
 {
     // gx = conv2x2/2(gy) with KRSC filter w (C,2,2,K)
-    mrcnn_conv_desc d = {N, 2 * H, 2 * W, K, C, 2, 2, 2, 0, H, W};
+    const mrcnn_conv_desc d = deconv_adjoint_desc(N, H, W, C, K);
     return mrcnn_conv2d_fwd(&d, gy, w, nullptr, nullptr, nullptr, nullptr, gx, 0, nullptr, stream);
 }
 
@@ -2235,8 +1921,85 @@ extern "C" int mrcnn_deconv2x2s2_wgrad(const float *x, const float *gy, float *g
                   "deconv_wgrad: pointers must be 16-byte aligned");
     // gw[c, (a,b,o)] = sum_m x[m, c] * gy[pix(m,a,b), o] : wgrad of the adjoint conv with
     // "gy" := x and "x" := gy.
-    return wgrad_impl(x, C, gy, gw, C, (int64_t)N * H * W, N, 2 * H, 2 * W, K, H, W, 2, 2, 2, 0, ws,
-                      mrcnn::as_stream(stream));
+    const mrcnn_conv_desc d = deconv_adjoint_desc(N, H, W, C, K);
+    return wgrad_run(&d, x, gy, gw, ws, nullptr, stream);
+}
+
+// The plan of one call as text, no device touched (tests/test_gemm_edge_cases_cpu.py parses it):
+//   label=<branch> mode=<mode> M=<rows> N=<cols> k=<K extent the slabs cut>
+//   | kind=<profiler kernel> tags=<instantiation> rows=<lo>:<hi> grid=<x>x<y> slab=<depth> tail=<first>,<row0>,<pieces>,<depth>
+//   [| sum row0=<first row> slabs=<count>]
+extern "C" int mrcnn_conv_gemm_plan(const char *entry, const mrcnn_conv_desc *d, int has_ws, char *out,
+                                    int out_len)
+{
+    MRCNN_REQUIRE(entry && d && out && out_len > 0, "conv_gemm_plan: null argument");
+    const char *plus = strchr(entry, '+');
+    const size_t len = plus ? (size_t)(plus - entry) : strlen(entry);
+    auto is = [&](const char *name) { return strlen(name) == len && strncmp(entry, name, len) == 0; };
+    const bool dgrad = is("conv2d_dgrad") || is("conv2d_dgrad_ex"), dgrad_wt = is("conv2d_dgrad_wt");
+    MRCNN_REQUIRE(!plus || (strcmp(plus, "+res_g") == 0 && (dgrad || dgrad_wt)),
+                  "conv_gemm_plan: unknown entry '%s'", entry);
+    const bool fused_grad = plus != nullptr;
+    const mrcnn_conv_desc adj = deconv_adjoint_desc(d->N, d->H, d->W, d->C, d->K);
+    GemmParams p = {};
+    GemmShape shape = {};
+    int mode = FWD, rc = 0;
+    bool ws = has_ws != 0;                 // entry points without a workspace argument plan without one
+    if (is("conv2d_fwd")) {
+        rc = fwd_problem(d, p);
+    } else if (is("conv_stem_fwd")) {
+        rc = stem_problem(d->N, d->H, d->W, d->K, p);
+        ws = false;
+    } else if (dgrad) {
+        mode = DGRAD;
+        rc = dgrad_problem(d, fused_grad, p);
+        ws = ws && is("conv2d_dgrad_ex");
+    } else if (dgrad_wt) {
+        rc = dgrad_wt_problem(d, fused_grad, p);
+        ws = ws && p.out_mode == OUT_PLAIN;
+    } else if (is("conv2d_wgrad") || is("conv2d_wgrad_ex")) {
+        mode = WGRAD;
+        rc = check_desc(d);
+        if (!rc) rc = wgrad_problem(d, p, shape);
+    } else if (is("deconv2x2s2_fwd") || is("deconv2x2s2_fwd_wt")) {
+        mode = is("deconv2x2s2_fwd") ? DGRAD : FWD;
+        rc = deconv_problem(mode == FWD, d->N, d->H, d->W, d->C, d->K, p);
+        ws = false;
+    } else if (is("deconv2x2s2_dgrad")) {
+        rc = fwd_problem(&adj, p);
+        ws = false;
+    } else if (is("deconv2x2s2_wgrad")) {
+        mode = WGRAD;
+        rc = wgrad_problem(&adj, p, shape);
+    } else {
+        MRCNN_REQUIRE(false, "conv_gemm_plan: unknown entry '%s'", entry);
+    }
+    if (rc) return rc;
+    if (mode != WGRAD) shape = gemm_shape(p, mode, ws);
+    shape.has_ws = ws;
+    const GemmPlan plan = mode == WGRAD ? plan_wgrad(shape, g_knobs) : plan_gemm(shape, g_knobs);
+
+    static const char *const modes[] = {"FWD", "DGRAD", "WGRAD"};
+    static const char *const outs[] = {"OUT_PLAIN", "OUT_STRIDED", "OUT_DECONV"};
+    static const char *const variants[] = {"general", "PW", "K3", "WPERM", "W8"};
+    int at = snprintf(out, (size_t)out_len, "label=%s mode=%s M=%d N=%d k=%lld", plan.label, modes[mode], p.M, p.N,
+                      (long long)plan.k_extent);
+    for (int i = 0; i < plan.n && at < out_len; ++i) {
+        const GemmLaunch &l = plan.launch[i];
+        const bool w8 = l.tile == kW8BM;
+        at += snprintf(out + at, (size_t)(out_len - at),
+                       " | kind=conv_gemm_kernel<%d,%d,%s%s> tags=%s,%dx%d,%s,%s,%s%s%s rows=%d:%d grid=%lldx%d slab=%d "
+                       "tail=%d,%d,%d,%d",
+                       w8 ? 2 : l.tile / 64, w8 ? 2 : l.tile / 64, modes[mode], w8 ? ",W8" : "", modes[mode], l.tile,
+                       w8 ? kW8BN : l.tile, outs[p.out_mode], l.inst.split ? "split" : "fp32", variants[l.inst.variant],
+                       mode != WGRAD && p.perm_n > 0 ? ",perm" : "", mode != WGRAD && p.stem ? ",stem" : "", l.m_lo,
+                       l.m_hi, (long long)l.grid_x, l.grid_y, l.split_len, l.tail_first, l.tail_row0, l.tail_splits,
+                       l.tail_split_len);
+    }
+    if (plan.sum_splits && at < out_len)
+        at += snprintf(out + at, (size_t)(out_len - at), " | sum row0=%d slabs=%d", plan.sum_row0, plan.sum_splits);
+    MRCNN_REQUIRE(at < out_len, "conv_gemm_plan: the plan needs %d bytes, the buffer has %d", at + 1, out_len);
+    return 0;
 }
 
 #include "conv_winograd.h"

@@ -420,6 +420,18 @@ int64_t mrcnn_deconv2x2s2_wgrad_workspace_bytes(int N, int H, int W, int C, int 
 int mrcnn_deconv2x2s2_wgrad(const float *x, const float *gy, float *gw,
                             int N, int H, int W, int C, int K, void *ws,
                             void *stream);
+/* How the GEMM entry point mrcnn_<entry> would cut the call of descriptor d into kernel launches under
+ * the knobs currently set, as one line of text in `out`; no device is touched and no pointer needed
+ * (has_ws: the call would pass a split-K workspace).  entry: "conv2d_fwd", "conv_stem_fwd" (N, H, W, K
+ * of d), "conv2d_dgrad", "conv2d_dgrad_ex", "conv2d_dgrad_wt" (either with the suffix "+res_g": the
+ * call has a residual gradient), "conv2d_wgrad", "conv2d_wgrad_ex", and the "deconv2x2s2_*" entries, for
+ * which d carries the input map (N, H, W, C) and K.  The line names the branch of the policy
+ * (csrc/conv_gemm_plan.h) and, per GEMM launch, the kernel instantiation, the row range, the grid,
+ * the K-slab depth and the fused-tail fields, then the slab sum if there is one.  The descriptor
+ * checks are those of the entry point; an unknown entry, a rejected descriptor or a short buffer
+ * returns non-zero. */
+int mrcnn_conv_gemm_plan(const char *entry, const mrcnn_conv_desc *d, int has_ws, char *out,
+                         int out_len);
 
 /* ReLU / affine backward helper: g[m,c] = gy[m,c] * (y[m,c] > 0) * scale[c]
  * (scale NULL = 1; y NULL = no mask).  Backward of the fused conv epilogue. */

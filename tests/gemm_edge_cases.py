@@ -1,5 +1,6 @@
 """Degenerate and tile-edge shapes of the convolution GEMM family (csrc/conv_gemm.hip): the case
-lists of tests/test_gpu_gemm_edges.py and a restatement of the host launch policy.
+lists of tests/test_gpu_gemm_edges.py and a restatement of the host launch policy
+(csrc/conv_gemm_plan.h).
 
 Plain Python, importable without a device.  tests/test_gemm_edge_cases_cpu.py checks the lists
 (coverage of the policy's branches and of the kernel instantiations, size caps), the float64
@@ -10,9 +11,14 @@ Everything the kernels read is seeded N(0, 1) (filters scaled by 1 / sqrt(C R S)
 repeated rows or columns, so a dropped, duplicated or shifted K element, row, column or tap moves
 the result by orders of magnitude more than the bound.
 
-``route(entry, desc, flags, has_ws, knobs)`` restates conv_gemm.hip's decision tree on
-(M, N, Kc, R S, knobs).  The device test holds it to the C++ through the profiler: the GEMM launch
-counts per profiler kind of every case must equal ``Route.record``.
+``route(entry, desc, flags, has_ws, knobs)`` restates the decision tree of csrc/conv_gemm_plan.h on
+(M, N, Kc, R S, knobs), written by hand from the policy's description and not generated from the C++.
+Two things hold it to the C++.  Without a device, tests/test_gemm_edge_cases_cpu.py asks the library
+for its plan of the same call (mrcnn_conv_gemm_plan: the planner the entry points run, as text) and
+compares the branch label and the kernel instantiation of every launch, on every call of the lists
+and on a dense sweep of shapes; the plan's row ranges, grids and slab depths are checked for
+consistency there.  On the device, tests/test_gpu_gemm_edges.py counts the launches the profiler
+records per kind: they must equal ``Route.record``.
 """
 import collections
 import itertools
@@ -149,13 +155,13 @@ def can_split_rows(p):
 # The clamp is unreachable at the default knobs for every problem the entry points accept; each
 # caller bounds tiles x slabs before it gets here (a 64x64 tile of a slab is 16 KiB, a 128x128 one
 # 64 KiB, the workspace 192 MiB = 12288 / 3072 of them):
-#   launch(), one-round rule:   T x fit <= 512 tiles of 128x128                    = 32 MiB
-#   launch(), big_split_k > 0:  T < big_min_tiles = 384, <= 8 slabs: 383 x 8 x 64 KiB = 191.5 MiB
-#   launch_small, tiny split:   T <= 128 tiles of 64x64, <= 16 slabs                 = 32 MiB
-#   launch_small, leftover:     two slabs need < 256 leftover tiles, tiles x slabs < 512:  8 MiB
-#   launch_fused_tail (64x64):  < 154 tail tiles x 16 slabs                         = 38.5 MiB
-#   launch_fused_tail (128x128) and launch_remainder: two slabs need < 512 tail tiles and then
-#                               tiles x slabs < 1024 tiles                  <= 64 MiB / 16 MiB
+#   plan_gemm(), one-round rule:   T x fit <= 512 tiles of 128x128                    = 32 MiB
+#   plan_gemm(), big_split_k > 0:  T < big_min_tiles = 384, <= 8 slabs: 383 x 8 x 64 KiB = 191.5 MiB
+#   add_small(), tiny split:       T <= 128 tiles of 64x64, <= 16 slabs                 = 32 MiB
+#   add_small(), leftover:         two slabs need < 256 leftover tiles, tiles x slabs < 512:  8 MiB
+#   add_fused_tail() (64x64):      < 154 tail tiles x 16 slabs                         = 38.5 MiB
+#   add_fused_tail() (128x128) and add_remainder(): two slabs need < 512 tail tiles and then
+#                                  tiles x slabs < 1024 tiles                  <= 64 MiB / 16 MiB
 # (reachable only with big_min_tiles raised above 384 or small_m_split >= 24).  No case is invented
 # for it; route() still applies it.
 def fit_ws(splits, rows, N):
@@ -169,12 +175,12 @@ def k_splits(total_slices, depth_div, target_wgs, tiles, rows, N, cap):
     return fit_ws(min(cap, total_slices // depth_div, ceil_div(target_wgs, tiles)), rows, N)
 
 
-# launch_split_rows(): the slab count re-derived from the slab depth (one GEMM launch + slab sum)
+# add_split_rows(): the slab count re-derived from the slab depth (one GEMM launch + slab sum)
 def _split_rows(p, tm, knobs):
     return [(kind_name(tm, p.mode), instantiation(p, tm, knobs))]
 
 
-# launch_fused_tail(): whole tiles and the K-split pieces of the leftover rows in ONE launch
+# add_fused_tail(): whole tiles and the K-split pieces of the leftover rows in ONE launch
 def _fused_tail(p, tm, rows_main, knobs):
     BM = 64 * tm
     if (not knobs['fused_tail'] or not can_split_rows(p) or rows_main <= 0 or rows_main % BM != 0
@@ -186,14 +192,14 @@ def _fused_tail(p, tm, rows_main, knobs):
     return k_splits(p.total_slices, 4, target, tail_tiles, p.M - rows_main, p.N, 16) >= 2
 
 
-# launch_tiles(): a record only when the launch has blocks
+# add_tiles(): a record only when the launch has blocks
 def _tiles(p, tm, m_lo, m_hi, knobs):
     if ceil_div(m_hi - m_lo, 64 * tm) * ceil_div(p.N, 64 * tm) <= 0:
         return []
     return [(kind_name(tm, p.mode), instantiation(p, tm, knobs))]
 
 
-# launch_remainder(): the 64x64 remainder of a 128x128 launch, cut along K when it pays
+# add_remainder(): the 64x64 remainder of a 128x128 launch, cut along K when it pays
 def _remainder(p, rows_lo, knobs):
     left = ceil_div(p.M - rows_lo, 64) * ceil_div(p.N, 64)
     splits = k_splits(p.total_slices, 8, 512, left, p.M - rows_lo, p.N, 16)
@@ -202,7 +208,7 @@ def _remainder(p, rows_lo, knobs):
     return 'split', _split_rows(p, 1, knobs)
 
 
-# launch_small(): 64x64 tiles
+# add_small(): 64x64 tiles
 def _launch_small(p, knobs):
     tm, tn = ceil_div(p.M, 64), ceil_div(p.N, 64)
     T = tm * tn
@@ -240,7 +246,7 @@ def _w8_ok(p, knobs):
     return p.N >= 128 and p.Kc >= _W8_MIN_K and tm * tn >= 768 and (p.M % 256 == 0 or p.M >= 16 * 256)
 
 
-# launch<MODE>(): the forward / DGRAD policy
+# plan_gemm(): the forward / DGRAD policy
 def _launch(p, knobs):
     tm, tn = ceil_div(p.M, 128), ceil_div(p.N, 128)
     T = tm * tn
@@ -294,7 +300,7 @@ def wgrad_splits(tiles, pixels, slots):
     return best
 
 
-# wgrad_impl(): M = Kout rows, N = R S C columns, K = pixels
+# plan_wgrad(): M = Kout rows, N = R S C columns, K = pixels
 def _wgrad(Kout, pixels, n_img, C, P, Q, R, S, stride, pad, has_ws, knobs):
     M, N = Kout, R * S * C
     big = ceil_div(M, 128) * ceil_div(N, 128)
@@ -514,7 +520,7 @@ WGRAD_BY_PIXELS = [('wgrad %d pixels (%s) Kout%d RSC%d' % (px, 'fewer than 8 sli
                                                            else 'splits allowed', Ko, C),
                     desc(1, C, 1, px, Ko)) for px in WGRAD_PIXELS for Ko in WGRAD_KOUT for C in WGRAD_RSC]
 # the WPERM gate: position-major pixel order needs C % 64 (64x64 tiles) / C % 128 (128x128 tiles, here
-# under big_min_tiles = 1), >= 64 images (choose_perm; wgrad_impl's own N >= 32 is implied) and <= 256 positions
+# under big_min_tiles = 1), >= 64 images (choose_perm; plan_wgrad()'s own N >= 32 is implied) and <= 256 positions
 WGRAD_WPERM = [
     ('wperm64: C%64 == 0, 64 images', desc(64, 64, 2, 2, 4, 3, 3, 1, 1), {}, 'wgrad/wperm64'),
     ('no wperm: C=96, C%64 != 0', desc(64, 96, 2, 2, 4, 3, 3, 1, 1), {}, 'wgrad64/one_slab'),

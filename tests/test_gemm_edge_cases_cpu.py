@@ -2,8 +2,12 @@
 coverage of the launch policy's branches and of the kernel instantiations, the float64 references
 of tests/launch_ref.py at the degenerate geometries of the lists, the comparison of
 tests/test_gpu_gemm_edges.py on emulated kernels (right, and wrong the way each edge goes wrong),
-and the size caps."""
+the size caps, and the library's own launch plan (mrcnn_conv_gemm_plan: no device touched) against
+route() on every listed call and on a dense sweep of shapes."""
 import collections
+import contextlib
+import ctypes
+import itertools
 
 import numpy as np
 import pytest
@@ -377,3 +381,152 @@ def test_detector_strided_scatter_needs_exact_zeros():
     assert _accepts(got, ref) and bool((got[between] == 0).all())
     got[0, 0, 1, 1] = 1e-7 * float(ref.abs().max())
     assert _accepts(got, ref) and not bool((got[between] == 0).all())
+
+
+# ---- the library's launch plan (csrc/conv_gemm_plan.h) against route() -----------------------------
+# mrcnn_conv_gemm_plan prints what an entry point would launch for a descriptor under the knobs set, and
+# touches no device: label and instantiations are compared with route(), and every plan is checked for
+# what a launch count cannot show: row ranges, grids, slab depths and the workspace.
+
+Plan = collections.namedtuple('Plan', 'label mode M N k launches sum')
+PlanLaunch = collections.namedtuple('PlanLaunch', 'kind tags rows grid slab tail')
+
+
+@pytest.fixture(scope='module')
+def lib():
+    import __graft_entry__ as g
+    g.build()
+    from chainer_mask_rcnn_amd import _lib
+    return _lib.load()
+
+
+@contextlib.contextmanager
+def _knobs(kn):
+    from chainer_mask_rcnn_amd import _lib
+    try:
+        for k, v in kn.items():
+            _lib.set_tuning(k, v)
+        yield
+    finally:
+        for k, v in G.DEFAULT_KNOBS.items():
+            _lib.set_tuning(k, v)
+
+
+def _plan_line(lib, entry, d, has_ws, size=1024):
+    from chainer_mask_rcnn_amd._lib import ConvDesc
+    buf = ctypes.create_string_buffer(size)
+    cd = ConvDesc(d.N, d.H, d.W, d.C, d.K, d.R, d.S, d.stride, d.pad, d.P, d.Q)
+    rc = lib.mrcnn_conv_gemm_plan(entry.encode(), ctypes.byref(cd), int(has_ws), buf, size)
+    return rc, buf.value.decode()
+
+
+def _ints(text, sep):
+    return tuple(int(v) for v in text.split(sep))
+
+
+def _plan(lib, entry, d, has_ws):
+    rc, line = _plan_line(lib, entry, d, has_ws)
+    assert rc == 0, (entry, d, lib.mrcnn_last_error())
+    parts = [dict(f.split('=', 1) for f in part.split() if '=' in f) for part in line.split(' | ')]
+    head, rest = parts[0], parts[1:]
+    total = None
+    if rest and 'slabs' in rest[-1]:
+        total = (int(rest[-1]['row0']), int(rest[-1]['slabs']))
+        rest = rest[:-1]
+    launches = [PlanLaunch(f['kind'], tuple(f['tags'].split(',')), _ints(f['rows'], ':'), _ints(f['grid'], 'x'),
+                           int(f['slab']), _ints(f['tail'], ',')) for f in rest]
+    return Plan(head['label'], head['mode'], int(head['M']), int(head['N']), int(head['k']), launches, total)
+
+
+def _check_consistent(p, what):
+    """Row ranges tile [0, M); grid.x is the tile count of the range (plus the pieces of a fused tail);
+    slabs x slab depth cover the K extent with a non-empty last slab; the slabs fit their workspace."""
+    at, summed = 0, None
+    assert 1 <= len(p.launches) <= 2, what
+    for l in p.launches:
+        lo, hi = l.rows
+        assert lo == at and hi > lo, (what, l)
+        at = hi
+        bm, bn = (256, 128) if l.tags[1] == '256x128' else (int(l.tags[1].split('x')[0]),) * 2
+        tn = G.ceil_div(p.N, bn)
+        first, row0, pieces, depth = l.tail
+        if pieces:
+            assert lo < row0 < hi and (row0 - lo) % bm == 0 and first == (row0 - lo) // bm * tn, (what, l)
+            assert l.grid == (first + G.ceil_div(hi - row0, bm) * tn * pieces, 1) and l.slab == 0, (what, l)
+            assert pieces >= 2 and (pieces - 1) * depth < p.k <= pieces * depth, (what, l)
+            assert pieces * (hi - row0) * p.N * 4 <= G.SPLIT_WS_BYTES, (what, l)
+            summed = (row0, pieces)
+        else:
+            assert l.grid[0] == G.ceil_div(hi - lo, bm) * tn and l.tail == (0, 0, 0, 0), (what, l)
+        if l.slab:
+            assert (l.grid[1] - 1) * l.slab < p.k <= l.grid[1] * l.slab, (what, l)
+            if p.mode == G.WGRAD:
+                # the workspace of mrcnn_conv2d_wgrad_workspace_bytes holds 64 slabs of the whole gradient
+                assert l.grid[1] <= 64 and l.slab % G.BK == 0, (what, l)
+                summed = (0, l.grid[1]) if l.grid[1] > 1 else None
+            else:
+                assert l.grid[1] * (hi - lo) * p.N * 4 <= G.SPLIT_WS_BYTES, (what, l)
+                summed = (lo, l.grid[1])
+        else:
+            assert l.grid[1] == 1, (what, l)
+    assert at == p.M and p.sum == summed, (what, p)
+
+
+def _check_against_route(lib, entry, d, has_ws, kn, what):
+    r = G.route(entry, d, 0, has_ws, kn)
+    p = _plan(lib, entry, d, has_ws)
+    assert (p.label, [(l.kind, l.tags) for l in p.launches]) == (r.label, r.launches), (what, p, r)
+    _check_consistent(p, what)
+    return p.label
+
+
+def test_plan_equals_route_on_every_listed_call(lib):
+    for fam, i, entry, d, ws, kn in _calls():
+        with _knobs(kn):
+            _check_against_route(lib, entry, d, ws, kn, i)
+    for i, entry, d, kn, label in G.policy_cases():
+        with _knobs(kn):
+            assert _check_against_route(lib, entry, d, True, kn, i) == label, i
+
+
+def test_plan_rejects_what_the_entry_points_reject(lib):
+    """The two '+res_g' entries name a call with a residual gradient, which the strided forms refuse."""
+    for i, entry, d in G.REJECTED:
+        rc, _ = _plan_line(lib, entry, d, True)
+        assert rc != 0 and lib.mrcnn_last_error(), i
+    ok = G.desc(2, 8, 3, 3, 8, 3, 3, 1, 1)
+    for entry in G.ENTRIES:
+        assert _plan_line(lib, entry, ok if 'deconv' not in entry else G.DECONV[0][1], True)[0] == 0, entry
+    rc, _ = _plan_line(lib, 'conv2d_bwd', ok, True)
+    assert rc != 0 and b'unknown entry' in lib.mrcnn_last_error()
+    rc, _ = _plan_line(lib, 'conv2d_fwd+res_g', ok, True)
+    assert rc != 0 and b'unknown entry' in lib.mrcnn_last_error()
+    rc, _ = _plan_line(lib, 'conv2d_fwd', ok, True, size=40)
+    assert rc != 0 and b'buffer' in lib.mrcnn_last_error()
+
+
+# rows 64 k + 1 and 64 k: the policy reads the row count through its tile counts and through M % 256
+SWEEP_K = (1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 134, 135, 153, 154, 255, 256,
+           257, 383, 384, 385, 511, 512, 513, 767, 768, 769, 1023, 1024, 1025, 1093)
+SWEEP_ENTRIES = ('conv2d_fwd', 'conv2d_dgrad_ex', 'conv2d_dgrad_wt', 'conv2d_wgrad_ex')
+# full-size shapes the comments of conv_gemm_plan.h name: the batch-2 res4 3x3 layer and the 1x1 behind it,
+# the head's fused cls_loc / score layer (1024 x 408 x 2048), a 50 176-row 1x1 layer of the RoI head (W8)
+FULL_SIZE = (G.desc(2, 256, 51, 84, 256, 3, 3, 1, 1), G.desc(2, 1024, 51, 84, 256), G.desc(1024, 2048, 1, 1, 408),
+             G.desc(1024, 2048, 7, 7, 512))
+
+
+def test_plan_equals_route_on_a_dense_sweep_at_the_default_knobs(lib):
+    seen = collections.Counter()
+    with _knobs({}):
+        for entry in SWEEP_ENTRIES:
+            for d in FULL_SIZE:
+                seen[_check_against_route(lib, entry, d, True, {}, (entry, d))] += 1
+            for k, ragged, cols, depth, rs in itertools.product(SWEEP_K, (1, 0), (68, 132, 256, 512, 1024, 2048),
+                                                                (32, 256, 1024, 2048), (1, 9)):
+                d = G._policy_desc(entry, 64 * k + ragged, cols, depth, rs)
+                seen[_check_against_route(lib, entry, d, True, {}, (entry, d))] += 1
+    assert seen['w8'] > 0                                  # which no listed call reaches
+    assert G.route('conv2d_fwd', FULL_SIZE[3]).label == 'w8'
+    for label in ('small/plain', 'small/tiny_split', 'small/fused_tail', 'big/one_round_ksplit', 'big/all_rows',
+                  'big/fused_tail', 'wgrad64/one_slab', 'wgrad64/split+reduce', 'wgrad128/split+reduce'):
+        assert seen[label] > 0, label

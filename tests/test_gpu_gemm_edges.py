@@ -13,8 +13,8 @@ finds it.  Two more things are held:
   must come back bit-identical (gemm_edge_cases.Guarded).
 * the launch policy.  Around every case the profiler counts launches per kind; the GEMM counts must
   equal what gemm_edge_cases.route() predicts for the calls the case made.  That holds the Python
-  restatement of launch<MODE> / launch_small / launch_remainder / launch_fused_tail / wgrad_impl to
-  the C++ it restates (the Winograd entry points have a policy of their own and are not predicted).
+  restatement of the launch policy (csrc/conv_gemm_plan.h: plan_gemm / plan_wgrad) to what the
+  library launches (the Winograd entry points have a policy of their own and are not predicted).
 
 Tiny cases are grouped into loops, one test per family and axis, with the case id in the message.
 """
