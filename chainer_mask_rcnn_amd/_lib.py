@@ -164,6 +164,8 @@ SIGNATURES = {
     'mrcnn_mask_pack': (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mrcnn_paste_masks_packed': (c_int, [c_vp, c_vp, c_vp] + [c_int] * 5 + [c_vp] * 4),
     'mrcnn_mask_intersect': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp] + [c_int] * 3 + [c_vp, c_vp]),
+    'mrcnn_mask_boundary_workspace_bytes': (c_i64, [c_int] * 3),
+    'mrcnn_mask_boundary': (c_int, [c_vp, c_vp] + [c_int] * 4 + [c_vp, c_vp, c_vp, c_i64, c_vp]),
     'mrcnn_box_iou_voc': (c_int, [c_vp] * 5 + [c_int] * 3 + [c_i64, c_vp, c_vp]),
     'mrcnn_box_iou_coco': (c_int, [c_vp] * 6 + [c_int] * 3 + [c_i64, c_vp, c_vp]),
     'mrcnn_rle_encode': (c_int, [c_vp, c_vp] + [c_int] * 3 + [c_vp] * 4 + [c_int, c_vp, c_vp,

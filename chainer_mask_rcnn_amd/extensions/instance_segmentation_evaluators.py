@@ -18,6 +18,13 @@ rule).  The ground-truth boxes are whatever the dataset puts in the example, whi
 chainercv's detection evaluators are fed: for this project's COCO dataset that is the mask's tight
 box, not the annotation's ``bbox``.  ``('bbox',)`` alone skips the paste,
 pack and intersect work and reports only the ``bbox/`` keys.
+
+``'boundary'`` in ``iou_types`` adds Boundary AP (Cheng et al., CVPR 2021) under
+``validation/main/boundary/...``: the boundaries of the packed predictions and ground truth are cut
+on the device (``masks.boundary_packed``, erosion distance ``boundary_dilation_ratio`` of the image
+diagonal), intersected by the same kernel and carried in the same read-back; the matching runs on
+min(mask IoU, boundary IoU).  The masks are pasted, packed and intersected
+for it even without ``'segm'``.
 """
 import copy
 
@@ -55,15 +62,19 @@ class _InstanceSegmentationEvaluator(object):
     results_sink = None
     box_convention = None     # 'voc' | 'coco': boxes.queue_box_ious' convention
 
-    def __init__(self, iterator, target, label_names=None, iou_types=('segm',)):
+    IOU_TYPES = ('segm', 'bbox', 'boundary')
+
+    def __init__(self, iterator, target, label_names=None, iou_types=('segm',),
+                 boundary_dilation_ratio=0.02):
         self.iterator = iterator
         self.target = target
         self.label_names = label_names
         iou_types = (iou_types,) if isinstance(iou_types, str) else tuple(iou_types)
-        if not iou_types or any(t not in ('segm', 'bbox') for t in iou_types):
-            raise ValueError("iou_types: a non-empty subset of ('segm', 'bbox'), got %r"
-                             % (iou_types,))
+        if not iou_types or any(t not in self.IOU_TYPES for t in iou_types):
+            raise ValueError("iou_types: a non-empty subset of %r, got %r"
+                             % (self.IOU_TYPES, iou_types))
         self.iou_types = iou_types
+        self.boundary_dilation_ratio = boundary_dilation_ratio
 
     def __call__(self, trainer=None):
         return self.evaluate()
@@ -89,12 +100,19 @@ class _InstanceSegmentationEvaluator(object):
 
         With ``'bbox'`` in ``iou_types`` a fifth list follows, the images' box IoU records: the
         float32 (P, G) table (VOC evaluator) or ``(iou float64 (P,G), dt_area (P,), gt_box_area
-        (G,))`` (COCO evaluator).  Without ``'segm'`` every counts[i] is None."""
+        (G,))`` (COCO evaluator).  Without ``'segm'`` every counts[i] is None.
+
+        With ``'boundary'`` in ``iou_types`` six lists come back: the fifth as above (every
+        box_ious[i] None without ``'bbox'``), the sixth the boundaries' counts, boundary_counts[i] =
+        (inter (P,G), pred boundary area (P,), gt boundary area (G,)); counts[i] is then always
+        filled, as the matching takes the minimum of the two IoUs."""
         target = self.target
         sink = self.results_sink
-        segm, bbox = 'segm' in self.iou_types, 'bbox' in self.iou_types
+        bbox, boundary = 'bbox' in self.iou_types, 'boundary' in self.iou_types
+        segm = 'segm' in self.iou_types or boundary      # the masks are needed
         n_seen = 0
         counts, pred_labels, pred_scores, gts, box_ious = [], [], [], [], []
+        boundary_counts = []
         for batch in _batches(self.iterator):
             batch = list(batch)
             if not batch:
@@ -115,8 +133,11 @@ class _InstanceSegmentationEvaluator(object):
                                      % (tuple(gt_mask.shape), (H, W)))
                 pred = M.paste_packed(roi_masks[j], labels[j], bboxes[j], (H, W))
                 gt = M.pack_masks(gt_mask, device=dev)
-                inter = M.queue_intersections(pred, gt, W)
-                queued.append((inter, pred[1], gt[1]))
+                if boundary:
+                    queued.append(M.queue_mask_and_boundary_counts(
+                        pred, gt, (H, W), self.boundary_dilation_ratio))
+                else:
+                    queued.append((M.queue_intersections(pred, gt, W), pred[1], gt[1]))
                 if sink is not None:          # the packed masks just intersected, encoded
                     encodes.append(rle.queue_encode(pred[0], pred[1], pred[2], (H, W)))
             parts = [t.reshape(-1).to(torch.int64) for q in queued for t in q]
@@ -145,6 +166,9 @@ class _InstanceSegmentationEvaluator(object):
                     c_ga = host[o:o + G]
                     o += G
                     counts.append((c_inter, c_pa, c_ga))
+                    if boundary:
+                        triple, o = M.take_counts(host, o, P, G)
+                        boundary_counts.append(triple)
                 else:
                     counts.append(None)
                 pred_labels.append(l)
@@ -157,16 +181,22 @@ class _InstanceSegmentationEvaluator(object):
                 tables = B.split_tables(tail, shapes)
                 box_ious.extend(tables if areas is None else
                                 [(t,) + a for t, a in zip(tables, areas)])
+            else:
+                box_ious.extend([None] * len(batch))
+        if boundary:
+            return counts, pred_labels, pred_scores, gts, box_ious, boundary_counts
         if bbox:
             return counts, pred_labels, pred_scores, gts, box_ious
         return counts, pred_labels, pred_scores, gts
 
-    def _prefixed(self, report):
-        return {'bbox/' + k: v for k, v in report.items()}
+    def _prefixed(self, report, prefix='bbox/'):
+        return {prefix + k: v for k, v in report.items()}
 
-    def _check_records(self, box_ious):
-        if 'bbox' in self.iou_types and box_ious is None:
+    def _check_records(self, box_ious, boundary_counts=None):
+        if 'bbox' in self.iou_types and (box_ious is None or any(b is None for b in box_ious)):
             raise ValueError("iou_types has 'bbox' but the records carry no box IoU tables")
+        if 'boundary' in self.iou_types and boundary_counts is None:
+            raise ValueError("iou_types has 'boundary' but the records carry no boundary counts")
 
 
 class InstanceSegmentationVOCEvaluator(_InstanceSegmentationEvaluator):
@@ -178,17 +208,18 @@ class InstanceSegmentationVOCEvaluator(_InstanceSegmentationEvaluator):
     box_convention = 'voc'
 
     def __init__(self, iterator, target, use_07_metric=False, label_names=None,
-                 iou_types=('segm',)):
-        super(InstanceSegmentationVOCEvaluator, self).__init__(iterator, target, label_names,
-                                                               iou_types)
+                 iou_types=('segm',), boundary_dilation_ratio=0.02):
+        super(InstanceSegmentationVOCEvaluator, self).__init__(
+            iterator, target, label_names, iou_types, boundary_dilation_ratio)
         self.use_07_metric = use_07_metric
 
     def evaluate(self):
         return self.evaluate_collected(*self.collect())
 
-    def evaluate_collected(self, counts, pred_labels, pred_scores, gts, box_ious=None):
+    def evaluate_collected(self, counts, pred_labels, pred_scores, gts, box_ious=None,
+                           boundary_counts=None):
         """The host half of ``evaluate``: matching and AP from ``collect()``'s records."""
-        self._check_records(box_ious)
+        self._check_records(box_ious, boundary_counts)
         gt_labels = [g[1] for g in gts]
         gt_difficults = None
         if gts and len(gts[0]) == 4:
@@ -204,6 +235,11 @@ class InstanceSegmentationVOCEvaluator(_InstanceSegmentationEvaluator):
                                                         gt_labels, gt_difficults)
             ap = matching.calc_detection_voc_ap(prec, rec, use_07_metric=self.use_07_metric)
             report.update(self._prefixed(voc_report(ap, self.label_names)))
+        if 'boundary' in self.iou_types:
+            prec, rec = matching.voc_prec_rec_from_boundary_counts(
+                counts, boundary_counts, pred_labels, pred_scores, gt_labels, gt_difficults)
+            ap = matching.calc_detection_voc_ap(prec, rec, use_07_metric=self.use_07_metric)
+            report.update(self._prefixed(voc_report(ap, self.label_names), 'boundary/'))
         return self._observation(report)
 
 
@@ -216,8 +252,9 @@ class InstanceSegmentationCOCOEvaluator(_InstanceSegmentationEvaluator):
     segmentations)`` called for the i-th evaluated image with its detections and their masks as
     COCO compressed RLE (``utils.evaluations.coco_results.ResultsWriter`` writes a results
     file).  The packed masks that are intersected are the ones encoded, on the device; only the
-    strings come back, in one more read-back per batch.  Without ``'segm'`` in ``iou_types`` the
-    sink gets ``segmentations=None`` (bbox-only entries).
+    strings come back, in one more read-back per batch.  With ``iou_types=('bbox',)`` alone, which
+    pastes no masks, the sink gets ``segmentations=None`` (bbox-only entries); with ``'boundary'``
+    it still gets the masks, never the boundaries.
 
     With ``'bbox'`` in ``iou_types``: ``validation/main/bbox/map``, ``bbox/map@0.5``,
     ``bbox/map@0.75`` and ``bbox/ap/<name>``: pycocotools' iouType 'bbox' on the predicted boxes
@@ -227,17 +264,18 @@ class InstanceSegmentationCOCOEvaluator(_InstanceSegmentationEvaluator):
     box_convention = 'coco'
 
     def __init__(self, iterator, target, label_names=None, results_sink=None,
-                 iou_types=('segm',)):
-        super(InstanceSegmentationCOCOEvaluator, self).__init__(iterator, target, label_names,
-                                                                iou_types)
+                 iou_types=('segm',), boundary_dilation_ratio=0.02):
+        super(InstanceSegmentationCOCOEvaluator, self).__init__(
+            iterator, target, label_names, iou_types, boundary_dilation_ratio)
         self.results_sink = results_sink
 
     def evaluate(self):
         return self.evaluate_collected(*self.collect())
 
-    def evaluate_collected(self, counts, pred_labels, pred_scores, gts, box_ious=None):
+    def evaluate_collected(self, counts, pred_labels, pred_scores, gts, box_ious=None,
+                           boundary_counts=None):
         """The host half of ``evaluate``: matching and AP from ``collect()``'s records."""
-        self._check_records(box_ious)
+        self._check_records(box_ious, boundary_counts)
         gt_labels = [g[1] for g in gts]
         gt_crowdeds = gt_areas = None
         if gts and len(gts[0]) == 5:
@@ -252,26 +290,36 @@ class InstanceSegmentationCOCOEvaluator(_InstanceSegmentationEvaluator):
             result = matching.coco_results(matching.coco_evaluate_from_ious(
                 box_ious, pred_labels, pred_scores, gt_labels, gt_crowdeds, gt_areas))
             report.update(self._prefixed(coco_report(result, self.label_names)))
+        if 'boundary' in self.iou_types:
+            result = matching.coco_results(matching.coco_evaluate_from_boundary_counts(
+                counts, boundary_counts, pred_labels, pred_scores, gt_labels, gt_crowdeds,
+                gt_areas))
+            report.update(self._prefixed(coco_report(result, self.label_names), 'boundary/'))
         return self._observation(report)
 
 
-def strip_records(counts, pred_labels, pred_scores, gts, box_ious=None):
+def strip_records(counts, pred_labels, pred_scores, gts, box_ious=None, boundary_counts=None):
     """``collect()``'s records without what the host matching never reads: each ground-truth
     tuple keeps its length and its labels (and difficult / crowd / area) but loses the boxes and
-    masks, which are by far the largest part.  The box IoU records, when present, stay whole."""
+    masks, which are by far the largest part.  The box IoU records and the boundary counts, when
+    present, stay whole."""
     gts = [(None, g[1], None) + tuple(g[3:]) for g in gts]
     out = (list(counts), list(pred_labels), list(pred_scores), gts)
+    if boundary_counts is not None:
+        box_ious = [None] * len(gts) if box_ious is None else box_ious
+        return out + (list(box_ious), list(boundary_counts))
     return out if box_ious is None else out + (list(box_ious),)
 
 
 def merge_records(per_rank):
     """Concatenate the ranks' records (each ``(counts, pred_labels, pred_scores, gts[,
-    box_ious])``) in rank order, which is the test set's order when rank i holds the i-th
+    box_ious[, boundary_counts]])``) in rank order, which is the test set's order when rank i holds the i-th
     contiguous shard."""
     per_rank = list(per_rank)
     widths = set(len(r) for r in per_rank)
     if len(widths) > 1:
-        raise ValueError('records with and without box IoU tables cannot be merged')
+        raise ValueError('records with and without box IoU tables or boundary counts cannot be '
+                         'merged')
     merged = tuple([] for _ in range(widths.pop() if widths else 4))
     for records in per_rank:
         for out, part in zip(merged, records):

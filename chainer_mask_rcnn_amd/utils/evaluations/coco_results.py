@@ -98,10 +98,10 @@ def _check_bbox(k, e):
 
 def _load(results, dataset, iou_type='segm'):
     """load_results with each entry's position in the file: image_id -> [(k, entry), ...]."""
-    if iou_type not in ('segm', 'bbox'):
-        raise ValueError("iou_type must be 'segm' or 'bbox', got %r" % (iou_type,))
+    if iou_type not in ('segm', 'bbox', 'boundary'):
+        raise ValueError("iou_type must be 'segm', 'bbox' or 'boundary', got %r" % (iou_type,))
     needed = ('image_id', 'category_id', 'score') + (
-        ('segmentation',) if iou_type == 'segm' else ('bbox',))
+        ('bbox',) if iou_type == 'bbox' else ('segmentation',))
     if isinstance(results, str):
         with open(results) as f:
             results = json.load(f)
@@ -151,7 +151,7 @@ def load_results(results, dataset, iou_type='segm'):
     list of the image's size.  ``bbox`` is optional (Detectron's segmentation results have
     none); polygons are refused, as pycocotools' ``loadRes`` refuses them for segm results.
     With ``iou_type='bbox'`` an entry needs ``bbox`` ([x, y, w, h] numbers) instead and need not
-    have a ``segmentation``."""
+    have a ``segmentation``; ``'boundary'`` reads what ``'segm'`` reads."""
     return OrderedDict((i, [e for _, e in v])
                        for i, v in _load(results, dataset, iou_type).items())
 
@@ -181,7 +181,8 @@ def _eval_bbox_results(grouped, dataset, n, label_names):
             for k, v in coco_report(result, label_names).items()}
 
 
-def eval_coco_results(results, dataset, limit=None, label_names=None, iou_type='segm'):
+def eval_coco_results(results, dataset, limit=None, label_names=None, iou_type='segm',
+                      dilation_ratio=0.02):
     """Score a results file (path or list of entries) against ``dataset`` (a
     COCOInstanceSegmentationDataset; its images in order, the first ``limit`` when given; an
     image without entries has no detections).  Each image's segmentations are decoded in one
@@ -191,7 +192,12 @@ def eval_coco_results(results, dataset, limit=None, label_names=None, iou_type='
 
     ``iou_type='bbox'``: the entries' ``bbox`` fields are scored against the boxes of
     ``dataset.get_annotations(i)`` (the masks' tight boxes) instead, and the evaluator's
-    ``validation/main/bbox/...`` keys come back; the entries need no ``segmentation``."""
+    ``validation/main/bbox/...`` keys come back; the entries need no ``segmentation``.
+
+    ``iou_type='boundary'``: the decoded segmentations and the ground truth are scored by Boundary
+    AP (boundaries cut on the device at ``dilation_ratio`` of the image diagonal, matching on
+    min(mask IoU, boundary IoU)) and the evaluator's ``validation/main/boundary/...`` keys come
+    back."""
     import torch
     from ...extensions.instance_segmentation_evaluators import coco_report
     grouped = _load(results, dataset, iou_type)
@@ -199,7 +205,8 @@ def eval_coco_results(results, dataset, limit=None, label_names=None, iou_type='
     if iou_type == 'bbox':
         return _eval_bbox_results(grouped, dataset, n, label_names)
     dev = M._device()
-    counts, pred_labels, pred_scores, gts = [], [], [], []
+    boundary = iou_type == 'boundary'
+    counts, boundary_counts, pred_labels, pred_scores, gts = [], [], [], [], []
     for i in range(n):
         img_id = dataset.img_ids[i]
         H, W = dataset.img_sizes[img_id]
@@ -208,16 +215,21 @@ def eval_coco_results(results, dataset, limit=None, label_names=None, iou_type='
         job = R.queue_decode([e['segmentation'] for e in entries], size=(H, W), device=dev)
         pred = job.packed
         gt_p = M.pack_masks(gt[2], device=dev)
-        inter = M.queue_intersections(pred, gt_p, W)
-        P, G = inter.shape
+        if boundary:
+            queued = M.queue_mask_and_boundary_counts(pred, gt_p, (H, W), dilation_ratio)
+        else:
+            queued = (M.queue_intersections(pred, gt_p, W), pred[1], gt_p[1])
+        P, G = queued[0].shape
         host = torch.cat([t.reshape(-1).to(torch.int64) for t in
-                          (job.status, inter, pred[1], gt_p[1])]).cpu().numpy()
+                          (job.status,) + tuple(queued)]).cpu().numpy()
         R.check_decoded(host[:P], ['results entry %d (image %r)' % (k, img_id)
                                    for k, _ in grouped.get(img_id, [])])
         o = P
         c_inter = host[o:o + P * G].reshape(P, G)
         o += P * G
         counts.append((c_inter, host[o:o + P], host[o + P:o + P + G]))
+        if boundary:
+            boundary_counts.append(M.take_counts(host, o + P + G, P, G)[0])
         pred_labels.append(np.array([dataset.cat_id_to_class_id[e['category_id']]
                                      for e in entries], np.int32))
         pred_scores.append(np.array([e['score'] for e in entries], np.float32))
@@ -227,6 +239,11 @@ def eval_coco_results(results, dataset, limit=None, label_names=None, iou_type='
     if gts and len(gts[0]) == 5:                      # as the evaluator: crowds and areas
         gt_crowdeds = [g[3] for g in gts]
         gt_areas = [g[4] for g in gts]
+    if boundary:
+        result = matching.coco_results(matching.coco_evaluate_from_boundary_counts(
+            counts, boundary_counts, pred_labels, pred_scores, gt_labels, gt_crowdeds, gt_areas))
+        return {'validation/main/boundary/%s' % k: v
+                for k, v in coco_report(result, label_names).items()}
     result = matching.coco_results(matching.coco_evaluate_from_counts(
         counts, pred_labels, pred_scores, gt_labels, gt_crowdeds, gt_areas))
     return {'validation/main/%s' % k: v for k, v in coco_report(result, label_names).items()}

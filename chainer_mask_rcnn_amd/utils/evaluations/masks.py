@@ -6,6 +6,8 @@ synchronises.  ``mask_iou`` is the reference's ``mask_iou`` (utils/evaluations/
 eval_instance_segmentation_voc.py) on top of them: the counts come from the device, the float64
 IoU is formed on the host.  There is no host fallback: a device is required.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -131,3 +133,110 @@ def mask_iou(mask_a, mask_b):
     if tuple(mask_a.shape[1:]) != tuple(mask_b.shape[1:]):
         raise ValueError
     return iou_from_counts(*mask_counts(mask_a, mask_b))
+
+
+# ---------------------------------------------------------------------------- Boundary IoU
+# Cheng et al., "Boundary IoU: Improving Object-Centric Image Segmentation Evaluation" (CVPR
+# 2021) as the boundary-iou-api computes it: the boundary of a mask is what an erosion by the
+# (2d+1) x (2d+1) square removes, with the outside of the image as background (DESIGN.md
+# section 22).  The erosion runs on the packed words (csrc/mask_boundary.hip).
+def boundary_dilation(size, dilation_ratio=0.02):
+    """The erosion distance d in pixels for an image of ``size`` (H, W): the image diagonal times
+    ``dilation_ratio``, rounded (Python's ``round``), at least 1."""
+    H, W = int(size[0]), int(size[1])
+    return max(int(round(dilation_ratio * math.sqrt(H ** 2 + W ** 2))), 1)
+
+
+def boundary_packed(packed_set, size, dilation_ratio=0.02, dilation=None):
+    """The boundary set ``(packed, area, extent)`` of a packed set of an image of ``size`` (H, W)
+    (queued, not synchronised).  ``dilation`` gives d directly instead of ``dilation_ratio``.
+    The boundary set shares the input's extent tensor: a mask's outermost pixels are always
+    boundary."""
+    packed, _, extent = packed_set
+    H, W = int(size[0]), int(size[1])
+    N = packed.shape[0]
+    if tuple(packed.shape[1:]) != (H, packed_words(W)):
+        raise ValueError('packed masks of shape %s for an image of size %s'
+                         % (tuple(packed.shape), (H, W)))
+    d = boundary_dilation((H, W), dilation_ratio) if dilation is None else int(dilation)
+    if d < 1:
+        raise ValueError('dilation must be >= 1, got %d' % d)
+    _lib.require_device(packed)
+    dev = packed.device
+    out = torch.empty_like(packed)
+    area = torch.empty((N,), dtype=torch.int32, device=dev)
+    if N == 0 or H == 0 or W == 0:
+        out.zero_()
+        area.zero_()
+        return out, area, extent
+    nbytes = _lib.load().mrcnn_mask_boundary_workspace_bytes(N, H, W)
+    ws = _lib.workspace(nbytes, dev, tag='mask_boundary')
+    _lib.call('mrcnn_mask_boundary', _lib.ptr(packed), _lib.ptr(extent), N, H, W, d,
+              _lib.ptr(out), _lib.ptr(area), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+    return out, area, extent
+
+
+def mask_to_boundary(masks, dilation_ratio=0.02, dilation=None):
+    """boundary_iou.utils.boundary_utils.mask_to_boundary for a set: (N, H, W) masks -> (N, H, W)
+    uint8 {0, 1} boundaries (a host array for a host array, a device tensor for a device
+    tensor).  Pack, boundary and unpack all run on the device."""
+    packed = pack_masks(masks)
+    N, H, W = packed[0].shape[0], int(masks.shape[1]), int(masks.shape[2])
+    out = torch.empty((N, H, W), dtype=torch.uint8, device=packed[0].device)
+    if N and H and W:
+        b = boundary_packed(packed, (H, W), dilation_ratio, dilation)
+        _lib.call('mrcnn_mask_unpack', _lib.ptr(b[0]), N, H, W, _lib.ptr(out), _lib.stream_ptr())
+    return out if isinstance(masks, torch.Tensor) else out.cpu().numpy()
+
+
+def queue_mask_and_boundary_counts(a, b, size, dilation_ratio=0.02, dilation=None):
+    """For packed sets a and b of an image of ``size``: the six device tensors (inter, area_a,
+    area_b, boundary inter, boundary area_a, boundary area_b), queued."""
+    W = int(size[1])
+    ba = boundary_packed(a, size, dilation_ratio, dilation)
+    bb = boundary_packed(b, size, dilation_ratio, dilation)
+    return (queue_intersections(a, b, W), a[1], b[1], queue_intersections(ba, bb, W), ba[1], bb[1])
+
+
+def take_counts(host, o, P, G):
+    """The (inter (P,G), area_a (P,), area_b (G,)) triple that starts at offset ``o`` of a flat
+    host buffer, and the offset behind it."""
+    end = o + P * G + P + G
+    return (host[o:o + P * G].reshape(P, G), host[o + P * G:o + P * G + P],
+            host[o + P * G + P:end]), end
+
+
+def fetch_counts(tensors, P, G):
+    """One read-back of device count tensors laid out (P*G, P, G) repeatedly -> a list of
+    (inter (P,G), area_a (P,), area_b (G,)) host int64 triples."""
+    host = torch.cat([t.reshape(-1).to(torch.int64) for t in tensors]).cpu().numpy()
+    out, o = [], 0
+    for _ in range(len(tensors) // 3):
+        triple, o = take_counts(host, o, P, G)
+        out.append(triple)
+    return out
+
+
+def mask_and_boundary_counts(mask_a, mask_b, dilation_ratio=0.02, dilation=None):
+    """``(mask_counts, boundary_counts)`` of two mask sets of the same image size from one
+    read-back: each ``(inter (P,G), area_a (P,), area_b (G,))`` host int64."""
+    if tuple(mask_a.shape[1:]) != tuple(mask_b.shape[1:]):
+        raise ValueError('mask sets of different image sizes: %s vs %s'
+                         % (tuple(mask_a.shape[1:]), tuple(mask_b.shape[1:])))
+    size = (int(mask_a.shape[1]), int(mask_a.shape[2]))
+    a = pack_masks(mask_a)
+    b = pack_masks(mask_b, device=a[0].device)
+    q = queue_mask_and_boundary_counts(a, b, size, dilation_ratio, dilation)
+    m, bd = fetch_counts(q, a[0].shape[0], b[0].shape[0])
+    return m, bd
+
+
+def boundary_counts(mask_a, mask_b, dilation_ratio=0.02, dilation=None):
+    """``mask_counts`` of the two sets' boundaries: (inter (P,G), area_a (P,), area_b (G,))."""
+    return mask_and_boundary_counts(mask_a, mask_b, dilation_ratio, dilation)[1]
+
+
+def boundary_iou(mask_a, mask_b, dilation_ratio=0.02, dilation=None):
+    """float64 (P, G) Boundary IoU of two (N, H, W) mask sets: |B_a & B_b| / |B_a | B_b|, 0 where
+    the boundaries do not meet.  The pure measure; Boundary AP matches on min(mask IoU, this)."""
+    return iou_from_counts(*boundary_counts(mask_a, mask_b, dilation_ratio, dilation))

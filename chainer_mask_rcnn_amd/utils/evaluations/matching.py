@@ -42,6 +42,20 @@ def voc_prec_rec_from_ious(ious, pred_labels, pred_scores, gt_labels, gt_difficu
                          iou_thresh)
 
 
+def voc_prec_rec_from_boundary_counts(counts, boundary_counts, pred_labels, pred_scores,
+                                      gt_labels, gt_difficults=None, iou_thresh=0.5):
+    """The VOC matching on min(mask IoU, boundary IoU) (Boundary AP): ``counts`` and
+    ``boundary_counts`` are the per-image ``(inter, pred_area, gt_area)`` of the masks and of
+    their boundaries."""
+    counts, boundary_counts = list(counts), list(boundary_counts)
+    if len(counts) != len(boundary_counts):
+        raise ValueError('Length of input iterables need to be same.')
+    tables = [np.minimum(iou_from_counts(*c), iou_from_counts(*b))
+              for c, b in zip(counts, boundary_counts)]
+    return _voc_prec_rec(tables, np.asarray, pred_labels, pred_scores, gt_labels, gt_difficults,
+                         iou_thresh)
+
+
 def _voc_prec_rec(tables, iou_of, pred_labels, pred_scores, gt_labels, gt_difficults, iou_thresh):
     """The VOC matching and accumulation; ``iou_of(tables[i])`` is image i's (P, G) IoU."""
     counts, pred_labels, pred_scores, gt_labels = (
@@ -256,6 +270,31 @@ def _iou_image(table, n_dt, n_gt):
     def ious(d_idx, g_idx, gc):
         return iou[d_idx][:, g_idx]
     return ious, np.asarray(dt_area, np.float64).ravel(), np.asarray(gt_area, np.float64).ravel()
+
+
+def _boundary_image(table, n_dt, n_gt):
+    """Image record of the boundary form: ``table`` = (mask counts, boundary counts); the lookup
+    is min(mask IoU, boundary IoU), the crowd rule applied to each before the min; the areas are
+    the masks'."""
+    mask_ious, pred_area, gt_area_px = _count_image(table[0], n_dt, n_gt)
+    boundary_ious, _, _ = _count_image(table[1], n_dt, n_gt)
+
+    def ious(d_idx, g_idx, gc):
+        return np.minimum(mask_ious(d_idx, g_idx, gc), boundary_ious(d_idx, g_idx, gc))
+    return ious, pred_area, gt_area_px
+
+
+def coco_evaluate_from_boundary_counts(counts, boundary_counts, pred_labels, pred_scores,
+                                       gt_labels, gt_crowdeds=None, gt_areas=None):
+    """COCOeval(gt, dt, 'boundary').evaluate() + accumulate() of the boundary-iou-api: the
+    loops of ``coco_evaluate_from_counts`` on min(mask IoU, boundary IoU).  ``boundary_counts``
+    are the per-image ``(inter, pred_area, gt_area_px)`` of the masks' boundaries; area ranges
+    use the masks' areas, as for 'segm'."""
+    counts, boundary_counts = list(counts), list(boundary_counts)
+    if len(counts) != len(boundary_counts):
+        raise ValueError('Length of input iterables need to be same.')
+    return _coco_evaluate(list(zip(counts, boundary_counts)), _boundary_image, pred_labels,
+                          pred_scores, gt_labels, gt_crowdeds, gt_areas)
 
 
 def coco_evaluate_from_counts(counts, pred_labels, pred_scores, gt_labels, gt_crowdeds=None,

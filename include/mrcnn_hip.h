@@ -652,6 +652,20 @@ int mrcnn_paste_masks_packed(const float *mask_logits, const int32_t *label, con
 int mrcnn_mask_intersect(const uint64_t *a, const int32_t *ext_a, int P, const uint64_t *b,
                          const int32_t *ext_b, int G, int H, int W, int32_t *inter,
                          void *stream);
+/* Mask boundaries for Boundary IoU (csrc/mask_boundary.hip): out (N,H,Wq) = M & ~E, where
+ * E(y,x) = 1 iff every pixel (y',x') with |y'-y| <= d and |x'-x| <= d lies inside the image and
+ * is foreground; out_area (N) its exact bit count.  Replaces mask_to_boundary of the
+ * boundary-iou-api (cv2.erode with a 3x3 kernel, d iterations, on the mask padded by a ring of
+ * zeros) behind COCOeval's iouType 'boundary'.  Every word of out is written (zero outside the
+ * extent and in the pad bits); the boundary set reuses the input extent (N,4), inside which
+ * alone packed is read, so slack in the extent does not change the result; an empty extent gives
+ * zeros and area 0.  d >= 1 and may exceed 63, W and H.  out must not alias packed.  workspace:
+ * caller-owned scratch of at least mrcnn_mask_boundary_workspace_bytes(N, H, W) bytes (the
+ * row-eroded masks between the two launches).  N <= 65535; N == 0 returns without a launch. */
+int64_t mrcnn_mask_boundary_workspace_bytes(int N, int H, int W);
+int mrcnn_mask_boundary(const uint64_t *packed, const int32_t *extent, int N, int H, int W,
+                        int d, uint64_t *out, int32_t *out_area, void *workspace,
+                        int64_t workspace_bytes, void *stream);
 
 /* ---- Box IoU for evaluation (csrc/bbox_eval.hip) ---------------------------------------------
  * The IoU tables of a whole evaluation batch of images in one launch (ragged): boxes_a (n_a,4)

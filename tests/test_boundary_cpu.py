@@ -1,0 +1,426 @@
+"""Boundary AP without a device: the NumPy reference against scipy's restatement of the rule, the
+host matching on min(mask IoU, boundary IoU) from hand-built and reference counts, the six-entry
+records, the switches of the tools, and the kernels' per-word arithmetic run by a host program."""
+import ctypes
+import importlib
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+import boundary_ref as BR
+import instseg_eval_ref as R
+from chainer_mask_rcnn_amd.extensions import instance_segmentation_evaluators as E
+from chainer_mask_rcnn_amd.utils.evaluations import matching
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ['c%d' % i for i in range(BR.N_CLASS)]
+COCO_KEY = 'map/iou=0.50:0.95/area=all/maxDets=100'
+
+
+def same(a, b):
+    assert sorted(a) == sorted(b)
+    for k in a:
+        assert np.array_equal(np.asarray(a[k]), np.asarray(b[k]), equal_nan=True), k
+
+
+def _tool(name):
+    tools = os.path.join(ROOT, 'tools')
+    if tools not in sys.path:
+        sys.path.insert(0, tools)
+    return importlib.import_module(name)
+
+
+# ------------------------------------------------------------------------------- the reference
+@pytest.mark.parametrize('shape', [(1, 1), (3, 200), (70, 130), (65, 64), (40, 129)])
+def test_reference_erosion_is_cv2s_iterated_3x3_on_the_padded_mask(shape):
+    ndimage = pytest.importorskip('scipy.ndimage')
+    rng = np.random.RandomState(shape[0] * 1000 + shape[1])
+    masks = [np.ones(shape, bool), rng.uniform(size=shape) < 0.97, rng.uniform(size=shape) < 0.5]
+    blob = np.zeros(shape, bool)
+    blob[shape[0] // 4:shape[0] - shape[0] // 8, shape[1] // 5:] = True
+    masks.append(blob)
+    for d in (1, 2, 5, 31, 70):
+        for m in masks:
+            want = ndimage.binary_erosion(np.pad(m, 1), np.ones((3, 3)), iterations=d,
+                                          border_value=1)[1:-1, 1:-1]
+            assert np.array_equal(BR.erode(m, d), want), (shape, d)
+    for d in (1, 2, 5):                                # the two forms the reference states
+        assert np.array_equal(BR.erode(masks[1], d), BR.erode_by_shifts(masks[1], d))
+
+
+def test_reference_dilation_values_and_boundary_properties():
+    from chainer_mask_rcnn_amd.utils.evaluations.masks import boundary_dilation
+    for (H, W), d in (((800, 1333), 31), ((1024, 1024), 29), ((96, 160), 4), ((20, 20), 1),
+                      ((3000, 4000), 100)):
+        assert BR.dilation(H, W) == d and boundary_dilation((H, W)) == d
+    assert boundary_dilation((96, 160), 0.1) == BR.dilation(96, 160, 0.1) == 19
+    full = np.ones((30, 40), bool)
+    b = BR.boundary(full, 3)                            # a frame of width d
+    assert b.sum() == 30 * 40 - 24 * 34 and not b[3:-3, 3:-3].any()
+    assert not BR.boundary(np.zeros((5, 5), bool), 2).any()
+    disc = BR._shape(0, 48, 80, 30, 96, 160)
+    assert (BR.boundary(disc, 4) <= disc).all() and 0 < BR.boundary(disc, 4).sum() < disc.sum()
+
+
+@pytest.fixture(scope='module')
+def data():
+    return BR.crafted_set()
+
+
+def test_crafted_set_separates_boundary_ap_from_mask_ap(data):
+    assert all(m.shape[1:] == BR.SIZE for m in data['gt_masks'] + data['pred_masks'])
+    assert BR.dilation(*BR.SIZE) == 4
+    assert any(c.any() for c in data['gt_crowdeds']) and sum(len(l) for l in data['pred_labels']) > 8
+    for crowds in (True, False):
+        segm, boundary = BR.coco_maps(data, crowds)
+        assert 0 < boundary < segm, (segm, boundary)
+
+
+# -------------------------------------------------------------------------------- the matching
+def _one(inter, pa, ga):
+    return (np.array([[inter]], np.int64), np.array([pa], np.int64), np.array([ga], np.int64))
+
+
+def test_a_detection_with_a_good_mask_and_a_bad_contour_is_unmatched_under_boundary():
+    counts = [_one(80, 100, 100)]                       # mask IoU 80 / 120
+    bounds = [_one(10, 40, 40)]                         # boundary IoU 10 / 70
+    labels, scores = [np.array([0])], [np.array([0.9], np.float32)]
+    segm = matching.coco_results(matching.coco_evaluate_from_counts(counts, labels, scores, labels))
+    bnd = matching.coco_results(matching.coco_evaluate_from_boundary_counts(
+        counts, bounds, labels, scores, labels))
+    assert segm['map/iou=0.50/area=all/maxDets=100'] == 1.
+    assert bnd['map/iou=0.50/area=all/maxDets=100'] == 0.
+    ap = matching.calc_detection_voc_ap(*matching.voc_prec_rec_from_counts(counts, labels, scores, labels))
+    assert ap[0] == 1.
+    ap = matching.calc_detection_voc_ap(*matching.voc_prec_rec_from_boundary_counts(
+        counts, bounds, labels, scores, labels))
+    assert ap[0] == 0.
+    # the other way round the mask IoU decides: the table is the minimum, not the boundary IoU
+    ap = matching.calc_detection_voc_ap(*matching.voc_prec_rec_from_boundary_counts(
+        bounds, counts, labels, scores, labels))
+    assert ap[0] == 0.
+    before = matching.coco_results(matching.coco_evaluate_from_counts(counts, labels, scores, labels))
+    assert np.array_equal(before['coco_eval']['precision'], segm['coco_eval']['precision'])
+    with pytest.raises(ValueError):
+        matching.coco_evaluate_from_boundary_counts(counts, [], labels, scores, labels)
+
+
+def test_the_crowd_denominator_is_applied_to_both_tables_before_the_min():
+    table = (_one(50, 60, 1000), _one(20, 25, 300))
+    ious, dt_area, gt_area = matching._boundary_image(table, 1, 1)
+    idx = np.array([0])
+    assert ious(idx, idx, np.array([True]))[0, 0] == min(50 / 60, 20 / 25) == 20 / 25
+    assert ious(idx, idx, np.array([False]))[0, 0] == min(50 / 1010, 20 / 305)
+    table = (_one(50, 100, 1000), _one(24, 25, 300))    # now the mask's crowd IoU is the smaller
+    ious, _, _ = matching._boundary_image(table, 1, 1)
+    assert ious(idx, idx, np.array([True]))[0, 0] == 50 / 100
+    assert dt_area.tolist() == [60] and gt_area.tolist() == [1000]          # the masks' areas
+
+
+def _records(data, kind, with_flags=True):
+    masks, bounds = BR.all_counts(data['pred_masks'], data['gt_masks'])
+    if kind == 'coco':
+        gts = [(None, l, None, c, a) if with_flags else (None, l, None)
+               for l, c, a in zip(data['gt_labels'], data['gt_crowdeds'], data['gt_areas'])]
+    else:
+        gts = [(None, l, None, d) if with_flags else (None, l, None)
+               for l, d in zip(data['gt_labels'], data['gt_difficults'])]
+    none = [None] * len(gts)
+    return (masks, data['pred_labels'], data['pred_scores'], gts, none, bounds)
+
+
+def _coco_expected(data, with_flags, boundary):
+    args = (data['pred_masks'], data['pred_labels'], data['pred_scores'], data['gt_masks'],
+            data['gt_labels']) + ((data['gt_crowdeds'], data['gt_areas']) if with_flags else ())
+    p, r, cats = (BR.coco_eval if boundary else R.coco_eval)(*args)
+    s = R.coco_summary(p, r)
+    out = {'map': s[COCO_KEY], 'map@0.5': s['map/iou=0.50/area=all/maxDets=100'],
+           'map@0.75': s['map/iou=0.75/area=all/maxDets=100']}
+    per = s['ap/iou=0.50:0.95/area=all/maxDets=100']
+    for l, n in enumerate(NAMES):
+        out['ap/' + n] = per[cats.index(l)] if l in cats else np.nan
+    return out, p, r
+
+
+def _voc_expected(data, with_flags, boundary):
+    args = (data['pred_masks'], data['pred_labels'], data['pred_scores'], data['gt_masks'],
+            data['gt_labels'], data['gt_difficults'] if with_flags else None)
+    ap = R.voc_ap(*(BR.voc_prec_rec if boundary else R.voc_prec_rec)(*args), use_07_metric=True)
+    out = {'map': np.nanmean(ap)}
+    for l, n in enumerate(NAMES):
+        out['ap/' + n] = ap[l] if l < len(ap) else np.nan
+    return out
+
+
+@pytest.mark.parametrize('with_flags', [True, False])
+def test_evaluate_collected_on_six_entry_records_equals_the_reference(data, with_flags):
+    rec = _records(data, 'coco', with_flags)
+    ev = E.InstanceSegmentationCOCOEvaluator(None, None, label_names=NAMES,
+                                             iou_types=('segm', 'boundary'))
+    got = ev.evaluate_collected(*rec)
+    want = {'validation/main/' + k: v for k, v in _coco_expected(data, with_flags, False)[0].items()}
+    exp_b, p, r = _coco_expected(data, with_flags, True)
+    want.update({'validation/main/boundary/' + k: v for k, v in exp_b.items()})
+    same(got, want)
+    assert 0 < got['validation/main/boundary/map'] < got['validation/main/map']
+    labels = [g[1] for g in rec[3]]
+    flags = ([g[3] for g in rec[3]], [g[4] for g in rec[3]]) if with_flags else (None, None)
+    full = matching.coco_evaluate_from_boundary_counts(rec[0], rec[5], rec[1], rec[2], labels, *flags)
+    assert np.array_equal(full['precision'], p) and np.array_equal(full['recall'], r)
+    only = E.InstanceSegmentationCOCOEvaluator(None, None, label_names=NAMES, iou_types=('boundary',))
+    same(only.evaluate_collected(*rec), {k: v for k, v in got.items() if '/boundary/' in k})
+    # asking for the boundary changes no segm value
+    plain = E.InstanceSegmentationCOCOEvaluator(None, None, label_names=NAMES)
+    same(plain.evaluate_collected(*rec[:4]), {k: v for k, v in got.items() if '/boundary/' not in k})
+
+    rec = _records(data, 'voc', with_flags)
+    ev = E.InstanceSegmentationVOCEvaluator(None, None, use_07_metric=True, label_names=NAMES,
+                                            iou_types=('segm', 'boundary'))
+    got = ev.evaluate_collected(*rec)
+    want = {'validation/main/' + k: v for k, v in _voc_expected(data, with_flags, False).items()}
+    want.update({'validation/main/boundary/' + k: v
+                 for k, v in _voc_expected(data, with_flags, True).items()})
+    same(got, want)
+    assert got['validation/main/boundary/map'] < got['validation/main/map']
+
+
+# --------------------------------------------------------------------------------- the records
+def test_six_entry_records_strip_merge_and_score_like_the_whole(data):
+    rec = _records(data, 'coco')
+    s = E.strip_records(*rec)
+    assert isinstance(s, tuple) and len(s) == 6 and s[4] == [None] * len(rec[3])
+    assert s[5] == list(rec[5]) and all(g[0] is None and g[2] is None and len(g) == 5 for g in s[3])
+    assert len(E.strip_records(rec[0], rec[1], rec[2], rec[3], None, rec[5])) == 6
+    m = E.merge_records([s, s])
+    assert len(m) == 6 and m[5] == list(rec[5]) * 2 and m[0] == list(rec[0]) * 2
+    ev = E.InstanceSegmentationCOCOEvaluator(None, None, label_names=NAMES,
+                                             iou_types=('segm', 'boundary'))
+    whole = ev.evaluate_collected(*rec)
+    halves = E.merge_records([E.strip_records(*[r[:3] for r in rec]),
+                              E.strip_records(*[r[3:] for r in rec])])
+    assert len(halves) == 6
+    same(ev.evaluate_collected(*halves), whole)
+    four, five = E.strip_records(*rec[:4]), E.strip_records(*rec[:5])
+    assert len(four) == 4 and len(five) == 5                    # the narrower forms as they were
+    for mixed in ([four, s], [five, s], [s, four]):
+        with pytest.raises(ValueError):
+            E.merge_records(mixed)
+    with pytest.raises(ValueError, match='boundary'):           # 'boundary' needs the sixth list
+        ev.evaluate_collected(*rec[:4])
+    both = E.InstanceSegmentationCOCOEvaluator(None, None, iou_types=('bbox', 'boundary'))
+    with pytest.raises(ValueError, match='box IoU'):            # a list of None is no box record
+        both.evaluate_collected(*rec)
+
+
+# -------------------------------------------------------------------------------- the switches
+def test_iou_types_accept_boundary():
+    for cls in (E.InstanceSegmentationVOCEvaluator, E.InstanceSegmentationCOCOEvaluator):
+        assert cls(None, None, iou_types=('boundary',)).iou_types == ('boundary',)
+        ev = cls(None, None, iou_types=('segm', 'bbox', 'boundary'), boundary_dilation_ratio=0.05)
+        assert ev.iou_types == ('segm', 'bbox', 'boundary') and ev.boundary_dilation_ratio == 0.05
+        assert cls(None, None).boundary_dilation_ratio == 0.02
+        assert cls(None, None, iou_types='boundary').iou_types == ('boundary',)
+        for bad in ((), ('boundaries',), ('segm', 'keypoints')):
+            with pytest.raises(ValueError):
+                cls(None, None, iou_types=bad)
+
+
+def test_tool_switches():
+    import argparse
+    evaluate = _tool('evaluate')
+    assert evaluate._iou_types('segm,boundary') == ('segm', 'boundary')
+    assert evaluate._iou_types('boundary') == ('boundary',)
+    assert evaluate._iou_types('segm, bbox ,boundary') == ('segm', 'bbox', 'boundary')
+    for bad in ('boundary,boundary', 'edge', ''):
+        with pytest.raises(argparse.ArgumentTypeError):
+            evaluate._iou_types(bad)
+    ns = argparse.Namespace(iou_types=('segm', 'boundary'), boundary_dilation_ratio=0.03)
+    assert evaluate._evaluator_kwargs(ns) == {'iou_types': ('segm', 'boundary'),
+                                              'boundary_dilation_ratio': 0.03}
+    assert evaluate._evaluator_kwargs(argparse.Namespace()) == {}
+    assert evaluate._evaluator_kwargs(argparse.Namespace(iou_types=('segm', 'bbox'))) == {
+        'iou_types': ('segm', 'bbox')}
+
+    train = _tool('train')
+    args = train.parse_args([])
+    assert not hasattr(args, 'eval_boundary')
+    before = {k: v for k, v in vars(args).items()
+              if k not in ('grad_clip', 'skip_nonfinite', 'warmup_iters', 'warmup_factor', 'eval_bbox')}
+    assert train.recorded_params(args) == before and 'eval_boundary' not in before
+    args = train.parse_args(['--eval-boundary'])
+    assert args.eval_boundary is True and train.recorded_params(args)['eval_boundary'] is True
+    assert 'eval_bbox' not in train.recorded_params(args)
+
+
+class _Loop(object):
+    """What Trainer needs of a TrainLoop."""
+
+    class _It(object):
+        batch_size = 1
+        dataset = list(range(1000))
+
+    class _Chain(object):
+        report = {}
+
+    class _Opt(object):
+        lr, lr_scale = 0.5, 1.0
+
+    def __init__(self):
+        self.iterator, self.chain, self.optimizer = self._It(), self._Chain(), self._Opt()
+        self.iteration = 0
+
+    def step(self):
+        self.iteration += 1
+
+
+def test_print_report_gets_the_boundary_column_only_when_asked(tmp_path):
+    import io
+    T = _tool('trainer')
+    for bbox, boundary in ((False, False), (False, True), (True, True)):
+        tr = T.Trainer(_Loop(), (2, 'iteration'), out=str(tmp_path / ('%d%d' % (bbox, boundary))))
+        out = io.StringIO()
+        T.extend_reference_set(tr, model=None, plot=False, print_out=out,
+                               log_interval=(2, 'iteration'), print_interval=(2, 'iteration'),
+                               eval_bbox=bbox, eval_boundary=boundary)
+        tr.run()
+        header = out.getvalue().splitlines()[0].split()
+        assert header == (['iteration', 'epoch', 'elapsed_time', 'lr'] + T.LOG_KEYS
+                          + ['validation/main/map']
+                          + (['validation/main/bbox/map'] if bbox else [])
+                          + (['validation/main/boundary/map'] if boundary else []))
+
+
+def test_summarize_logs_shows_the_boundary_column_only_when_a_log_has_it(tmp_path, capsys):
+    yaml = pytest.importorskip('yaml')
+    pytest.importorskip('pandas')
+    pytest.importorskip('tabulate')
+    summarize_logs = _tool('summarize_logs')
+    for name, value in (('run_a', 0.12), ('run_b', None)):
+        (tmp_path / name).mkdir()
+        with open(str(tmp_path / name / 'params.yaml'), 'w') as f:
+            yaml.safe_dump({'model': 'resnet50', 'lr': 0.01}, f)
+        entry = {'epoch': 1, 'iteration': 20, 'elapsed_time': 10.0, 'validation/main/map': 0.25}
+        if value is not None:
+            entry['validation/main/boundary/map'] = value
+        with open(str(tmp_path / name / 'log'), 'w') as f:
+            json.dump([entry], f)
+    rows, _ = summarize_logs.summarize_logs(str(tmp_path))
+    out = capsys.readouterr().out
+    assert 'validation/main/boundary/map' in out and '0.120' in out and '/bbox/' not in out
+    assert [r[-1] for r in rows] == ['<none>< <none>', '0.120< 0.120']       # run_b, run_a
+    assert len(rows[0]) == len(summarize_logs.KEYS) + 1
+    (tmp_path / 'run_a' / 'log').write_text(json.dumps(
+        [{'epoch': 1, 'iteration': 20, 'elapsed_time': 10.0, 'validation/main/map': 0.25}]))
+    rows, _ = summarize_logs.summarize_logs(str(tmp_path))
+    assert 'boundary' not in capsys.readouterr().out and len(rows[0]) == len(summarize_logs.KEYS)
+
+
+# ------------------------------------------------------- the kernels' arithmetic, on the host
+@pytest.fixture(scope='module')
+def host_program(tmp_path_factory):
+    """tests/mask_boundary_host.cpp: the per-word functions of csrc/mask_boundary.h run thread for
+    thread as the kernels call them, built with the undefined-behaviour sanitizer (the funnel
+    shifts must never shift by 64)."""
+    import shutil
+    import subprocess
+    cxx = shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
+    if cxx is None:
+        pytest.skip('no host C++ compiler')
+    exe = str(tmp_path_factory.mktemp('mask_boundary') / 'mask_boundary_host')
+    subprocess.run([cxx, '-O1', '-g', '-std=c++17', '-fsanitize=undefined',
+                    '-fno-sanitize-recover=all',
+                    '-I' + os.path.join(ROOT, 'chainer_mask_rcnn_amd', 'csrc'),
+                    os.path.join(ROOT, 'tests', 'mask_boundary_host.cpp'), '-o', exe],
+                   check=True, capture_output=True, text=True)
+    return exe
+
+
+@pytest.mark.parametrize('H,W,d', BR.KERNEL_CASES)
+def test_word_arithmetic_is_the_rule_whatever_the_extent(host_program, tmp_path, H, W, d):
+    import subprocess
+    masks = BR.kernel_masks(H, W, d)
+    N, Wq = len(masks), (W + 63) // 64
+    want_bits = BR.boundaries(masks, d)
+    want, want_area = BR.packbits(want_bits), want_bits.reshape(N, -1).sum(1)
+    packed = BR.packbits(masks)
+    tight = np.zeros((N, 4), np.int32)
+    for n, m in enumerate(masks):
+        ys, xs = np.nonzero(m)
+        tight[n] = (ys.min(), ys.max() + 1, xs.min() // 64, xs.max() // 64 + 1) if len(ys) else \
+            (H, 0, Wq, 0)
+    rng = np.random.RandomState(d)
+    loose = np.array([[rng.randint(0, t[0] + 1), rng.randint(t[1], H + 1), rng.randint(0, t[2] + 1),
+                       rng.randint(t[3], Wq + 1)] if t[0] < t[1] else
+                      [rng.randint(0, H + 1), rng.randint(0, H + 1), 0, rng.randint(0, Wq + 1)]
+                      for t in tight], np.int32)
+    beyond = np.array([[-5, H + 7, -2, Wq + 3]] * N, np.int32)       # clamped to the image
+    for name, extent in (('tight', tight), ('loose', loose), ('beyond', beyond)):
+        src, dst = str(tmp_path / (name + '.in')), str(tmp_path / (name + '.out'))
+        with open(src, 'wb') as f:
+            f.write(np.array([N, H, W, d], np.int32).tobytes())
+            f.write(np.ascontiguousarray(packed).tobytes())
+            f.write(extent.tobytes())
+        r = subprocess.run([host_program, src, dst], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-2000:]
+        raw = open(dst, 'rb').read()
+        got = np.frombuffer(raw[:N * H * Wq * 8], '<i8').reshape(N, H, Wq)
+        got_area = np.frombuffer(raw[N * H * Wq * 8:], np.int32)
+        bad = np.flatnonzero((got != want).reshape(N, -1).any(1))
+        assert len(bad) == 0, '%s extents: masks %s differ' % (name, bad.tolist())
+        assert np.array_equal(got_area, want_area), name
+
+
+def test_boundary_kernels_use_no_scratch_and_no_lds():
+    import re
+    import subprocess
+    csrc = os.path.join(ROOT, 'chainer_mask_rcnn_amd', 'csrc')
+    cmd = ['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC',
+           '-I' + os.path.join(ROOT, 'include'), '-I' + csrc,
+           '-Rpass-analysis=kernel-resource-usage', '-c', os.path.join(csrc, 'mask_boundary.hip'),
+           '-o', os.devnull]
+    err = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
+    res, name = {}, None
+    for line in err.splitlines():
+        m = re.search(r'Function Name: (\S+)', line)
+        if m:
+            name = m.group(1)
+            res[name] = {}
+            continue
+        m = re.search(r'remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)', line)
+        if m and name:
+            res[name][m.group(1).strip()] = int(m.group(2))
+    for k in ('erode_rows_kernel', 'boundary_kernel'):
+        assert any(k in n for n in res), k
+    assert len(res) == 2                                       # at most two launches per call
+    for n, v in res.items():
+        assert v.get('ScratchSize', 0) == 0 and v.get('VGPRs Spill', 0) == 0, (n, v)
+        assert v.get('LDS Size', 0) == 0, (n, v)
+
+
+# ------------------------------------------------------------------------------------ the C ABI
+def test_mask_boundary_validates_without_a_device():
+    import __graft_entry__ as g
+    g.build()
+    from chainer_mask_rcnn_amd import _lib
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(4096)
+    p, q = ctypes.cast(buf, ctypes.c_void_p), ctypes.c_void_p(ctypes.addressof(buf) + 2048)
+    err = lib.mrcnn_last_error
+    need = lib.mrcnn_mask_boundary_workspace_bytes(3, 5, 65)
+    assert need == 3 * 5 * 2 * 8 and lib.mrcnn_mask_boundary_workspace_bytes(0, 5, 65) == 0
+
+    def call(packed=p, extent=p, N=1, H=4, W=4, d=1, out=q, area=p, ws=p, ws_bytes=1 << 20):
+        return lib.mrcnn_mask_boundary(packed, extent, N, H, W, d, out, area, ws, ws_bytes, None)
+    assert call(H=0) != 0 and b'bad shape' in err()
+    assert call(N=-1) != 0 and b'bad shape' in err()
+    assert call(d=0) != 0 and b'd must be >= 1' in err()
+    assert call(H=65536, W=32768) != 0 and b'2^31' in err()
+    assert call(packed=None) != 0 and b'null' in err()
+    assert call(ws=None) != 0 and b'null' in err()
+    assert call(out=p) != 0 and b'alias' in err()
+    assert call(ws_bytes=31) != 0 and b'workspace smaller' in err()
+    assert call(N=65536, ws_bytes=1 << 30) != 0 and b'65535' in err()
+    assert call(packed=None, extent=None, N=0, out=None, area=None, ws=None, ws_bytes=0) == 0

@@ -11,6 +11,7 @@ examples/evaluate_common.py + examples/coco/evaluate.py.
     python tools/evaluate.py --coco-root DIR --split test-dev --detectron model.pkl --save-results res.json
     python tools/evaluate.py --coco-root DIR --results res.json   # score a results file (no model)
     python tools/evaluate.py --synthetic 16 --iou-types segm,bbox   # box AP beside mask AP
+    python tools/evaluate.py --synthetic 16 --iou-types segm,boundary   # Boundary AP beside mask AP
     python tools/evaluate.py --coco-root DIR --detectron model.pkl --soft-nms linear --bbox-vote 0.8
     python tools/evaluate.py --coco-root DIR --detectron model.pkl --test-aug-h-flip \
         --test-aug-scales 500,1000 --test-aug-scale-h-flip --soft-nms linear --bbox-vote 0.8
@@ -24,6 +25,10 @@ does not score.  ``--results`` scores such a file against the annotations alone.
 ``--iou-types segm,bbox`` adds the box AP block (``validation/main/bbox/...``: the predicted boxes
 against the dataset's boxes, IoU tables from the device); ``--iou-types bbox`` alone skips the mask
 work, and with ``--save-results`` then writes a bbox-only file, the detection track's format.
+``--iou-types segm,boundary`` adds Boundary AP (``validation/main/boundary/...``: matching on
+min(mask IoU, boundary IoU), the boundaries cut from the packed masks on the device, DESIGN.md
+section 22); ``--boundary-dilation-ratio R`` sets the boundary width as a fraction of the image
+diagonal.
 ``--soft-nms {linear,gaussian}`` and ``--bbox-vote THRESH`` turn on Detectron's test-time options
 (TEST.SOFT_NMS, TEST.BBOX_VOTE; both decided on the device); the values
 used are written into the result file as ``postprocessing``.
@@ -64,8 +69,10 @@ class _TimedTarget(object):
 
 def _iou_types(text):
     types = tuple(t.strip() for t in text.split(',') if t.strip())
-    if not types or any(t not in ('segm', 'bbox') for t in types) or len(set(types)) != len(types):
-        raise argparse.ArgumentTypeError("a comma-separated subset of 'segm,bbox', got %r" % text)
+    if (not types or any(t not in ('segm', 'bbox', 'boundary') for t in types)
+            or len(set(types)) != len(types)):
+        raise argparse.ArgumentTypeError("a comma-separated subset of 'segm,bbox,boundary', got %r"
+                                         % text)
     return types
 
 
@@ -182,18 +189,30 @@ def apply_postprocessing_flags(model, args):
 
 
 def _print_result(result):
-    """The report: one block as it always was; the segm block and the bbox block when box AP was
-    asked for."""
+    """The report: one block as it always was; a segm, a bbox and a boundary block when box AP
+    or Boundary AP was asked for."""
     bbox = {k: v for k, v in result.items() if '/bbox/' in k}
-    if not bbox:
+    boundary = {k: v for k, v in result.items() if '/boundary/' in k}
+    if not bbox and not boundary:
         pprint.pprint(result)
         return
-    segm = {k: v for k, v in result.items() if k not in bbox}
-    if segm:
-        print('segm:')
-        pprint.pprint(segm)
-    print('bbox:')
-    pprint.pprint(bbox)
+    segm = {k: v for k, v in result.items() if k not in bbox and k not in boundary}
+    for name, block in (('segm', segm), ('bbox', bbox), ('boundary', boundary)):
+        if block:
+            print('%s:' % name)
+            pprint.pprint(block)
+
+
+def _evaluator_kwargs(args):
+    """iou_types / boundary_dilation_ratio for the evaluators, only when they differ from the
+    defaults."""
+    kw = {}
+    iou_types = getattr(args, 'iou_types', ('segm',))
+    if iou_types != ('segm',):
+        kw['iou_types'] = iou_types
+    if 'boundary' in iou_types:
+        kw['boundary_dilation_ratio'] = getattr(args, 'boundary_dilation_ratio', 0.02)
+    return kw
 
 
 def main():
@@ -228,9 +247,12 @@ def main():
     ap.add_argument('--results', default=None, metavar='FILE',
                     help='score a COCO results file against --coco-root / --split (no model, '
                          'no images needed)')
-    ap.add_argument('--iou-types', type=_iou_types, default=('segm',), metavar='segm[,bbox]',
-                    help='what to score: mask AP (segm), box AP (bbox) or both; with --results, '
-                         'each type is scored from the file')
+    ap.add_argument('--iou-types', type=_iou_types, default=('segm',),
+                    metavar='segm[,bbox][,boundary]',
+                    help='what to score: mask AP (segm), box AP (bbox), Boundary AP (boundary) or '
+                         'any of them together; with --results, each type is scored from the file')
+    ap.add_argument('--boundary-dilation-ratio', type=float, default=0.02, metavar='R',
+                    help='Boundary AP: the boundary width as a fraction of the image diagonal')
     add_postprocessing_flags(ap)
     args = ap.parse_args()
     check_postprocessing_flags(ap, args, no_model=bool(args.results))
@@ -308,8 +330,7 @@ def main():
     writer = _results_writer(args, data)
     if writer is not None:
         kw['results_sink'] = writer
-    if args.iou_types != ('segm',):
-        kw['iou_types'] = args.iou_types
+    kw.update(_evaluator_kwargs(args))
     evaluator = cls(batches, target, label_names=class_names, **kw)
     t0 = time.perf_counter()
     if args.split == 'test-dev':
@@ -392,7 +413,10 @@ def score_results(args):
     for iou_type in getattr(args, 'iou_types', ('segm',)):
         result.update(eval_coco_results(args.results, data, limit=args.limit or None,
                                         label_names=[str(n) for n in data.class_names],
-                                        iou_type=iou_type))
+                                        iou_type=iou_type,
+                                        **({'dilation_ratio': getattr(
+                                            args, 'boundary_dilation_ratio', 0.02)}
+                                           if iou_type == 'boundary' else {})))
     seconds = time.perf_counter() - t0
     result = {k: float(v) for k, v in result.items()}
     _print_result(result)
@@ -466,9 +490,7 @@ def evaluate_log_dir(args):
     writer = _results_writer(args, test_data)
     if writer is not None and evaluator_type != 'coco':
         raise SystemExit('--save-results needs the coco evaluator')
-    kw = {}
-    if getattr(args, 'iou_types', ('segm',)) != ('segm',):
-        kw['iou_types'] = args.iou_types
+    kw = _evaluator_kwargs(args)
     if evaluator_type == 'voc':
         evaluator = cmr.extensions.InstanceSegmentationVOCEvaluator(
             batches, model, use_07_metric=True, label_names=class_names, **kw)

@@ -7,7 +7,8 @@ One row per run directory (params.yaml + log of tools/train.py), newest first: t
 entry with the best ``validation/main/map``, the run's settings and, when tools/evaluate.py
 --log-dir has been run on it, the map of snapshot_model.npz.eval_result.yaml.  Directories
 without params.yaml are listed as ignored.  A ``validation/main/bbox/map`` column (box AP, tools/
-train.py --eval-bbox) is shown when some run's log has it.
+train.py --eval-bbox) is shown when some run's log has it, and likewise a
+``validation/main/boundary/map`` column (Boundary AP, --eval-boundary).
 """
 import argparse
 import datetime
@@ -20,6 +21,7 @@ KEYS = ['name', 'elapsed_time', 'last_time', 'git_hash', 'hostname', 'model', 'i
 
 
 BBOX_KEY = 'validation/main/bbox/map'
+BOUNDARY_KEY = 'validation/main/boundary/map'
 
 
 def log_has_key(logs_dir, name, key):
@@ -117,9 +119,10 @@ def summarize_logs(logs_dir, keys=KEYS, target_key='validation/main/map', object
     import tabulate
     assert objective in ('min', 'max')
     assert target_key in keys
-    if BBOX_KEY not in keys and any(log_has_key(logs_dir, name, BBOX_KEY)
-                                    for name in sorted(os.listdir(logs_dir))):
-        keys = list(keys) + [BBOX_KEY]
+    for optional in (BBOX_KEY, BOUNDARY_KEY):
+        if optional not in keys and any(log_has_key(logs_dir, name, optional)
+                                        for name in sorted(os.listdir(logs_dir))):
+            keys = list(keys) + [optional]
     rows, ignored = [], []
     for name in sorted(os.listdir(logs_dir)):
         row, _, ignored_dir = summarize_log(logs_dir, name, keys, target_key, objective)

@@ -82,6 +82,10 @@ def parse_args(argv=None):
     ap.add_argument('--eval-bbox', action='store_true',
                     help='the evaluator also scores the boxes: validation/main/bbox/map joins the '
                          'log and the printed report (the best snapshot stays on the mask map)')
+    ap.add_argument('--eval-boundary', action='store_true', default=argparse.SUPPRESS,
+                    help='the evaluator also scores Boundary AP (min of mask and boundary IoU): '
+                         'validation/main/boundary/map joins the log and the printed report (the '
+                         'best snapshot stays on the mask map)')
     ap.add_argument('--grad-clip', type=float, default=0.,
                     help='clip the global L2 norm of the averaged gradient at T '
                          '(optimizers.GradientClipping; 0: off).  Like --skip-nonfinite it turns '
@@ -314,7 +318,10 @@ def assemble(args, comm, model, train_data, test_data, evaluator_type, synthetic
                                 chain, opt, comm.device)
     test_iter = train_loop.SerialIterator(test, args.batch_size_per_gpu, shuffle=False)
     eval_bbox = bool(getattr(args, 'eval_bbox', False))
-    kw = {'iou_types': ('segm', 'bbox')} if eval_bbox else {}
+    eval_boundary = bool(getattr(args, 'eval_boundary', False))
+    iou_types = ('segm',) + (('bbox',) if eval_bbox else ()) + (
+        ('boundary',) if eval_boundary else ())
+    kw = {'iou_types': iou_types} if len(iou_types) > 1 else {}
     if evaluator_type == 'voc':
         evaluator = cmr.extensions.InstanceSegmentationVOCEvaluator(
             test_iter, model, use_07_metric=True, label_names=args.class_names, **kw)
@@ -336,6 +343,7 @@ def assemble(args, comm, model, train_data, test_data, evaluator_type, synthetic
                            params=params, plot=not args.no_plot,
                            print_out=print_out if comm.rank == 0 else None, rank=comm.rank,
                            gather=comm.gather if comm.parallel else None, eval_bbox=eval_bbox,
+                           eval_boundary=eval_boundary,
                            warmup=warmup, grad_report=bool(hooks), **intervals)
     return Run(tr, loop, chain, opt, evaluator, train_data, test_data)
 

@@ -738,11 +738,13 @@ def extend_reference_set(trainer, model, evaluator=None, vis_iterator=None, clas
                          step_size=None, params=None, eval_interval=(1, 'epoch'),
                          log_interval=(20, 'iteration'), plot_interval=(0.1, 'epoch'),
                          print_interval=(20, 'iteration'), plot=True, print_out=sys.stdout,
-                         rank=0, gather=None, eval_bbox=False, warmup=None, grad_report=False):
+                         rank=0, gather=None, eval_bbox=False, warmup=None, grad_report=False,
+                         eval_boundary=False):
     """The extensions of examples/train_common.py:251-372 (without dump_graph / ProgressBar)
     with the same triggers and priorities; ``model``: the MaskRCNN (``chain.mask_rcnn``).
     ``eval_bbox``: the evaluator also reports ``validation/main/bbox/map``, which then joins the
-    printed report (the best snapshot and accuracy.png stay on ``validation/main/map``).
+    printed report (the best snapshot and accuracy.png stay on ``validation/main/map``);
+    ``eval_boundary``: likewise for ``validation/main/boundary/map`` (Boundary AP).
     ``warmup``: a LinearWarmup, run every iteration on every rank.  ``grad_report``: the optimizer
     has a gradient-norm hook: ``main/grad_norm`` and ``main/skipped`` join the printed report and
     StopWhenEverythingSkipped ends a run whose whole log window was skipped.
@@ -783,7 +785,8 @@ def extend_reference_set(trainer, model, evaluator=None, vis_iterator=None, clas
         extend_lead(PrintReport(['iteration', 'epoch', 'elapsed_time', 'lr'] + LOG_KEYS[:1]
                                 + LOG_KEYS[1:] + (GRAD_KEYS if grad_report else [])
                                 + ['validation/main/map']
-                                + (['validation/main/bbox/map'] if eval_bbox else []),
+                                + (['validation/main/bbox/map'] if eval_bbox else [])
+                                + (['validation/main/boundary/map'] if eval_boundary else []),
                                 out=print_out),
                     trigger=print_interval)
     if plot:
