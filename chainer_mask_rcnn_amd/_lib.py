@@ -262,6 +262,30 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+ALIGN = 16      # bytes: the kernels read maps, filters and box rows as float4 / uint4
+
+
+def dense(t, dtype, fn, arg, align=False):
+    """``t`` as the library may read it through a raw pointer: a tensor of ``dtype`` in contiguous
+    memory (``align``: starting at a multiple of ALIGN bytes, for operands read with vector
+    accesses).  A wrong dtype is the caller's bug and raises TypeError naming the function
+    ``fn`` and the argument ``arg`` — it is never cast; any other layout is copied once.  A dense
+    input comes back as it is: attribute comparisons only, no kernel, no synchronisation."""
+    if t.dtype != dtype:
+        raise TypeError('%s: %s must be %s, got %s' % (fn, arg, dtype, t.dtype))
+    if not t.is_contiguous() or (align and t.data_ptr() % ALIGN):
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t
+
+
+def addr(t, field):
+    """The address of a tensor that crosses inside a host-side table (an array of pointers, or of
+    structs that hold one) instead of as an argument of its own; ``field`` names the table's
+    member, for whoever watches the boundary (tests/abi_contract.py swaps this function as it
+    swaps ``ptr``)."""
+    return None if t is None else t.data_ptr()
+
+
 def check(rc, what=''):
     if rc != 0:
         msg = load().mrcnn_last_error()

@@ -78,8 +78,8 @@ class Extractor(object):
     def forward(self, x, rois, outh, outw, spatial_scale, scalars, bin_stride, order):
         """-> (y, rois as passed to the kernel, extra)"""
         _lib.require_device(x, rois)
-        x = nhwc(x)
-        rois = rois.contiguous()
+        x = nhwc(x, torch.float32, self.name)
+        rois = _lib.dense(rois, torch.float32, self.name, 'rois')
         N, C, H, W = x.shape
         R = rois.shape[0]
         shape = (R, C, out_size(outh, bin_stride), out_size(outw, bin_stride))
@@ -96,7 +96,7 @@ class Extractor(object):
         """The gradient of the (N, C, H, W) map from ``gy`` (R, C, oh, ow)."""
         N, C, H, W = map_shape
         R = rois.shape[0]
-        gy = nhwc(gy)
+        gy = nhwc(gy, torch.float32, self.name, 'gy')
         t = dict(gy=gy, rois=rois, extra=extra, gx=empty_nhwc(map_shape, gy.device))
         ws = None
         if use_ws:

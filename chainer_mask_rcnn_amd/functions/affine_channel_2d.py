@@ -21,11 +21,13 @@ class AffineChannel2DFunction(torch.autograd.Function):
         if not (x.is_floating_point() and W.is_floating_point() and b.is_floating_point()
                 and x.dim() == 4 and W.dim() == 4 and b.dim() == 4
                 and W.shape[1] == b.shape[1]):
-            raise TypeError('affine_channel_2d expects x (N,C,H,W), W and b (1,C,1,1) floats')
-        x = nhwc(x)
+            raise TypeError('affine_channel_2d expects x (N,C,H,W), W and b (1,C,1,1) floats (float32), '
+                            'got %s %s, %s %s and %s %s' % (x.dtype, tuple(x.shape), W.dtype, tuple(W.shape),
+                                                           b.dtype, tuple(b.shape)))
+        x = nhwc(x, torch.float32, 'affine_channel_2d')
         N, C, H, Wd = x.shape
-        Wf = W.reshape(-1).contiguous()
-        bf = b.reshape(-1).contiguous()
+        Wf = _lib.dense(W.reshape(-1), torch.float32, 'affine_channel_2d', 'W', align=True)
+        bf = _lib.dense(b.reshape(-1), torch.float32, 'affine_channel_2d', 'b', align=True)
         y = empty_nhwc((N, C, H, Wd), x.device)
         _lib.call('mrcnn_affine_fwd', _lib.ptr(x), _lib.ptr(Wf), _lib.ptr(bf), _lib.ptr(y),
                   N * H * Wd, C, _lib.stream_ptr())
@@ -36,7 +38,7 @@ class AffineChannel2DFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, Wf = ctx.saved_tensors
-        gy = nhwc(gy)
+        gy = nhwc(gy, torch.float32, 'affine_channel_2d', 'gy')
         N, C, H, Wd = x.shape
         gx = empty_nhwc((N, C, H, Wd), gy.device)
         gW = torch.empty((C,), dtype=torch.float32, device=gy.device)

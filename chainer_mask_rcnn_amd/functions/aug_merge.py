@@ -35,11 +35,11 @@ def decode_cls_boxes_views(views, n_class, mean, std, size):
         if loc.dtype != torch.float32 or tuple(loc.shape) != (R, 4 * n_class):
             raise ValueError('view %d: cls_loc must be float32 (%d, %d), got %s %s'
                              % (v, R, 4 * n_class, loc.dtype, tuple(loc.shape)))
-        roi = roi.contiguous()
+        roi = _lib.dense(roi, torch.float32, 'decode_cls_boxes_views', 'roi', align=True)
         if R and (loc.stride(1) != 1 or loc.stride(0) < loc.shape[1]):
             loc = loc.contiguous()
         keep.append((roi, loc))
-        recs[v] = _lib.TestAugView(roi.data_ptr() if R else None, loc.data_ptr() if R else None,
+        recs[v] = _lib.TestAugView(_lib.addr(roi, 'roi') if R else None, _lib.addr(loc, 'cls_loc') if R else None,
                                    loc.stride(0) if R else 4 * n_class, R, float(scale),
                                    int(bool(flip)))
         total += R
@@ -74,8 +74,8 @@ def mask_aug_combine(maps, flips, heur='soft_avg'):
     out = empty_nhwc(shape, maps[0].device)
     if D == 0:
         return out
-    maps = [nhwc(m) for m in maps]
-    ptrs = (_lib.c_vp * V)(*[m.data_ptr() for m in maps])
+    maps = [nhwc(m, torch.float32, 'mask_aug_combine', 'maps') for m in maps]
+    ptrs = (_lib.c_vp * V)(*[_lib.addr(m, 'maps') for m in maps])
     flags = (ctypes.c_int32 * V)(*[int(bool(f)) for f in flips])
     _lib.call('mrcnn_mask_aug_combine', ptrs, flags, V, D, M, Kc, heur, _lib.ptr(out),
               _lib.stream_ptr())

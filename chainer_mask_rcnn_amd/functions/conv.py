@@ -87,9 +87,15 @@ def split_ws(device):
 
 def epilogue_bwd(gy, y=None, scale=None):
     """g = gy * (y > 0) * scale[c] on NHWC tensors (any of y/scale may be None)."""
+    _lib.require_device(gy, y, scale)
+    gy = nhwc(gy, torch.float32, 'epilogue_bwd', 'gy')
+    if y is not None:
+        y = nhwc(y, torch.float32, 'epilogue_bwd', 'y')
+    if scale is not None:
+        scale = _lib.dense(scale, torch.float32, 'epilogue_bwd', 'scale', align=True)
     N, C = gy.shape[0], gy.shape[1]
     M = gy.numel() // C
-    g = torch.empty_like(gy)
+    g = empty_nhwc(tuple(gy.shape), gy.device)
     _lib.call('mrcnn_epilogue_bwd', _lib.ptr(gy), _lib.ptr(y), _lib.ptr(scale), _lib.ptr(g),
               M, C, _lib.stream_ptr())
     return g
@@ -196,9 +202,13 @@ class _Conv2dFn(torch.autograd.Function):
     def forward(ctx, x, W, b, scale, shift, residual, stride, pad, relu, records_graph, grad_rows):
         # ``records_graph``: torch.is_grad_enabled() at the call (in here grad mode is always off and
         # ctx.needs_input_grad reports the inputs' requires_grad flags even under torch.no_grad())
-        _lib.require_device(x, W)
-        x = nhwc(x)
-        Wc = nhwc(W) if W.dim() == 4 else W.contiguous()
+        _lib.require_device(x, W, b, scale, shift, residual)
+        x = nhwc(x, torch.float32, 'conv2d')
+        Wc = nhwc(W, torch.float32, 'conv2d', 'W') if W.dim() == 4 else \
+            _lib.dense(W, torch.float32, 'conv2d', 'W', align=True)
+        b_param = b
+        b, scale, shift = (v if v is None else _lib.dense(v, torch.float32, 'conv2d', name, align=True)
+                           for name, v in (('b', b), ('scale', scale), ('shift', shift)))
         d = make_desc(x.shape, W.shape, stride, pad)
         if grad_rows is not None:
             _check_grad_rows(d, stride, pad, scale, residual)
@@ -208,7 +218,7 @@ class _Conv2dFn(torch.autograd.Function):
         if scale is not None:
             flags |= EPI_AFFINE
         if residual is not None:
-            residual = nhwc(residual)
+            residual = nhwc(residual, torch.float32, 'conv2d', 'residual')
             flags |= EPI_RESIDUAL
         if relu:
             flags |= EPI_RELU
@@ -228,7 +238,7 @@ class _Conv2dFn(torch.autograd.Function):
         ctx.has_res = residual is not None
         ctx.sparse_hint = grad_rows
         ctx.W_param = W
-        ctx.b_param = b
+        ctx.b_param = b_param
         ctx.save_for_backward(x, Wc, scale, y if relu else None)
         if RELU_TAP is not None and relu:
             RELU_TAP.append(('conv', y))
@@ -238,7 +248,7 @@ class _Conv2dFn(torch.autograd.Function):
     def backward(ctx, gy):
         x, Wc, scale, y = ctx.saved_tensors
         d = ctx.d
-        gy = nhwc(gy)
+        gy = nhwc(gy, torch.float32, 'conv2d', 'gy')
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], \
             ctx.has_bias and ctx.needs_input_grad[2]
         # through ReLU, then through the affine scale
@@ -285,9 +295,13 @@ class _StemFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x4, w784, b, scale, shift):
-        _lib.require_device(x4, w784)
+        _lib.require_device(x4, w784, b, scale, shift)
+        x4 = _lib.dense(x4, torch.float32, 'stem_conv', 'x4', align=True)
+        w784 = _lib.dense(w784, torch.float32, 'stem_conv', 'w784', align=True)
+        b, scale, shift = (v if v is None else _lib.dense(v, torch.float32, 'stem_conv', name, align=True)
+                           for name, v in (('b', b), ('scale', scale), ('shift', shift)))
         N, H, W_, four = x4.shape
-        assert four == 4 and x4.is_contiguous()
+        assert four == 4
         K = w784.shape[0]
         P, Q = conv_out_size(H, 7, 2, 3), conv_out_size(W_, 7, 2, 3)
         y = empty_nhwc((N, K, P, Q), x4.device)
@@ -319,9 +333,12 @@ class _Deconv2x2Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, W, b, relu):
-        _lib.require_device(x, W)
-        x = nhwc(x)
-        Wc = nhwc(W)     # logical (C, K, 2, 2) -> physical (C, 2, 2, K)
+        _lib.require_device(x, W, b)
+        x = nhwc(x, torch.float32, 'deconv2x2s2')
+        Wc = nhwc(W, torch.float32, 'deconv2x2s2', 'W')     # logical (C, K, 2, 2) -> physical (C, 2, 2, K)
+        b_param = b
+        if b is not None:
+            b = _lib.dense(b, torch.float32, 'deconv2x2s2', 'b', align=True)
         N, C, H, Wd = x.shape
         K = W.shape[1]
         if tuple(W.shape) != (C, K, 2, 2):
@@ -341,7 +358,7 @@ class _Deconv2x2Fn(torch.autograd.Function):
                       N, H, Wd, C, K, flags, _lib.stream_ptr())
         ctx.dims = (N, H, Wd, C, K)
         ctx.relu = relu
-        ctx.W_param, ctx.b_param = W, b
+        ctx.W_param, ctx.b_param = W, b_param
         ctx.save_for_backward(x, Wc, y if relu else None)
         if RELU_TAP is not None and relu:
             RELU_TAP.append(('deconv', y))
@@ -351,7 +368,7 @@ class _Deconv2x2Fn(torch.autograd.Function):
     def backward(ctx, gy):
         x, Wc, y = ctx.saved_tensors
         N, H, Wd, C, K = ctx.dims
-        gy = nhwc(gy)
+        gy = nhwc(gy, torch.float32, 'deconv2x2s2', 'gy')
         g = epilogue_bwd(gy, y, None) if ctx.relu else gy
         gx = gW = gb = None
         if ctx.needs_input_grad[0]:
@@ -425,8 +442,8 @@ def _stage_transposes(blocks, device):
         t = buf[off:off + Wc.numel()]
         off += Wc.numel()
         out[bi][key] = t
-        w[i], wT[i] = Wc.data_ptr(), t.data_ptr()
-        sc[i] = scale.data_ptr() if scale is not None else None
+        w[i], wT[i] = _lib.addr(Wc, 'w'), _lib.addr(t, 'wT')
+        sc[i] = _lib.addr(scale, 'row_scale')
         K[i], R[i], S[i], C[i] = d.K, d.R, d.S, d.C
     _lib.call('mrcnn_filter_flip_transpose_batched', n, w, wT, K, R, S, C, sc, _lib.stream_ptr())
     return out
@@ -454,7 +471,8 @@ def _dgrad_raw(d, g, Wc, res_g=None, res_y=None, out=None, accum=False,
         # fold_scale applied), else rebuilt here (it moves 2 x the filter bytes)
         if wT is None:
             wT = _flip_transpose(Wc, d, fold_scale,
-                                 _lib.workspace(4 * d.K * d.R * d.S * d.C, g.device, 'wT'))
+                                 _lib.workspace(4 * d.K * d.R * d.S * d.C, g.device,
+                                                'wT').view(torch.float32))
         _lib.call('mrcnn_conv2d_dgrad_wt', ctx_desc(d), _lib.ptr(g), _lib.ptr(wT), _lib.ptr(gx),
                   EPI_ACCUM if accum else 0, _lib.ptr(res_g), _lib.ptr(res_y), _lib.ptr(out_mask_y),
                   _lib.ptr(out_scale), _lib.ptr(split_ws(g.device)), _lib.stream_ptr())
@@ -784,7 +802,10 @@ class RoiSpec(object):
         # ``proj`` (inference only): the two projections of the map, ``projected_map(...)``, when the
         # caller pools several RoI sets from one map (MaskRCNN.predict_prepared: one head call per image)
         self.proj = proj
-        self.rois = rois.contiguous()
+        _lib.require_device(rois, order)
+        self.rois = _lib.dense(rois, torch.float32, 'RoiSpec', 'rois')
+        if order is not None:
+            order = _lib.dense(order, torch.int32, 'RoiSpec', 'order')
         self.outh, self.outw = int(outh), int(outw)
         self.spatial_scale = float(spatial_scale)
         self.bin_stride = int(bin_stride)
@@ -805,7 +826,8 @@ _proj_cache = {}
 def projected_map(x, W1, W4):
     """(conv1x1(x, W1), conv1x1(x, W4)) of an NHWC map, bias-free and without epilogue — the inputs
     ``RoiSpec(proj=)`` takes.  Cached per (map, filters) while autograd is off."""
-    x = nhwc(x)
+    _lib.require_device(x, W1, W4)
+    x = nhwc(x, torch.float32, 'projected_map')
     key = (id(x), x._version, x.data_ptr(), tuple(x.shape), id(W1), W1._version, W1.data_ptr(),
            id(W4), W4._version, W4.data_ptr())
     hit = _proj_cache.get('entry')
@@ -813,8 +835,8 @@ def projected_map(x, W1, W4):
         return hit[2], hit[3]
     d1 = make_desc(x.shape, W1.shape, 1, 0)
     d4 = make_desc(x.shape, W4.shape, 1, 0)
-    z1 = _fwd_raw(x, nhwc(W1), d1, None, None, None, False)
-    z4 = _fwd_raw(x, nhwc(W4), d4, None, None, None, False)
+    z1 = _fwd_raw(x, nhwc(W1, torch.float32, 'projected_map', 'W1'), d1, None, None, None, False)
+    z4 = _fwd_raw(x, nhwc(W4, torch.float32, 'projected_map', 'W4'), d4, None, None, None, False)
     _proj_cache['entry'] = (key, x, z1, z4)
     return z1, z4
 
@@ -871,6 +893,14 @@ class _StageBlock(object):
         (self.W1, self.s1, self.b1, self.W2, self.s2, self.b2,
          self.W3, self.s3, self.b3) = params[at:at + 9]
         self.W4, self.s4, self.b4 = params[at + 9:at + 12] if has_proj else (None, None, None)
+        for name in ('W1', 'W2', 'W3', 'W4', 's1', 'b1', 's2', 'b2', 's3', 'b3', 's4', 'b4'):
+            t = getattr(self, name)
+            if t is None:
+                continue
+            if t.dtype != torch.float32:
+                raise TypeError('building_block: %s must be %s, got %s' % (name, torch.float32, t.dtype))
+            if name[0] != 'W':      # (the filters go through nhwc() where they are read)
+                setattr(self, name, _lib.dense(t, torch.float32, 'building_block', name, align=True))
         w1 = _StageFn.FIXED_INPUTS + at
         self.i1, self.i2, self.i3, self.i4 = w1, w1 + 3, w1 + 6, w1 + 9
         self.d1 = self.d2 = self.d3 = self.d4 = None
@@ -921,8 +951,12 @@ class _StageFn(torch.autograd.Function):
         requires_grad flags even under torch.no_grad()); ``params``: per block
         W1,s1,b1,W2,s2,b2,W3,s3,b3 (+ W4,s4,b4 when proj[i])."""
         assert len(ctx.needs_input_grad) == _StageFn.FIXED_INPUTS + len(params)
-        _lib.require_device(x, params[0])
-        x = nhwc(x)
+        _lib.require_device(x, tail_rows, tail_slot, *params)
+        x = nhwc(x, torch.float32, 'building_block')
+        if tail_rows is not None and tail_rows.dtype != torch.int64:
+            raise TypeError('building_block: tail_rows must be %s, got %s' % (torch.int64, tail_rows.dtype))
+        if tail_slot is not None:
+            tail_slot = _lib.dense(tail_slot, torch.int32, 'building_block', 'tail_slot')
         ng = ctx.needs_input_grad
         training = records_graph and any(ng)
         blocks, at = [], 0
@@ -1022,7 +1056,8 @@ class _StageFn(torch.autograd.Function):
             R_, C_, Hh, Ww = y_top.shape
             if gy is None:
                 gy = torch.zeros((R_, C_), dtype=torch.float32, device=dev_)
-            gp = gy.reshape(R_, C_).contiguous()
+            gp = _lib.dense(gy.reshape(R_, C_), torch.float32, 'building_block', 'the pooled gradient',
+                            align=True)
             gr = nhwc(g_rows) if g_rows is not None else None
             gm = empty_nhwc((R_, C_, Hh, Ww), dev_)
             _lib.call('mrcnn_head_tail_bwd', _lib.ptr(gp), _lib.ptr(gr),

@@ -47,7 +47,7 @@ def copy_paste_meta(img_t, masks_t, img_s, masks_s, idx):
     meta = torch.empty((5 * n,), dtype=torch.int32, device=dev)
     idx_d = torch.from_numpy(idx.astype(np.int32)).to(dev) if K else None
     with torch.cuda.device(dev):
-        rows = _lib.workspace(n * S * 3 * 4, dev, tag='copy_paste_rows')
+        rows = _lib.workspace(n * S * 3 * 4, dev, tag='copy_paste_rows').view(torch.int32)
         _lib.call('mrcnn_copy_paste', _lib.ptr(t_nhwc), _lib.ptr(s_nhwc),
                   _lib.ptr(masks_t) if Gt else None, Gt, _lib.ptr(masks_s) if K else None, Gs,
                   _lib.ptr(idx_d), K, S, _lib.ptr(out), _lib.ptr(masks) if n else None,

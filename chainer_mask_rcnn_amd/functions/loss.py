@@ -14,6 +14,16 @@ def _ws(device, rows=0):
     return _lib.workspace(_lib.load().mrcnn_loss_workspace_bytes(rows), device, 'loss')
 
 
+def _rows(x, fn):
+    """x (R, ncls) float32 as the row-strided operand mrcnn_softmax / mrcnn_softmax_ce take (``ldx``):
+    unit inner stride and rows that do not overlap; anything else is copied."""
+    if x.dtype != torch.float32:
+        raise TypeError('%s: x must be %s, got %s' % (fn, torch.float32, x.dtype))
+    if x.dim() == 2 and (x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1])):
+        x = x.contiguous()
+    return x
+
+
 def _scalar(device):
     return torch.empty((), dtype=torch.float32, device=device)
 
@@ -23,8 +33,8 @@ class _SigmoidCEFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, t):
         _lib.require_device(x, t)
-        xc = x.contiguous()
-        t = t.contiguous()
+        xc = _lib.dense(x, torch.float32, 'sigmoid_cross_entropy', 'x')
+        t = _lib.dense(t, torch.int32, 'sigmoid_cross_entropy', 't')
         loss = _scalar(x.device)
         gx = torch.empty_like(xc) if x.requires_grad else None
         _lib.call('mrcnn_sigmoid_ce', _lib.ptr(xc), _lib.ptr(t), xc.numel(), _lib.ptr(loss),
@@ -53,13 +63,14 @@ class _MaskSigmoidCEFn(torch.autograd.Function):
     def forward(ctx, roi_masks, gt_label, gt_mask):
         from ._layout import nhwc, empty_nhwc
         _lib.require_device(roi_masks, gt_label, gt_mask)
-        x = nhwc(roi_masks)
+        x = nhwc(roi_masks, torch.float32, 'mask_sigmoid_cross_entropy', 'roi_masks')
         R, Kc, H, W = x.shape
         loss = _scalar(x.device)
         gx = empty_nhwc((R, Kc, H, W), x.device) if roi_masks.requires_grad else None
         # bind temporaries to names: a tensor created inside the argument list would be freed
         # (and its block possibly re-used) before the asynchronous kernel reads it
-        gt_label, gt_mask = gt_label.contiguous(), gt_mask.contiguous()
+        gt_label = _lib.dense(gt_label, torch.int32, 'mask_sigmoid_cross_entropy', 'gt_roi_labels')
+        gt_mask = _lib.dense(gt_mask, torch.int32, 'mask_sigmoid_cross_entropy', 'gt_roi_masks')
         _lib.call('mrcnn_mask_sigmoid_ce', _lib.ptr(x), _lib.ptr(gt_label),
                   _lib.ptr(gt_mask), R, H * W, Kc, _lib.ptr(loss), _lib.ptr(gx),
                   _lib.ptr(_ws(x.device)), _lib.stream_ptr())
@@ -89,7 +100,7 @@ class _SoftmaxCEFn(torch.autograd.Function):
         loss = _scalar(x.device)
         gx = torch.empty((R, ncls), dtype=torch.float32, device=x.device) \
             if x.requires_grad else None
-        t = t.contiguous()
+        t = _lib.dense(t, torch.int32, 'softmax_cross_entropy', 't')
         _lib.call('mrcnn_softmax_ce', _lib.ptr(x), ldx, _lib.ptr(t), R,
                   ncls, _lib.ptr(loss), _lib.ptr(gx), ncls, _lib.ptr(_ws(x.device, R)),
                   _lib.stream_ptr())
@@ -105,8 +116,7 @@ def softmax_cross_entropy(x, t):
     """F.softmax_cross_entropy(x (R,ncls), t int32), ignore_label=-1."""
     if t.dtype != torch.int32:
         raise TypeError('softmax_cross_entropy: t must be int32')
-    if x.stride(1) != 1:
-        x = x.contiguous()
+    x = _rows(x, 'softmax_cross_entropy')
     return _SoftmaxCEFn.apply(x, t)
 
 
@@ -114,10 +124,13 @@ class _SmoothL1Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, gt_loc, gt_label, sigma, cls):
-        _lib.require_device(pred, gt_loc, gt_label)
+        _lib.require_device(pred, gt_loc, gt_label, cls)
         assert pred.dim() == 2
-        pc = pred.contiguous()
-        gt_loc, gt_label = gt_loc.contiguous(), gt_label.contiguous()
+        pc = _lib.dense(pred, torch.float32, 'fast_rcnn_loc_loss', 'pred_loc')
+        gt_loc = _lib.dense(gt_loc, torch.float32, 'fast_rcnn_loc_loss', 'gt_loc')
+        gt_label = _lib.dense(gt_label, torch.int32, 'fast_rcnn_loc_loss', 'gt_label')
+        if cls is not None:
+            cls = _lib.dense(cls, torch.int32, 'fast_rcnn_loc_loss', 'cls')
         n, width = pc.shape
         loss = _scalar(pred.device)
         # the kernel writes only the selected 4-vectors of rows with label > 0
@@ -149,8 +162,7 @@ def fast_rcnn_loc_loss(pred_loc, gt_loc, gt_label, sigma, cls=None):
 def softmax(x):
     """F.softmax over axis 1 of (R, ncls) (models/mask_rcnn.py:208)."""
     _lib.require_device(x)
-    if x.stride(1) != 1:
-        x = x.contiguous()
+    x = _rows(x, 'softmax')
     R, ncls = x.shape
     y = torch.empty((R, ncls), dtype=torch.float32, device=x.device)
     _lib.call('mrcnn_softmax', _lib.ptr(x), x.stride(0), _lib.ptr(y), ncls, R, ncls,
@@ -177,6 +189,6 @@ def observe_accumulate(values, sums):
     for v in values:
         if v.dtype != torch.float32 or v.numel() != 1:
             raise ValueError('observe_accumulate: values must be float32 scalars')
-    ptrs = (ctypes.c_void_p * max(n, 1))(*[v.data_ptr() for v in values])
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[_lib.addr(v, 'values') for v in values])
     _lib.call('mrcnn_observe_accumulate', ptrs, n, _lib.ptr(sums), _lib.stream_ptr())
     return sums

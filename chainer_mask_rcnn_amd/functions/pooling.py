@@ -20,7 +20,7 @@ class _MaxPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         _lib.require_device(x)
-        x = nhwc(x)
+        x = nhwc(x, torch.float32, 'max_pooling_2d')
         N, C, H, W = x.shape
         P, Q = cover_all_out_size(H), cover_all_out_size(W)
         y = empty_nhwc((N, C, P, Q), x.device)
@@ -46,7 +46,7 @@ class _AvgPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         _lib.require_device(x)
-        x = nhwc(x)
+        x = nhwc(x, torch.float32, 'average_pooling_2d')
         R, C, H, W = x.shape
         y = torch.empty((R, C), dtype=torch.float32, device=x.device)
         _lib.call('mrcnn_avgpool_fwd', _lib.ptr(x), _lib.ptr(y), R, H * W, C, _lib.stream_ptr())
@@ -56,7 +56,7 @@ class _AvgPoolFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         R, C, H, W = ctx.shape
-        gy = gy.reshape(R, C).contiguous()
+        gy = _lib.dense(gy.reshape(R, C), torch.float32, 'average_pooling_2d', 'gy', align=True)
         gx = empty_nhwc((R, C, H, W), gy.device)
         _lib.call('mrcnn_avgpool_bwd', _lib.ptr(gy), _lib.ptr(gx), R, H * W, C, 0,
                   _lib.stream_ptr())

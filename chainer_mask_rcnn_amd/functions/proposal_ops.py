@@ -15,8 +15,8 @@ def decode_clip(anchor, loc, img_size, min_size=0., out=None):
     (``out`` = preallocated contiguous (roi, valid) to write into)."""
     _lib.require_device(anchor, loc)
     n = anchor.shape[0]
-    anchor = anchor.contiguous()
-    loc = loc.contiguous()
+    anchor = _lib.dense(anchor, torch.float32, 'decode_clip', 'anchor', align=True)
+    loc = _lib.dense(loc, torch.float32, 'decode_clip', 'loc', align=True)
     if out is not None:
         roi, valid = out
     else:
@@ -31,8 +31,8 @@ def decode_clip(anchor, loc, img_size, min_size=0., out=None):
 def topk_desc_batched(score, k, valid=None):
     """Stable descending top-k of every row of score (G, n) (valid (G, n) uint8 or None).
     Returns (order int32 (G, k), n_out int32 (G,))."""
-    _lib.require_device(score)
-    score = score.contiguous()
+    _lib.require_device(score, valid)
+    score = _lib.dense(score, torch.float32, 'topk_desc_batched', 'score')
     G, n = score.shape
     k = int(min(k, n)) if k > 0 else n
     order = torch.empty((G, max(k, 1)), dtype=torch.int32, device=score.device)
@@ -40,7 +40,7 @@ def topk_desc_batched(score, k, valid=None):
     per = (_lib.load().mrcnn_topk_workspace_bytes(n) + 63) // 64 * 64
     ws = _lib.workspace(per * G, score.device, 'topk')
     if valid is not None:
-        valid = valid.contiguous()
+        valid = _lib.dense(valid, torch.uint8, 'topk_desc_batched', 'valid')
     _lib.call('mrcnn_topk_desc_batched', _lib.ptr(score), _lib.ptr(valid), G, n, k,
               _lib.ptr(order), _lib.ptr(n_out), _lib.ptr(ws), _lib.stream_ptr())
     return order, n_out
@@ -48,8 +48,10 @@ def topk_desc_batched(score, k, valid=None):
 
 def topk_desc(score, k, valid=None):
     """Stable descending top-k. Returns (order int32 (k,), n_out int32 device scalar)."""
-    _lib.require_device(score)
-    score = score.contiguous()
+    _lib.require_device(score, valid)
+    score = _lib.dense(score, torch.float32, 'topk_desc', 'score')
+    if valid is not None:
+        valid = _lib.dense(valid, torch.uint8, 'topk_desc', 'valid')
     n = score.numel()
     k = int(min(k, n)) if k > 0 else n
     order = torch.empty((max(k, 1),), dtype=torch.int32, device=score.device)
@@ -62,7 +64,11 @@ def topk_desc(score, k, valid=None):
 
 def gather_rows(src, idx, n_dev=None):
     """dst[j] = src[idx[j]] for j < n_dev (zero rows after)."""
-    src = src.contiguous()
+    _lib.require_device(src, idx, n_dev)
+    src = _lib.dense(src, torch.float32, 'gather_rows', 'src')
+    idx = _lib.dense(idx, torch.int32, 'gather_rows', 'idx')
+    if n_dev is not None:
+        n_dev = _lib.dense(n_dev, torch.int32, 'gather_rows', 'n_dev')
     cols = src.shape[1]
     n_max = idx.numel()
     dst = torch.empty((n_max, cols), dtype=torch.float32, device=src.device)
@@ -73,8 +79,10 @@ def gather_rows(src, idx, n_dev=None):
 
 def nms_sorted(bbox, thresh, n_dev=None, limit=0):
     """NMS over score-sorted boxes. Returns (keep int32 (n_max,), n_keep int32 device scalar)."""
-    _lib.require_device(bbox)
-    bbox = bbox.contiguous()
+    _lib.require_device(bbox, n_dev)
+    bbox = _lib.dense(bbox, torch.float32, 'nms_sorted', 'bbox', align=True)
+    if n_dev is not None:
+        n_dev = _lib.dense(n_dev, torch.int32, 'nms_sorted', 'n_dev')
     n_max = bbox.shape[0]
     keep = torch.empty((max(n_max, 1),), dtype=torch.int32, device=bbox.device)
     n_keep = torch.empty((1,), dtype=torch.int32, device=bbox.device)
@@ -88,7 +96,8 @@ def nms_sorted(bbox, thresh, n_dev=None, limit=0):
 def nms_sorted_batched(bbox, n_dev, thresh, limit=0):
     """bbox (G, n_max, 4) sorted per group, n_dev (G,) int32. Returns keep (G,n_max), n_keep (G,)."""
     _lib.require_device(bbox, n_dev)
-    bbox = bbox.contiguous()
+    bbox = _lib.dense(bbox, torch.float32, 'nms_sorted_batched', 'bbox', align=True)
+    n_dev = _lib.dense(n_dev, torch.int32, 'nms_sorted_batched', 'n_dev')
     G, n_max = bbox.shape[0], bbox.shape[1]
     keep = torch.empty((G, max(n_max, 1)), dtype=torch.int32, device=bbox.device)
     n_keep = torch.empty((G,), dtype=torch.int32, device=bbox.device)
@@ -112,12 +121,13 @@ def soft_nms_method(method):
                      % (sorted(SOFT_NMS_METHODS), method))
 
 
-def _require_array(name, t, dtype, shape):
-    """The C ABI reads raw pointers: a wrong dtype or shape would read out of bounds."""
+def _require_array(name, t, dtype, shape, align=False):
+    """The C ABI reads raw pointers: a wrong dtype or shape would read out of bounds.  ``align``: the
+    operand holds box rows, read as one float4 — a view that starts off a 16-byte boundary is copied."""
     if t.dtype != dtype or tuple(t.shape) != tuple(shape):
         raise ValueError('%s must be %s of shape %s, got %s %s'
                          % (name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
-    return t.contiguous()
+    return _lib.dense(t, dtype, name, name, align=align)
 
 
 def soft_nms_sorted_batched(bbox, prob, n_dev, method, overlap_thresh=0.3, sigma=0.5,
@@ -130,7 +140,7 @@ def soft_nms_sorted_batched(bbox, prob, n_dev, method, overlap_thresh=0.3, sigma
     if bbox.dim() != 3 or bbox.shape[2] != 4:
         raise ValueError('bbox must be (G, n_max, 4), got %s' % (tuple(bbox.shape),))
     G, n_max = bbox.shape[0], bbox.shape[1]
-    bbox = _require_array('bbox', bbox, torch.float32, (G, n_max, 4))
+    bbox = _require_array('bbox', bbox, torch.float32, (G, n_max, 4), align=True)
     prob = _require_array('prob', prob, torch.float32, (G, n_max))
     n_dev = _require_array('n_dev', n_dev, torch.int32, (G,))
     keep = torch.empty((G, max(n_max, 1)), dtype=torch.int32, device=bbox.device)
@@ -150,7 +160,7 @@ def box_vote(bbox, prob, n_dev, keep, n_keep, vote_thresh=0.8):
     if bbox.dim() != 3 or bbox.shape[2] != 4:
         raise ValueError('bbox must be (G, n_max, 4), got %s' % (tuple(bbox.shape),))
     G, n_max = bbox.shape[0], bbox.shape[1]
-    bbox = _require_array('bbox', bbox, torch.float32, (G, n_max, 4))
+    bbox = _require_array('bbox', bbox, torch.float32, (G, n_max, 4), align=True)
     prob = _require_array('prob', prob, torch.float32, (G, n_max))
     n_dev = _require_array('n_dev', n_dev, torch.int32, (G,))
     keep = _require_array('keep', keep, torch.int32, (G, max(n_max, 1)))

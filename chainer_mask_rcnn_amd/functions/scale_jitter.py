@@ -26,12 +26,27 @@ def prepare_image_crop(model_mean, img_chw, scale, resized, offset, crop_size, x
     stage = torch.empty(host.shape, dtype=torch.uint8 if is_u8 else torch.float32, pin_memory=True)
     np.copyto(stage.numpy(), host)
     src = stage.to(device, non_blocking=True)
+    return prepare_image_crop_device(model_mean, src, scale, (rH, rW), (oy, ox), S, x_flip)
+
+
+def prepare_image_crop_device(model_mean, src, scale, resized, offset, crop_size, x_flip):
+    """``prepare_image_crop`` for an image that is on the device already: ``src`` (3, H, W) uint8 or
+    float32 device tensor, as uploaded."""
+    _lib.require_device(src)
+    if src.dtype not in (torch.uint8, torch.float32):
+        raise TypeError('prepare_image_crop_device: src must be %s or %s, got %s'
+                        % (torch.uint8, torch.float32, src.dtype))
+    src = _lib.dense(src, src.dtype, 'prepare_image_crop_device', 'src')
+    S = int(crop_size)
+    (rH, rW), (oy, ox) = (int(v) for v in resized), (int(v) for v in offset)
+    _, H, W = src.shape
+    device = src.device
     canvas = torch.empty((1, S, S, 3), dtype=torch.float32, device=device)
     mean = (_lib.c_f32 * 3)(*[float(v) for v in np.asarray(model_mean).ravel()])
     with torch.cuda.device(device):
-        _lib.call('mrcnn_prepare_image_crop', _lib.ptr(src), int(is_u8), 3, int(H), int(W),
-                  float(scale), mean, _lib.ptr(canvas), S, S, rH, rW, oy, ox, 0, int(bool(x_flip)),
-                  _lib.stream_ptr())
+        _lib.call('mrcnn_prepare_image_crop', _lib.ptr(src), int(src.dtype == torch.uint8), 3, int(H),
+                  int(W), float(scale), mean, _lib.ptr(canvas), S, S, rH, rW, oy, ox, 0,
+                  int(bool(x_flip)), _lib.stream_ptr())
     return canvas.permute(0, 3, 1, 2)[0]
 
 
@@ -76,7 +91,7 @@ def resize_crop_masks_meta(packed_device, resized, offset, crop_size, x_flip=Fal
     ys, xs = crop_tables((H, W), resized, offset, S, x_flip)
     tables = torch.from_numpy(np.concatenate([ys, xs])).to(dev)
     with torch.cuda.device(dev):
-        row_stats = _lib.workspace(G * S * 3 * 4, dev, tag='scale_jitter_rows')
+        row_stats = _lib.workspace(G * S * 3 * 4, dev, tag='scale_jitter_rows').view(torch.int32)
         _lib.call('mrcnn_mask_resize_crop', _lib.ptr(words), G, H, W, _lib.ptr(tables[:S]),
                   _lib.ptr(tables[S:]), S, _lib.ptr(out), _lib.ptr(meta), _lib.ptr(meta[G * 4:]),
                   _lib.ptr(row_stats), _lib.stream_ptr())

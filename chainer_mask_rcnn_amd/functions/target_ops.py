@@ -12,7 +12,8 @@ def bbox_iou_argmax(boxes_a, boxes_b, want_matrix=False):
     i32[, iou (na,g), col_max (g,)]).  No rows and ``want_matrix``: ValueError, as NumPy's max of
     an empty column (the library writes no col_max then)."""
     _lib.require_device(boxes_a, boxes_b)
-    boxes_a, boxes_b = boxes_a.contiguous(), boxes_b.contiguous()
+    boxes_a = _lib.dense(boxes_a, torch.float32, 'bbox_iou_argmax', 'boxes_a')
+    boxes_b = _lib.dense(boxes_b, torch.float32, 'bbox_iou_argmax', 'boxes_b')
     na, g = boxes_a.shape[0], boxes_b.shape[0]
     if want_matrix and na == 0:
         raise ValueError('bbox_iou_argmax: column maxima of an IoU matrix without rows')
@@ -29,6 +30,10 @@ def bbox_iou_argmax(boxes_a, boxes_b, want_matrix=False):
 
 
 def anchor_labels(iou, max_iou, gt_max, neg_iou_thresh, pos_iou_thresh):
+    _lib.require_device(iou, max_iou, gt_max)
+    iou = _lib.dense(iou, torch.float32, 'anchor_labels', 'iou')
+    max_iou = _lib.dense(max_iou, torch.float32, 'anchor_labels', 'max_iou')
+    gt_max = _lib.dense(gt_max, torch.float32, 'anchor_labels', 'gt_max')
     na, g = iou.shape
     label = torch.empty((na,), dtype=torch.int32, device=iou.device)
     _lib.call('mrcnn_anchor_labels', _lib.ptr(iou), _lib.ptr(max_iou), _lib.ptr(gt_max), na, g,
@@ -37,6 +42,15 @@ def anchor_labels(iou, max_iou, gt_max, neg_iou_thresh, pos_iou_thresh):
 
 
 def anchor_targets_finish(anchor_inside, inside_index, label_inside, argmax, bbox, disabled, n_anchor):
+    fn = 'anchor_targets_finish'
+    _lib.require_device(anchor_inside, inside_index, label_inside, argmax, bbox, disabled)
+    anchor_inside = _lib.dense(anchor_inside, torch.float32, fn, 'anchor_inside')
+    inside_index = _lib.dense(inside_index, torch.int32, fn, 'inside_index')
+    label_inside = _lib.dense(label_inside, torch.int32, fn, 'label_inside')
+    argmax = _lib.dense(argmax, torch.int32, fn, 'argmax')
+    bbox = _lib.dense(bbox, torch.float32, fn, 'bbox')
+    if disabled is not None:
+        disabled = _lib.dense(disabled, torch.int32, fn, 'disabled')
     dev = anchor_inside.device
     loc = torch.empty((n_anchor, 4), dtype=torch.float32, device=dev)
     label = torch.empty((n_anchor,), dtype=torch.int32, device=dev)
@@ -49,6 +63,13 @@ def anchor_targets_finish(anchor_inside, inside_index, label_inside, argmax, bbo
 
 
 def proposal_targets_gather(cand, bbox, gt_label, assigned, chosen, n_fg, mean, std):
+    fn = 'proposal_targets_gather'
+    _lib.require_device(cand, bbox, gt_label, assigned, chosen)
+    cand = _lib.dense(cand, torch.float32, fn, 'cand', align=True)    # rows read as one float4
+    bbox = _lib.dense(bbox, torch.float32, fn, 'bbox')
+    gt_label = _lib.dense(gt_label, torch.int32, fn, 'gt_label')
+    assigned = _lib.dense(assigned, torch.int32, fn, 'assigned')
+    chosen = _lib.dense(chosen, torch.int32, fn, 'chosen')
     dev = cand.device
     n = int(chosen.numel())
     sample_roi = torch.empty((n, 4), dtype=torch.float32, device=dev)
@@ -67,8 +88,10 @@ def mask_targets(masks_u8, sample_roi, gt_index, n_fg, mask_size, n=None):
     """masks_u8 (G,H,W) uint8 device -> (n, M, M) int32 {-1,0,1}.  ``n`` defaults to the rows of
     ``sample_roi``; a caller that holds only the ``n_fg`` foreground rows (the library reads no
     others) passes the full row count."""
-    _lib.require_device(masks_u8, sample_roi)
-    assert masks_u8.dtype == torch.uint8 and masks_u8.is_contiguous()
+    _lib.require_device(masks_u8, sample_roi, gt_index)
+    masks_u8 = _lib.dense(masks_u8, torch.uint8, 'mask_targets', 'masks_u8')
+    sample_roi = _lib.dense(sample_roi, torch.float32, 'mask_targets', 'sample_roi')
+    gt_index = _lib.dense(gt_index, torch.int32, 'mask_targets', 'gt_index')
     G, H, W = masks_u8.shape
     n = int(sample_roi.shape[0]) if n is None else int(n)
     assert int(n_fg) <= min(n, int(sample_roi.shape[0]), int(gt_index.shape[0]))

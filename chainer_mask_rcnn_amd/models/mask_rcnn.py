@@ -89,7 +89,9 @@ class MaskRCNN(torch.nn.Module):
         counts = torch.empty((n_fg,), dtype=torch.int32, device=dev)
         ws = _lib.workspace(_lib.load().mrcnn_detect_sort_workspace_bytes(R, self.n_class), dev,
                             'detect')
-        prob, cls_bbox = prob.contiguous(), cls_bbox.contiguous()
+        _lib.require_device(prob, cls_bbox)
+        prob = _lib.dense(prob, torch.float32, '_suppress_queue', 'prob')
+        cls_bbox = _lib.dense(cls_bbox, torch.float32, '_suppress_queue', 'cls_bbox', align=True)
         _lib.call('mrcnn_detect_sort', _lib.ptr(prob), _lib.ptr(cls_bbox),
                   R, self.n_class, float(self.score_thresh), _lib.ptr(sorted_boxes),
                   _lib.ptr(sorted_prob), _lib.ptr(counts), _lib.ptr(ws), _lib.stream_ptr())
@@ -161,8 +163,13 @@ class MaskRCNN(torch.nn.Module):
         queued = []
         for index in range(len(sizes)):
             lo, hi = int(bounds[index]), int(bounds[index + 1])
-            roi = rois[lo:hi].contiguous()
+            # box rows are read as one float4: a slice that starts off a 16-byte boundary is copied
+            _lib.require_device(rois, roi_cls_locs)
+            roi = _lib.dense(rois[lo:hi], torch.float32, '_queue_detections', 'rois', align=True)
             loc = roi_cls_locs[lo:hi]
+            if loc.dtype != torch.float32:
+                raise TypeError('_queue_detections: roi_cls_locs must be %s, got %s'
+                                % (torch.float32, loc.dtype))
             prob = probs[lo:hi].contiguous()
             R = roi.shape[0]
             cls_bbox = torch.empty((R, self.n_class, 4), dtype=torch.float32, device=roi.device)
@@ -290,7 +297,8 @@ class MaskRCNN(torch.nn.Module):
                 masks.append(np.zeros((0, size[0], size[1]), dtype=bool))
                 continue
             from ..functions._layout import nhwc
-            logits = nhwc(roi_mask)
+            _lib.require_device(roi_mask)
+            logits = nhwc(roi_mask, torch.float32, '_to_masks', 'roi_masks')
             dev = logits.device
             out = torch.empty((D, size[0], size[1]), dtype=torch.uint8, device=dev)
             label_d = torch.tensor(label, dtype=torch.int32, device=dev)

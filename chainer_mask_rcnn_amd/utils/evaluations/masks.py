@@ -75,7 +75,8 @@ def paste_packed(roi_mask_logits, label, bbox, size):
     extent = torch.empty((D, 4), dtype=torch.int32, device=dev)
     if D == 0:
         return packed, area, extent
-    logits = nhwc(roi_mask_logits)
+    _lib.require_device(roi_mask_logits)
+    logits = nhwc(roi_mask_logits, torch.float32, 'paste_packed', 'roi_mask_logits')
     label_d = torch.tensor(np.asarray(label, np.int32), device=dev)
     bbox_d = torch.tensor(np.asarray(bbox, np.float32), device=dev)
     _lib.call('mrcnn_paste_masks_packed', _lib.ptr(logits), _lib.ptr(label_d), _lib.ptr(bbox_d),
@@ -98,6 +99,9 @@ def queue_intersections(a, b, W):
                          % (tuple(pa.shape[1:]), tuple(pb.shape[1:])))
     inter = torch.zeros((P, G), dtype=torch.int32, device=pa.device)
     if P and G and H:
+        _lib.require_device(pa, ea, pb, eb)
+        pa, pb = (_lib.dense(t, torch.int64, 'queue_intersections', 'packed') for t in (pa, pb))
+        ea, eb = (_lib.dense(t, torch.int32, 'queue_intersections', 'extent') for t in (ea, eb))
         _lib.call('mrcnn_mask_intersect', _lib.ptr(pa), _lib.ptr(ea), P, _lib.ptr(pb),
                   _lib.ptr(eb), G, H, int(W), _lib.ptr(inter), _lib.stream_ptr())
     return inter
@@ -161,14 +165,16 @@ def boundary_packed(packed_set, size, dilation_ratio=0.02, dilation=None):
     d = boundary_dilation((H, W), dilation_ratio) if dilation is None else int(dilation)
     if d < 1:
         raise ValueError('dilation must be >= 1, got %d' % d)
-    _lib.require_device(packed)
+    _lib.require_device(packed, extent)
     dev = packed.device
-    out = torch.empty_like(packed)
+    out = torch.empty(tuple(packed.shape), dtype=torch.int64, device=dev)
     area = torch.empty((N,), dtype=torch.int32, device=dev)
     if N == 0 or H == 0 or W == 0:
         out.zero_()
         area.zero_()
         return out, area, extent
+    packed = _lib.dense(packed, torch.int64, 'boundary_packed', 'packed')
+    extent = _lib.dense(extent, torch.int32, 'boundary_packed', 'extent')
     nbytes = _lib.load().mrcnn_mask_boundary_workspace_bytes(N, H, W)
     ws = _lib.workspace(nbytes, dev, tag='mask_boundary')
     _lib.call('mrcnn_mask_boundary', _lib.ptr(packed), _lib.ptr(extent), N, H, W, d,

@@ -78,7 +78,8 @@ def queue_encode(packed, area, extent, size):
         raise ValueError('packed masks of shape %s for an image of size %s'
                          % (tuple(packed.shape), (H, W)))
     _lib.require_device(packed, extent)
-    packed, extent = packed.contiguous(), extent.contiguous()
+    packed = _lib.dense(packed, torch.int64, 'queue_encode', 'packed')
+    extent = _lib.dense(extent, torch.int32, 'queue_encode', 'extent')
     N = packed.shape[0]
     # every offset of one launch stays below 2^31 (at most 7 characters per count)
     step = max(1, _I31 // (7 * (H * W + 1)) - 1)

@@ -74,7 +74,9 @@ def _convert(label_instance, label_class, return_masks, mask_by_class):
     if H == 0 or W == 0:
         return empty(0), 0, no_masks
     ws = _lib.workspace(4 * 4 * _WINDOW_WORDS, dev, tag='label_instances')
-    bitmaps, prefix = ws[:8 * _WINDOW_WORDS], ws[8 * _WINDOW_WORDS:16 * _WINDOW_WORDS]
+    # the prototypes name 32-bit words: typed views of the byte workspace
+    bitmaps = ws[:8 * _WINDOW_WORDS].view(torch.int32)
+    prefix = ws[8 * _WINDOW_WORDS:16 * _WINDOW_WORDS].view(torch.int32)
     meta = empty(6)
     args = (_lib.ptr(ins), ins.element_size(), _lib.ptr(cls), cls.element_size(), H, W,
             int(bool(mask_by_class)))

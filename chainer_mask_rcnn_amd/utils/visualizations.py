@@ -117,7 +117,8 @@ def _packed_masks(masks, boxes, on, H, W, dev):
             raise ValueError('packed masks of shape %s for %d instances on a %dx%d image'
                              % (tuple(packed.shape), N, H, W))
         _lib.require_device(packed, extent)
-        return packed.to(dev).contiguous(), extent.to(dev, torch.int32).contiguous()
+        return (_lib.dense(packed.to(dev), torch.int64, 'draw_instance_bboxes', 'masks[0] (packed)'),
+                extent.to(dev, torch.int32).contiguous())
     if isinstance(masks, torch.Tensor):
         if tuple(masks.shape) != (N, H, W):
             raise ValueError('device masks must be (N, H, W) = %s, got %s'
@@ -152,6 +153,10 @@ def draw_instances_device(img, boxes, labels, n_class, masks=None, captions=None
                           thickness=1, alpha=0.5, draw=None):
     """draw_instance_bboxes on a device image: img (H, W, 3) uint8 device tensor drawn IN
     PLACE (queued, not synchronised); boxes (N, 4) host array, truncated with astype(int)."""
+    _lib.require_device(img)
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or not img.is_contiguous():
+        raise TypeError('draw_instances_device: img must be a contiguous %s (H, W, 3) tensor (it is '
+                        'drawn in place), got %s %s' % (torch.uint8, img.dtype, tuple(img.shape)))
     H, W = int(img.shape[0]), int(img.shape[1])
     dev = img.device
     boxes = np.clip(np.asarray(boxes).astype(int), -_BOX_LIMIT, _BOX_LIMIT).reshape(-1, 4)
@@ -285,7 +290,7 @@ def tile_images_device(imgs, tile_shape):
         _lib.require_device(t)
         if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8 or t.device != dev:
             raise ValueError('get_tile_image expects (h, w, 3) uint8 images on one device')
-        table[k] = _TileCell(t.data_ptr(), t.shape[0], t.shape[1], oh, ow, oy, ox)
+        table[k] = _TileCell(_lib.addr(t, 'src'), t.shape[0], t.shape[1], oh, ow, oy, ox)
     _lib.call('mrcnn_tile_images', table, len(cells), rows, cols, cell_h, cell_w, _lib.ptr(out),
               _lib.stream_ptr())
     return out
