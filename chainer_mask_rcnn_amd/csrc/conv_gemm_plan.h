@@ -40,6 +40,8 @@ constexpr bool single_buffered(int tm, int mode)
 struct GemmKnobs {
     int split_bf16 = 3;            // bit 0: 128x128 kernels, bit 1: 64x64 forward form on the split-operand
                                    // arithmetic (see SPLIT); 0 = fp32 MFMA everywhere
+    int split_planes = 3;          // bf16 planes per operand of those launches (conv_gemm_kernel's NP): 3, 2 or 1.
+                                   // Read by pick_inst() alone: the plan is the same for all three
     int big_split_k = -1;          // small-M problems as 128x128 tiles cut along K: -1 = the one-round rule of
                                    // plan_gemm(), 0 = off (64x64 tiles), k > 0 = aim at k workgroups
     int big_split_min_slices = 16; // fewest K slices per slab of the one-round rule
@@ -52,11 +54,17 @@ struct GemmKnobs {
     int position_major_rows = 1;   // position-major GEMM rows (choose_perm)
 };
 
+// Is `value` legal for the knob called `name`?  (Knobs without a closed value set take any.)
+inline bool knob_value_ok(const char *name, int value)
+{
+    return strcmp(name, "split_planes") != 0 || (value >= 1 && value <= 3);
+}
+
 // Sets the knob called `name`; false when it is not one of GemmKnobs'.
 inline bool set_knob(GemmKnobs &k, const char *name, int value)
 {
     const struct { const char *name; int *at; } table[] = {
-        {"split_bf16", &k.split_bf16}, {"big_split_k", &k.big_split_k},
+        {"split_bf16", &k.split_bf16}, {"split_planes", &k.split_planes}, {"big_split_k", &k.big_split_k},
         {"big_split_min_slices", &k.big_split_min_slices}, {"w8_min_k", &k.w8_min_k}, {"w8", &k.w8},
         {"pw", &k.pw}, {"fused_tail", &k.fused_tail}, {"big_min_tiles", &k.big_min_tiles},
         {"small_m_split", &k.small_m_split}, {"tiny_split", &k.tiny_split},
@@ -125,21 +133,22 @@ enum Variant { INST_GENERAL = 0, INST_PW, INST_K3, INST_WPERM, INST_W8 };
 struct GemmInst {
     bool split;      // split-operand arithmetic (SPLIT), else fp32 MFMA
     int variant;     // Variant
+    int planes;      // split: bf16 planes per operand (GemmKnobs::split_planes), else 0
 };
 
 // the instantiation of a launch on 64 tm x 64 tm tiles
 inline GemmInst pick_inst(const GemmShape &p, int tm, const GemmKnobs &k)
 {
     if (p.mode == WGRAD) {
-        if (tm == 2 && (k.split_bf16 & 1) && p.perm_n == 0) return {true, INST_GENERAL};
-        return {false, p.perm_n > 0 ? INST_WPERM : INST_GENERAL};
+        if (tm == 2 && (k.split_bf16 & 1) && p.perm_n == 0) return {true, INST_GENERAL, k.split_planes};
+        return {false, p.perm_n > 0 ? INST_WPERM : INST_GENERAL, 0};
     }
     if (p.mode == FWD && (k.split_bf16 & (tm == 2 ? 1 : 2))) {
-        if ((k.pw & 1) && pw_plain(p)) return {true, INST_PW};
-        if ((k.pw & 2) && k3_plain(p)) return {true, INST_K3};
-        return {true, INST_GENERAL};
+        if ((k.pw & 1) && pw_plain(p)) return {true, INST_PW, k.split_planes};
+        if ((k.pw & 2) && k3_plain(p)) return {true, INST_K3, k.split_planes};
+        return {true, INST_GENERAL, k.split_planes};
     }
-    return {false, INST_GENERAL};
+    return {false, INST_GENERAL, 0};
 }
 
 struct GemmLaunch {
@@ -292,7 +301,7 @@ inline void add_w8(GemmPlan &g, const GemmShape &p, const GemmKnobs &k)
     l.m_hi = p.M;
     l.grid_x = T;
     l.grid_y = 1;
-    l.inst = {true, INST_W8};
+    l.inst = {true, INST_W8, k.split_planes};
     if (splits >= 2) set_tail(g, l, rows_main, main_rows_tiles * tn, tail_tiles, slices, splits);
 }
 

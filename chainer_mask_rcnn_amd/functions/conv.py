@@ -345,7 +345,7 @@ class _Deconv2x2Fn(torch.autograd.Function):
             raise ValueError('deconv: filter must be (in, out, 2, 2), got %s' % (tuple(W.shape),))
         y = empty_nhwc((N, K, 2 * H, 2 * Wd), x.device)
         flags = (EPI_BIAS if b is not None else 0) | (EPI_RELU if relu else 0)
-        if DECONV_FORWARD_FORM and GEMM_ARITHMETIC == 'split_bf16x3':
+        if DECONV_FORWARD_FORM and GEMM_ARITHMETIC in SPLIT_GEMM_ARITHMETICS:
             # forward form on the transposed filter (4K, C): both operands K-contiguous -> the
             # split-operand kernels; the K-strided form below runs on fp32 MFMA
             wT = _lib.workspace(4 * C * 4 * K, x.device, 'deconv-wT').view(torch.float32)
@@ -531,6 +531,10 @@ WINOGRAD_TRAIN_FORWARD = True         # False / 'conv2d' / 'stage' / True (both;
 def uses_winograd(d):
     if not (USE_WINOGRAD and d.R == 3 and d.S == 3 and d.stride == 1 and d.pad == 1):
         return False
+    # 'bf16x1': the direct kernel at one product per tap (9 units of matrix work per output) beats the
+    # Winograd GEMMs, which always run six (36 / 16 x 6 = 13.5), and is the arithmetic asked for
+    if GEMM_ARITHMETIC == 'bf16x1':
+        return False
     tiles = d.N * ((d.H + 3) // 4) * ((d.W + 3) // 4)
     return min(d.C, d.K) >= WINOGRAD_MIN_CHANNELS and tiles * d.C * d.K >= WINOGRAD_MIN_WORK
 
@@ -563,8 +567,15 @@ _wino_u_cache = {}
 # gradient, the position-major and the 64x64 weight gradient stay on fp32 MFMA.
 # 'fp32': v_mfma_f32_32x32x2_f32 everywhere (the default up to round 3; bench.py reports it as
 # `fp32_mfma`).
+# 'split_bf16x2' / 'bf16x1': the same kernels staging two planes / one plane and issuing three
+# products / one product per K step ("split_planes" knob; csrc/conv_gemm_kernel.h, NP): reduced
+# precision on request — 16-bit-class operands (tighter than the TF32 the reference's cuDNN uses by
+# default) and plain bf16 operands.  Same launch plan, same K order, fp32 accumulation and storage.
 DEFAULT_GEMM_ARITHMETIC = 'split_bf16x3'
 GEMM_ARITHMETIC = DEFAULT_GEMM_ARITHMETIC
+# name -> (split_bf16, split_planes) of mrcnn_set_tuning
+GEMM_ARITHMETICS = {'fp32': (0, 3), 'split_bf16x3': (3, 3), 'split_bf16x2': (3, 2), 'bf16x1': (3, 1)}
+SPLIT_GEMM_ARITHMETICS = ('split_bf16x3', 'split_bf16x2', 'bf16x1')     # the split-operand kernel family
 
 
 def set_gemm_arithmetic(kind):
@@ -579,12 +590,36 @@ def set_gemm_arithmetic(kind):
     * parts of an element below 2^-126 may be flushed to zero: the error of an element's
       representation is < 3 x 2^-126 in absolute terms (relative to elements below ~1e-33 that is
       more than an fp32 rounding).
-    Asserted by tests/test_gpu_split_bf16.py (device) and tests/test_split_arithmetic_cpu.py (model)."""
+    Asserted by tests/test_gpu_split_bf16.py (device) and tests/test_split_arithmetic_cpu.py (model).
+
+    'split_bf16x2' and 'bf16x1' run the same kernels on fewer planes of the same split
+    (x = hi + mid + lo; hi = bf16(x), mid = bf16(x - hi)), fp32 accumulation and fp32 storage as ever:
+    * 'split_bf16x2' multiplies hi + mid of each operand (16 significand bits) as hi*hi + hi*mid +
+      mid*hi: an error of about 3 x 2^-16 of sum |a||b| per output, half the matrix-pipe work;
+    * 'bf16x1' multiplies hi of each operand (8 significand bits), the single bf16 product of mixed
+      precision: about 2^-7 of sum |a||b| per output, one sixth of the matrix-pipe work.
+    Epilogue operands (bias, scale, shift, residual, masks) are never rounded.  Kernels that run fp32
+    MFMA under 'split_bf16x3' (strided data gradient, position-major and 64x64 weight gradient) do
+    so under every name.  The Winograd route (``uses_winograd``) always runs three planes — its
+    transforms amplify operand rounding; it stays on under 'split_bf16x2' and is switched OFF
+    under 'bf16x1', where the direct 3x3 kernel at one product per tap is both cheaper and the
+    arithmetic that was asked for.  (The library knob alone, ``MRCNN_TUNE=split_planes=1``, does
+    not change the route: routed layers then still run Winograd on three planes.)
+    Operand range: the finite ranges and the flushing of 'split_bf16x3' apply (one or two parts
+    instead of three).  A NaN operand gives NaN.  An infinite operand, or a finite one beyond
+    3.3895e38, gives NaN under 'split_bf16x2' (mid = inf - inf) as under 'split_bf16x3', but under
+    'bf16x1' hi = +-inf is the only plane and the outputs that read it are +-inf as in IEEE
+    multiplication (NaN where it meets a zero or an infinity of the other sign).  Asserted by
+    tests/test_gpu_arithmetic_ladder.py."""
     global GEMM_ARITHMETIC
-    if kind not in ('fp32', 'split_bf16x3'):
-        raise ValueError("gemm arithmetic must be 'fp32' or 'split_bf16x3', got %r" % (kind,))
-    _lib.set_tuning('split_bf16', 3 if kind == 'split_bf16x3' else 0)
+    if kind not in GEMM_ARITHMETICS:
+        raise ValueError('gemm arithmetic must be one of %s, got %r' % (', '.join(map(repr, GEMM_ARITHMETICS)), kind))
+    split_bf16, planes = GEMM_ARITHMETICS[kind]
+    _lib.load()                                     # (a library that cannot be loaded changes nothing)
+    _lib.set_tuning('split_planes', planes)
+    _lib.set_tuning('split_bf16', split_bf16)
     GEMM_ARITHMETIC = kind
+    _wino_u_cache.clear()                           # the route may change with the name: no stale filters
 
 
 def weights_changed():

@@ -280,6 +280,16 @@ int64_t mrcnn_conv2d_split_workspace_bytes(void);
  *   staged as three bf16 planes whose sum is the fp32 element exactly, six bf16 MFMAs per K step,
  *   fp32 accumulation.  Error against float64 is at (measured: below) the fp32-MFMA kernels' level
  *   (tests/test_gpu_split_bf16.py, tests/test_split_arithmetic_cpu.py).
+ *   "split_planes" (default 3; legal 1, 2, 3 — any other value is an error and keeps the setting):
+ *   how many of those planes the launches that "split_bf16" puts on the split kernels stage and
+ *   multiply.  3: all six products, fp32-accurate.  2: hi and mid, the products mid*hi, hi*mid,
+ *   hi*hi — operands of 16 significand bits, error about 3 x 2^-16 of sum |a||b|, half the
+ *   matrix-pipe work.  1: hi only, the product hi*hi — bf16 operands, error about 2^-7 of
+ *   sum |a||b|, one sixth.  fp32 accumulation, fp32 in / out and unrounded epilogue operands in
+ *   all three.  No effect while "split_bf16" is 0, none on the kernels that run fp32 MFMA anyway,
+ *   none on the launch plan (same route, tiles and K cuts for 1, 2 and 3), and none on the
+ *   launches of the Winograd entry points (mrcnn_conv3x3_wino_*), which always run three planes.
+ *   (tests/test_gpu_arithmetic_ladder.py, tests/test_arithmetic_ladder_cpu.py)
  *   "big_min_tiles" (default 384): fewest 128x128 tiles for which the 128x128 kernels are used
  *   (1 forces them; lets small test problems exercise the kernels of the full-size step).
  *   "big_split_k" (default -1 since round 6): with -1, a small-M, K-deep forward-form problem whose

@@ -1,9 +1,9 @@
 """Developer tool: per-shape TFLOP/s of the implicit-GEMM conv family on the C2 shapes."""
-import sys, os, ctypes
+import argparse, sys, os, ctypes
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from chainer_mask_rcnn_amd import _lib
-from chainer_mask_rcnn_amd.functions.conv import make_desc, ctx_desc, split_ws
+from chainer_mask_rcnn_amd.functions.conv import make_desc, ctx_desc, split_ws, set_gemm_arithmetic
 from chainer_mask_rcnn_amd.functions._layout import empty_nhwc
 
 dev = torch.device('cuda:0')
@@ -44,8 +44,17 @@ def timeit(fn, iters=10):
 
 
 def main():
-    only = sys.argv[1] if len(sys.argv) > 1 else None
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument('only', nargs='?', default=None, help='substring of the shape names to run')
+    ap.add_argument('--arithmetic', default=None, choices=['fp32', 'split_bf16x3', 'split_bf16x2', 'bf16x1'],
+                    help='arithmetic of the convolution GEMMs (functions.conv.set_gemm_arithmetic; default '
+                         'split_bf16x3: fp32-accurate; split_bf16x2: 16-bit-class operands; bf16x1: bf16 '
+                         'operands; all with fp32 accumulation and fp32 weights)')
+    args = ap.parse_args()
+    only = args.only
     lib = _lib.load()
+    if args.arithmetic is not None:
+        set_gemm_arithmetic(args.arithmetic)
     for kv in os.environ.get('BENCH_TUNE', '').split(','):
         if '=' in kv:
             k, v = kv.split('=')

@@ -39,7 +39,14 @@ def main():
                          'names for --dataset voc, class0..class79 for coco)')
     ap.add_argument('--out', default='demo_out', help='output directory')
     add_postprocessing_flags(ap)
+    ap.add_argument('--arithmetic', default=None, choices=['fp32', 'split_bf16x3', 'split_bf16x2', 'bf16x1'],
+                    help='arithmetic of the convolution GEMMs (functions.conv.set_gemm_arithmetic; default '
+                         'split_bf16x3: fp32-accurate; split_bf16x2: 16-bit-class operands; bf16x1: bf16 '
+                         'operands; all with fp32 accumulation and fp32 weights)')
     args = ap.parse_args()
+    if args.arithmetic is not None:
+        from chainer_mask_rcnn_amd.functions import conv
+        conv.set_gemm_arithmetic(args.arithmetic)
     check_postprocessing_flags(ap, args)
     if not (args.snapshot or args.detectron):
         ap.error('--snapshot or --detectron is required')

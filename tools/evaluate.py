@@ -253,6 +253,10 @@ def main():
                          'any of them together; with --results, each type is scored from the file')
     ap.add_argument('--boundary-dilation-ratio', type=float, default=0.02, metavar='R',
                     help='Boundary AP: the boundary width as a fraction of the image diagonal')
+    ap.add_argument('--arithmetic', default=None, choices=['fp32', 'split_bf16x3', 'split_bf16x2', 'bf16x1'],
+                    help='arithmetic of the convolution GEMMs (functions.conv.set_gemm_arithmetic; default '
+                         'split_bf16x3: fp32-accurate; split_bf16x2: 16-bit-class operands; bf16x1: bf16 '
+                         'operands; all with fp32 accumulation and fp32 weights)')
     add_postprocessing_flags(ap)
     args = ap.parse_args()
     check_postprocessing_flags(ap, args, no_model=bool(args.results))
@@ -260,6 +264,9 @@ def main():
         if args.coco_root is None:
             ap.error('--results needs --coco-root')
         return score_results(args)
+    if args.arithmetic is not None:          # (a --log-dir run's own arithmetic is not re-applied: say it here)
+        from chainer_mask_rcnn_amd.functions import conv
+        conv.set_gemm_arithmetic(args.arithmetic)
     if args.save_results and (args.synthetic or (args.dataset != 'coco' and not args.log_dir)):
         ap.error('--save-results needs COCO data: VOC, SBD and --synthetic have no COCO image or '
                  'category ids')

@@ -3,7 +3,7 @@ examples/coco/README.md:48-72: 3.24 Hz on a GTX 1080 Ti): `model.predict([img])`
 5 warm-up calls, then N timed calls including host<->device copies, box NMS, the mask head and
 the mask paste.  Synthetic image and random weights here (no dataset / snapshot offline), head
 scores scaled so that detections exist (100 per image, the maximum)."""
-import os, sys, time
+import argparse, os, sys, time
 import numpy as np
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -12,7 +12,16 @@ import bench
 
 
 def main():
-    times = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument('times', nargs='?', type=int, default=10, help='timed calls')
+    ap.add_argument('--arithmetic', default=None, choices=['fp32', 'split_bf16x3', 'split_bf16x2', 'bf16x1'],
+                    help='arithmetic of the convolution GEMMs (functions.conv.set_gemm_arithmetic; default '
+                         'split_bf16x3: fp32-accurate; split_bf16x2: 16-bit-class operands; bf16x1: bf16 '
+                         'operands; all with fp32 accumulation and fp32 weights)')
+    args = ap.parse_args()
+    times = args.times
+    if args.arithmetic is not None:
+        cmr.functions.conv.set_gemm_arithmetic(args.arithmetic)
     dev = torch.device('cuda:0')
     torch.manual_seed(0)
     model = cmr.models.MaskRCNNResNet(50, n_fg_class=80, min_size=800, max_size=1333,

@@ -98,6 +98,10 @@ def parse_args(argv=None):
                     help="Detectron's linear lr warm-up over the first N updates (0: off)")
     ap.add_argument('--warmup-factor', type=float, default=1. / 3.,
                     help='lr factor of update 0 with --warmup-iters')
+    ap.add_argument('--arithmetic', default=argparse.SUPPRESS, choices=['fp32', 'split_bf16x3', 'split_bf16x2', 'bf16x1'],
+                    help='arithmetic of the convolution GEMMs (functions.conv.set_gemm_arithmetic; default '
+                         'split_bf16x3: fp32-accurate; split_bf16x2: 16-bit-class operands; bf16x1: bf16 '
+                         'operands; all with fp32 accumulation and fp32 weights).  Recorded in params.yaml when given')
     ap.add_argument('--logs-dir', default=osp.join(ROOT, 'logs'))
     ap.add_argument('--no-plot', action='store_true', help='do not write loss.png / accuracy.png')
     args = ap.parse_args(argv)
@@ -373,6 +377,9 @@ def main(argv=None):
     try:
         train_data, test_data, class_names, settings, evaluator_type = datasets(args)
         configure(args, comm, class_names, settings)
+        if getattr(args, 'arithmetic', None) is not None:
+            from chainer_mask_rcnn_amd.functions import conv
+            conv.set_gemm_arithmetic(args.arithmetic)
         model = build_model(args, weights)
         args.imagenet_weights = weights
         run = assemble(args, comm, model, train_data, test_data, evaluator_type,
