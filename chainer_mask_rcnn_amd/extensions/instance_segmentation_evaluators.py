@@ -6,8 +6,9 @@ chainer_mask_rcnn/extensions/instance_segmentation_{voc,coco}_evaluator.py.
 ``predict_images(masks_to_host=False)`` -> packed paste -> intersections
 against the uploaded and packed ground truth, all queued before one read-back of the counts
 and areas.  Boxes, labels and scores come back as ``predict_images`` returns them (with the
-model's test-time augmentation, if it has any configured).  Matching
-and accumulation run on the host from those counts (utils/evaluations/matching.py).
+model's test-time augmentation, if it has any configured).  ``collect()`` returns it all as one
+``EvalRecords`` (utils/evaluations/records.py), which ``evaluate_collected()`` takes and the ranks
+exchange; the host scores its tables (utils/evaluations/scoring.py, matching.py).
 
 ``iou_types=('segm', 'bbox')`` adds box AP under ``validation/main/bbox/...``: the batch's box IoU
 tables (predicted boxes against the examples' ``bbox`` field) are made in one more launch
@@ -28,14 +29,12 @@ for it even without ``'segm'``.
 """
 import copy
 
-import numpy as np
-import torch
-
 from ..utils.evaluations import boxes as B
 from ..utils.evaluations import eval_detection as D
 from ..utils.evaluations import masks as M
-from ..utils.evaluations import matching
 from ..utils.evaluations import rle
+from ..utils.evaluations.records import EvalRecords, Readback
+from ..utils.evaluations.scoring import coco_report, score_coco, score_voc, voc_report  # noqa: F401
 
 
 def _batches(iterator):
@@ -61,6 +60,7 @@ class _InstanceSegmentationEvaluator(object):
     name = 'validation'
     results_sink = None
     box_convention = None     # 'voc' | 'coco': boxes.queue_box_ious' convention
+    flag_names = ()           # the EvalRecords flag lists this evaluator's examples may carry
 
     IOU_TYPES = ('segm', 'bbox', 'boundary')
 
@@ -79,40 +79,28 @@ class _InstanceSegmentationEvaluator(object):
     def __call__(self, trainer=None):
         return self.evaluate()
 
-    def _observation(self, report):
-        return {'%s/main/%s' % (self.name, k): v for k, v in report.items()}
-
-    def _queue_box_ious(self, bboxes, batch, dev):
-        """The batch's box IoU tables, queued: (flat device tensor, shapes, per-image areas)."""
+    def _queue_box_ious(self, readback, bboxes, batch, dev):
+        """Queue the batch's box IoU tables: (their ``fetch()`` slice, per-image areas or None)."""
         gt_boxes = [ex[1] for ex in batch]
         if self.box_convention == 'voc':
-            iou, shapes = B.queue_box_ious(bboxes, gt_boxes, 'voc', device=dev)
-            return iou, shapes, None
+            return readback.add_split(*B.queue_box_ious(bboxes, gt_boxes, 'voc', device=dev)), None
         pred, gt = [B.to_xywh64(b) for b in bboxes], [B.to_xywh64(b) for b in gt_boxes]
         crowd = [ex[4] for ex in batch] if len(batch[0]) == 6 else None
-        iou, shapes = B.queue_box_ious(pred, gt, 'coco', crowd_b=crowd, device=dev)
-        return iou, shapes, [(D.box_areas(p), D.box_areas(g)) for p, g in zip(pred, gt)]
+        slots = readback.add_split(*B.queue_box_ious(pred, gt, 'coco', crowd_b=crowd, device=dev))
+        return slots, [(D.box_areas(p), D.box_areas(g)) for p, g in zip(pred, gt)]
 
     def collect(self):
-        """Run the model over the iterator.  Returns (counts, pred_labels, pred_scores,
-        ground-truth tuples): counts[i] = (inter (P,G), pred_area (P,), gt_area (G,)) host int64
-        arrays; gt tuple = the example's entries after the image (bbox, label, mask, ...).
-
-        With ``'bbox'`` in ``iou_types`` a fifth list follows, the images' box IoU records: the
-        float32 (P, G) table (VOC evaluator) or ``(iou float64 (P,G), dt_area (P,), gt_box_area
-        (G,))`` (COCO evaluator).  Without ``'segm'`` every counts[i] is None.
-
-        With ``'boundary'`` in ``iou_types`` six lists come back: the fifth as above (every
-        box_ious[i] None without ``'bbox'``), the sixth the boundaries' counts, boundary_counts[i] =
-        (inter (P,G), pred boundary area (P,), gt boundary area (G,)); counts[i] is then always
-        filled, as the matching takes the minimum of the two IoUs."""
+        """Run the model over the iterator: the device half of ``evaluate``.  Returns the
+        ``EvalRecords`` of the images seen, with the tables ``iou_types`` asks for ('boundary'
+        brings 'segm' with it: the matching takes the minimum of the two IoUs)."""
         target = self.target
         sink = self.results_sink
         bbox, boundary = 'bbox' in self.iou_types, 'boundary' in self.iou_types
         segm = 'segm' in self.iou_types or boundary      # the masks are needed
         n_seen = 0
-        counts, pred_labels, pred_scores, gts, box_ious = [], [], [], [], []
-        boundary_counts = []
+        records = EvalRecords(tables={k: [] for k, on in (
+            ('segm', segm), ('bbox', bbox), ('boundary', boundary)) if on})
+        flags = []
         for batch in _batches(self.iterator):
             batch = list(batch)
             if not batch:
@@ -124,7 +112,7 @@ class _InstanceSegmentationEvaluator(object):
             bboxes, roi_masks, labels, scores, sizes = target.predict_images(
                 [ex[0] for ex in batch], masks_to_host=False)
             dev = roi_masks[0].device
-            queued, encodes = [], []
+            readback, slots, encodes = Readback(), [], []
             for j, ex in enumerate(batch if segm else ()):
                 gt_mask = ex[3]
                 H, W = sizes[j]
@@ -133,70 +121,43 @@ class _InstanceSegmentationEvaluator(object):
                                      % (tuple(gt_mask.shape), (H, W)))
                 pred = M.paste_packed(roi_masks[j], labels[j], bboxes[j], (H, W))
                 gt = M.pack_masks(gt_mask, device=dev)
-                if boundary:
-                    queued.append(M.queue_mask_and_boundary_counts(
-                        pred, gt, (H, W), self.boundary_dilation_ratio))
-                else:
-                    queued.append((M.queue_intersections(pred, gt, W), pred[1], gt[1]))
+                slots.append(M.queue_counts(readback, pred, gt, (H, W), boundary,
+                                            self.boundary_dilation_ratio))
                 if sink is not None:          # the packed masks just intersected, encoded
                     encodes.append(rle.queue_encode(pred[0], pred[1], pred[2], (H, W)))
-            parts = [t.reshape(-1).to(torch.int64) for q in queued for t in q]
             if bbox:
-                # the IoU bit patterns ride at the end of the int64 buffer (a float32 pattern
-                # widened from int32, a float64 one reinterpreted): exact both ways
-                iou_d, shapes, areas = self._queue_box_ious(bboxes, batch, dev)
-                parts.append(iou_d.view(torch.int32).to(torch.int64)
-                             if iou_d.dtype == torch.float32 else iou_d.view(torch.int64))
-            # one read-back for the whole batch
-            flat = torch.cat(parts)
-            host = flat.cpu().numpy()
+                box_slots, areas = self._queue_box_ious(readback, bboxes, batch, dev)
+            host = readback.fetch()           # one read-back for the whole batch
             if sink is not None:              # the batch's strings: one more small read-back
                 all_segs = rle.fetch_encoded(encodes) if segm else [None] * len(batch)
                 for j, segs in enumerate(all_segs):
                     sink(n_seen + j, bboxes[j], labels[j], scores[j], segs)
             n_seen += len(batch)
-            o = 0
-            for j, (l, s, ex) in enumerate(zip(labels, scores, batch)):
-                if segm:
-                    P, G = queued[j][0].shape
-                    c_inter = host[o:o + P * G].reshape(P, G)
-                    o += P * G
-                    c_pa = host[o:o + P]
-                    o += P
-                    c_ga = host[o:o + G]
-                    o += G
-                    counts.append((c_inter, c_pa, c_ga))
-                    if boundary:
-                        triple, o = M.take_counts(host, o, P, G)
-                        boundary_counts.append(triple)
-                else:
-                    counts.append(None)
-                pred_labels.append(l)
-                pred_scores.append(s)
-                gts.append(tuple(ex[1:]))
+            for image in slots:
+                for k, s in zip(('segm', 'boundary'), image):
+                    records.tables[k].append(tuple(host[s]))
             if bbox:
-                tail = host[o:]
-                tail = (tail.astype(np.int32).view(np.float32) if self.box_convention == 'voc'
-                        else tail.view(np.float64))
-                tables = B.split_tables(tail, shapes)
-                box_ious.extend(tables if areas is None else
-                                [(t,) + a for t, a in zip(tables, areas)])
-            else:
-                box_ious.extend([None] * len(batch))
-        if boundary:
-            return counts, pred_labels, pred_scores, gts, box_ious, boundary_counts
-        if bbox:
-            return counts, pred_labels, pred_scores, gts, box_ious
-        return counts, pred_labels, pred_scores, gts
+                tables = host[box_slots]
+                records.tables['bbox'].extend(tables if areas is None else
+                                              [(t,) + a for t, a in zip(tables, areas)])
+            records.pred_labels.extend(labels)
+            records.pred_scores.extend(scores)
+            records.gt_labels.extend(ex[2] for ex in batch)
+            # this evaluator's flags, from the examples that carry exactly them
+            flags.extend(ex[4:] for ex in batch if len(ex) == 4 + len(self.flag_names))
+        if len(flags) not in (0, n_seen):
+            raise ValueError('%d of %d examples carry %s' % (len(flags), n_seen, self.flag_names))
+        for i, name in enumerate(self.flag_names if flags else ()):
+            setattr(records, name, [f[i] for f in flags])
+        return records
 
-    def _prefixed(self, report, prefix='bbox/'):
-        return {prefix + k: v for k, v in report.items()}
+    def evaluate(self):
+        return self.evaluate_collected(self.collect())
 
-    def _check_records(self, box_ious, boundary_counts=None):
-        if 'bbox' in self.iou_types and (box_ious is None or any(b is None for b in box_ious)):
-            raise ValueError("iou_types has 'bbox' but the records carry no box IoU tables")
-        if 'boundary' in self.iou_types and boundary_counts is None:
-            raise ValueError("iou_types has 'boundary' but the records carry no boundary counts")
+    def evaluate_collected(self, records):
+        """The host half of ``evaluate``: matching and AP from ``collect()``'s records."""
+        records.require(self.iou_types)
+        return {'%s/main/%s' % (self.name, k): v for k, v in self._score(records).items()}
 
 
 class InstanceSegmentationVOCEvaluator(_InstanceSegmentationEvaluator):
@@ -206,6 +167,7 @@ class InstanceSegmentationVOCEvaluator(_InstanceSegmentationEvaluator):
     ``eval_detection_voc`` of the predicted boxes against the examples' boxes."""
 
     box_convention = 'voc'
+    flag_names = ('gt_difficults',)           # taken from 5-tuple examples
 
     def __init__(self, iterator, target, use_07_metric=False, label_names=None,
                  iou_types=('segm',), boundary_dilation_ratio=0.02):
@@ -213,34 +175,8 @@ class InstanceSegmentationVOCEvaluator(_InstanceSegmentationEvaluator):
             iterator, target, label_names, iou_types, boundary_dilation_ratio)
         self.use_07_metric = use_07_metric
 
-    def evaluate(self):
-        return self.evaluate_collected(*self.collect())
-
-    def evaluate_collected(self, counts, pred_labels, pred_scores, gts, box_ious=None,
-                           boundary_counts=None):
-        """The host half of ``evaluate``: matching and AP from ``collect()``'s records."""
-        self._check_records(box_ious, boundary_counts)
-        gt_labels = [g[1] for g in gts]
-        gt_difficults = None
-        if gts and len(gts[0]) == 4:
-            gt_difficults = [g[3] for g in gts]
-        report = {}
-        if 'segm' in self.iou_types:
-            prec, rec = matching.voc_prec_rec_from_counts(counts, pred_labels, pred_scores,
-                                                          gt_labels, gt_difficults)
-            ap = matching.calc_detection_voc_ap(prec, rec, use_07_metric=self.use_07_metric)
-            report.update(voc_report(ap, self.label_names))
-        if 'bbox' in self.iou_types:
-            prec, rec = matching.voc_prec_rec_from_ious(box_ious, pred_labels, pred_scores,
-                                                        gt_labels, gt_difficults)
-            ap = matching.calc_detection_voc_ap(prec, rec, use_07_metric=self.use_07_metric)
-            report.update(self._prefixed(voc_report(ap, self.label_names)))
-        if 'boundary' in self.iou_types:
-            prec, rec = matching.voc_prec_rec_from_boundary_counts(
-                counts, boundary_counts, pred_labels, pred_scores, gt_labels, gt_difficults)
-            ap = matching.calc_detection_voc_ap(prec, rec, use_07_metric=self.use_07_metric)
-            report.update(self._prefixed(voc_report(ap, self.label_names), 'boundary/'))
-        return self._observation(report)
+    def _score(self, records):
+        return score_voc(records, self.iou_types, self.use_07_metric, self.label_names)
 
 
 class InstanceSegmentationCOCOEvaluator(_InstanceSegmentationEvaluator):
@@ -262,6 +198,7 @@ class InstanceSegmentationCOCOEvaluator(_InstanceSegmentationEvaluator):
     areas as for the masks."""
 
     box_convention = 'coco'
+    flag_names = ('gt_crowdeds', 'gt_areas')  # taken from 6-tuple examples
 
     def __init__(self, iterator, target, label_names=None, results_sink=None,
                  iou_types=('segm',), boundary_dilation_ratio=0.02):
@@ -269,69 +206,15 @@ class InstanceSegmentationCOCOEvaluator(_InstanceSegmentationEvaluator):
             iterator, target, label_names, iou_types, boundary_dilation_ratio)
         self.results_sink = results_sink
 
-    def evaluate(self):
-        return self.evaluate_collected(*self.collect())
-
-    def evaluate_collected(self, counts, pred_labels, pred_scores, gts, box_ious=None,
-                           boundary_counts=None):
-        """The host half of ``evaluate``: matching and AP from ``collect()``'s records."""
-        self._check_records(box_ious, boundary_counts)
-        gt_labels = [g[1] for g in gts]
-        gt_crowdeds = gt_areas = None
-        if gts and len(gts[0]) == 5:
-            gt_crowdeds = [g[3] for g in gts]
-            gt_areas = [g[4] for g in gts]
-        report = {}
-        if 'segm' in self.iou_types:
-            result = matching.coco_results(matching.coco_evaluate_from_counts(
-                counts, pred_labels, pred_scores, gt_labels, gt_crowdeds, gt_areas))
-            report.update(coco_report(result, self.label_names))
-        if 'bbox' in self.iou_types:
-            result = matching.coco_results(matching.coco_evaluate_from_ious(
-                box_ious, pred_labels, pred_scores, gt_labels, gt_crowdeds, gt_areas))
-            report.update(self._prefixed(coco_report(result, self.label_names)))
-        if 'boundary' in self.iou_types:
-            result = matching.coco_results(matching.coco_evaluate_from_boundary_counts(
-                counts, boundary_counts, pred_labels, pred_scores, gt_labels, gt_crowdeds,
-                gt_areas))
-            report.update(self._prefixed(coco_report(result, self.label_names), 'boundary/'))
-        return self._observation(report)
-
-
-def strip_records(counts, pred_labels, pred_scores, gts, box_ious=None, boundary_counts=None):
-    """``collect()``'s records without what the host matching never reads: each ground-truth
-    tuple keeps its length and its labels (and difficult / crowd / area) but loses the boxes and
-    masks, which are by far the largest part.  The box IoU records and the boundary counts, when
-    present, stay whole."""
-    gts = [(None, g[1], None) + tuple(g[3:]) for g in gts]
-    out = (list(counts), list(pred_labels), list(pred_scores), gts)
-    if boundary_counts is not None:
-        box_ious = [None] * len(gts) if box_ious is None else box_ious
-        return out + (list(box_ious), list(boundary_counts))
-    return out if box_ious is None else out + (list(box_ious),)
-
-
-def merge_records(per_rank):
-    """Concatenate the ranks' records (each ``(counts, pred_labels, pred_scores, gts[,
-    box_ious[, boundary_counts]])``) in rank order, which is the test set's order when rank i holds the i-th
-    contiguous shard."""
-    per_rank = list(per_rank)
-    widths = set(len(r) for r in per_rank)
-    if len(widths) > 1:
-        raise ValueError('records with and without box IoU tables or boundary counts cannot be '
-                         'merged')
-    merged = tuple([] for _ in range(widths.pop() if widths else 4))
-    for records in per_rank:
-        for out, part in zip(merged, records):
-            out.extend(part)
-    return merged
+    def _score(self, records):
+        return score_coco(records, self.iou_types, self.label_names)
 
 
 def gather_records(records, group=None):
-    """Every rank's stripped records, merged in rank order, on every rank.  They travel on the
-    control plane (pickled into uint8 CPU tensors over gloo, parallel.all_gather_bytes)."""
+    """Every rank's records, merged in rank order, on every rank.  They travel on the control
+    plane (pickled into uint8 CPU tensors over gloo, parallel.all_gather_bytes)."""
     from .. import parallel
-    return merge_records(parallel.all_gather_object_cpu(strip_records(*records), group))
+    return EvalRecords.merge(parallel.all_gather_object_cpu(records, group))
 
 
 class _MultiNodeEvaluator(object):
@@ -347,40 +230,17 @@ class _MultiNodeEvaluator(object):
         return self.evaluate()
 
     def evaluate(self):
-        records = gather_records(self.evaluator.collect(), self.group)
-        return self.evaluator.evaluate_collected(*records)
+        return self.evaluator.evaluate_collected(
+            gather_records(self.evaluator.collect(), self.group))
 
 
 def create_multi_node_evaluator(evaluator, group=None):
     """chainermn.create_multi_node_evaluator's role for the instance-segmentation evaluators, with
     an exact result: each rank runs ``collect()`` (the device part) on its own test shard, the
-    stripped records of all ranks are gathered in rank order and every rank runs the unchanged
+    records of all ranks are gathered in rank order and every rank runs the unchanged
     host matching over all of them.  Every rank gets the same observation, the one a single
     evaluator produces over the concatenated shards (chainermn averages the ranks' observations
     instead, which is not the test set's mAP).  Batching pads images, so a prediction depends on
     the images of its batch: the statement holds exactly when the test batches are the same,
     e.g. with batch size 1."""
     return _MultiNodeEvaluator(evaluator, group)
-
-
-def voc_report(ap, label_names=None):
-    report = {'map': np.nanmean(ap)}
-    if label_names is not None:
-        for l, label_name in enumerate(label_names):
-            report['ap/{:s}'.format(label_name)] = ap[l] if l < len(ap) else np.nan
-    return report
-
-
-def coco_report(result, label_names=None):
-    report = {
-        'map': result['map/iou=0.50:0.95/area=all/maxDets=100'],
-        'map@0.5': result['map/iou=0.50/area=all/maxDets=100'],
-        'map@0.75': result['map/iou=0.75/area=all/maxDets=100'],
-    }
-    if label_names is not None:
-        per_class = result['ap/iou=0.50:0.95/area=all/maxDets=100']
-        k_of = {int(c): k for k, c in enumerate(result['coco_eval']['params']['catIds'])}
-        for l, label_name in enumerate(label_names):
-            k = k_of.get(l)
-            report['ap/{:s}'.format(label_name)] = per_class[k] if k is not None else np.nan
-    return report

@@ -7,8 +7,8 @@ one of two conventions:
   ``utils.bbox.bbox_iou(a + [0, 0, 1, 1], b + [0, 0, 1, 1])``;
 * ``'coco'``: (x, y, w, h) float64 with crowd flags — pycocotools' ``bbIou``.
 
-Nothing here synchronises; ``split_tables`` cuts the flat result, once it is on the host, into the
-per-image tables.  There is no host fallback: a device is required.
+Nothing here synchronises; ``records.Readback.add_split`` brings the flat result to the host as
+the per-image tables.  There is no host fallback: a device is required.
 """
 import numpy as np
 import torch
@@ -103,12 +103,3 @@ def queue_box_ious(boxes_a, boxes_b, convention, crowd_b=None, device=None):
     # kernel (same stream), as in masks.paste_packed
     return iou, shapes
 
-
-def split_tables(flat, shapes):
-    """The host copy of ``queue_box_ious``' flat result -> the per-image (P_i, G_i) tables."""
-    flat = np.asarray(flat)
-    out, o = [], 0
-    for p, g in shapes:
-        out.append(flat[o:o + p * g].reshape(p, g))
-        o += p * g
-    return out

@@ -21,8 +21,9 @@ import numpy as np
 from . import boxes as B
 from . import eval_detection as D
 from . import masks as M
-from . import matching
 from . import rle as R
+from .records import EvalRecords, Readback
+from .scoring import SCORERS, score_coco
 
 
 def results_entries(img_id, bboxes, labels, scores, segmentations, class_id_to_cat_id):
@@ -156,31 +157,6 @@ def load_results(results, dataset, iou_type='segm'):
                        for i, v in _load(results, dataset, iou_type).items())
 
 
-def _eval_bbox_results(grouped, dataset, n, label_names):
-    """eval_coco_results for iou_type 'bbox': one launch makes every image's bbIou table."""
-    from ...extensions.instance_segmentation_evaluators import coco_report
-    pred, gt_boxes, pred_labels, pred_scores, gts = [], [], [], [], []
-    for i in range(n):
-        entries = [e for _, e in grouped.get(dataset.img_ids[i], [])]
-        gt = dataset.get_annotations(i)
-        pred.append(np.array([e['bbox'] for e in entries], np.float64).reshape(-1, 4))
-        gt_boxes.append(B.to_xywh64(gt[0]))
-        pred_labels.append(np.array([dataset.cat_id_to_class_id[e['category_id']]
-                                     for e in entries], np.int32))
-        pred_scores.append(np.array([e['score'] for e in entries], np.float32))
-        gts.append(gt)
-    gt_labels = [g[1] for g in gts]
-    gt_crowdeds = gt_areas = None
-    if gts and len(gts[0]) == 5:                      # as the evaluator: crowds and areas
-        gt_crowdeds = [g[3] for g in gts]
-        gt_areas = [g[4] for g in gts]
-    tables = D.coco_box_tables(pred, gt_boxes, gt_crowdeds)
-    result = matching.coco_results(matching.coco_evaluate_from_ious(
-        tables, pred_labels, pred_scores, gt_labels, gt_crowdeds, gt_areas))
-    return {'validation/main/bbox/%s' % k: v
-            for k, v in coco_report(result, label_names).items()}
-
-
 def eval_coco_results(results, dataset, limit=None, label_names=None, iou_type='segm',
                       dilation_ratio=0.02):
     """Score a results file (path or list of entries) against ``dataset`` (a
@@ -198,52 +174,40 @@ def eval_coco_results(results, dataset, limit=None, label_names=None, iou_type='
     AP (boundaries cut on the device at ``dilation_ratio`` of the image diagonal, matching on
     min(mask IoU, boundary IoU)) and the evaluator's ``validation/main/boundary/...`` keys come
     back."""
-    import torch
-    from ...extensions.instance_segmentation_evaluators import coco_report
     grouped = _load(results, dataset, iou_type)
     n = len(dataset) if not limit else min(int(limit), len(dataset))
-    if iou_type == 'bbox':
-        return _eval_bbox_results(grouped, dataset, n, label_names)
-    dev = M._device()
-    boundary = iou_type == 'boundary'
-    counts, boundary_counts, pred_labels, pred_scores, gts = [], [], [], [], []
+    bbox, boundary = iou_type == 'bbox', iou_type == 'boundary'
+    dev = None if bbox else M._device()
+    records = EvalRecords(tables={k: [] for k in SCORERS[iou_type][2]})
+    pred_boxes, gt_boxes, flags = [], [], []
     for i in range(n):
         img_id = dataset.img_ids[i]
-        H, W = dataset.img_sizes[img_id]
         gt = dataset.get_annotations(i)
         entries = [e for _, e in grouped.get(img_id, [])]
-        job = R.queue_decode([e['segmentation'] for e in entries], size=(H, W), device=dev)
-        pred = job.packed
-        gt_p = M.pack_masks(gt[2], device=dev)
-        if boundary:
-            queued = M.queue_mask_and_boundary_counts(pred, gt_p, (H, W), dilation_ratio)
-        else:
-            queued = (M.queue_intersections(pred, gt_p, W), pred[1], gt_p[1])
-        P, G = queued[0].shape
-        host = torch.cat([t.reshape(-1).to(torch.int64) for t in
-                          (job.status,) + tuple(queued)]).cpu().numpy()
-        R.check_decoded(host[:P], ['results entry %d (image %r)' % (k, img_id)
-                                   for k, _ in grouped.get(img_id, [])])
-        o = P
-        c_inter = host[o:o + P * G].reshape(P, G)
-        o += P * G
-        counts.append((c_inter, host[o:o + P], host[o + P:o + P + G]))
-        if boundary:
-            boundary_counts.append(M.take_counts(host, o + P + G, P, G)[0])
-        pred_labels.append(np.array([dataset.cat_id_to_class_id[e['category_id']]
-                                     for e in entries], np.int32))
-        pred_scores.append(np.array([e['score'] for e in entries], np.float32))
-        gts.append(gt)
-    gt_labels = [g[1] for g in gts]
-    gt_crowdeds = gt_areas = None
-    if gts and len(gts[0]) == 5:                      # as the evaluator: crowds and areas
-        gt_crowdeds = [g[3] for g in gts]
-        gt_areas = [g[4] for g in gts]
-    if boundary:
-        result = matching.coco_results(matching.coco_evaluate_from_boundary_counts(
-            counts, boundary_counts, pred_labels, pred_scores, gt_labels, gt_crowdeds, gt_areas))
-        return {'validation/main/boundary/%s' % k: v
-                for k, v in coco_report(result, label_names).items()}
-    result = matching.coco_results(matching.coco_evaluate_from_counts(
-        counts, pred_labels, pred_scores, gt_labels, gt_crowdeds, gt_areas))
-    return {'validation/main/%s' % k: v for k, v in coco_report(result, label_names).items()}
+        records.pred_labels.append(np.array([dataset.cat_id_to_class_id[e['category_id']]
+                                             for e in entries], np.int32))
+        records.pred_scores.append(np.array([e['score'] for e in entries], np.float32))
+        records.gt_labels.append(gt[1])
+        if len(gt) == 5:                              # as the evaluator: crowds and areas
+            flags.append(gt[3:])
+        if bbox:
+            pred_boxes.append(np.array([e['bbox'] for e in entries], np.float64).reshape(-1, 4))
+            gt_boxes.append(B.to_xywh64(gt[0]))
+            continue
+        size = dataset.img_sizes[img_id]
+        job = R.queue_decode([e['segmentation'] for e in entries], size=size, device=dev)
+        readback = Readback()
+        status = readback.add(job.status)
+        slots = M.queue_counts(readback, job.packed, M.pack_masks(gt[2], device=dev), size,
+                               boundary, dilation_ratio)
+        host = readback.fetch()
+        R.check_decoded(host[status][0], ['results entry %d (image %r)' % (k, img_id)
+                                          for k, _ in grouped.get(img_id, [])])
+        for k, s in zip(('segm', 'boundary'), slots):
+            records.tables[k].append(tuple(host[s]))
+    if flags:
+        records.gt_crowdeds, records.gt_areas = [f[0] for f in flags], [f[1] for f in flags]
+    if bbox:                                          # one launch makes every image's table
+        records.tables['bbox'] = D.coco_box_tables(pred_boxes, gt_boxes, records.gt_crowdeds)
+    return {'validation/main/%s' % k: v
+            for k, v in score_coco(records, (iou_type,), label_names).items()}

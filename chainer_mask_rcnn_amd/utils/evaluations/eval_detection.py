@@ -7,21 +7,24 @@ import numpy as np
 
 from . import boxes as B
 from . import matching
+from .records import Readback
 
 
 def voc_box_tables(pred_bboxes, gt_bboxes):
     """Per-image float32 (P, G) IoU tables in the VOC convention (+1 on the max corners)."""
-    iou, shapes = B.queue_box_ious(pred_bboxes, gt_bboxes, 'voc')
-    return B.split_tables(iou.cpu().numpy(), shapes)
+    readback = Readback()
+    readback.add_split(*B.queue_box_ious(pred_bboxes, gt_bboxes, 'voc'))
+    return readback.fetch()
 
 
 def coco_box_tables(pred_xywh, gt_xywh, gt_crowdeds=None):
     """Per-image ``(iou, dt_area, gt_box_area)`` for ``matching.coco_evaluate_from_ious`` from
     float64 (x, y, w, h) boxes: bbIou tables from the device, areas ``w*h``."""
     pred_xywh, gt_xywh = list(pred_xywh), list(gt_xywh)
-    iou, shapes = B.queue_box_ious(pred_xywh, gt_xywh, 'coco', crowd_b=gt_crowdeds)
-    tables = B.split_tables(iou.cpu().numpy(), shapes)
-    return [(t, box_areas(d), box_areas(g)) for t, d, g in zip(tables, pred_xywh, gt_xywh)]
+    readback = Readback()
+    readback.add_split(*B.queue_box_ious(pred_xywh, gt_xywh, 'coco', crowd_b=gt_crowdeds))
+    return [(t, box_areas(d), box_areas(g))
+            for t, d, g in zip(readback.fetch(), pred_xywh, gt_xywh)]
 
 
 def box_areas(xywh):

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from ... import _lib
+from .records import Readback
 
 
 def _device():
@@ -107,18 +108,36 @@ def queue_intersections(a, b, W):
     return inter
 
 
-def mask_counts(mask_a, mask_b):
-    """(inter (P,G), area_a (P,), area_b (G,)) as host int64 arrays for two mask sets of the
-    same image size (host arrays or device tensors)."""
+def queue_counts(readback, a, b, size, boundary=False, dilation_ratio=0.02, dilation=None):
+    """One image's step of every evaluation: for packed sets a (predictions) and b (ground truth)
+    of an image of ``size`` (H, W), queue (inter (P,G), area_a (P,), area_b (G,)) onto
+    ``readback`` and, with ``boundary``, the same triple of the two sets' boundaries.  Returns
+    the triples' slices of ``readback.fetch()``: [masks] or [masks, boundaries]."""
+    W = int(size[1])
+    slots = [readback.add(queue_intersections(a, b, W), a[1], b[1])]
+    if boundary:
+        ba = boundary_packed(a, size, dilation_ratio, dilation)
+        bb = boundary_packed(b, size, dilation_ratio, dilation)
+        slots.append(readback.add(queue_intersections(ba, bb, W), ba[1], bb[1]))
+    return slots
+
+
+def _counts(mask_a, mask_b, boundary, dilation_ratio=0.02, dilation=None):
     if tuple(mask_a.shape[1:]) != tuple(mask_b.shape[1:]):
         raise ValueError('mask sets of different image sizes: %s vs %s'
                          % (tuple(mask_a.shape[1:]), tuple(mask_b.shape[1:])))
-    W = mask_a.shape[2]
     a = pack_masks(mask_a)
     b = pack_masks(mask_b, device=a[0].device)
-    inter = queue_intersections(a, b, W)
-    return (inter.cpu().numpy().astype(np.int64), a[1].cpu().numpy().astype(np.int64),
-            b[1].cpu().numpy().astype(np.int64))
+    readback = Readback()
+    slots = queue_counts(readback, a, b, mask_a.shape[1:], boundary, dilation_ratio, dilation)
+    host = readback.fetch()
+    return [tuple(host[s]) for s in slots]
+
+
+def mask_counts(mask_a, mask_b):
+    """(inter (P,G), area_a (P,), area_b (G,)) as host int64 arrays for two mask sets of the
+    same image size (host arrays or device tensors)."""
+    return _counts(mask_a, mask_b, False)[0]
 
 
 def iou_from_counts(inter, area_a, area_b):
@@ -195,46 +214,10 @@ def mask_to_boundary(masks, dilation_ratio=0.02, dilation=None):
     return out if isinstance(masks, torch.Tensor) else out.cpu().numpy()
 
 
-def queue_mask_and_boundary_counts(a, b, size, dilation_ratio=0.02, dilation=None):
-    """For packed sets a and b of an image of ``size``: the six device tensors (inter, area_a,
-    area_b, boundary inter, boundary area_a, boundary area_b), queued."""
-    W = int(size[1])
-    ba = boundary_packed(a, size, dilation_ratio, dilation)
-    bb = boundary_packed(b, size, dilation_ratio, dilation)
-    return (queue_intersections(a, b, W), a[1], b[1], queue_intersections(ba, bb, W), ba[1], bb[1])
-
-
-def take_counts(host, o, P, G):
-    """The (inter (P,G), area_a (P,), area_b (G,)) triple that starts at offset ``o`` of a flat
-    host buffer, and the offset behind it."""
-    end = o + P * G + P + G
-    return (host[o:o + P * G].reshape(P, G), host[o + P * G:o + P * G + P],
-            host[o + P * G + P:end]), end
-
-
-def fetch_counts(tensors, P, G):
-    """One read-back of device count tensors laid out (P*G, P, G) repeatedly -> a list of
-    (inter (P,G), area_a (P,), area_b (G,)) host int64 triples."""
-    host = torch.cat([t.reshape(-1).to(torch.int64) for t in tensors]).cpu().numpy()
-    out, o = [], 0
-    for _ in range(len(tensors) // 3):
-        triple, o = take_counts(host, o, P, G)
-        out.append(triple)
-    return out
-
-
 def mask_and_boundary_counts(mask_a, mask_b, dilation_ratio=0.02, dilation=None):
     """``(mask_counts, boundary_counts)`` of two mask sets of the same image size from one
     read-back: each ``(inter (P,G), area_a (P,), area_b (G,))`` host int64."""
-    if tuple(mask_a.shape[1:]) != tuple(mask_b.shape[1:]):
-        raise ValueError('mask sets of different image sizes: %s vs %s'
-                         % (tuple(mask_a.shape[1:]), tuple(mask_b.shape[1:])))
-    size = (int(mask_a.shape[1]), int(mask_a.shape[2]))
-    a = pack_masks(mask_a)
-    b = pack_masks(mask_b, device=a[0].device)
-    q = queue_mask_and_boundary_counts(a, b, size, dilation_ratio, dilation)
-    m, bd = fetch_counts(q, a[0].shape[0], b[0].shape[0])
-    return m, bd
+    return tuple(_counts(mask_a, mask_b, True, dilation_ratio, dilation))
 
 
 def boundary_counts(mask_a, mask_b, dilation_ratio=0.02, dilation=None):

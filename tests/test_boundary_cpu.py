@@ -1,6 +1,6 @@
 """Boundary AP without a device: the NumPy reference against scipy's restatement of the rule, the
-host matching on min(mask IoU, boundary IoU) from hand-built and reference counts, the six-entry
-records, the switches of the tools, and the kernels' per-word arithmetic run by a host program."""
+host matching on min(mask IoU, boundary IoU) from hand-built and reference counts, the records
+with boundary tables, the switches of the tools, and the kernels' per-word arithmetic run by a host program."""
 import ctypes
 import importlib
 import json
@@ -14,6 +14,8 @@ import boundary_ref as BR
 import instseg_eval_ref as R
 from chainer_mask_rcnn_amd.extensions import instance_segmentation_evaluators as E
 from chainer_mask_rcnn_amd.utils.evaluations import matching
+from chainer_mask_rcnn_amd.utils.evaluations.records import EvalRecords
+from records_util import ATTRS, same_lists, take
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ['c%d' % i for i in range(BR.N_CLASS)]
@@ -122,14 +124,21 @@ def test_the_crowd_denominator_is_applied_to_both_tables_before_the_min():
 
 def _records(data, kind, with_flags=True):
     masks, bounds = BR.all_counts(data['pred_masks'], data['gt_masks'])
-    if kind == 'coco':
-        gts = [(None, l, None, c, a) if with_flags else (None, l, None)
-               for l, c, a in zip(data['gt_labels'], data['gt_crowdeds'], data['gt_areas'])]
-    else:
-        gts = [(None, l, None, d) if with_flags else (None, l, None)
-               for l, d in zip(data['gt_labels'], data['gt_difficults'])]
-    none = [None] * len(gts)
-    return (masks, data['pred_labels'], data['pred_scores'], gts, none, bounds)
+    flags = {}
+    if with_flags and kind == 'coco':
+        flags = {'gt_crowdeds': data['gt_crowdeds'], 'gt_areas': data['gt_areas']}
+    elif with_flags:
+        flags = {'gt_difficults': data['gt_difficults']}
+    return EvalRecords(data['pred_labels'], data['pred_scores'], data['gt_labels'],
+                       tables={'segm': masks, 'boundary': bounds}, **flags)
+
+
+def _without(rec, *keys):
+    """The record without some of its tables."""
+    out = take(rec, 0, None)
+    for k in keys:
+        del out.tables[k]
+    return out
 
 
 def _coco_expected(data, with_flags, boundary):
@@ -160,26 +169,29 @@ def test_evaluate_collected_on_six_entry_records_equals_the_reference(data, with
     rec = _records(data, 'coco', with_flags)
     ev = E.InstanceSegmentationCOCOEvaluator(None, None, label_names=NAMES,
                                              iou_types=('segm', 'boundary'))
-    got = ev.evaluate_collected(*rec)
+    got = ev.evaluate_collected(rec)
     want = {'validation/main/' + k: v for k, v in _coco_expected(data, with_flags, False)[0].items()}
     exp_b, p, r = _coco_expected(data, with_flags, True)
     want.update({'validation/main/boundary/' + k: v for k, v in exp_b.items()})
     same(got, want)
     assert 0 < got['validation/main/boundary/map'] < got['validation/main/map']
-    labels = [g[1] for g in rec[3]]
-    flags = ([g[3] for g in rec[3]], [g[4] for g in rec[3]]) if with_flags else (None, None)
-    full = matching.coco_evaluate_from_boundary_counts(rec[0], rec[5], rec[1], rec[2], labels, *flags)
+    flags = (data['gt_crowdeds'], data['gt_areas']) if with_flags else (None, None)
+    assert same_lists(rec.gt_crowdeds, flags[0]) and same_lists(rec.gt_areas, flags[1])
+    full = matching.coco_evaluate_from_boundary_counts(
+        rec.tables['segm'], rec.tables['boundary'], rec.pred_labels, rec.pred_scores,
+        data['gt_labels'], *flags)
     assert np.array_equal(full['precision'], p) and np.array_equal(full['recall'], r)
     only = E.InstanceSegmentationCOCOEvaluator(None, None, label_names=NAMES, iou_types=('boundary',))
-    same(only.evaluate_collected(*rec), {k: v for k, v in got.items() if '/boundary/' in k})
+    same(only.evaluate_collected(rec), {k: v for k, v in got.items() if '/boundary/' in k})
     # asking for the boundary changes no segm value
     plain = E.InstanceSegmentationCOCOEvaluator(None, None, label_names=NAMES)
-    same(plain.evaluate_collected(*rec[:4]), {k: v for k, v in got.items() if '/boundary/' not in k})
+    same(plain.evaluate_collected(_without(rec, 'boundary')),
+         {k: v for k, v in got.items() if '/boundary/' not in k})
 
     rec = _records(data, 'voc', with_flags)
     ev = E.InstanceSegmentationVOCEvaluator(None, None, use_07_metric=True, label_names=NAMES,
                                             iou_types=('segm', 'boundary'))
-    got = ev.evaluate_collected(*rec)
+    got = ev.evaluate_collected(rec)
     want = {'validation/main/' + k: v for k, v in _voc_expected(data, with_flags, False).items()}
     want.update({'validation/main/boundary/' + k: v
                  for k, v in _voc_expected(data, with_flags, True).items()})
@@ -190,29 +202,34 @@ def test_evaluate_collected_on_six_entry_records_equals_the_reference(data, with
 # --------------------------------------------------------------------------------- the records
 def test_six_entry_records_strip_merge_and_score_like_the_whole(data):
     rec = _records(data, 'coco')
-    s = E.strip_records(*rec)
-    assert isinstance(s, tuple) and len(s) == 6 and s[4] == [None] * len(rec[3])
-    assert s[5] == list(rec[5]) and all(g[0] is None and g[2] is None and len(g) == 5 for g in s[3])
-    assert len(E.strip_records(rec[0], rec[1], rec[2], rec[3], None, rec[5])) == 6
-    m = E.merge_records([s, s])
-    assert len(m) == 6 and m[5] == list(rec[5]) * 2 and m[0] == list(rec[0]) * 2
+    assert isinstance(rec, EvalRecords) and set(rec.tables) == {'segm', 'boundary'}
+    assert 'bbox' not in rec.tables
+    # labels and flags as given; nothing in the record is a box or a mask
+    assert set(vars(rec)) == ATTRS and same_lists(rec.gt_labels, data['gt_labels'])
+    assert same_lists(rec.gt_crowdeds, data['gt_crowdeds'])
+    assert same_lists(rec.gt_areas, data['gt_areas']) and rec.gt_difficults is None
+    m = EvalRecords.merge([rec, rec])
+    assert set(m.tables) == {'segm', 'boundary'}
+    assert same_lists(m.tables['boundary'], rec.tables['boundary'] * 2)
+    assert same_lists(m.tables['segm'], rec.tables['segm'] * 2)
     ev = E.InstanceSegmentationCOCOEvaluator(None, None, label_names=NAMES,
                                              iou_types=('segm', 'boundary'))
-    whole = ev.evaluate_collected(*rec)
-    halves = E.merge_records([E.strip_records(*[r[:3] for r in rec]),
-                              E.strip_records(*[r[3:] for r in rec])])
-    assert len(halves) == 6
-    same(ev.evaluate_collected(*halves), whole)
-    four, five = E.strip_records(*rec[:4]), E.strip_records(*rec[:5])
-    assert len(four) == 4 and len(five) == 5                    # the narrower forms as they were
-    for mixed in ([four, s], [five, s], [s, four]):
+    whole = ev.evaluate_collected(rec)
+    halves = EvalRecords.merge([take(rec, 0, 3), take(rec, 3, None)])
+    assert set(halves.tables) == {'segm', 'boundary'}
+    same(ev.evaluate_collected(halves), whole)
+    segm_only = _without(rec, 'boundary')
+    with_boxes = take(rec, 0, None)
+    with_boxes.tables['bbox'] = [None] * len(rec)               # any third key set
+    assert set(segm_only.tables) == {'segm'}                    # the narrower form as it was
+    for mixed in ([segm_only, rec], [with_boxes, rec], [rec, segm_only]):
         with pytest.raises(ValueError):
-            E.merge_records(mixed)
-    with pytest.raises(ValueError, match='boundary'):           # 'boundary' needs the sixth list
-        ev.evaluate_collected(*rec[:4])
+            EvalRecords.merge(mixed)
+    with pytest.raises(ValueError, match='boundary'):           # 'boundary' needs its table
+        ev.evaluate_collected(segm_only)
     both = E.InstanceSegmentationCOCOEvaluator(None, None, iou_types=('bbox', 'boundary'))
-    with pytest.raises(ValueError, match='box IoU'):            # a list of None is no box record
-        both.evaluate_collected(*rec)
+    with pytest.raises(ValueError, match='box IoU'):            # no 'bbox' key is no box record
+        both.evaluate_collected(rec)
 
 
 # -------------------------------------------------------------------------------- the switches

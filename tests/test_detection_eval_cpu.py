@@ -8,6 +8,8 @@ import pytest
 import detection_eval_ref as R
 from chainer_mask_rcnn_amd.extensions import instance_segmentation_evaluators as E
 from chainer_mask_rcnn_amd.utils.evaluations import matching
+from chainer_mask_rcnn_amd.utils.evaluations.records import EvalRecords
+from records_util import ATTRS, same_lists, take
 
 ONE = 1.0 / (1.0 + np.spacing(1))     # accumulate's precision of one true positive: tp / (tp + eps)
 
@@ -171,40 +173,47 @@ def _records(data, n=6, box=None):
     H, W = data['H'], data['W']
     counts = R.counts([R.rasters(b, H, W) for b in data['pred_bboxes'][:n]],
                       [R.rasters(b, H, W) for b in data['gt_bboxes'][:n]])
-    gts = [(b, l, R.rasters(b, H, W), c, a) for b, l, c, a in zip(
-        data['gt_bboxes'][:n], data['gt_labels'][:n], data['gt_crowdeds'][:n],
-        data['gt_areas'][:n])]
-    rec = (counts, data['pred_labels'][:n], data['pred_scores'][:n], gts)
+    tables = {'segm': counts}
     if box == 'coco':
-        rec += (_coco_tables([R.xywh64(b) for b in data['pred_bboxes'][:n]],
-                             [R.xywh64(b) for b in data['gt_bboxes'][:n]],
-                             data['gt_crowdeds'][:n]),)
-    return rec
+        tables['bbox'] = _coco_tables([R.xywh64(b) for b in data['pred_bboxes'][:n]],
+                                      [R.xywh64(b) for b in data['gt_bboxes'][:n]],
+                                      data['gt_crowdeds'][:n])
+    return EvalRecords(data['pred_labels'][:n], data['pred_scores'][:n], data['gt_labels'][:n],
+                       gt_crowdeds=data['gt_crowdeds'][:n], gt_areas=data['gt_areas'][:n],
+                       tables=tables)
 
 
 def test_strip_and_merge_round_trip_records_with_and_without_the_box_field(data):
     plain, boxed = _records(data), _records(data, box='coco')
-    s = E.strip_records(*plain)
-    assert isinstance(s, tuple) and len(s) == 4                       # as it always was
-    assert all(g[0] is None and g[2] is None and len(g) == 5 for g in s[3])
-    m = E.merge_records([s, s])
-    assert isinstance(m, tuple) and len(m) == 4 and all(isinstance(x, list) for x in m)
-    assert m[0] == list(plain[0]) * 2 and m[3] == s[3] * 2
-    sb = E.strip_records(*boxed)
-    assert len(sb) == 5 and sb[4] == list(boxed[4]) and sb[:4][3] == s[3]
-    mb = E.merge_records([sb, sb])
-    assert len(mb) == 5 and mb[4] == list(boxed[4]) * 2 and mb[0] == list(boxed[0]) * 2
+    assert set(plain.tables) == {'segm'}                              # as it always was
+    # the record holds the labels and flags and nothing that is a box, a mask or an image
+    assert set(vars(plain)) == set(vars(boxed)) == ATTRS
+    assert same_lists(plain.gt_labels, data['gt_labels'][:6])
+    assert same_lists(plain.gt_crowdeds, data['gt_crowdeds'][:6])
+    assert same_lists(plain.gt_areas, data['gt_areas'][:6]) and plain.gt_difficults is None
+    m = EvalRecords.merge([plain, plain])
+    assert isinstance(m, EvalRecords) and set(m.tables) == {'segm'}
+    assert all(isinstance(getattr(m, k), list) for k in ATTRS - {'tables', 'gt_difficults'})
+    assert same_lists(m.tables['segm'], plain.tables['segm'] * 2)
+    for k in ('gt_labels', 'gt_crowdeds', 'gt_areas'):
+        assert same_lists(getattr(m, k), getattr(plain, k) * 2), k
+    assert set(boxed.tables) == {'segm', 'bbox'} and same_lists(boxed.gt_labels, plain.gt_labels)
+    mb = EvalRecords.merge([boxed, boxed])
+    assert set(mb.tables) == {'segm', 'bbox'}
+    assert same_lists(mb.tables['bbox'], boxed.tables['bbox'] * 2)
+    assert same_lists(mb.tables['segm'], boxed.tables['segm'] * 2)
     with pytest.raises(ValueError):
-        E.merge_records([s, sb])
-    assert E.merge_records([]) == ([], [], [], [])
+        EvalRecords.merge([plain, boxed])
+    empty = EvalRecords.merge([])
+    assert all(getattr(empty, k) in ([], None) for k in ATTRS - {'tables'}) and empty.tables == {}
+    assert (empty.pred_labels, empty.pred_scores, empty.gt_labels) == ([], [], [])
     # the host half: two shards merged score what the whole scores, segm and bbox keys
     names = ['c%d' % i for i in range(4)]
     both = E.InstanceSegmentationCOCOEvaluator(None, None, label_names=names,
                                                iou_types=('segm', 'bbox'))
-    whole = both.evaluate_collected(*boxed)
-    halves = E.merge_records([E.strip_records(*[r[:3] for r in boxed]),
-                              E.strip_records(*[r[3:] for r in boxed])])
-    merged = both.evaluate_collected(*halves)
+    whole = both.evaluate_collected(boxed)
+    halves = EvalRecords.merge([take(boxed, 0, 3), take(boxed, 3, None)])
+    merged = both.evaluate_collected(halves)
     assert sorted(merged) == sorted(whole)
     for k in whole:
         assert np.array_equal(np.asarray(whole[k]), np.asarray(merged[k]), equal_nan=True), k
@@ -217,7 +226,7 @@ def test_strip_and_merge_round_trip_records_with_and_without_the_box_field(data)
                               np.asarray(whole['validation/main/' + k]), equal_nan=True), k
     assert whole['validation/main/bbox/map'] > 0
     with pytest.raises(ValueError, match='box IoU'):
-        both.evaluate_collected(*plain)
+        both.evaluate_collected(plain)
 
 
 def test_default_arguments_report_what_they_always_did(data):
@@ -225,27 +234,28 @@ def test_default_arguments_report_what_they_always_did(data):
     plain = _records(data)
     default = E.InstanceSegmentationCOCOEvaluator(None, None, label_names=names)
     assert default.iou_types == ('segm',)
-    obs = default.evaluate_collected(*plain)
+    obs = default.evaluate_collected(plain)
     result = matching.coco_results(matching.coco_evaluate_from_counts(
-        plain[0], plain[1], plain[2], [g[1] for g in plain[3]], [g[3] for g in plain[3]],
-        [g[4] for g in plain[3]]))
+        plain.tables['segm'], plain.pred_labels, plain.pred_scores, data['gt_labels'][:6],
+        data['gt_crowdeds'][:6], data['gt_areas'][:6]))
     want = {'validation/main/' + k: v for k, v in E.coco_report(result, names).items()}
     assert sorted(obs) == sorted(want) and not any('bbox' in k for k in obs)
     for k in want:
         assert np.array_equal(np.asarray(obs[k]), np.asarray(want[k]), equal_nan=True), k
     both = E.InstanceSegmentationCOCOEvaluator(None, None, label_names=names,
                                                iou_types=('segm', 'bbox'))
-    obs2 = both.evaluate_collected(*_records(data, box='coco'))
+    obs2 = both.evaluate_collected(_records(data, box='coco'))
     for k in want:                                    # asking for boxes changes no segm value
         assert np.array_equal(np.asarray(obs2[k]), np.asarray(want[k]), equal_nan=True), k
     only = E.InstanceSegmentationCOCOEvaluator(None, None, label_names=names, iou_types=('bbox',))
-    obs3 = only.evaluate_collected(*_records(data, box='coco'))
+    obs3 = only.evaluate_collected(_records(data, box='coco'))
     assert sorted(obs3) == sorted(k for k in obs2 if '/bbox/' in k)
     for k in obs3:
         assert np.array_equal(np.asarray(obs3[k]), np.asarray(obs2[k]), equal_nan=True), k
     voc = E.InstanceSegmentationVOCEvaluator(None, None, use_07_metric=True, label_names=names)
-    gts4 = [g[:3] for g in plain[3]]
-    assert sorted(voc.evaluate_collected(plain[0], plain[1], plain[2], gts4)) == sorted(
+    flagless = EvalRecords(plain.pred_labels, plain.pred_scores, plain.gt_labels,
+                           tables=plain.tables)
+    assert sorted(voc.evaluate_collected(flagless)) == sorted(
         ['validation/main/map'] + ['validation/main/ap/' + n for n in names])
     for bad in ((), ('boxes',), ('segm', 'keypoints')):
         with pytest.raises(ValueError):

@@ -9,9 +9,9 @@ import boundary_ref as BR
 import instseg_eval_ref as R
 import chainer_mask_rcnn_amd as cmr
 from chainer_mask_rcnn_amd import _lib
-from chainer_mask_rcnn_amd.extensions import instance_segmentation_evaluators as E
 from chainer_mask_rcnn_amd.utils.evaluations import coco_results as CR
 from chainer_mask_rcnn_amd.utils.evaluations import masks as M
+from chainer_mask_rcnn_amd.utils.evaluations.records import EvalRecords
 
 pytestmark = pytest.mark.gpu
 
@@ -197,16 +197,16 @@ def runs(request, dev, model):
     batches = [examples[0:2], examples[2:4], examples[4:5]]
     out = dict(kind=kind, data=examples, batches=batches, names=NAMES)
     out['plain_records'] = _evaluator(kind, batches, model).collect()
-    out['plain'] = _evaluator(kind, None, model).evaluate_collected(*out['plain_records'])
+    out['plain'] = _evaluator(kind, None, model).evaluate_collected(out['plain_records'])
     ev = _evaluator(kind, batches, model, ('segm', 'bbox'))
     out['boxed_records'] = ev.collect()
-    out['boxed'] = ev.evaluate_collected(*out['boxed_records'])
+    out['boxed'] = ev.evaluate_collected(out['boxed_records'])
     ev = _evaluator(kind, batches, model, ('segm', 'bbox', 'boundary'))
     out['records'] = ev.collect()
-    out['all'] = ev.evaluate_collected(*out['records'])
+    out['all'] = ev.evaluate_collected(out['records'])
     ev = _evaluator(kind, batches, model, ('boundary',))
     out['only_records'] = ev.collect()
-    out['only'] = ev.evaluate_collected(*out['only_records'])
+    out['only'] = ev.evaluate_collected(out['only_records'])
     masks, labels, scores = [], [], []
     for b in batches:                      # same batch composition (padding) as the evaluator
         _, m, l, s = model.predict([ex[0] for ex in b])
@@ -252,18 +252,24 @@ def test_boundary_alone_reports_the_same_keys_and_changes_no_other(runs):
 
 def test_record_widths(runs):
     n = len(runs['data'])
-    assert len(runs['plain_records']) == 4 and len(runs['boxed_records']) == 5
+    assert set(runs['plain_records'].tables) == {'segm'}
+    assert set(runs['boxed_records'].tables) == {'segm', 'bbox'}
+    assert set(runs['records'].tables) == {'segm', 'bbox', 'boundary'}
+    assert set(runs['only_records'].tables) == {'segm', 'boundary'}
     for rec in (runs['records'], runs['only_records']):
-        assert len(rec) == 6 and all(len(part) == n for part in rec)
-        for (inter, pa, ga), (b_inter, b_pa, b_ga) in zip(rec[0], rec[5]):
+        assert all(len(part) == n for part in list(rec.tables.values()) + [
+            rec.pred_labels, rec.pred_scores, rec.gt_labels])
+        for (inter, pa, ga), (b_inter, b_pa, b_ga) in zip(rec.tables['segm'],
+                                                          rec.tables['boundary']):
             assert b_inter.shape == inter.shape and (b_inter <= inter).all()
             assert (b_pa <= pa).all() and (b_ga <= ga).all() and ((b_pa > 0) == (pa > 0)).all()
-    assert all(b is None for b in runs['only_records'][4])
-    assert all(b is not None for b in runs['records'][4])
-    for a, b in zip(runs['records'][0] + runs['records'][5],
-                    runs['only_records'][0] + runs['only_records'][5]):
-        assert all(np.array_equal(x, y) for x, y in zip(a, b))
-    for a, b in zip(runs['records'][0], runs['plain_records'][0]):    # the mask counts as they were
+    assert 'bbox' not in runs['only_records'].tables
+    assert all(b is not None for b in runs['records'].tables['bbox'])
+    for k in ('segm', 'boundary'):
+        for a, b in zip(runs['records'].tables[k], runs['only_records'].tables[k]):
+            assert all(np.array_equal(x, y) for x, y in zip(a, b))
+    # the mask counts as they were
+    for a, b in zip(runs['records'].tables['segm'], runs['plain_records'].tables['segm']):
         assert all(np.array_equal(x, y) for x, y in zip(a, b))
 
 
@@ -274,9 +280,9 @@ def test_two_shards_merged_equal_the_single_run_at_batch_size_one(runs, model):
     single = _evaluator(kind, [[ex] for ex in examples], model, types).evaluate()
     shards = [_evaluator(kind, [[ex] for ex in part], model, types).collect()
               for part in (examples[:3], examples[3:])]
-    merged = E.merge_records([E.strip_records(*s) for s in shards])
-    assert len(merged) == 6
-    same(_evaluator(kind, None, model, types).evaluate_collected(*merged), single)
+    merged = EvalRecords.merge(shards)
+    assert set(merged.tables) == {'segm', 'boundary'}
+    same(_evaluator(kind, None, model, types).evaluate_collected(merged), single)
     assert any('/boundary/' in k for k in single)
 
 

@@ -10,10 +10,10 @@ import torch
 
 import detection_eval_ref as R
 import chainer_mask_rcnn_amd as cmr
-from chainer_mask_rcnn_amd.extensions import instance_segmentation_evaluators as E
 from chainer_mask_rcnn_amd.utils.evaluations import boxes as B
 from chainer_mask_rcnn_amd.utils.evaluations import coco_results as CR
 from chainer_mask_rcnn_amd.utils.evaluations import matching
+from chainer_mask_rcnn_amd.utils.evaluations.records import EvalRecords, Readback
 
 pytestmark = pytest.mark.gpu
 
@@ -52,7 +52,9 @@ def test_ragged_batch_is_bit_identical_to_numpy(dev, convention, on_device):
     iou, shapes = B.queue_box_ious(a, b, convention, crowd_b=crowd)
     assert shapes == [(0, 3), (5, 0), (1, 1), (100, 7), (65, 64)]
     assert iou.is_cuda and iou.shape == (1 + 700 + 65 * 64,)
-    got = B.split_tables(iou.cpu().numpy(), shapes)
+    readback = Readback()
+    readback.add_split(iou, shapes)
+    got = readback.fetch()
     for g, w in zip(got, want):
         assert g.dtype == dtype and w.dtype == dtype and g.shape == w.shape
         assert np.array_equal(_as_bits(g), _as_bits(w))
@@ -78,7 +80,9 @@ def test_batches_without_pairs_return_without_a_launch(dev, convention):
         iou, shapes = B.queue_box_ious(a, b, convention)
         torch.cuda.synchronize()
         assert iou.shape == (0,) and shapes == [(len(x), len(y)) for x, y in zip(a, b)]
-        assert [t.shape for t in B.split_tables(iou.cpu().numpy(), shapes)] == shapes
+        readback = Readback()
+        readback.add_split(iou, shapes)
+        assert [t.shape for t in readback.fetch()] == shapes
     with pytest.raises(ValueError):
         B.queue_box_ious([some], [some, some], convention)
 
@@ -215,7 +219,7 @@ def runs(request, dev, model):
     out['default'] = _evaluator(kind, batches, model).evaluate()
     ev = _evaluator(kind, batches, model, ('segm', 'bbox'))
     out['records'] = ev.collect()
-    out['both'] = ev.evaluate_collected(*out['records'])
+    out['both'] = ev.evaluate_collected(out['records'])
     out['bbox'] = _evaluator(kind, batches, model, ('bbox',)).evaluate()
     boxes, labels, scores = [], [], []
     for b in batches:                      # same batch composition (padding) as the evaluator
@@ -231,7 +235,8 @@ def test_segm_keys_are_the_default_evaluators(runs):
     segm = {k: v for k, v in runs['both'].items() if '/bbox/' not in k}
     same(segm, runs['default'])
     assert not any('bbox' in k for k in runs['default'])
-    assert len(runs['records']) == 5 and len(runs['records'][4]) == len(runs['data'])
+    assert set(runs['records'].tables) == {'segm', 'bbox'}
+    assert len(runs['records'].tables['bbox']) == len(runs['data'])
 
 
 def test_bbox_keys_equal_eval_detection_on_predict(runs):
@@ -266,9 +271,9 @@ def test_two_shards_merged_equal_the_single_run_at_batch_size_one(runs, model):
     single = _evaluator(kind, [[ex] for ex in data], model, types).evaluate()
     shards = [_evaluator(kind, [[ex] for ex in part], model, types).collect()
               for part in (data[:3], data[3:])]
-    merged = E.merge_records([E.strip_records(*s) for s in shards])
-    assert len(merged) == 5
-    same(_evaluator(kind, None, model, types).evaluate_collected(*merged), single)
+    merged = EvalRecords.merge(shards)
+    assert set(merged.tables) == {'segm', 'bbox'}
+    same(_evaluator(kind, None, model, types).evaluate_collected(merged), single)
     assert any('/bbox/' in k for k in single)
 
 

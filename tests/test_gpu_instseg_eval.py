@@ -267,3 +267,81 @@ def test_ground_truth_as_prediction_gives_map_one(dev):
     r = cmr.utils.eval_instseg_coco(gm, gl, ones, gm, gl)
     assert r['map/iou=0.50:0.95/area=all/maxDets=100'] == 1.
     assert r['map/iou=0.75/area=all/maxDets=100'] == 1.
+
+
+# ----------------------------------------------------------------- the records and the read-back
+def test_readback_of_device_tensors_equals_each_tensors_own_copy(dev):
+    from records_util import check_readback, readback_parts
+    from chainer_mask_rcnn_amd.utils.evaluations.records import Readback
+    on_device = [t.to(dev) for t in readback_parts()]
+    readback = Readback()
+    for t in on_device:
+        readback.add(t)
+    check_readback([t.cpu() for t in on_device], readback.fetch())
+
+
+def test_one_readback_per_batch_and_results_files_score_the_observation(dev, tmp_path,
+                                                                        monkeypatch):
+    """Two batches of two images, all three IoU types: ``collect()`` reads back once per batch
+    (once more per batch for the sink's strings), ``eval_coco_results`` once per image, and the
+    file the sink wrote scores the evaluator's observation for every IoU type."""
+    from test_gpu_coco_results import same
+    from test_gpu_detection_eval import _small_model as small_model, _synthetic as synthetic
+    from chainer_mask_rcnn_amd.utils.evaluations import coco_results as CR
+    from chainer_mask_rcnn_amd.utils.evaluations import records, rle
+    calls = {'fetch': 0, 'fetch_encoded': 0}
+
+    def counting(name, fn):
+        def wrapper(*args, **kwargs):
+            calls[name] += 1
+            return fn(*args, **kwargs)
+        return wrapper
+    monkeypatch.setattr(records.Readback, 'fetch', counting('fetch', records.Readback.fetch))
+    monkeypatch.setattr(rle, 'fetch_encoded', counting('fetch_encoded', rle.fetch_encoded))
+
+    class Annotations(object):
+        """What eval_coco_results reads of a COCOInstanceSegmentationDataset."""
+        def __init__(self, examples):
+            self.examples = examples
+            self.img_ids = [100 + i for i in range(len(examples))]
+            self.img_sizes = {i: tuple(ex[0].shape[1:]) for i, ex in zip(self.img_ids, examples)}
+            self.class_id_to_cat_id = {l: 2 * l + 1 for l in range(80)}
+            self.cat_id_to_class_id = {c: l for l, c in self.class_id_to_cat_id.items()}
+
+        def __len__(self):
+            return len(self.examples)
+
+        def get_annotations(self, i):
+            return self.examples[i][1:]
+
+    examples = synthetic(np.random.RandomState(11), 4, with_crowd=True)
+    data = Annotations(examples)
+    names = ['c%d' % l for l in range(80)]
+    model = small_model(dev)
+    batches = [examples[0:2], examples[2:4]]
+    types = ('segm', 'bbox', 'boundary')
+    path = str(tmp_path / 'res.json')
+    with CR.ResultsWriter(path, data.img_ids, data.class_id_to_cat_id) as w:
+        ev = cmr.extensions.InstanceSegmentationCOCOEvaluator(
+            batches, model, label_names=names, results_sink=w, iou_types=types)
+        rec = ev.collect()
+    assert calls == {'fetch': 2, 'fetch_encoded': 2} and w.n_entries > 0
+    assert set(rec.tables) == set(types) and len(rec) == 4
+    plain = cmr.extensions.InstanceSegmentationCOCOEvaluator(
+        batches, model, label_names=names, iou_types=types).collect()
+    assert calls == {'fetch': 4, 'fetch_encoded': 2}
+    for k in types:
+        for a, b in zip(rec.tables[k], plain.tables[k]):
+            assert all(np.array_equal(x, y) for x, y in zip(a, b)), k
+    mem = ev.evaluate_collected(rec)
+    assert len(mem) == 3 * (3 + len(names)) and calls['fetch'] == 4
+    # once per image; the box tables of all images are one launch and one read-back
+    for iou_type, prefix, per_call in (('segm', '', 4), ('boundary', 'boundary/', 4),
+                                       ('bbox', 'bbox/', 1)):
+        before = calls['fetch']
+        got = CR.eval_coco_results(path, data, limit=4, label_names=names, iou_type=iou_type)
+        assert calls['fetch'] - before == per_call, iou_type
+        keys = ['validation/main/' + prefix + k
+                for k in ['map', 'map@0.5', 'map@0.75'] + ['ap/' + n for n in names]]
+        same(got, {k: mem[k] for k in keys})
+    assert calls['fetch_encoded'] == 2

@@ -17,6 +17,8 @@ from chainer_mask_rcnn_amd.extensions import instance_segmentation_evaluators as
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
 import train  # noqa: E402
+from chainer_mask_rcnn_amd.utils.evaluations.records import EvalRecords  # noqa: E402
+from records_util import ATTRS, same_lists, take  # noqa: E402
 import trainer as T  # noqa: E402
 
 TIMEOUT = 120
@@ -76,7 +78,7 @@ def _records(kind, seed=0, n_img=9):
     """collect()-shaped records: ragged P x G counts, images without predictions or ground truth,
     difficult (VOC) or crowd / area (COCO) flags."""
     rng = np.random.RandomState(seed)
-    counts, pls, pss, gts = [], [], [], []
+    counts, pls, pss, gls, flags = [], [], [], [], []
     for i in range(n_img):
         G = 0 if i == 2 else rng.randint(1, 5)
         P = 0 if i == 5 else rng.randint(1, 9)
@@ -94,14 +96,16 @@ def _records(kind, seed=0, n_img=9):
             ps[1] = ps[0]                                       # ties across the ranks' records
         pss.append(ps)
         labels = rng.randint(0, 3, G).astype(np.int32)
-        bbox = rng.uniform(0, 50, (G, 4)).astype(np.float32)
-        mask = rng.uniform(size=(G, 8, 8)) > 0.5
+        rng.uniform(0, 50, (G, 4)), rng.uniform(size=(G, 8, 8))     # the example's boxes and masks
+        gls.append(labels)
         if kind == 'voc':
-            gts.append((bbox, labels, mask, (rng.uniform(size=G) < 0.3)))
+            flags.append(((rng.uniform(size=G) < 0.3),))
         else:
-            gts.append((bbox, labels, mask, (rng.uniform(size=G) < 0.25).astype(np.int32),
-                        ga.astype(np.float32) * np.float32(rng.uniform(0.8, 1.2))))
-    return counts, pls, pss, gts
+            flags.append(((rng.uniform(size=G) < 0.25).astype(np.int32),
+                          ga.astype(np.float32) * np.float32(rng.uniform(0.8, 1.2))))
+    names = ('gt_difficults',) if kind == 'voc' else ('gt_crowdeds', 'gt_areas')
+    return EvalRecords(pls, pss, gls, tables={'segm': counts},
+                       **{k: [f[i] for f in flags] for i, k in enumerate(names)})
 
 
 def _evaluator(kind):
@@ -112,9 +116,8 @@ def _evaluator(kind):
 
 
 def _shard(records, rank, world):
-    n = len(records[0])
-    lo, hi = n * rank // world, n * (rank + 1) // world
-    return tuple(list(r[lo:hi]) for r in records)
+    n = len(records)
+    return take(records, n * rank // world, n * (rank + 1) // world)
 
 
 class _Collected(object):
@@ -126,8 +129,8 @@ class _Collected(object):
     def collect(self):
         return self.records
 
-    def evaluate_collected(self, *records):
-        return self.evaluator.evaluate_collected(*records)
+    def evaluate_collected(self, records):
+        return self.evaluator.evaluate_collected(records)
 
 
 def _free_port():
@@ -150,8 +153,8 @@ def _worker(rank, world, port, q):
         ev = E.create_multi_node_evaluator(_Collected(_evaluator(kind), records))
         out[kind] = ev.evaluate()
         merged = E.gather_records(records)
-        out[kind + '/stripped'] = all(g[0] is None and g[2] is None for g in merged[3])
-        out[kind + '/n'] = len(merged[0])
+        out[kind + '/stripped'] = set(vars(merged)) == ATTRS and set(merged.tables) == {'segm'}
+        out[kind + '/n'] = len(merged.tables['segm'])
     # the log reduction: every rank's window sums, rank-order float32 mean
     rng = np.random.RandomState(rank)
     sums = (rng.standard_normal(6) * 1e3).astype(np.float32)
@@ -180,7 +183,7 @@ def test_sharded_evaluation_equals_one_process_at_world_2():
                 p.kill()
     assert [p.exitcode for p in procs] == [0, 0]
     for kind in ('voc', 'coco'):
-        want = _evaluator(kind).evaluate_collected(*_records(kind))
+        want = _evaluator(kind).evaluate_collected(_records(kind))
         assert 'validation/main/map' in want
         for rank in (0, 1):
             got = res[rank][kind]
@@ -212,13 +215,23 @@ def test_rank_order_mean_is_a_float32_sequential_sum():
     assert np.array_equal(one, sums[0] / np.float32(3))
 
 
-def test_strip_records_keeps_what_matching_reads():
-    counts, pls, pss, gts = _records('coco', n_img=3)
-    s = E.strip_records(counts, pls, pss, gts)
-    for g, h in zip(gts, s[3]):
-        assert len(h) == len(g) == 5 and h[0] is None and h[2] is None
-        assert h[1] is g[1] and h[3] is g[3] and h[4] is g[4]
-    assert E.merge_records([s, s])[0] == list(counts) + list(counts)
+def test_records_keep_what_matching_reads():
+    """The record never holds an example's boxes or masks: its attributes are the labels, the
+    scores, the flags and the tables, and a pickle round trip (how it travels) keeps them."""
+    import pickle
+    rec = _records('coco', n_img=3)
+    assert set(vars(rec)) == ATTRS == {'pred_labels', 'pred_scores', 'gt_labels', 'gt_difficults',
+                                       'gt_crowdeds', 'gt_areas', 'tables'}
+    assert rec.gt_difficults is None and len(rec.gt_crowdeds) == len(rec.gt_areas) == 3
+    back = pickle.loads(pickle.dumps(rec))
+    for h, g in zip(back.gt_labels + back.gt_crowdeds + back.gt_areas,
+                    rec.gt_labels + rec.gt_crowdeds + rec.gt_areas):
+        assert h.dtype == g.dtype and np.array_equal(h, g)
+    m = EvalRecords.merge([rec, rec])
+    assert same_lists(m.tables['segm'], rec.tables['segm'] * 2)
+    assert same_lists(m.gt_labels, rec.gt_labels * 2)
+    assert same_lists(m.gt_crowdeds, rec.gt_crowdeds * 2)
+    assert same_lists(m.gt_areas, rec.gt_areas * 2)
 
 
 # ---- launch ----------------------------------------------------------------------------------

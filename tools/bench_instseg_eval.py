@@ -27,6 +27,7 @@ sys.path.insert(0, ROOT)
 from chainer_mask_rcnn_amd import _lib  # noqa: E402
 from chainer_mask_rcnn_amd.functions._layout import nhwc  # noqa: E402
 from chainer_mask_rcnn_amd.utils.evaluations import masks as M  # noqa: E402
+from chainer_mask_rcnn_amd.utils.evaluations.records import Readback  # noqa: E402
 
 
 def make(rng, D, G, H, W, dev):
@@ -45,10 +46,9 @@ def make(rng, D, G, H, W, dev):
 def device_path(bbox, label, logits, gt, H, W):
     pred = M.paste_packed(logits, label, bbox, (H, W))
     g = M.pack_masks(gt, device=logits.device)
-    inter = M.queue_intersections(pred, g, W)
-    flat = torch.cat([inter.reshape(-1).to(torch.int64), pred[1].to(torch.int64),
-                      g[1].to(torch.int64)])
-    return flat.cpu().numpy()
+    readback = Readback()
+    M.queue_counts(readback, pred, g, (H, W))
+    return readback.fetch()
 
 
 def host_masks(bbox, label, logits, H, W):
@@ -107,9 +107,7 @@ def main():
         r['host_masks'] = timed(lambda: host_path(bbox, label, logits, gt, H, W), args.reps)
         r['numpy'] = timed(lambda: numpy_path(pm, gt), args.numpy_reps, warmup=False)
         # the three paths agree on the IoU
-        cnt = device_path(bbox, label, logits, gt, H, W)
-        inter = cnt[:D * G].reshape(D, G)
-        iou = M.iou_from_counts(inter, cnt[D * G:D * G + D], cnt[D * G + D:])
+        iou = M.iou_from_counts(*device_path(bbox, label, logits, gt, H, W))
         assert np.array_equal(iou, host_path(bbox, label, logits, gt, H, W))
         if G <= 10:
             assert np.array_equal(iou, numpy_path(pm, gt))
