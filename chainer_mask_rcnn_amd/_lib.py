@@ -143,6 +143,8 @@ SIGNATURES = {
     'mrcnn_mask_resize_nearest': (c_int, [c_vp] + [c_int] * 3 + [c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
     'mrcnn_mask_resize_crop': (c_int, [c_vp] + [c_int] * 3 + [c_vp, c_vp, c_int] + [c_vp] * 5),
     'mrcnn_copy_paste': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int] + [c_vp] * 6),
+    'mrcnn_mask_union_pack': (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    'mrcnn_box_coverage': (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp]),
     'mrcnn_allreduce_unique_id': (c_int, [c_vp]),
     'mrcnn_allreduce_init': (c_int, [c_vp, c_int, c_int, ctypes.POINTER(c_vp)]),
     'mrcnn_allreduce_destroy': (c_int, [c_vp]),

@@ -27,7 +27,12 @@ class CopyPasteDataset(object):
     lose those pixels, the pasted masks are appended, labels likewise.  Instances left without a
     pixel are dropped — targets the paste covers, and pixel-less instances the jitter's fallback
     can carry on either side — and ``bbox`` becomes the tight float32 box of every kept mask.
-    ``scale`` stays the example's.  If nothing would be kept the example is returned as it is."""
+    ``scale`` stays the example's.  If nothing would be kept the example is returned as it is.
+
+    Examples of length 6 (``MaskRCNNTransform(crowd_ignore=True)``: an ignore plane or ``None``
+    last) keep their sixth element; when a paste happens the example's plane loses the pasted
+    pixels (``functions.union_plane(pasted masks, base=plane)``: what is pasted is real
+    foreground).  The source's plane is not carried.  Example and source must have one length."""
 
     def __init__(self, dataset, prob=0.5):
         if not 0 <= prob <= 1:
@@ -62,6 +67,9 @@ class CopyPasteDataset(object):
         if not random.random() < self.prob:
             return ex
         src = self.dataset[random.randrange(len(self.dataset))]
+        if len(ex) != len(src) or len(ex) not in (5, 6):
+            raise ValueError('CopyPasteDataset: example and source must both have 5 elements, or both '
+                             '6 (with an ignore plane), got %d and %d' % (len(ex), len(src)))
         self._check(ex, src)
         if len(src[3]) == 0:
             return ex
@@ -83,4 +91,12 @@ class CopyPasteDataset(object):
             masks = masks[torch.from_numpy(np.flatnonzero(keep)).to(masks.device)]
         bbox = meta[:4 * n].reshape(n, 4)[keep].astype(np.float32)
         label = np.concatenate([np.asarray(ex[2]), np.asarray(src[2])[idx]])[keep]
-        return img, bbox, label, masks, ex[4]
+        if len(ex) == 5:
+            return img, bbox, label, masks, ex[4]
+        plane = ex[5]
+        if plane is not None:
+            from ..functions.ignore_regions import union_plane
+            # the pasted rows are the last len(idx) of the launch's output; those the paste left
+            # without a pixel add nothing to the union
+            plane = union_plane(masks[int(keep[:n - len(idx)].sum()):], base=plane)
+        return img, bbox, label, masks, ex[4], plane

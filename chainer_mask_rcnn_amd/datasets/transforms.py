@@ -144,13 +144,29 @@ class MaskRCNNTransform(object):
     nothing is drawn), the example is resized by ``min(S/H, S/W)`` at offset 0 and every instance
     is kept with its given box resized and flipped: the plain path on an S x S canvas.  The image
     is (3, S, S), the masks (G', S, S), ``scale`` the resize scale.  With ``scale_jitter=None``
-    nothing changes."""
+    nothing changes.
+
+    ``crowd_ignore=True`` (training mode with ``device_masks=True`` only):
+    ``in_data`` is ``(img, bbox, label, mask, crowd)`` or the 6-tuple with ``area``, as a dataset
+    built with ``use_crowd=True, return_crowd=True`` gives it.  The crowd instances
+    (``crowd != 0``) ride through the same device calls as the others — rows of the one packed
+    upload and of the one resize launch, under the same flip and jitter geometry — and are then
+    split off: ``bbox``, ``label`` and ``mask`` hold the regular instances only, and a sixth
+    element ``ignore`` is returned, the union of the crowd rows as a bit plane of the output size
+    (``functions.union_plane``), or ``None`` when no crowd pixel is left.  The draws are those of
+    the transform without it; under ``scale_jitter`` a geometry is accepted when a REGULAR
+    instance keeps a pixel, and an example whose instances are all crowds takes the path of an
+    example without instances.  With ``crowd_ignore=False`` nothing changes."""
 
     def __init__(self, mask_rcnn, train=True, device_masks=False, scale_jitter=None,
-                 crop_size=1024):
+                 crop_size=1024, crowd_ignore=False):
         self.mask_rcnn = mask_rcnn
         self.train = train
         self.device_masks = device_masks
+        if crowd_ignore and not (train and device_masks):
+            raise ValueError('MaskRCNNTransform: crowd_ignore requires train=True and '
+                             'device_masks=True (the ignore plane is built on the device)')
+        self.crowd_ignore = bool(crowd_ignore)
         if scale_jitter is not None:
             if not (train and device_masks):
                 raise ValueError('MaskRCNNTransform: scale_jitter requires train=True and '
@@ -167,6 +183,8 @@ class MaskRCNNTransform(object):
         self.crop_size = crop_size
 
     def __call__(self, in_data):
+        if self.crowd_ignore:
+            return self._with_crowds(in_data)
         if len(in_data) not in (4, 6):
             raise ValueError
         img, bbox, label, mask = in_data[:4]
@@ -201,6 +219,48 @@ class MaskRCNNTransform(object):
         mask = stack[0] if mask.ndim == 2 else stack
         return x, bbox, label, mask, scales[0]
 
+    def _with_crowds(self, in_data):
+        """``crowd_ignore=True`` (class docstring): the same draws and device calls as without it,
+        over all the instances; the crowd rows leave as one bit plane."""
+        import torch
+        from ..functions import ignore_regions
+        if len(in_data) not in (5, 6):
+            raise ValueError('MaskRCNNTransform: crowd_ignore expects (img, bbox, label, mask, crowd[, '
+                             'area]), got %d elements' % len(in_data))
+        img, bbox, label, mask, crowd = in_data[:5]
+        crowd = np.asarray(crowd) != 0
+        if mask.ndim != 3 or crowd.shape != (len(mask),):
+            raise ValueError('MaskRCNNTransform: crowd_ignore expects (G, H, W) masks and one crowd '
+                             'flag per instance, got %r and %r' % (tuple(mask.shape), crowd.shape))
+        if not isinstance(mask, PackedMasks):
+            mask = PackedMasks.from_dense(mask)
+        chw = img.transpose(2, 0, 1)
+        x_flip = random.choice([True, False])
+        in_size = chw.shape[1:]
+        if self.scale_jitter is not None:
+            x, bbox, label, masks, scale, (crowd, present) = self._scale_jitter(
+                chw, bbox, label, mask, x_flip, regular=~crowd)
+        else:
+            imgs, _, scales = self.mask_rcnn.prepare([chw], x_flips=[x_flip])
+            x, scale = imgs[0], scales[0]
+            out_size = tuple(x.shape[1:])
+            if len(bbox) > 0:
+                bbox = resize_bbox(bbox, in_size, out_size)
+            bbox = flip_bbox(bbox, out_size, x_flip=x_flip)
+            masks = self._device_mask(mask, out_size, x_flip, x.device)
+            present = crowd.copy()
+            if crowd.any():
+                # a crowd pixel survives iff one lies on a sampled row and a sampled column
+                ys, xs = _nearest_index(out_size[0], in_size[0]), _nearest_index(out_size[1], in_size[1])
+                dense = mask[crowd].unpack(np.uint8)
+                present[crowd] = dense[:, np.unique(ys)][:, :, np.unique(xs)].any(axis=(1, 2))
+        # crowd, present: over the rows of masks / bbox / label as they stand now
+        rows = lambda sel: masks[torch.from_numpy(np.flatnonzero(sel)).to(masks.device)]
+        ignore = ignore_regions.union_plane(rows(present)) if present.any() else None
+        if crowd.any():
+            masks, bbox, label = rows(~crowd), bbox[~crowd], label[~crowd]
+        return x, bbox, label, masks, scale, ignore
+
     @staticmethod
     def _device_mask(mask, out_size, x_flip, device):
         """The network-size masks as a uint8 device tensor; only the packed words are uploaded."""
@@ -212,8 +272,11 @@ class MaskRCNNTransform(object):
                                             x_flip=x_flip)
         return out[0] if flat else out
 
-    def _scale_jitter(self, chw, bbox, label, mask, x_flip):
-        """The jittered example (class docstring); the flip has been drawn."""
+    def _scale_jitter(self, chw, bbox, label, mask, x_flip, regular=None):
+        """The jittered example (class docstring); the flip has been drawn.  ``regular`` (G,) bool
+        (``crowd_ignore``): only these instances decide whether a geometry is accepted, and the
+        result — still over ALL the instances it keeps — gains a sixth element: two (G',) bool
+        arrays, the crowd rows among them and the crowd rows that hold a pixel."""
         import torch
         from ..functions import gt_masks, scale_jitter as SJ
         model, S = self.mask_rcnn, self.crop_size
@@ -225,12 +288,13 @@ class MaskRCNNTransform(object):
         G = len(mask)
         packed = gt_masks.upload_packed_masks(mask, dev)
         masks = None
-        for _ in range(SCALE_JITTER_ATTEMPTS if G > 0 else 0):
+        decides = np.ones((G,), bool) if regular is None else regular
+        for _ in range(SCALE_JITTER_ATTEMPTS if decides.any() else 0):
             scale, resized, offset = draw_scale_jitter(in_size, S, self.scale_jitter)
             cropped, meta = SJ.resize_crop_masks_meta(packed, resized, offset, S, x_flip)
             meta = meta.cpu().numpy()                  # boxes and areas: the one read-back
             keep = meta[4 * G:] >= 1
-            if keep.any():
+            if (keep & decides).any():
                 masks = cropped
                 break
         if masks is not None:
@@ -238,12 +302,19 @@ class MaskRCNNTransform(object):
                 masks = masks[torch.from_numpy(np.flatnonzero(keep)).to(dev)]
                 label = label[keep]
             bbox = meta[:4 * G].reshape(G, 4)[keep].astype(np.float32)
+            crowd_rows = None if regular is None else (~regular[keep],) * 2
         else:
             scale = min(float(S) / in_size[0], float(S) / in_size[1])
             resized, offset = _resized_size(in_size, scale), (0, 0)
-            masks = SJ.resize_crop_masks(packed, resized, offset, S, x_flip)[0]
+            masks, meta = SJ.resize_crop_masks_meta(packed, resized, offset, S, x_flip)
             if len(bbox) > 0:
                 bbox = resize_bbox(bbox, in_size, resized)
             bbox = flip_bbox(bbox, resized, x_flip=x_flip)
+            crowd_rows = None if regular is None else (~regular, ~regular)
+            if regular is not None and not regular.all():
+                # every instance is kept here; which crowd rows still hold a pixel is read back
+                crowd_rows = (~regular, ~regular & (meta.cpu().numpy()[4 * G:] >= 1))
         x = SJ.prepare_image_crop(model.mean, chw, scale, resized, offset, S, x_flip, dev)
+        if regular is not None:
+            return x, bbox, label, masks, scale, crowd_rows
         return x, bbox, label, (masks[0] if flat else masks), scale

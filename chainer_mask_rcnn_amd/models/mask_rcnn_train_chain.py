@@ -156,12 +156,23 @@ class MaskRCNNTrainChain(torch.nn.Module):
         # when the caller already has it — a resident batch, the input pipeline's prefetched one.
         # Its frozen prefix then runs beside this step's backbone backward.  None: off.
         self.next_imgs = None
+        # Ignore regions: a proposal or an anchor is ignored when the image's
+        # ignore plane covers MORE than this fraction of its pixels (Detectron's
+        # TRAIN.CROWD_FILTER_THRESH).  Read only for images that come with a plane.
+        self.crowd_ignore_thresh = 0.7
 
-    def forward(self, imgs, bboxes, labels, masks, scales):
+    def forward(self, imgs, bboxes, labels, masks, scales, ignores=None):
         """imgs (N,3,H,W) device tensor; bboxes / labels / masks: per-image sequences of
         host (or device) arrays (G,4) f32 / (G,) i32 / (G,H,W) i32; scales (N,) floats.  Masks
         that are device tensors (uint8, ``MaskRCNNTransform(device_masks=True)``) are never copied
-        back: their mask targets come from ``mrcnn_mask_targets`` in both target paths."""
+        back: their mask targets come from ``mrcnn_mask_targets`` in both target paths.
+
+        ``ignores``: per image ``None`` or the ignore plane of its network-size image (int64
+        (H_i, Wq_i) device tensor as ``functions.union_plane`` returns it).  For such an
+        image one ``mrcnn_box_coverage`` launch over its anchors and proposals and one read-back
+        decide which of them the target creators leave out (``crowd_ignore_thresh``).  ``None``, or
+        no image with a plane: the launches, draws and loss of a call without the argument.  With a
+        list, ``report`` also carries the host counts ``n_ignored_rois`` / ``n_ignored_anchors``."""
         tl = self.host_timeline
         mark = (lambda label: tl.append((label, time.perf_counter()))) if tl is not None \
             else (lambda label: None)
@@ -197,8 +208,16 @@ class MaskRCNNTrainChain(torch.nn.Module):
         ptc = self.proposal_target_creator
         device_path = self.device_targets and dev.type == 'cuda' and hasattr(ptc, 'sample_device') \
             and hasattr(atc, 'prepare_device')
+        reports_ignored = ignores is not None
+        if ignores is not None:
+            ignores = list(ignores)
+            if len(ignores) != batch_size:
+                raise ValueError('ignores must hold one entry (a plane or None) per image, got %d for '
+                                 '%d images' % (len(ignores), batch_size))
+            if all(p is None for p in ignores):
+                ignores = None
         t = (self._forward_device_targets if device_path else self._forward_host_targets)(
-            features, img_size, scales, bboxes, labels, masks, anchor_h, mark)
+            features, img_size, scales, bboxes, labels, masks, anchor_h, mark, ignores)
         rpn_locs = t.rpn_locs.reshape(-1, 4)
         rpn_scores = t.rpn_scores.reshape(-1)
         rpn_loc_loss = F.fast_rcnn_loc_loss(rpn_locs, t.gt_rpn_locs, t.gt_rpn_labels, self.rpn_sigma)
@@ -225,18 +244,50 @@ class MaskRCNNTrainChain(torch.nn.Module):
                        'roi_cls_loss': roi_cls_loss.detach(),
                        'roi_mask_loss': roi_mask_loss.detach(),
                        'loss': loss.detach()}
+        if reports_ignored:
+            # host counts, logged beside the losses (as main/n_ignored_*) where planes are passed
+            self.report['n_ignored_rois'], self.report['n_ignored_anchors'] = self._n_ignored
         mark('losses queued')
         self.last_targets = {'sample_rois': t.sample_rois, 'sample_roi_indices': t.sample_roi_indices,
                              'feature_shape': tuple(features.shape), 'gt_roi_labels': t.gt_roi_labels,
                              'gt_roi_masks': t.gt_roi_masks, 'gt_rpn_labels': t.gt_rpn_labels,
                              'n_rois': int(t.sample_rois.shape[0]), 'roi_hints': t.roi_hints,
-                             'n_fg': t.n_fg}                  # host count, no read-back
+                             'n_fg': t.n_fg,                  # host count, no read-back
+                             'n_ignored_rois': self._n_ignored[0],
+                             'n_ignored_anchors': self._n_ignored[1]}
         if t.roi_hints is not None:
             # read by the benchmark's isolated ROIAlign measurement only, never by this package
             t.sample_rois._mrcnn_order = t.roi_hints.order
         return loss
 
-    def _forward_host_targets(self, features, img_size, scales, bboxes, labels, masks, anchor_h, mark):
+    def _ignored_boxes(self, ignores, proposals, img_size):
+        """Per image ``None`` or ``(ignored anchors (S,) bool, ignored proposals (R_i,) bool)``: one
+        ``mrcnn_box_coverage`` launch over cat(anchors, the image's proposals) and one read-back
+        for each image that has a plane, none for the others.  The boxes are clipped by the plane's
+        own H_i x W_i (the image before batch padding).  Sets ``self._n_ignored`` (host ints)."""
+        self._n_ignored = (0, 0)
+        if ignores is None:
+            return None
+        out, n_roi, n_anchor = [], 0, 0
+        bounds = np.concatenate([[0], np.cumsum(proposals.counts)]).astype(int)
+        S = int(proposals.anchor.shape[0])
+        for i, plane in enumerate(ignores):
+            if plane is None:
+                out.append(None)
+                continue
+            # (a plane that does not say how many pixels its rows hold: all its words' worth)
+            width = getattr(plane, '_mrcnn_width', min(int(img_size[1]), 64 * int(plane.shape[1])))
+            rois = proposals.rois[int(bounds[i]):int(bounds[i + 1])].detach()
+            counts = F.box_coverage(plane, int(width), torch.cat((proposals.anchor, rois), 0))
+            ign = F.ignored_from_counts(counts.cpu().numpy(), self.crowd_ignore_thresh)
+            out.append((ign[:S], ign[S:]))
+            n_anchor += int(ign[:S].sum())
+            n_roi += int(ign[S:].sum())
+        self._n_ignored = (n_roi, n_anchor)
+        return out
+
+    def _forward_host_targets(self, features, img_size, scales, bboxes, labels, masks, anchor_h, mark,
+                              ignores=None):
         """RPN, host target creators (the reference's arrangement, :126-158) and the RoI head."""
         dev = features.device
         to_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
@@ -246,6 +297,9 @@ class MaskRCNNTrainChain(torch.nn.Module):
             atc_jobs = [_pool().submit(atc.prepare, bbox, anchor_h, img_size) for bbox in bboxes]
         # (proposals also as host arrays, in the synchronisation that reads their counts)
         proposals = self.mask_rcnn.rpn.propose(features, img_size, scales, host_copy=True)
+        ignored = self._ignored_boxes(ignores, proposals, img_size)
+        # (the keyword is passed only where an image has a plane: creators without it keep working)
+        ign = lambda i, k: {} if ignored is None or ignored[i] is None else dict(ignore=ignored[i][k])
         # proposal targets: host-side sampling, exactly as the reference (:126-146)
         mark('extractor+rpn queued')
         mark('rois on host')
@@ -256,11 +310,12 @@ class MaskRCNNTrainChain(torch.nn.Module):
         for batch_index, (bbox, label, mask) in enumerate(zip(bboxes, labels, masks)):
             roi = proposals.host_rois[batch_index]
             if split:
-                sample_roi, gt_roi_loc, gt_roi_label, job = ptc.sample(roi, bbox, label)
+                sample_roi, gt_roi_loc, gt_roi_label, job = ptc.sample(roi, bbox, label,
+                                                                       **ign(batch_index, 1))
                 mask_jobs.append((job, mask, sample_roi))
             else:
                 sample_roi, gt_roi_loc, gt_roi_label, gt_roi_mask = \
-                    ptc(roi, bbox, label, to_np(mask))
+                    ptc(roi, bbox, label, to_np(mask), **ign(batch_index, 1))
                 gt_roi_masks.append(gt_roi_mask)
             mark('ptc.sample')
             sample_rois.append(sample_roi)
@@ -326,8 +381,10 @@ class MaskRCNNTrainChain(torch.nn.Module):
         gt_rpn_locs, gt_rpn_labels = [], []
         for i, bbox in enumerate(bboxes):
             if atc_jobs is not None:
-                gt_rpn_loc, gt_rpn_label = atc.finish(atc_jobs[i].result())
+                gt_rpn_loc, gt_rpn_label = atc.finish(atc_jobs[i].result(), **ign(i, 0))
             else:
+                if ign(i, 0):
+                    raise ValueError('ignores: the anchor target creator needs prepare / finish')
                 gt_rpn_loc, gt_rpn_label = atc(bbox, anchor_h, img_size)
             gt_rpn_locs.append(gt_rpn_loc)
             gt_rpn_labels.append(gt_rpn_label)
@@ -371,7 +428,7 @@ class MaskRCNNTrainChain(torch.nn.Module):
         return T.mask_targets(m.contiguous(), roi_d, gt_index_d, n_fg, M, n=n)
 
     def _forward_device_targets(self, features, img_size, scales, bboxes, labels, masks, anchor_h,
-                                mark):
+                                mark, ignores=None):
         """Same step with the target arithmetic on the device.  The
         np.random call order is the reference's: every ProposalTargetCreator draw (foreground,
         background, image by image), then every AnchorTargetCreator draw."""
@@ -383,6 +440,8 @@ class MaskRCNNTrainChain(torch.nn.Module):
         atc_states = [atc.prepare_device(bbox, anchor_d, anchor_h, img_size, upload=_upload)
                       for bbox in bboxes]
         proposals = self.mask_rcnn.rpn.propose(features, img_size, scales)
+        ignored = self._ignored_boxes(ignores, proposals, img_size)
+        ign = lambda i, k: {} if ignored is None or ignored[i] is None else dict(ignore=ignored[i][k])
         mark('extractor+rpn queued')
         bounds = np.concatenate([[0], np.cumsum(proposals.counts)]).astype(int)
         mark('rois on host')
@@ -390,7 +449,7 @@ class MaskRCNNTrainChain(torch.nn.Module):
         for i, (bbox, label) in enumerate(zip(bboxes, labels)):
             roi_i = proposals.rois[int(bounds[i]):int(bounds[i + 1])]
             sample_roi, gt_roi_loc, gt_roi_label, job = ptc.sample_device(roi_i, bbox, label,
-                                                                          upload=_upload)
+                                                                          upload=_upload, **ign(i, 1))
             mark('ptc.sample')
             s_rois.append(sample_roi)
             s_idx.append(torch.full((job['n'],), i, dtype=torch.int32, device=dev))
@@ -432,7 +491,7 @@ class MaskRCNNTrainChain(torch.nn.Module):
             parts.append(_upload(t, torch.int32, dev))
         gt_roi_masks = torch.cat(parts, 0)
         mark('mask targets')
-        g_rl, g_rlab = zip(*[atc.finish_device(st) for st in atc_states])
+        g_rl, g_rlab = zip(*[atc.finish_device(st, **ign(i, 0)) for i, st in enumerate(atc_states)])
         gt_rpn_locs, gt_rpn_labels = torch.cat(g_rl, 0), torch.cat(g_rlab, 0)
         mark('rpn targets')
         return StepTargets(proposals.rpn_locs, proposals.rpn_scores, sample_rois, sample_roi_indices,

@@ -64,9 +64,9 @@ class AnchorTargetCreator(object):
             inside = np.where((anchor_h[:, 0] >= 0) & (anchor_h[:, 1] >= 0) &
                               (anchor_h[:, 2] <= H) & (anchor_h[:, 3] <= W))[0].astype(np.int32)
             inside_d = torch.tensor(inside, device=dev)
-            cache = (key, inside_d, anchor_d.index_select(0, inside_d.long()).contiguous())
+            cache = (key, inside_d, anchor_d.index_select(0, inside_d.long()).contiguous(), inside)
             self._inside_cache = cache
-        _, inside_d, a_d = cache
+        _, inside_d, a_d, inside_h = cache
         bbox_d = upload(np.asarray(bbox, np.float32), torch.float32, dev)
         max_iou, argmax, iou, gt_max = T.bbox_iou_argmax(a_d, bbox_d, want_matrix=True)
         label_d = T.anchor_labels(iou, max_iou, gt_max, self.neg_iou_thresh, self.pos_iou_thresh)
@@ -74,17 +74,22 @@ class AnchorTargetCreator(object):
         label_h.copy_(label_d, non_blocking=True)
         done = torch.cuda.Event()
         done.record()
-        return dict(n_anchor=int(anchor_h.shape[0]), inside=inside_d, anchor=a_d, bbox=bbox_d,
+        return dict(n_anchor=int(anchor_h.shape[0]), inside=inside_d, inside_h=inside_h, anchor=a_d, bbox=bbox_d,
                     argmax=argmax, label_d=label_d, label_h=label_h, done=done, upload=upload)
 
-    def finish_device(self, st):
+    def finish_device(self, st, ignore=None):
         """The np.random draws of ``finish`` on the host copy of the labels (same calls, same
-        order), then the full-size targets on the device: loc (S,4), label (S,)."""
+        order), then the full-size targets on the device: loc (S,4), label (S,).  ``ignore``: as
+        in ``finish``; the anchors it takes out join the ``disabled`` list of the launch."""
         import torch
         from ...functions import target_ops as T
         st['done'].synchronize()
         label = st['label_h'].numpy()
         disabled = []
+        d = _ignored_negatives(label, ignore, st['inside_h'], st['n_anchor'])
+        if d is not None:
+            label[d] = -1
+            disabled.append(d)
         n_pos = int(self.pos_ratio * self.n_sample)
         pos = np.where(label == 1)[0]
         if len(pos) > n_pos:
@@ -104,8 +109,16 @@ class AnchorTargetCreator(object):
         return T.anchor_targets_finish(st['anchor'], st['inside'], st['label_d'], st['argmax'],
                                        st['bbox'], dis_d, st['n_anchor'])
 
-    def finish(self, state):
+    def finish(self, state, ignore=None):
+        """``ignore``: host bool array over all S anchors.  An inside anchor
+        that the label rule left at 0 and that is ignored becomes -1 BEFORE the draws, so it is
+        neither a negative nor counted against ``n_sample``; positives are kept.  (Detectron
+        filters proposals only: this half is this project's extension.)  ``None`` or all-false:
+        the draws and results of a call without it."""
         n_anchor, inside, label, loc = state
+        d = _ignored_negatives(label, ignore, inside, n_anchor)
+        if d is not None:
+            label[d] = -1
         n_pos = int(self.pos_ratio * self.n_sample)
         pos = np.where(label == 1)[0]
         if len(pos) > n_pos:
@@ -120,3 +133,16 @@ class AnchorTargetCreator(object):
         full_loc = np.zeros((n_anchor, 4), dtype=np.float32)
         full_loc[inside] = loc
         return full_loc, full_label
+
+
+def _ignored_negatives(label, ignore, inside, n_anchor):
+    """Indices into the inside anchors of the negatives (label 0) that ``ignore`` (S,) marks, or
+    None when there is none."""
+    if ignore is None:
+        return None
+    ignore = np.asarray(ignore, bool)
+    if ignore.shape != (n_anchor,):
+        raise ValueError('ignore must be a bool array over the %d anchors, got shape %s'
+                         % (n_anchor, ignore.shape))
+    d = np.where((label == 0) & ignore[inside])[0]
+    return d if d.size else None

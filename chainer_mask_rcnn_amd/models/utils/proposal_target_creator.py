@@ -27,20 +27,25 @@ class ProposalTargetCreator(object):
 
     def __call__(self, roi, bbox, label, mask,
                  loc_normalize_mean=(0., 0., 0., 0.),
-                 loc_normalize_std=(0.1, 0.1, 0.2, 0.2)):
+                 loc_normalize_std=(0.1, 0.1, 0.2, 0.2), ignore=None):
         """roi (R,4), bbox (G,4), label (G,), mask (G,H,W) host arrays ->
         sample_roi (S,4) f32, gt_roi_loc (S,4) f32, gt_roi_label (S,) i32 (0 = bg),
-        gt_roi_mask (S,14,14) i32 in {-1,0,1}."""
+        gt_roi_mask (S,14,14) i32 in {-1,0,1}.  ``ignore``: see ``sample``."""
         sample_roi, gt_roi_loc, gt_roi_label, job = self.sample(
-            roi, bbox, label, loc_normalize_mean, loc_normalize_std)
+            roi, bbox, label, loc_normalize_mean, loc_normalize_std, ignore=ignore)
         return sample_roi, gt_roi_loc, gt_roi_label, self.mask_targets(job, mask)
 
     def sample(self, roi, bbox, label, loc_normalize_mean=(0., 0., 0., 0.),
-               loc_normalize_std=(0.1, 0.1, 0.2, 0.2)):
+               loc_normalize_std=(0.1, 0.1, 0.2, 0.2), ignore=None):
         """Everything that consumes ``np.random`` (and everything the RoI head needs before it
         can be launched): the sampled RoIs, their regression targets and labels, plus an
         opaque job for ``mask_targets``.  The train chain launches the head on the GPU right
-        after this and builds the 14x14 mask targets on the host meanwhile."""
+        after this and builds the 14x14 mask targets on the host meanwhile.
+
+        ``ignore``: host bool array over the R proposals.  An ignored
+        proposal is taken out of the foreground pool and of the background pool before the
+        draws, as Detectron's crowd filter does; the ground-truth boxes appended as candidates
+        are never ignored.  ``None`` or all-false: the draws and results of a call without it."""
         roi = np.asarray(roi, np.float32)
         bbox = np.asarray(bbox, np.float32)
         label = np.asarray(label)
@@ -52,7 +57,7 @@ class ProposalTargetCreator(object):
         n_pos_max = np.round(self.n_sample * self.pos_ratio)
         iou_t = bbox_iou_t(cand, bbox)            # (G, R): the long axis contiguous
         assigned = iou_t.argmax(axis=0)
-        best = iou_t.max(axis=0)
+        best = _without_ignored(iou_t.max(axis=0), ignore, len(roi), self.neg_iou_thresh_lo)
         cand_label = label[assigned] + 1          # 0 is background (:129)
 
         fg = np.where(best >= self.pos_iou_thresh)[0]
@@ -79,14 +84,15 @@ class ProposalTargetCreator(object):
 
     # ------------------------------------------------------------------ device half (8f-3)
     def sample_device(self, roi, bbox, label, loc_normalize_mean=(0., 0., 0., 0.),
-                      loc_normalize_std=(0.1, 0.1, 0.2, 0.2), upload=None):
+                      loc_normalize_std=(0.1, 0.1, 0.2, 0.2), upload=None, ignore=None):
         """``sample`` with the arithmetic on the device: roi (R,4) is a
         DEVICE tensor, bbox / label host arrays.  The IoU matrix, its row max / argmax, the
         gather of the chosen candidates, labels and normalised regression targets run as HIP
         kernels; only the per-candidate max IoU comes back to the host, where the SAME
         ``np.random.choice`` calls as ``sample`` pick the rows (foreground first, then
         background).  Returns device tensors sample_roi (S,4), gt_roi_loc (S,4), gt_roi_label
-        (S,) and a job for ``mask_targets_device``; ``job['n_fg']`` / ``job['n']`` are host ints."""
+        (S,) and a job for ``mask_targets_device``; ``job['n_fg']`` / ``job['n']`` are host ints.
+        ``ignore``: as in ``sample``, applied to the host copy of the max IoU."""
         import torch
         from ...functions import target_ops as T
         bbox = np.asarray(bbox, np.float32)
@@ -101,6 +107,7 @@ class ProposalTargetCreator(object):
         cand = torch.cat((roi.detach().to(torch.float32), bbox_d), dim=0).contiguous()   # :121
         best_d, assigned_d = T.bbox_iou_argmax(cand, bbox_d)
         best = best_d.cpu().numpy()                    # the one read-back: (R+G,) floats
+        best = _without_ignored(best, ignore, roi.shape[0], self.neg_iou_thresh_lo)
         n_pos_max = np.round(self.n_sample * self.pos_ratio)
         fg = np.where(best >= self.pos_iou_thresh)[0]
         n_fg = int(min(n_pos_max, fg.size))
@@ -148,6 +155,24 @@ class ProposalTargetCreator(object):
         if n_fg > 0:
             gt_roi_mask[:n_fg] = _mask_targets(boxes, gt_index, np.asarray(mask), M)
         return gt_roi_mask
+
+
+def _without_ignored(best, ignore, n_roi, neg_iou_thresh_lo):
+    """``best`` (R+G,) with the ignored proposals at -1: below ``pos_iou_thresh`` and below
+    ``neg_iou_thresh_lo`` >= 0, so in neither pool.  ``best`` itself when nothing is ignored."""
+    if ignore is None:
+        return best
+    ignore = np.asarray(ignore, bool)
+    if ignore.shape != (n_roi,):
+        raise ValueError('ignore must be a bool array over the %d proposals, got shape %s'
+                         % (n_roi, ignore.shape))
+    if not ignore.any():
+        return best
+    if neg_iou_thresh_lo < 0:
+        raise ValueError('ignore needs neg_iou_thresh_lo >= 0, got %r' % (neg_iou_thresh_lo,))
+    best = best.copy()
+    best[:n_roi][ignore] = -1
+    return best
 
 
 def _mask_targets(boxes, gt_index, mask, M):

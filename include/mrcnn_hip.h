@@ -980,6 +980,30 @@ int mrcnn_copy_paste(const float *img_t, const float *img_s, const uint8_t *mask
                      float *img_out, uint8_t *masks_out, int32_t *box, int32_t *area,
                      int32_t *row_stats, void *stream);
 
+/* ---- Ignore regions of the train step (csrc/ignore_regions.hip) --------
+ * A region that training must neither reward nor punish (a COCO `iscrowd` annotation) travels as
+ * ONE bit plane of the network-size image, in the "Packed masks" format above.  Replaces the crowd
+ * filter of Detectron (roidb.py `_filter_crowd_proposals`: host box overlaps against the crowd
+ * BOXES); the reference (chainer_mask_rcnn/datasets/coco/coco_instance_segm.py, use_crowd=False)
+ * drops crowd annotations before training sees them. */
+/* plane (H,Wq) uint64, Wq = ceil(W/64), pad bits zero.
+ * U = OR over g of (masks[g] != 0), masks (G,H,W) uint8.
+ * base == NULL: plane = U.   base != NULL: plane = base & ~U   (base (H,Wq), may not alias plane;
+ * its pad bits are cleared too).  Every word of plane is written.  G == 0: U is empty (plane = 0,
+ * or a copy of base; masks may then be NULL).  H * W < 2^31. */
+int mrcnn_mask_union_pack(const uint8_t *masks, int G, int H, int W, const uint64_t *base,
+                          uint64_t *plane, void *stream);
+/* out (n,2) int32 = (covered, area) per box.  boxes (n,4) float32 (y1,x1,y2,x2).
+ * Integer rectangle: each coordinate rounded half to even (np.round, as mrcnn_mask_targets
+ * rounds), then y clamped to [0,H] and x to [0,W]; rows [y0,y1) and columns [x0,x1).
+ * area = max(y1-y0,0) * max(x1-x0,0);  covered = number of set bits of plane in the rectangle.
+ * A box with a non-finite coordinate gives (0,0); the clamp is applied in float before the
+ * conversion, so no coordinate overflows an int.  Only words of plane inside the clamped rectangle
+ * are read.  out is 8-byte aligned (each row is one store).  n == 0 returns without a launch.
+ * H * W < 2^31. */
+int mrcnn_box_coverage(const uint64_t *plane, int H, int W, const float *boxes, int n,
+                       int32_t *out, void *stream);
+
 /* ---- Gradient exchange over RCCL / xGMI ---------------------------------------------- */
 /* Replaces ChainerMN's communicator as the reference uses it
  * (examples/train_common.py:97-103 `chainermn.create_communicator('hierarchical')`, :178

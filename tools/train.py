@@ -79,6 +79,12 @@ def parse_args(argv=None):
                          'kernel (COCO: the dataset also keeps them packed on the host)')
     train_loop.add_scale_jitter_arguments(ap)
     train_loop.add_copy_paste_argument(ap)
+    ap.add_argument('--crowd-ignore', nargs='?', type=float, const=0.7, default=argparse.SUPPRESS,
+                    metavar='THRESH',
+                    help="COCO crowd regions are ignored in training instead of being background: a "
+                         "proposal or an anchor more than THRESH of which a crowd mask covers is not "
+                         "sampled (Detectron's TRAIN.CROWD_FILTER_THRESH, 0.7; DESIGN.md section 24).  "
+                         "Needs --device-masks and --dataset coco.  Recorded in params.yaml when given")
     ap.add_argument('--eval-bbox', action='store_true',
                     help='the evaluator also scores the boxes: validation/main/bbox/map joins the '
                          'log and the printed report (the best snapshot stays on the mask map)')
@@ -107,6 +113,13 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     train_loop.scale_jitter_options(ap, args)
     train_loop.copy_paste_option(ap, args)
+    if getattr(args, 'crowd_ignore', None) is not None:
+        if not args.device_masks:
+            ap.error('--crowd-ignore needs --device-masks (the ignore plane is built on the device)')
+        if args.dataset != 'coco':
+            ap.error('--crowd-ignore needs --dataset coco (crowd regions are COCO annotations)')
+        if not 0 <= args.crowd_ignore <= 1:
+            ap.error('--crowd-ignore THRESH must lie in [0, 1], got %r' % (args.crowd_ignore,))
     return args
 
 
@@ -213,11 +226,14 @@ def datasets(args):
     test_data, evaluator_type = test_dataset(args)
     if args.dataset == 'coco':
         packed = getattr(args, 'device_masks', False)
+        # --crowd-ignore: the crowd regions come along, flagged, and leave the transform as a plane
+        crowds = dict(use_crowd=True, return_crowd=True) \
+            if getattr(args, 'crowd_ignore', None) is not None else {}
         train_data = T.ConcatenatedDataset(
             cmr.datasets.COCOInstanceSegmentationDataset('train', root_dir=args.coco_root,
-                                                         packed_masks=packed),
+                                                         packed_masks=packed, **crowds),
             cmr.datasets.COCOInstanceSegmentationDataset('valminusminival', root_dir=args.coco_root,
-                                                         packed_masks=packed))
+                                                         packed_masks=packed, **crowds))
         return train_data, test_data, test_data.class_names, COCO_MODEL, evaluator_type
     if args.dataset == 'voc':
         train_data = cmr.datasets.SBDInstanceSegmentationDataset('train', root_dir=args.sbd_root)
@@ -314,7 +330,10 @@ def assemble(args, comm, model, train_data, test_data, evaluator_type, synthetic
                                              force_equal_length=False)
     train = train_loop.TransformDataset(train_data, cmr.datasets.MaskRCNNTransform(
         model, device_masks=getattr(args, 'device_masks', False),
-        scale_jitter=getattr(args, 'scale_jitter', None), crop_size=getattr(args, 'crop_size', 1024)))
+        scale_jitter=getattr(args, 'scale_jitter', None), crop_size=getattr(args, 'crop_size', 1024),
+        crowd_ignore=getattr(args, 'crowd_ignore', None) is not None))
+    if getattr(args, 'crowd_ignore', None) is not None:
+        chain.crowd_ignore_thresh = float(args.crowd_ignore)
     if getattr(args, 'copy_paste', None) is not None:   # the partner comes from the rank's own shard
         train = cmr.datasets.CopyPasteDataset(train, args.copy_paste)
     test = train_loop.TransformDataset(test_data, cmr.datasets.MaskRCNNTransform(model, train=False))

@@ -98,7 +98,9 @@ class SerialIterator(object):
 def make_converter(device):
     """examples/train_common.py:219-225.  The reference also moves the boxes to the device, where
     its (cupy) target creators run; this build's creators consume boxes / labels / masks on the
-    host (models/mask_rcnn_train_chain.py), so only the image batch is a device tensor."""
+    host (models/mask_rcnn_train_chain.py), so only the image batch is a device tensor.  A sixth
+    field (the ignore planes of MaskRCNNTransform(crowd_ignore=True), a device tensor or None per
+    example) is neither stacked nor moved: it stays a list."""
     from chainer_mask_rcnn_amd.datasets import concat_examples
     return functools.partial(concat_examples, device=device, padding=0,
                              indices_concat=[0, 2, 3, 4],   # img, _, labels, masks, scales
@@ -174,9 +176,11 @@ class TrainLoop(object):
             main.wait_event(ready)
             # allocated on the copy stream, read on the compute stream: the image batch and, with
             # device masks, the mask batch (the allocator must not reuse either under the step)
+            # (and, with --crowd-ignore, the ignore planes: a list, one plane or None per image)
             for field in batch:
-                if isinstance(field, torch.Tensor) and field.is_cuda:
-                    field.record_stream(main)
+                for t in field if isinstance(field, list) else (field,):
+                    if isinstance(t, torch.Tensor) and t.is_cuda:
+                        t.record_stream(main)
         return batch
 
     def _peek_next_images(self):
@@ -197,8 +201,10 @@ class TrainLoop(object):
             # the extractor's frozen prefix of batch k+1 runs beside step k's backbone backward,
             # if the worker has delivered that batch by then (never waits for it)
             self.chain.next_imgs = self._peek_next_images
-        imgs, bboxes, labels, masks, scales = batch
-        loss = self.optimizer.update(self.chain, imgs, bboxes, labels, masks, scales)
+        imgs, bboxes, labels, masks, scales = batch[:5]
+        # a sixth field (MaskRCNNTransform(crowd_ignore=True)): the ignore planes, a list
+        extra = dict(ignores=batch[5]) if len(batch) > 5 else {}
+        loss = self.optimizer.update(self.chain, imgs, bboxes, labels, masks, scales, **extra)
         self.iteration += 1
         return loss
 
