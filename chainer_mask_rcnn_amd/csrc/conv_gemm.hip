@@ -109,19 +109,17 @@ void launch_kernel(const GemmParams &p, GemmInst inst, int64_t tiles, int splits
     go(conv_gemm_kernel<TM, TN, MODE>);
 }
 
-// the same on the instantiation the policy picks for p (the batched launches of conv_winograd.h), always
-// on three planes: the Winograd transforms amplify operand rounding, and six products on 36 / 16 of
-// the outputs are already less matrix work than three on nine taps
+// a batched launch of conv_winograd.h: the 36 per-frequency problems in grid z, on the instantiation its
+// plan (plan_wino_gemm / plan_wino_wgrad) picked
 template <int TM, int TN, int MODE>
-void launch_kernel(const GemmParams &p, int64_t tiles, int splits, hipStream_t s, int batch = 1)
+void launch_wino_kernel(const GemmParams &p, const GemmLaunch &l, hipStream_t s)
 {
-    GemmInst inst = pick_inst(gemm_shape(p, MODE, false), TM, g_knobs);
-    if (inst.split) inst.planes = 3;
-    launch_kernel<TM, TN, MODE>(p, inst, tiles, splits, s, batch);
+    launch_kernel<TM, TN, MODE>(p, l.inst, l.grid_x, l.grid_y, s, kWinoXi);
 }
 
 // ---- W8 launches (see the note above conv_gemm_kernel) -------------------------------------------
-// (planes: the plan's; the Winograd launches of conv_winograd.h leave the default)
+// (planes: the plan's; three on the Winograd launches of conv_winograd.h: the transforms amplify operand
+// rounding, and six products on 36 / 16 of the outputs are already less matrix work than three on nine taps)
 void launch_w8_kernel(const GemmParams &p, int64_t wgs, int batch, hipStream_t s, int planes = 3)
 {
     hipEvent_t ev0, ev1;
@@ -468,6 +466,7 @@ int wgrad_run(const mrcnn_conv_desc *d, const float *gy, const float *x, float *
 }
 
 extern float g_wino_ambiguity;
+int wino_check(const mrcnn_conv_desc *d, const char *who);      // conv_winograd.h
 
 }  // namespace
 
@@ -745,6 +744,8 @@ extern "C" int mrcnn_deconv2x2s2_wgrad(const float *x, const float *gy, float *g
 //   label=<branch> mode=<mode> M=<rows> N=<cols> k=<K extent the slabs cut>
 //   | kind=<profiler kernel> tags=<instantiation> rows=<lo>:<hi> grid=<x>x<y> slab=<depth> tail=<first>,<row0>,<pieces>,<depth>
 //   [| sum row0=<first row> slabs=<count>]
+// The Winograd entries (conv3x3_wino_fwd / _dgrad / _wgrad: plan_wino_gemm / plan_wino_wgrad over the tiles of
+// the maps) print batch=36 behind the grid of every launch.
 extern "C" int mrcnn_conv_gemm_plan(const char *entry, const mrcnn_conv_desc *d, int has_ws, char *out,
                                     int out_len)
 {
@@ -760,6 +761,7 @@ extern "C" int mrcnn_conv_gemm_plan(const char *entry, const mrcnn_conv_desc *d,
     GemmParams p = {};
     GemmShape shape = {};
     int mode = FWD, rc = 0;
+    bool wino = false;
     bool ws = has_ws != 0;                 // entry points without a workspace argument plan without one
     if (is("conv2d_fwd")) {
         rc = fwd_problem(d, p);
@@ -787,13 +789,28 @@ extern "C" int mrcnn_conv_gemm_plan(const char *entry, const mrcnn_conv_desc *d,
     } else if (is("deconv2x2s2_wgrad")) {
         mode = WGRAD;
         rc = wgrad_problem(&adj, p, shape);
+    } else if (is("conv3x3_wino_fwd") || is("conv3x3_wino_dgrad") || is("conv3x3_wino_wgrad")) {
+        wino = true;
+        mode = is("conv3x3_wino_wgrad") ? WGRAD : FWD;
+        rc = wino_check(d, "conv_gemm_plan");
     } else {
         MRCNN_REQUIRE(false, "conv_gemm_plan: unknown entry '%s'", entry);
     }
     if (rc) return rc;
-    if (mode != WGRAD) shape = gemm_shape(p, mode, ws);
-    shape.has_ws = ws;
-    const GemmPlan plan = mode == WGRAD ? plan_wgrad(shape, g_knobs) : plan_gemm(shape, g_knobs);
+    GemmPlan plan;
+    if (wino) {
+        // rows = tiles of the maps; the data gradient's columns are the input channels
+        const int64_t T = (int64_t)d->N * ((d->H + 3) / 4) * ((d->W + 3) / 4);
+        const bool dgrad_form = is("conv3x3_wino_dgrad");
+        p.M = mode == WGRAD ? d->K : (int)T;
+        p.N = mode == WGRAD || dgrad_form ? d->C : d->K;
+        plan = mode == WGRAD ? plan_wino_wgrad(T, d->K, d->C, g_knobs)
+                             : plan_wino_gemm(T, p.N, dgrad_form ? d->K : d->C, g_knobs);
+    } else {
+        if (mode != WGRAD) shape = gemm_shape(p, mode, ws);
+        shape.has_ws = ws;
+        plan = mode == WGRAD ? plan_wgrad(shape, g_knobs) : plan_gemm(shape, g_knobs);
+    }
 
     static const char *const modes[] = {"FWD", "DGRAD", "WGRAD"};
     static const char *const outs[] = {"OUT_PLAIN", "OUT_STRIDED", "OUT_DECONV"};
@@ -804,12 +821,12 @@ extern "C" int mrcnn_conv_gemm_plan(const char *entry, const mrcnn_conv_desc *d,
         const GemmLaunch &l = plan.launch[i];
         const bool w8 = l.tile == kW8BM;
         at += snprintf(out + at, (size_t)(out_len - at),
-                       " | kind=conv_gemm_kernel<%d,%d,%s%s> tags=%s,%dx%d,%s,%s,%s%s%s rows=%d:%d grid=%lldx%d slab=%d "
+                       " | kind=conv_gemm_kernel<%d,%d,%s%s> tags=%s,%dx%d,%s,%s,%s%s%s rows=%d:%d grid=%lldx%d%s slab=%d "
                        "tail=%d,%d,%d,%d",
                        w8 ? 2 : l.tile / 64, w8 ? 2 : l.tile / 64, modes[mode], w8 ? ",W8" : "", modes[mode], l.tile,
                        w8 ? kW8BN : l.tile, outs[p.out_mode], l.inst.split ? "split" : "fp32", variants[l.inst.variant],
                        mode != WGRAD && p.perm_n > 0 ? ",perm" : "", mode != WGRAD && p.stem ? ",stem" : "", l.m_lo,
-                       l.m_hi, (long long)l.grid_x, l.grid_y, l.split_len, l.tail_first, l.tail_row0, l.tail_splits,
+                       l.m_hi, (long long)l.grid_x, l.grid_y, wino ? " batch=36" : "", l.split_len, l.tail_first, l.tail_row0, l.tail_splits,
                        l.tail_split_len);
     }
     if (plan.sum_splits && at < out_len)

@@ -4,6 +4,8 @@
 // mrcnn_set_tuning knobs (GemmKnobs) alone, so it can be computed, swept and compared where there is
 // no device.  conv_gemm.hip builds the shape from a descriptor, runs the plan (run_plan) and prints it
 // (mrcnn_conv_gemm_plan); tests/test_gemm_edge_cases_cpu.py holds it to tests/gemm_edge_cases.route().
+// The Winograd route's launches (conv_winograd.h) have a policy of their own at the end of this file,
+// planned, run, printed and tested the same way.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -168,7 +170,7 @@ struct GemmLaunch {
 // A value: what to launch for one problem, in order, then the ordered sum of `sum_splits` slabs of rows
 // [sum_row0, M) where sum_splits > 0
 struct GemmPlan {
-    const char *label;         // the branch taken (tests/gemm_edge_cases.py: FWD_LABELS, WGRAD_LABELS, OTHER_LABELS)
+    const char *label;         // the branch taken (tests/gemm_edge_cases.py: FWD_LABELS, WGRAD_LABELS, OTHER_LABELS, WINO_LABELS)
     int n;
     GemmLaunch launch[2];
     int sum_row0, sum_splits;
@@ -472,6 +474,95 @@ inline GemmPlan plan_wgrad(const GemmShape &p0, const GemmKnobs &k)
               : p.perm_n ? (use_big ? "wgrad/wperm128" : "wgrad/wperm64")
               : use_big  ? (l.grid_y > 1 ? "wgrad128/split+reduce" : "wgrad128/one_slab")
                          : (l.grid_y > 1 ? "wgrad64/split+reduce" : "wgrad64/one_slab");
+    return g;
+}
+
+// ---- the Winograd route (conv_winograd.h) -----------------------------------------------------------
+// A pass runs its 36 per-frequency GEMMs as ONE grid (blockIdx.z = frequency): forward and data gradient
+// M[xi] (T x N) = V[xi] (T x Kc) . U[xi]^T (N x Kc) over the T tiles of the maps, the weight gradient
+// dU[xi] (K x C) summed over the T tiles.  The policy below is these launches' own; every launch has the
+// batch kWinoXi, and the split-operand instantiations always run on three planes (launch_kernel's note in
+// conv_gemm.hip).
+constexpr int kWinoXi = 36;            // frequencies of F(4x4, 3x3)
+constexpr int kWinoMaxSplits = 8;      // weight-gradient slabs the workspace holds (mrcnn_conv3x3_wino_workspace_bytes)
+
+// one per-frequency GEMM as the policy reads it: a pointwise problem with plain output rows
+inline GemmShape wino_shape(int mode, int M, int N, int Kc)
+{
+    GemmShape p = {};
+    p.mode = mode;
+    p.M = M; p.N = N; p.Kc = Kc;
+    p.R = p.S = 1; p.stride = 1; p.pad = 0;
+    p.gp = p.gq = p.sh = p.sw = 1;
+    p.ldc = N; p.out_mode = OUT_PLAIN;
+    return p;
+}
+
+inline GemmLaunch *add_wino_launch(GemmPlan &g, const GemmShape &p, int tile, int m_lo, int m_hi, int64_t grid_x,
+                                   const GemmKnobs &k)
+{
+    GemmLaunch &l = g.launch[g.n++];
+    l.tile = tile;
+    l.m_lo = m_lo;
+    l.m_hi = m_hi;
+    l.grid_x = grid_x;
+    l.grid_y = 1;
+    l.inst = tile == kW8BM ? GemmInst{true, INST_W8, 3} : pick_inst(p, tile / 64, k);
+    if (l.inst.split) l.inst.planes = 3;
+    return &l;
+}
+
+// Forward / data gradient: T rows (tiles of the maps), N output channels, Kc input channels.
+//   wino/small64         at most 64 rows or 64 columns: 64x64 tiles
+//   wino/w8              w8_ok() over the 36 problems: 256x128 tiles on 512 threads
+//   wino/main128+tail64  a last 128-row tile that is at most half full, from 256 rows on (the RPN's 546
+//                        tiles of a 2 x 51 x 84 map: 4 x 128 + 34): rows [0, T - T % 128) as 128x128 tiles,
+//                        the rest as one row of 64x64 tiles that starts at m_lo = T - T % 128
+//   wino/big128          128x128 tiles
+inline GemmPlan plan_wino_gemm(int64_t T, int N, int Kc, const GemmKnobs &k)
+{
+    GemmPlan g = {};
+    const GemmShape p = wino_shape(FWD, (int)T, N, Kc);
+    g.k_extent = total_slices(p);
+    const bool big = p.M > 64 && p.N > 64;
+    const int rem = p.M % 128;
+    if (big && w8_ok(p, k, kWinoXi)) {
+        add_wino_launch(g, p, kW8BM, 0, p.M, cdiv(p.M, kW8BM) * cdiv(p.N, kW8BN), k);
+        g.label = "wino/w8";
+    } else if (big && rem > 0 && rem <= 64 && p.M >= 256) {
+        const int full = p.M - rem;
+        add_wino_launch(g, p, 128, 0, full, (int64_t)(full / 128) * cdiv(p.N, 128), k);
+        add_wino_launch(g, p, 64, full, p.M, cdiv(p.N, 64), k);
+        g.label = "wino/main128+tail64";
+    } else if (big) {
+        add_wino_launch(g, p, 128, 0, p.M, cdiv(p.M, 128) * cdiv(p.N, 128), k);
+        g.label = "wino/big128";
+    } else {
+        add_wino_launch(g, p, 64, 0, p.M, cdiv(p.M, 64) * cdiv(p.N, 64), k);
+        g.label = "wino/small64";
+    }
+    return g;
+}
+
+// Weight gradient: K x C outputs per frequency, summed over the T tiles in at most kWinoMaxSplits slabs
+// of whole K slices (wgrad_splits() over the 36 x tiles workgroups; the last slab may be short), then the
+// ordered slab sum of wino_wgrad_finish_kernel.  128x128 tiles count 768 resident slots whatever the
+// arithmetic.
+inline GemmPlan plan_wino_wgrad(int64_t T, int K, int C, const GemmKnobs &k)
+{
+    GemmPlan g = {};
+    const GemmShape p = wino_shape(WGRAD, K, C, (int)T);
+    g.k_extent = T;
+    const bool big = p.M > 64 && p.N > 64;
+    const int64_t tiles = big ? cdiv(p.M, 128) * cdiv(p.N, 128) : cdiv(p.M, 64) * cdiv(p.N, 64);
+    const int64_t slots = big ? (single_buffered(2, WGRAD) ? 768 : kSlotsBig) : kSlotsSmall;
+    const int splits = std::min(kWinoMaxSplits, wgrad_splits(tiles * kWinoXi, T, slots));
+    GemmLaunch &l = *add_wino_launch(g, p, big ? 128 : 64, 0, p.M, tiles, k);
+    l.split_len = (int)(cdiv(cdiv(T, splits), BK) * BK);
+    l.grid_y = (int)cdiv(T, l.split_len);
+    g.sum_splits = l.grid_y > 1 ? l.grid_y : 0;
+    g.label = big ? (l.grid_y > 1 ? "wino_wgrad128/split+sum" : "wino_wgrad128/one_slab")
+                  : (l.grid_y > 1 ? "wino_wgrad64/split+sum" : "wino_wgrad64/one_slab");
     return g;
 }
 

@@ -28,7 +28,7 @@
 
 namespace {
 
-constexpr int kXi = 36;
+constexpr int kXi = kWinoXi;
 
 struct F2 { float x, y; };
 __device__ __forceinline__ F2 operator+(F2 a, F2 b) { return {a.x + b.x, a.y + b.y}; }
@@ -431,7 +431,6 @@ inline int64_t wino_plane_floats(const mrcnn_conv_desc *d, int ch)
 {
     return (int64_t)kXi * wino_geom(d).T * ch;
 }
-constexpr int kWinoMaxSplits = 8;
 
 template <bool GRAD_TILE>
 void wino_launch_data_transform(const float *x, float *v, const WinoGeom &g, int C, hipStream_t s)
@@ -444,7 +443,8 @@ void wino_launch_data_transform(const float *x, float *v, const WinoGeom &g, int
                        g.TH, g.TW, g.T);
 }
 
-// the 36 per-frequency GEMMs  out[xi] (T x N) = a[xi] (T x Kc) . b[xi]^T (N x Kc)
+// the 36 per-frequency GEMMs  out[xi] (T x N) = a[xi] (T x Kc) . b[xi]^T (N x Kc), as plan_wino_gemm()
+// (conv_gemm_plan.h) cuts them into launches
 int wino_batched_gemm(const float *a, const float *b, float *out, int64_t T, int N, int Kc,
                       hipStream_t s)
 {
@@ -457,33 +457,22 @@ int wino_batched_gemm(const float *a, const float *b, float *out, int64_t T, int
     p.out_mode = OUT_PLAIN;
     p.batch_a = T * Kc; p.batch_b = (int64_t)N * Kc; p.batch_c = T * N;
     if (int rc = set_extents(p, T * Kc, (int64_t)N * Kc, T * N)) return rc;
-    const bool big = p.M > 64 && p.N > 64;
-    const int64_t tiles = big ? mrcnn::ceil_div(p.M, 128) * mrcnn::ceil_div(p.N, 128)
-                              : mrcnn::ceil_div(p.M, 64) * mrcnn::ceil_div(p.N, 64);
+    const GemmPlan plan = plan_wino_gemm(T, N, Kc, g_knobs);
     const double flops = 2.0 * kXi * (double)T * N * Kc;
     const double bytes = 4.0 * kXi * ((double)T * N + (double)T * Kc + (double)N * Kc);
-    const int rem = p.M % 128;
-    const bool two_launches = big && rem > 0 && rem <= 64 && p.M >= 256;
-    const bool w8 = big && w8_ok(gemm_shape(p, FWD, false), g_knobs, kXi);
-    mrcnn::ProfKernelScope prof(w8 ? mrcnn::PROF_CONV_FWD_W8 : big ? mrcnn::PROF_CONV_FWD_128 : mrcnn::PROF_CONV_FWD_64,
-                                flops, bytes, two_launches && !w8 ? 2 : 1);
-    if (w8) {
-        // 256 x 128 tiles on 512-thread workgroups (conv_gemm.hip, W8): the 36 problems in one grid
-        launch_w8_kernel(p, mrcnn::ceil_div(p.M, kW8BM) * mrcnn::ceil_div(p.N, kW8BN), kXi, s);
-    } else if (two_launches) {
-        // a last row tile that is at most half full (the RPN's 546 tiles of a 2 x 51 x 84 map:
-        // 4 x 128 + 34) runs as 64-row tiles instead of a whole 128-row tile of mostly padding
-        const int full = p.M - rem;
+    const int tile = plan.launch[0].tile;
+    mrcnn::ProfKernelScope prof(tile == kW8BM ? mrcnn::PROF_CONV_FWD_W8
+                                : tile == 128 ? mrcnn::PROF_CONV_FWD_128 : mrcnn::PROF_CONV_FWD_64,
+                                flops, bytes, plan.n);
+    for (int i = 0; i < plan.n; ++i) {
+        const GemmLaunch &l = plan.launch[i];
         GemmParams q = p;
-        q.M = full;
-        launch_kernel<2, 2, FWD>(q, (int64_t)(full / 128) * mrcnn::ceil_div(p.N, 128), 1, s, kXi);
-        q.M = p.M;
-        q.m_lo = full;
-        launch_kernel<1, 1, FWD>(q, mrcnn::ceil_div(p.N, 64), 1, s, kXi);
-    } else if (big) {
-        launch_kernel<2, 2, FWD>(p, tiles, 1, s, kXi);
-    } else {
-        launch_kernel<1, 1, FWD>(p, tiles, 1, s, kXi);
+        q.m_lo = l.m_lo;
+        q.M = l.m_hi;
+        // W8: 256 x 128 tiles on 512-thread workgroups (conv_gemm.hip), the 36 problems in one grid
+        if (l.tile == kW8BM) launch_w8_kernel(q, l.grid_x, kXi, s, l.inst.planes);
+        else if (l.tile == 128) launch_wino_kernel<2, 2, FWD>(q, l, s);
+        else launch_wino_kernel<1, 1, FWD>(q, l, s);
     }
     return mrcnn::check_launch("wino_batched_gemm");
 }
@@ -641,23 +630,20 @@ extern "C" int mrcnn_conv3x3_wino_wgrad(const mrcnn_conv_desc *d, const float *x
     p.R = p.S = 1; p.stride = 1; p.pad = 0;
     p.lda = d->C; p.ldg = d->K; p.cin = d->C; p.ldc = d->C;
     const int64_t kc = (int64_t)d->K * d->C;
-    const bool big = p.M > 64 && p.N > 64;
-    const int64_t tiles = big ? mrcnn::ceil_div(p.M, 128) * mrcnn::ceil_div(p.N, 128)
-                              : mrcnn::ceil_div(p.M, 64) * mrcnn::ceil_div(p.N, 64);
-    const int64_t slots = big ? (single_buffered(2, WGRAD) ? 768 : kSlotsBig) : kSlotsSmall;
-    int splits = std::min(kWinoMaxSplits, wgrad_splits(tiles * kXi, g.T, slots));
-    p.split_len = (int)(mrcnn::ceil_div(mrcnn::ceil_div(g.T, splits), BK) * BK);
-    splits = (int)mrcnn::ceil_div(g.T, p.split_len);
+    const GemmPlan plan = plan_wino_wgrad(g.T, d->K, d->C, g_knobs);
+    const GemmLaunch &l = plan.launch[0];
+    const int splits = l.grid_y;
+    p.split_len = l.split_len;
     p.split_stride = kXi * kc;
     p.batch_a = g.T * d->K; p.batch_b = g.T * d->C; p.batch_c = kc;
     if (int rc = set_extents(p, g.T * d->K, g.T * d->C, kc)) return rc;
     p.C = slabs;
     {
-        mrcnn::ProfKernelScope prof(big ? mrcnn::PROF_CONV_WGRAD_128 : mrcnn::PROF_CONV_WGRAD_64,
+        mrcnn::ProfKernelScope prof(l.tile == 128 ? mrcnn::PROF_CONV_WGRAD_128 : mrcnn::PROF_CONV_WGRAD_64,
                                     2.0 * kXi * (double)kc * (double)g.T,
                                     4.0 * kXi * ((double)kc * splits + (double)g.T * (d->K + d->C)));
-        if (big) launch_kernel<2, 2, WGRAD>(p, tiles, splits, s, kXi);
-        else launch_kernel<1, 1, WGRAD>(p, tiles, splits, s, kXi);
+        if (l.tile == 128) launch_wino_kernel<2, 2, WGRAD>(p, l, s);
+        else launch_wino_kernel<1, 1, WGRAD>(p, l, s);
     }
     hipLaunchKernelGGL(wino_wgrad_finish_kernel, dim3((unsigned)mrcnn::ceil_div(kc, 256)), dim3(256),
                        0, s, (const float *)slabs, splits, p.split_stride, gw, out_row_scale, d->K,

@@ -377,8 +377,13 @@ int mrcnn_conv3x3_wino_fwd(const mrcnn_conv_desc *d, const float *x, const float
                            const float *u, const float *scale, const float *shift, float *y,
                            int epi_flags, float *v, void *ws, void *stream);
 int mrcnn_conv3x3_wino_fixup_count(const mrcnn_conv_desc *d, const void *ws, void *stream,
-                                   int *count);   /* diagnostics: outputs recomputed by the last
-                                                     EXACT_SIGNS forward on ws (synchronises) */
+                                   int *count);   /* diagnostics (synchronises): outputs the last
+                                                     EXACT_SIGNS forward on ws found within the
+                                                     rounding bound of zero.  The list behind the
+                                                     forward's buffers holds cap = min(2^20,
+                                                     (8 * 36 * K * C - 4) / 2) of them: min(count,
+                                                     cap) outputs are recomputed, the rest keep
+                                                     their Winograd value */
 int mrcnn_conv3x3_wino_dgrad(const mrcnn_conv_desc *d, const float *gy, const float *w,
                              const float *w_row_scale, float *gx, const float *out_scale,
                              const float *out_mask_y, void *ws, void *stream);
@@ -435,9 +440,12 @@ int mrcnn_deconv2x2s2_wgrad(const float *x, const float *gy, float *gw,
  * (has_ws: the call would pass a split-K workspace).  entry: "conv2d_fwd", "conv_stem_fwd" (N, H, W, K
  * of d), "conv2d_dgrad", "conv2d_dgrad_ex", "conv2d_dgrad_wt" (either with the suffix "+res_g": the
  * call has a residual gradient), "conv2d_wgrad", "conv2d_wgrad_ex", and the "deconv2x2s2_*" entries, for
- * which d carries the input map (N, H, W, C) and K.  The line names the branch of the policy
- * (csrc/conv_gemm_plan.h) and, per GEMM launch, the kernel instantiation, the row range, the grid,
- * the K-slab depth and the fused-tail fields, then the slab sum if there is one.  The descriptor
+ * which d carries the input map (N, H, W, C) and K; and the Winograd route's "conv3x3_wino_fwd",
+ * "conv3x3_wino_dgrad" and "conv3x3_wino_wgrad" (has_ws is not read: they always have their scratch),
+ * whose GEMM rows are the 4x4 tiles of the maps (forward, data gradient) or K (weight gradient).  The
+ * line names the branch of the policy (csrc/conv_gemm_plan.h) and, per GEMM launch, the kernel
+ * instantiation, the row range, the grid (the Winograd entries add batch=36: the frequencies in
+ * grid z), the K-slab depth and the fused-tail fields, then the slab sum if there is one.  The descriptor
  * checks are those of the entry point; an unknown entry, a rejected descriptor or a short buffer
  * returns non-zero. */
 int mrcnn_conv_gemm_plan(const char *entry, const mrcnn_conv_desc *d, int has_ws, char *out,

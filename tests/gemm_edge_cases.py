@@ -19,6 +19,11 @@ compares the branch label and the kernel instantiation of every launch, on every
 and on a dense sweep of shapes; the plan's row ranges, grids and slab depths are checked for
 consistency there.  On the device, tests/test_gpu_gemm_edges.py counts the launches the profiler
 records per kind: they must equal ``Route.record``.
+
+The Winograd route (csrc/conv_winograd.h) has a launch policy of its own, plan_wino_gemm /
+plan_wino_wgrad: ``wino_plan()`` restates it (``route()`` takes its three entries too), and the lists
+``wino_policy_cases()``, ``WINO_THRESHOLDS``, ``WINO_EPILOGUE_SHAPES`` and ``WINO_FIXUP_SHAPES`` are the
+cases of tests/test_gpu_winograd_edges.py.
 """
 import collections
 import itertools
@@ -46,10 +51,16 @@ FWD_LABELS = ('small/plain', 'small/tiny_split', 'small/fused_tail', 'small/main
               'big/main+split_remainder')
 WGRAD_LABELS = ('wgrad64/one_slab', 'wgrad64/split+reduce', 'wgrad128/split+reduce', 'wgrad/wperm64',
                 'wgrad/wperm128', 'wgrad/no_ws')
-# branches the policy has beside the label set above: the W8 launches (out of scope here: their
-# smallest problem has 768 tiles of 256x128), the occupancy split behind the small_m_split knob
+# branches the policy has beside the label set above: the W8 launches of a plain GEMM (their smallest
+# problem has 768 tiles of 256x128; the W8 kernel itself is reached through the Winograd route's batch
+# of 36, 'wino/w8' below, at 22 tiles per frequency), the occupancy split behind the small_m_split knob
 # (default 0 = off), and a 128x128 weight gradient that ends up with one slab
 OTHER_LABELS = ('w8', 'small/m_split', 'wgrad128/one_slab')
+# the Winograd route's own policy (plan_wino_gemm / plan_wino_wgrad)
+WINO_LABELS = ('wino/small64', 'wino/big128', 'wino/main128+tail64', 'wino/w8',
+               'wino_wgrad64/one_slab', 'wino_wgrad64/split+sum', 'wino_wgrad128/one_slab',
+               'wino_wgrad128/split+sum')
+WINO_XI, WINO_MAX_SPLITS = 36, 8
 
 
 class Desc(collections.namedtuple('Desc', 'N H W C K R S stride pad')):
@@ -237,13 +248,14 @@ def _launch_small(p, knobs):
 
 
 # w8_ok(): the 256x128-tile launches (out of scope; restated so that no case takes them unnoticed)
-def _w8_ok(p, knobs):
+def _w8_ok(p, knobs, batch=1):
     if (not _W8 or not (knobs['split_bf16'] & 1) or p.out_mode != OUT_PLAIN or p.stem or
             not (p.R == 1 and p.S == 1 and p.stride == 1 and p.pad == 0 and p.perm_n == 0 and
                  p.gp == p.sh and p.gq == p.sw)):
         return False
     tm, tn = ceil_div(p.M, 256), ceil_div(p.N, 128)
-    return p.N >= 128 and p.Kc >= _W8_MIN_K and tm * tn >= 768 and (p.M % 256 == 0 or p.M >= 16 * 256)
+    return (p.N >= 128 and p.Kc >= _W8_MIN_K and tm * tn * batch >= 768 and
+            (p.M % 256 == 0 or p.M >= 16 * 256))
 
 
 # plan_gemm(): the forward / DGRAD policy
@@ -330,6 +342,87 @@ def _wgrad(Kout, pixels, n_img, C, P, Q, R, S, stride, pad, has_ws, knobs):
     return label, [(kind_name(tm, WGRAD), instantiation(p, tm, knobs))]
 
 
+# ---- the Winograd route: 36 per-frequency GEMMs per launch (blockIdx.z), three planes when split ------
+W8_KIND = 'conv_gemm_kernel<2,2,FWD,W8>'
+WinoLaunch = collections.namedtuple('WinoLaunch', 'kind tags rows grid slab')
+"""rows: (m_lo, m_hi); grid: (x, y) with the batch of 36 in z; slab: K slices' worth of tiles per slab
+(weight gradient), else 0."""
+WinoPlan = collections.namedtuple('WinoPlan', 'label M N k launches slabs')
+
+
+def wino_tiles(d):
+    return d.N * ceil_div(d.H, 4) * ceil_div(d.W, 4)
+
+
+def _wino_p(mode, M, N, Kc):
+    return _P(mode, M, N, Kc, gp=1, gq=1, sh=1, sw=1)
+
+
+# plan_wino_gemm(): forward (rows = tiles, columns = K, depth = C) and data gradient (columns = C, depth = K)
+def wino_gemm_plan(T, N, Kc, knobs):
+    p = _wino_p(FWD, T, N, Kc)
+    big = T > 64 and N > 64
+    rem = T % 128
+
+    def launch(tm, lo, hi):
+        return WinoLaunch(kind_name(tm, FWD), instantiation(p, tm, knobs), (lo, hi),
+                          (ceil_div(hi - lo, 64 * tm) * ceil_div(N, 64 * tm), 1), 0)
+    if big and _w8_ok(p, knobs, WINO_XI):
+        return WinoPlan('wino/w8', T, N, ceil_div(Kc, BK), [WinoLaunch(
+            W8_KIND, (FWD, '256x128', OUT_PLAIN, 'split', 'W8'), (0, T), (ceil_div(T, 256) * ceil_div(N, 128), 1), 0)], 0)
+    if big and 0 < rem <= 64 and T >= 256:
+        return WinoPlan('wino/main128+tail64', T, N, ceil_div(Kc, BK), [launch(2, 0, T - rem), launch(1, T - rem, T)], 0)
+    if big:
+        return WinoPlan('wino/big128', T, N, ceil_div(Kc, BK), [launch(2, 0, T)], 0)
+    return WinoPlan('wino/small64', T, N, ceil_div(Kc, BK), [launch(1, 0, T)], 0)
+
+
+# plan_wino_wgrad(): K rows, C columns, summed over the T tiles in at most WINO_MAX_SPLITS slabs
+def wino_wgrad_plan(T, K, C, knobs):
+    p = _wino_p(WGRAD, K, C, T)
+    big = K > 64 and C > 64
+    tm = 2 if big else 1
+    tiles = ceil_div(K, 64 * tm) * ceil_div(C, 64 * tm)
+    # (768 slots for the 128x128 tiles whatever the arithmetic: single_buffered(2, WGRAD))
+    slots = (768 if _single_buffered(2, WGRAD) else SLOTS_BIG) if big else SLOTS_SMALL
+    splits = min(WINO_MAX_SPLITS, wgrad_splits(tiles * WINO_XI, T, slots))
+    split_len = ceil_div(ceil_div(T, splits), BK) * BK
+    splits = ceil_div(T, split_len)
+    label = 'wino_wgrad%d/%s' % (64 * tm, 'split+sum' if splits > 1 else 'one_slab')
+    return WinoPlan(label, K, C, T, [WinoLaunch(kind_name(tm, WGRAD), instantiation(p, tm, knobs), (0, K),
+                                                (tiles, splits), split_len)], splits)
+
+
+WINO_ENTRIES = ('conv3x3_wino_fwd', 'conv3x3_wino_dgrad', 'conv3x3_wino_wgrad')
+
+
+def wino_plan(entry, d, knobs=None):
+    """The WinoPlan of one call of a WINO_ENTRIES name."""
+    kn = dict(DEFAULT_KNOBS)
+    kn.update(knobs or {})
+    T = wino_tiles(d)
+    if entry == 'conv3x3_wino_fwd':
+        return wino_gemm_plan(T, d.K, d.C, kn)
+    if entry == 'conv3x3_wino_dgrad':
+        return wino_gemm_plan(T, d.C, d.K, kn)
+    if entry == 'conv3x3_wino_wgrad':
+        return wino_wgrad_plan(T, d.K, d.C, kn)
+    raise ValueError(entry)
+
+
+def wino_rejects(d):
+    """wino_check(): why the Winograd entry points refuse ``d`` (None: accepted)."""
+    if (d.R, d.S, d.stride, d.pad) != (3, 3, 1, 1):
+        return 'the Winograd path serves 3x3 / stride 1 / pad 1 only'
+    if d.C % 4 or d.K % 4:
+        return 'channel'
+    if d.N * d.H * d.W * d.C >= 2 ** 31 - 1 or d.N * d.P * d.Q * d.K >= 2 ** 31 - 1:
+        return 'tensor exceeds 2^31 elements'
+    if wino_tiles(d) * max(d.C, d.K) >= 1 << 29:
+        return 'one frequency plane exceeds 2 GiB'
+    return None
+
+
 ENTRIES = ('conv2d_fwd', 'conv_stem_fwd', 'conv2d_dgrad', 'conv2d_dgrad_ex', 'conv2d_dgrad_wt',
            'conv2d_wgrad', 'conv2d_wgrad_ex', 'deconv2x2s2_fwd', 'deconv2x2s2_fwd_wt',
            'deconv2x2s2_dgrad', 'deconv2x2s2_wgrad')
@@ -374,11 +467,16 @@ def gemm_problem(entry, d, has_ws, knobs):
 
 
 def route(entry, d, flags=0, has_ws=True, knobs=None):
-    """The branch, the launches and the profiler record of one call of ``entry`` (an ENTRIES name)
+    """The branch, the launches and the profiler record of one call of ``entry`` (an ENTRIES or
+    WINO_ENTRIES name)
     with descriptor ``d`` under ``knobs`` (DEFAULT_KNOBS updated by the dict given).  ``flags`` (the
     MRCNN_EPI_* bits) do not steer the policy; they are accepted so that a call site states them."""
     kn = dict(DEFAULT_KNOBS)
     kn.update(knobs or {})
+    if entry in WINO_ENTRIES:
+        # one profiler record per GEMM scope: the main128+tail64 pair is ONE record of the 128x128 kind
+        w = wino_plan(entry, d, kn)
+        return Route(w.label, [(l.kind, l.tags) for l in w.launches], {w.launches[0].kind: 1})
     if entry in ('conv2d_wgrad', 'conv2d_wgrad_ex'):        # mrcnn_conv2d_wgrad_ex
         label, launches = _wgrad(d.K, d.N * d.P * d.Q, d.N, d.C, d.P, d.Q, d.R, d.S, d.stride, d.pad,
                                  has_ws, kn)
@@ -667,6 +765,172 @@ def all_calls():
     for i, e, d, kn, _ in policy_cases():
         for arith in (both if e == 'conv2d_fwd' else ({},)):
             yield 'policy', i, e, d, True, dict(kn, **arith)
+
+
+# ---- the Winograd route: policy branches, thresholds, epilogue shapes ----------------------------
+def wino_desc(N, C, H, W, K):
+    return desc(N, C, H, W, K, 3, 3, 1, 1)
+
+
+def wino_moved_bytes(d):
+    """Bytes of x, y / gy and gx of one case (fp32); the filter is small beside them."""
+    return 4 * d.N * d.H * d.W * (d.C + d.K)
+
+
+def _wino_policy_desc(entry, rows, cols, depth):
+    """rows maps of 4x4 (one tile each, every row and column of the transforms read)."""
+    if entry == 'conv3x3_wino_fwd':
+        return wino_desc(rows, depth, 4, 4, cols)              # columns = K, depth = C
+    if entry == 'conv3x3_wino_dgrad':
+        return wino_desc(rows, cols, 4, 4, depth)              # columns = C, depth = K
+    return wino_desc(depth, cols, 4, 4, rows)                  # weight gradient: rows = K, depth = tiles
+
+
+def wino_smallest_problem(label, entry):
+    """The 4x4-map problem with the fewest bytes moved that reaches ``label`` with a partial last tile
+    in the rows and a column count of 4 mod 64."""
+    best = None
+    if entry == 'conv3x3_wino_wgrad':
+        rows, cols = (132, 132) if '128' in label else (36, 68)
+        for tiles in range(1, 5000):
+            if tiles % BK == 0:
+                continue
+            d = _wino_policy_desc(entry, rows, cols, tiles)
+            if wino_plan(entry, d).label == label:
+                return d
+        return None
+    cols = 68 if label == 'wino/small64' else 132
+    for depth in (32, 64, 128, 256, 512):
+        for rows in range(1, 5000):
+            if rows % 64 == 0:
+                continue
+            d = _wino_policy_desc(entry, rows, cols, depth)
+            if best is not None and wino_moved_bytes(d) >= best[0]:
+                break
+            if wino_plan(entry, d).label == label:
+                best = (wino_moved_bytes(d), d)
+                break
+    return None if best is None else best[1]
+
+
+# why a Winograd case may move more than 16 MiB: the W8 branch needs 22 tiles of 256x128 per frequency,
+# 256 channels deep (w8_min_k), i.e. >= 2816 maps (whole row tiles) or >= 4096 (a ragged last one)
+WINO_SIZE_REASON = 'size forced by wino/w8: >= 22 tiles of 256x128 per frequency at >= 256 channels'
+_WINO_POLICY_CACHE = []
+
+
+def wino_policy_cases():
+    """[(id, entry, desc, label)]: per WINO_LABELS entry (forward and data gradient each for the four
+    GEMM branches, the weight gradient for its four) the smallest ragged 4x4-map problem that reaches it."""
+    if _WINO_POLICY_CACHE:
+        return _WINO_POLICY_CACHE
+    for label in WINO_LABELS:
+        for entry in (WINO_ENTRIES[2:] if label.startswith('wino_wgrad') else WINO_ENTRIES[:2]):
+            d = wino_smallest_problem(label, entry)
+            if d is None:
+                continue
+            forced = ' (%s)' % WINO_SIZE_REASON if wino_moved_bytes(d) > (16 << 20) else ''
+            _WINO_POLICY_CACHE.append(('%s %s: %d maps of 4x4, C%d K%d%s' % (
+                label, entry[len('conv3x3_'):], d.N, d.C, d.K, forced), entry, d, label))
+    return _WINO_POLICY_CACHE
+
+
+# Both sides of every comparison of the two plans: ((N, C, H, W, K), forward label, data-gradient label,
+# (weight-gradient tile, slabs, slab depth, depth of the last slab)).  Labels without their 'wino/' prefix.
+WINO_THRESHOLDS = [
+    ((64, 68, 4, 4, 68), 'small64', 'small64', (128, 1, 64, 64)),            # T > 64: below
+    ((65, 68, 4, 4, 68), 'big128', 'big128', (128, 1, 96, 65)),              # ... above
+    ((65, 64, 4, 4, 68), 'big128', 'small64', (64, 1, 96, 65)),              # columns > 64: 64 / 68, by C
+    ((65, 68, 4, 4, 64), 'small64', 'big128', (64, 1, 96, 65)),              # ... by K
+    ((192, 68, 4, 4, 132), 'big128', 'big128', (128, 1, 192, 192)),          # rem = 64 but T < 256: one launch
+    ((256, 68, 4, 4, 68), 'big128', 'big128', (128, 1, 256, 256)),           # rem = 0
+    ((257, 68, 4, 4, 68), 'main128+tail64', 'main128+tail64', (128, 1, 288, 257)),   # rem = 1
+    ((320, 68, 4, 4, 68), 'main128+tail64', 'main128+tail64', (128, 1, 320, 320)),   # rem = 64
+    ((321, 68, 4, 4, 68), 'big128', 'big128', (128, 1, 352, 321)),           # rem = 65
+    ((47, 68, 5, 9, 132), 'main128+tail64', 'main128+tail64', (128, 1, 288, 282)),   # ragged 2x3-tile maps
+    ((511, 64, 4, 4, 64), 'small64', 'small64', (64, 1, 512, 511)),          # fewer than 2 x 8 K slices
+    ((512, 64, 4, 4, 64), 'small64', 'small64', (64, 2, 256, 256)),          # two whole slabs
+    ((513, 64, 4, 4, 64), 'small64', 'small64', (64, 2, 288, 225)),          # a short last slab
+    ((700, 132, 4, 4, 132), 'main128+tail64', 'main128+tail64', (128, 2, 352, 348)),
+    ((2050, 64, 3, 3, 64), 'small64', 'small64', (64, 8, 288, 34)),          # the cap of 8 slabs, 64x64 tiles
+    ((2049, 132, 2, 2, 68), 'main128+tail64', 'main128+tail64', (128, 8, 288, 33)),  # ... 128x128 tiles
+    # W8: 3 column tiles with 4 ragged columns, depth 260 = 8 slices + 4
+    ((2816, 260, 4, 4, 260), 'w8', 'w8', (128, 7, 416, 320)),
+    ((4100, 260, 2, 2, 260), 'w8', 'w8', (128, 7, 608, 452)),                # T >= 4096: a ragged last row tile
+    ((4095, 260, 2, 2, 260), 'big128', 'big128', (128, 7, 608, 447)),        # T % 256 != 0 below 4096
+    ((2816, 252, 4, 4, 260), 'big128', 'w8', (128, 7, 416, 320)),            # depth 252 < w8_min_k, forward only
+    ((2816, 256, 4, 4, 128), 'big128', 'big128', (128, 8, 352, 352)),        # only 11 x 36 tiles
+]
+
+# Epilogue shapes: a one-pixel map, maps smaller than a tile in one axis only (2x7, 5x4), 7x7 (2x2 tiles,
+# ragged both ways), 5x9; channels of 4 and 36 / 40; 64x64 tiles, 128x128 tiles, and the main128+tail64 pair
+WINO_EPILOGUE_SHAPES = [(1, 4, 1, 1, 4), (3, 36, 2, 7, 40), (5, 40, 5, 4, 36), (33, 68, 7, 7, 132),
+                        (47, 68, 5, 9, 132)]
+# ... and the W8 kernel in front of the output transform: 704 maps of 7x7 = 2816 tiles, forward on W8 (the
+# data gradient, 132 deep, on 128x128 tiles); 54 MiB moved, the size the W8 branch forces
+WINO_EPILOGUE_W8 = (704, 260, 7, 7, 132)
+
+# Fix-up values (EXACT_SIGNS with every output inside the bound): C in {4, 36, 256, 260}, maps 1x1, 2x7, 7x7
+WINO_FIXUP_SHAPES = [(3, 4, 1, 1, 8), (2, 36, 2, 7, 40), (2, 256, 7, 7, 8), (3, 260, 2, 7, 12), (5, 4, 7, 7, 4)]
+WINO_FIXUP_OVERFLOW = (2050, 8, 3, 3, 4)          # fix_cap = (8 x 36 x 4 x 8 - 4) / 2 = 4606 of 73 800 outputs
+
+
+def wino_fix_cap(d):
+    """Entries of the fix list behind the forward's buffers: [count (16 B) | (pixel, channel) pairs] in the
+    8 x 36 K C floats the weight gradient's slabs use."""
+    return min(1 << 20, (8 * WINO_XI * d.K * d.C - 4) // 2)
+
+
+def wino_fixup_epilogue(d, kind):
+    """(flags name, scale, shift) fp32 arrays (or None) of the EXACT_SIGNS cases.  'affine0': mixed-sign
+    scale, zero shift, so that every output stays inside a bound of 2 |A^T||M||A| |scale|.  'bias' /
+    'affine': a shift of at most 0.03, which is below 0.1 x the rms of the pre-activation on every shape of
+    WINO_FIXUP_SHAPES (a 1x1 map sees one tap of nine: rms 1 / 3)."""
+    rng = np.random.RandomState(seed_of(*d) + 11)
+    sign = np.where(np.arange(d.K) % 2 == 0, 1., -1.)
+    scale = (rng.uniform(.5, 1.5, d.K) * sign).astype(np.float32)
+    shift = rng.uniform(-.03, .03, d.K).astype(np.float32)
+    shift[shift == 0] = .01
+    if kind == 'affine0':
+        return scale, np.zeros(d.K, np.float32)
+    if kind == 'bias':
+        return None, shift
+    if kind == 'affine':
+        return scale, shift
+    raise ValueError(kind)
+
+
+def is_w8_case(d):
+    return any(wino_plan(e, d).label == 'wino/w8' for e in WINO_ENTRIES[:2])
+
+
+def wino_cases():
+    """[(family, id, desc)] of every Winograd case of the device test."""
+    out = [('policy', i, d) for i, _, d, _ in wino_policy_cases()]
+    out += [('threshold', 'winograd threshold %s' % (c,), wino_desc(*c)) for c, _, _, _ in WINO_THRESHOLDS]
+    out += [('epilogue', 'winograd epilogue %s' % (c,), wino_desc(*c)) for c in WINO_EPILOGUE_SHAPES + [WINO_EPILOGUE_W8]]
+    out += [('tiny maps', 'winograd %s' % (c,), wino_desc(*c)) for c in WINOGRAD]
+    return out
+
+
+def wino_calls():
+    """(family, id, entry, desc, knobs) of every Winograd GEMM call of the device test: the W8 cases on the
+    default arithmetic, the others on the split and the fp32 one."""
+    for fam, i, d in wino_cases():
+        for kn in ({},) if is_w8_case(d) else ({}, {'split_bf16': 0}):
+            for e in WINO_ENTRIES:
+                yield fam, i, e, d, kn
+
+
+WINO_REJECTED = [
+    ('1x1 filter', desc(2, 8, 7, 7, 8, 1, 1, 1, 0), 'Winograd'),
+    ('3x3 / stride 2', desc(2, 8, 7, 7, 8, 3, 3, 2, 1), 'Winograd'),
+    ('3x3 / pad 0', desc(2, 8, 7, 7, 8, 3, 3, 1, 0), 'Winograd'),
+    ('C = 6', wino_desc(2, 6, 7, 7, 8), 'multiples of 4'),
+    ('K = 6', wino_desc(2, 8, 7, 7, 6), 'multiples of 4'),
+    ('a frequency plane of 2^29 floats: 2^20 maps of 1x1, C = 512', wino_desc(1 << 20, 512, 1, 1, 8), 'frequency plane'),
+    ('2^20 maps of 4x4, C = 512: the tensor itself is over 2^31 elements', wino_desc(1 << 20, 512, 4, 4, 8), '2^31'),
+]
 
 
 # ---- rejected by design -------------------------------------------------------------------------

@@ -3,7 +3,9 @@ coverage of the launch policy's branches and of the kernel instantiations, the f
 of tests/launch_ref.py at the degenerate geometries of the lists, the comparison of
 tests/test_gpu_gemm_edges.py on emulated kernels (right, and wrong the way each edge goes wrong),
 the size caps, and the library's own launch plan (mrcnn_conv_gemm_plan: no device touched) against
-route() on every listed call and on a dense sweep of shapes."""
+route() on every listed call and on a dense sweep of shapes.  The same for the Winograd route's own
+policy (plan_wino_gemm / plan_wino_wgrad), whose plans are compared as whole lines, and a float64 model
+of that route (oracle/np_winograd.py) damaged the way its launches, fix-up and transforms can go wrong."""
 import collections
 import contextlib
 import ctypes
@@ -530,3 +532,282 @@ def test_plan_equals_route_on_a_dense_sweep_at_the_default_knobs(lib):
     for label in ('small/plain', 'small/tiny_split', 'small/fused_tail', 'big/one_round_ksplit', 'big/all_rows',
                   'big/fused_tail', 'wgrad64/one_slab', 'wgrad64/split+reduce', 'wgrad128/split+reduce'):
         assert seen[label] > 0, label
+
+
+# ---- the Winograd route: plan_wino_gemm / plan_wino_wgrad against wino_plan() ----------------------------
+
+def _wino_line(w, mode):
+    """The text mrcnn_conv_gemm_plan prints for WinoPlan ``w``: every field of every launch."""
+    out = 'label=%s mode=%s M=%d N=%d k=%d' % (w.label, mode, w.M, w.N, w.k)
+    for l in w.launches:
+        out += ' | kind=%s tags=%s rows=%d:%d grid=%dx%d batch=%d slab=%d tail=0,0,0,0' % (
+            l.kind, ','.join(l.tags), l.rows[0], l.rows[1], l.grid[0], l.grid[1], G.WINO_XI, l.slab)
+    if w.slabs > 1:
+        out += ' | sum row0=0 slabs=%d' % w.slabs
+    return out
+
+
+def _check_wino(lib, entry, d, kn, what):
+    w = G.wino_plan(entry, d, kn)
+    rc, line = _plan_line(lib, entry, d, True)
+    assert rc == 0, (what, lib.mrcnn_last_error())
+    assert line == _wino_line(w, G.WGRAD if entry.endswith('wgrad') else G.FWD), (what, entry, d)
+    r = G.route(entry, d, 0, True, kn)
+    assert r.label == w.label and sum(r.record.values()) == 1 and len(r.launches) == len(w.launches)
+    _check_consistent(_plan(lib, entry, d, True), what)       # (it has no workspace rule for these slabs:
+    assert w.slabs <= G.WINO_MAX_SPLITS                       #  the Winograd workspace holds 8)
+    return w
+
+
+def test_wino_plan_equals_route_on_every_listed_call(lib):
+    seen = collections.defaultdict(set)
+    for fam, i, entry, d, kn in G.wino_calls():
+        with _knobs(kn):
+            w = _check_wino(lib, entry, d, kn, i)
+        seen[(entry, 'fp32' if kn.get('split_bf16', 3) == 0 else 'split')].add(w.label)
+        assert G.wino_rejects(d) is None, i
+    gemm, wgrad = set(G.WINO_LABELS[:4]), set(G.WINO_LABELS[4:])
+    for e in G.WINO_ENTRIES[:2]:                       # every label, forward and data gradient alike
+        assert seen[(e, 'split')] == gemm, e
+        assert seen[(e, 'fp32')] == gemm - {'wino/w8'}, e
+    assert seen[(G.WINO_ENTRIES[2], 'split')] == wgrad and seen[(G.WINO_ENTRIES[2], 'fp32')] == wgrad
+    for i, entry, d, label in G.wino_policy_cases():
+        assert G.wino_plan(entry, d).label == label, i
+    assert {c[3] for c in G.wino_policy_cases()} == set(G.WINO_LABELS)
+
+
+WINO_SWEEP_T = tuple(range(1, 701)) + (2048, 2049, 2050, 2051, 2052, 2816, 4095, 4096, 4100, 5632)
+WINO_SWEEP_CH = (4, 36, 64, 68, 128, 132, 256, 260)
+
+
+def test_wino_plan_equals_route_on_a_dense_sweep(lib):
+    """T tiles (one 4x4 map each) x C x K x both arithmetics x the three entries, as whole lines."""
+    from chainer_mask_rcnn_amd._lib import ConvDesc
+    buf = ctypes.create_string_buffer(1024)
+    for sb in (3, 0):
+        kn = dict(G.DEFAULT_KNOBS, split_bf16=sb)
+        seen = collections.Counter()
+        with _knobs(kn):
+            for T in WINO_SWEEP_T:
+                gemm = {}
+                for C_, K_ in itertools.product(WINO_SWEEP_CH, WINO_SWEEP_CH):
+                    cd = ConvDesc(T, 4, 4, C_, K_, 3, 3, 1, 1, 4, 4)
+                    for entry, mode, key in (('conv3x3_wino_fwd', G.FWD, (K_, C_)), ('conv3x3_wino_dgrad', G.FWD, (C_, K_)),
+                                             ('conv3x3_wino_wgrad', G.WGRAD, None)):
+                        if key is None:
+                            w = G.wino_wgrad_plan(T, K_, C_, kn)
+                            want = _wino_line(w, mode)
+                        else:
+                            if key not in gemm:
+                                w = G.wino_gemm_plan(T, key[0], key[1], kn)
+                                gemm[key] = (w.label, _wino_line(w, mode))
+                            want = gemm[key][1]
+                        assert lib.mrcnn_conv_gemm_plan(entry.encode(), ctypes.byref(cd), 1, buf, 1024) == 0
+                        assert buf.value.decode() == want, (entry, T, C_, K_, sb)
+                        seen[want.split(' ', 1)[0][len('label='):]] += 1
+        want = set(G.WINO_LABELS) - ({'wino/w8'} if sb == 0 else set())
+        assert set(seen) == want, (sb, seen)               # on fp32 W8 vanishes
+
+
+def test_wino_policy_cases_are_the_smallest_that_reach_their_label():
+    for i, entry, d, label in G.wino_policy_cases():
+        rows = d.N
+        assert (d.H, d.W) == (4, 4) and rows % 64 != 0 and rows % G.BK != 0, i
+        cols = d.K if entry == 'conv3x3_wino_fwd' else d.C
+        assert cols % 64 == 4, i
+        if rows > 64:
+            assert G.wino_plan(entry, d._replace(N=rows - 64)).label != label, i
+
+
+# (this side, the other side, the entry that must change its label or its slab count)
+WINO_THRESHOLD_PAIRS = [
+    ((64, 68, 4, 4, 68), (65, 68, 4, 4, 68), 'conv3x3_wino_fwd'),
+    ((64, 68, 4, 4, 68), (65, 68, 4, 4, 68), 'conv3x3_wino_dgrad'),
+    ((65, 64, 4, 4, 68), (65, 68, 4, 4, 68), 'conv3x3_wino_dgrad'),
+    ((65, 68, 4, 4, 64), (65, 68, 4, 4, 68), 'conv3x3_wino_fwd'),
+    ((65, 64, 4, 4, 68), (65, 68, 4, 4, 68), 'conv3x3_wino_wgrad'),
+    ((256, 68, 4, 4, 68), (257, 68, 4, 4, 68), 'conv3x3_wino_fwd'),
+    ((320, 68, 4, 4, 68), (321, 68, 4, 4, 68), 'conv3x3_wino_fwd'),
+    ((320, 68, 4, 4, 68), (321, 68, 4, 4, 68), 'conv3x3_wino_dgrad'),
+    ((192, 68, 4, 4, 132), (320, 68, 4, 4, 68), 'conv3x3_wino_fwd'),
+    ((511, 64, 4, 4, 64), (512, 64, 4, 4, 64), 'conv3x3_wino_wgrad'),
+    ((4095, 260, 2, 2, 260), (4100, 260, 2, 2, 260), 'conv3x3_wino_fwd'),
+    ((4095, 260, 2, 2, 260), (4100, 260, 2, 2, 260), 'conv3x3_wino_dgrad'),
+    ((2816, 252, 4, 4, 260), (2816, 260, 4, 4, 260), 'conv3x3_wino_fwd'),
+    ((2816, 256, 4, 4, 128), (2816, 260, 4, 4, 260), 'conv3x3_wino_fwd'),
+]
+
+
+def test_wino_thresholds_land_where_the_table_says():
+    listed = {c for c, _, _, _ in G.WINO_THRESHOLDS}
+    for c, fwd, dgrad, (tile, slabs, depth, last) in G.WINO_THRESHOLDS:
+        d = G.wino_desc(*c)
+        pf, pg, pw = (G.wino_plan(e, d) for e in G.WINO_ENTRIES)
+        assert (pf.label, pg.label) == ('wino/' + fwd, 'wino/' + dgrad), c
+        l = pw.launches[0]
+        assert (int(l.tags[1].split('x')[0]), pw.slabs, l.slab, pw.k - (pw.slabs - 1) * l.slab) == \
+            (tile, slabs, depth, last), c
+        assert pw.label == 'wino_wgrad%d/%s' % (tile, 'split+sum' if slabs > 1 else 'one_slab'), c
+    for a, b, entry in WINO_THRESHOLD_PAIRS:
+        assert a in listed and b in listed
+        assert G.wino_plan(entry, G.wino_desc(*a)).label != G.wino_plan(entry, G.wino_desc(*b)).label, (a, b, entry)
+    # the slab counts the ordered sum is run at, each with a short last slab somewhere
+    assert {w[1] for _, _, _, w in G.WINO_THRESHOLDS} >= {1, 2, 7, 8}
+    # the tail launch's first row, and a tail of exactly 64 rows
+    two = G.wino_plan('conv3x3_wino_fwd', G.wino_desc(320, 68, 4, 4, 68))
+    assert [l.rows for l in two.launches] == [(0, 256), (256, 320)] and [l.grid for l in two.launches] == [(2, 1), (2, 1)]
+
+
+def test_wino_size_caps():
+    for fam, i, d in G.wino_cases():
+        b = G.wino_moved_bytes(d)
+        assert b <= 256 << 20, i
+        if b > 16 << 20:
+            assert G.is_w8_case(d) or d.N in (2816, 4095), i          # the W8 branch and its two near misses
+            assert fam != 'policy' or G.WINO_SIZE_REASON in i, i
+    for c in G.WINO_EPILOGUE_SHAPES + G.WINO_FIXUP_SHAPES + [G.WINO_FIXUP_OVERFLOW]:
+        assert G.wino_moved_bytes(G.wino_desc(*c)) <= 16 << 20, c
+    # the shapes the epilogue list promises
+    maps = {(c[2], c[3]) for c in G.WINO_EPILOGUE_SHAPES}
+    assert maps >= {(1, 1), (2, 7), (5, 4), (7, 7), (5, 9)}
+    chans = {c[1] for c in G.WINO_EPILOGUE_SHAPES} | {c[4] for c in G.WINO_EPILOGUE_SHAPES}
+    assert chans >= {4, 36, 40}
+    fams = {G.wino_plan('conv3x3_wino_fwd', G.wino_desc(*c)).label for c in G.WINO_EPILOGUE_SHAPES}
+    assert fams >= {'wino/small64', 'wino/big128', 'wino/main128+tail64'}
+    for c in G.WINO_FIXUP_SHAPES:                      # every output fits the fix list
+        d = G.wino_desc(*c)
+        assert d.N * d.H * d.W * d.K <= G.wino_fix_cap(d), c
+    assert {c[1] for c in G.WINO_FIXUP_SHAPES} >= {4, 36, 256, 260}
+    assert {(c[2], c[3]) for c in G.WINO_FIXUP_SHAPES} >= {(1, 1), (2, 7), (7, 7)}
+    w8 = G.wino_desc(*G.WINO_EPILOGUE_W8)
+    assert [G.wino_plan(e, w8).label for e in G.WINO_ENTRIES[:2]] == ['wino/w8', 'wino/big128']
+    assert (w8.H, w8.W) == (7, 7) and G.wino_moved_bytes(w8) <= 64 << 20
+    ov = G.wino_desc(*G.WINO_FIXUP_OVERFLOW)
+    assert G.wino_fix_cap(ov) == 4606 and ov.N * ov.H * ov.W * ov.K == 73800
+
+
+def test_wino_plan_rejects_what_wino_check_rejects(lib):
+    for i, d, why in G.WINO_REJECTED:
+        assert G.wino_rejects(d) is not None, i
+        for entry in G.WINO_ENTRIES:
+            rc, _ = _plan_line(lib, entry, d, True)
+            assert rc != 0 and why.encode() in lib.mrcnn_last_error(), (i, entry, lib.mrcnn_last_error())
+    for entry in G.WINO_ENTRIES:
+        assert _plan_line(lib, entry, G.wino_desc(2, 8, 7, 7, 8), True)[0] == 0
+    rc, _ = _plan_line(lib, 'conv3x3_wino_fwd+res_g', G.wino_desc(2, 8, 7, 7, 8), True)
+    assert rc != 0 and b'unknown entry' in lib.mrcnn_last_error()
+
+
+# ---- detectors on a float64 model of the Winograd route ---------------------------------------------
+from oracle import np_winograd as NW      # noqa: E402
+
+
+def _wino_model(d):
+    """float64 operands and the stages of the forward: tiles (N,TH,TW,C,6,6) -> V -> M (a,b,n,y,x,k)."""
+    x, w, gy = (a.astype(np.float64) for a in G.operands(d))
+    U = np.einsum('ai,kcij,bj->abkc', NW.G, w, NW.G)
+    V = np.einsum('ai,nyxcij,bj->abnyxc', NW.BT, NW._tiles(x, 6, 4, -1), NW.BT)
+    M = np.einsum('abnyxc,abkc->abnyxk', V, U)
+    return x, w, gy, U, V, M
+
+
+def _wino_out(M, H, W):
+    """Y (N,K,4TH,4TW), not yet cropped to the map."""
+    Y = np.einsum('ia,abnyxk,jb->nkyixj', NW.AT, M, NW.AT)
+    n, k, th, _, tw, _ = Y.shape
+    return Y.reshape(n, k, 4 * th, 4 * tw)
+
+
+def test_wino_model_is_the_convolution():
+    d = G.wino_desc(3, 4, 5, 9, 8)
+    x, w, gy, U, V, M = _wino_model(d)
+    _close64(_wino_out(M, 5, 9)[:, :, :5, :9], L.conv_fwd(_t(x), _t(w), 1, 1))
+    _close64(NW.conv3x3_wgrad(x, gy), L.conv_wgrad(_t(x), _t(gy), 3, 3, 1, 1))
+
+
+def test_detector_wino_wgrad_skips_its_short_last_slab_or_v_is_one_tile_short():
+    """(a) and (e): 2050 tiles in 8 slabs of 288 with 34 in the last; 513 tiles in 2 with 225."""
+    for c in ((2050, 4, 3, 3, 4), (513, 4, 4, 4, 4)):
+        d = G.wino_desc(*c)
+        big = G.wino_wgrad_plan(G.wino_tiles(d), 64, 64, dict(G.DEFAULT_KNOBS))      # the slabs of the listed case
+        slab, slabs = big.launches[0].slab, big.slabs
+        x, w, gy, U, V, M = _wino_model(d)
+        Gy = np.einsum('ai,nyxkij,bj->abnyxk', NW.G4, NW._tiles(gy, 4, 4, 0), NW.G4)
+        ref = _t(L.conv_wgrad(_t(x), _t(gy), 3, 3, 1, 1))
+
+        def gw(keep):
+            dU = np.einsum('abnk,abnc->abkc', Gy.reshape(6, 6, -1, d.K)[:, :, keep], V.reshape(6, 6, -1, d.C)[:, :, keep])
+            return _t(np.einsum('ra,abkc,sb->kcrs', NW.WGRAD_AT, dU, NW.WGRAD_AT))
+        T = G.wino_tiles(d)
+        assert _accepts(_f32(gw(slice(0, T))), ref)
+        assert not _accepts(_f32(gw(slice(0, (slabs - 1) * slab))), ref), 'last slab of %d tiles skipped' % (T - (slabs - 1) * slab)
+        assert not _accepts(_f32(gw(slice(0, T - 1))), ref), 'v one tile short'
+
+
+def test_detector_wino_tail_launch_rows():
+    """(b): the 64-row tail launch of wino/main128+tail64 started one tile row early, or without its m_lo
+    (it then computes rows [0, 64) again and the rows from `full` on keep what the workspace held)."""
+    d = G.wino_desc(47, 4, 5, 9, 8)                        # 282 tiles: rows [0, 256) + [256, 282)
+    plan = G.wino_gemm_plan(G.wino_tiles(d), 132, 68, dict(G.DEFAULT_KNOBS))
+    assert plan.label == 'wino/main128+tail64'
+    full = plan.launches[1].rows[0]
+    x, w, gy, U, V, M = _wino_model(d)
+    ref = L.conv_fwd(_t(x), _t(w), 1, 1)
+    shape = M.shape
+    rows = M.reshape(6, 6, -1, d.K)
+    assert _accepts(_f32(_t(_wino_out(M, 5, 9)[:, :, :5, :9])), ref)
+    early = rows.copy()
+    early[:, :, full:] = rows[:, :, full - 64:full - 64 + (rows.shape[2] - full)]
+    stale = rows.copy()
+    stale[:, :, full:] = 0.
+    for what, bad in (('tail launch starts at row full - 64', early), ('m_lo dropped', stale)):
+        assert not _accepts(_f32(_t(_wino_out(bad.reshape(shape), 5, 9)[:, :, :5, :9])), ref), what
+
+
+def test_detector_wino_output_transform_ragged_tile():
+    """(d): a ragged tile's pixels right of the map written anyway land at the start of the next row."""
+    for c in ((3, 4, 5, 9, 8), (2, 4, 2, 7, 4), (2, 4, 7, 7, 4)):
+        d = G.wino_desc(*c)
+        x, w, gy, U, V, M = _wino_model(d)
+        ref = L.conv_fwd(_t(x), _t(w), 1, 1)
+        Y = _wino_out(M, d.H, d.W)
+        bad = Y[:, :, :d.H, :d.W].copy()
+        over = Y.shape[3] - d.W
+        bad[:, :, 1:, :over] = Y[:, :, :d.H - 1, d.W:]
+        assert over > 0 and not _accepts(_f32(_t(bad)), ref), c
+
+
+def _abs_bound(M):
+    """|A^T| |M| |A| per output (N,K,4TH,4TW): what wino_output_transform_kernel<true> propagates."""
+    B = np.einsum('ia,abnyxk,jb->nkyixj', np.abs(NW.AT), np.abs(M), np.abs(NW.AT))
+    return B.reshape(M.shape[2], M.shape[5], 4 * M.shape[3], 4 * M.shape[4])
+
+
+@pytest.mark.parametrize('c', G.WINO_FIXUP_SHAPES, ids=str)
+def test_detector_wino_fixup_and_its_one_half_condition(c):
+    """(c), and the condition the device test puts on its BIAS / AFFINE-with-shift cases: at an ambiguity of
+    2.0 the float64 model of the bound selects every output when the shift is zero and at least half of
+    them with the shifts of wino_fixup_epilogue, which stay below 0.1 x rms of the pre-activation."""
+    d = G.wino_desc(*c)
+    x, w, gy, U, V, M = _wino_model(d)
+    conv = _wino_out(M, d.H, d.W)[:, :, :d.H, :d.W]
+    bound = 2.0 * _abs_bound(M)[:, :, :d.H, :d.W]
+    assert np.all(np.abs(conv) < bound)                                   # (i): every output qualifies
+    sc0, _ = G.wino_fixup_epilogue(d, 'affine0')
+    assert (sc0 > 0).any() and (sc0 < 0).any()
+    wrapped = TF.conv2d(TF.pad(_t(x), (1,) * 4, mode='circular'), _t(w))
+    if d.H > 1:       # (a one-pixel map has one real tap: the wrap reads the pixel itself for every other)
+        assert not _accepts(_f32(wrapped), _t(conv)), 'padding taps read the wrapped row'
+    for kind in ('bias', 'affine'):
+        sc, sh = G.wino_fixup_epilogue(d, kind)
+        sc = np.ones(d.K) if sc is None else sc.astype(np.float64)
+        pre = conv * sc[None, :, None, None]
+        ref = pre + sh.astype(np.float64)[None, :, None, None]
+        assert np.abs(sh).max() <= 0.1 * np.sqrt((pre ** 2).mean()), kind
+        chosen = np.abs(ref) < bound * np.abs(sc)[None, :, None, None]
+        assert chosen.mean() >= 0.75, (kind, chosen.mean())              # the model alone, with margin over 1/2
+        assert _accepts(_f32(_t(ref)), _t(ref))
+        no_shift = np.where(chosen, pre, ref)                             # a fix-up that drops the shift
+        assert not _accepts(_f32(_t(no_shift)), _t(ref)), kind
+        over = np.abs(no_shift - ref) > 1e-4 * np.abs(ref) + 1e-5 * np.abs(ref).max()
+        assert over.mean() >= 0.5, (kind, over.mean())

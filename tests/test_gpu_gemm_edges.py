@@ -14,7 +14,10 @@ finds it.  Two more things are held:
 * the launch policy.  Around every case the profiler counts launches per kind; the GEMM counts must
   equal what gemm_edge_cases.route() predicts for the calls the case made.  That holds the Python
   restatement of the launch policy (csrc/conv_gemm_plan.h: plan_gemm / plan_wgrad) to what the
-  library launches (the Winograd entry points have a policy of their own and are not predicted).
+  library launches.  The Winograd entry points have a policy of their own (plan_wino_gemm /
+  plan_wino_wgrad), restated and predicted the same way; tests/test_gpu_winograd_edges.py runs its
+  branches on this harness.  The W8 kernel (256x128 tiles), which a plain GEMM reaches only from
+  768 tiles on, is reached there through the Winograd route's batch of 36.
 
 Tiny cases are grouped into loops, one test per family and axis, with the case id in the message.
 """
@@ -83,6 +86,9 @@ _DECODE = {
     'mrcnn_deconv2x2s2_fwd_wt': lambda a: (G.Desc(a[4], a[5], a[6], a[7], a[8], 2, 2, 2, 0), False),
     'mrcnn_deconv2x2s2_dgrad': lambda a: (G.Desc(a[3], a[4], a[5], a[6], a[7], 2, 2, 2, 0), False),
     'mrcnn_deconv2x2s2_wgrad': lambda a: (G.Desc(a[3], a[4], a[5], a[6], a[7], 2, 2, 2, 0), bool(L._addr(a[8]))),
+    'mrcnn_conv3x3_wino_fwd': lambda a: (_desc_of(a[0]), True),
+    'mrcnn_conv3x3_wino_dgrad': lambda a: (_desc_of(a[0]), True),
+    'mrcnn_conv3x3_wino_wgrad': lambda a: (_desc_of(a[0]), True),
 }
 
 
@@ -525,7 +531,7 @@ def test_winograd_tiny_maps(dev, monkeypatch, case):
     N, Cc, H, W, K = case
     d = G.desc(N, Cc, H, W, K, 3, 3, 1, 1)
     x, w, gy = G.operands(d)
-    with Session(monkeypatch, 'winograd tiny maps', predict=False) as s:
+    with Session(monkeypatch, 'winograd tiny maps') as s:
         with s.case('winograd %s' % (case,)):
             xt, wt, gt = nhwc(_t(x, dev)), nhwc(_t(w, dev)), nhwc(_t(gy, dev))
             dd = C.make_desc(xt.shape, wt.shape, 1, 1)
