@@ -145,6 +145,8 @@ SIGNATURES = {
     'mrcnn_copy_paste': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int] + [c_vp] * 6),
     'mrcnn_mask_union_pack': (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     'mrcnn_box_coverage': (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp]),
+    'mrcnn_polygon_rasterize_workspace_bytes': (c_i64, [c_int] * 3),
+    'mrcnn_polygon_rasterize': (c_int, [c_vp] * 3 + [c_int] * 3 + [c_vp] * 6),
     'mrcnn_allreduce_unique_id': (c_int, [c_vp]),
     'mrcnn_allreduce_init': (c_int, [c_vp, c_int, c_int, ctypes.POINTER(c_vp)]),
     'mrcnn_allreduce_destroy': (c_int, [c_vp]),

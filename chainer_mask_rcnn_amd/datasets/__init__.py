@@ -5,6 +5,7 @@ from .transforms import MaskRCNNTransform  # NOQA
 from .transforms import resize_bbox, flip_bbox, resize_nearest, flip  # NOQA
 from .transforms import draw_scale_jitter  # NOQA
 from .packed_masks import PackedMasks  # NOQA
+from .polygon_masks import PolygonMasks  # NOQA
 from .concat_examples import concat_examples  # NOQA
 from .coco import COCOInstanceSegmentationDataset  # NOQA
 from .voc import VOC2012InstanceSegmentationDataset, SBDInstanceSegmentationDataset  # NOQA

@@ -5,7 +5,9 @@ third-party readers: the annotation index that ``pycocotools.coco.COCO`` builds 
 from the JSON directly, COCO run-length masks (``pycocotools.mask.frPyObjects`` / ``decode``)
 are decoded by ``rle_decode`` below, images are read with Pillow (the reference uses
 ``skimage.io.imread``, which returns the same RGB uint8 array for JPEG files).  Polygons are
-rasterised with ``PIL.ImageDraw`` exactly as the reference does (:136-143).
+rasterised with ``PIL.ImageDraw`` exactly as the reference does (:136-143); ``polygon_rule='coco'``
+draws them by COCO's own rule instead (``polygon_to_mask_coco``), and
+``device_polygons=True`` hands the vertices on as a ``datasets.PolygonMasks`` for the device to draw.
 
     dataset[i] -> img (H,W,3) uint8 RGB, bboxes (G,4) f32 (y1,x1,y2,x2), labels (G,) i32,
                   masks (G,H,W) i32 {0,1} [, crowds (G,) i32] [, areas (G,) f32]
@@ -72,13 +74,132 @@ def mask_to_bbox(mask):
     return y1, x1, y2, x2
 
 
+# ---- COCO's polygon rule on the host (pycocotools maskApi.c rleFrPoly) ----
+# The device draws the same rule (csrc/polygon_raster.hip); this is the CPU-only route and the
+# source of the dataset's exact boxes.  NumPy's float64 multiply and adds are never fused, which
+# the rule depends on.
+POLYGON_SCALE = 5.0
+_WALK_CHUNK = 1 << 20       # points of one edge handled at a time
+
+
+def upsample_ring(ring):
+    """One ring ``[x0, y0, x1, y1, ...]`` (or (k, 2)) -> (k, 2) int64 ``(int)(5.0 * c + .5)``, the
+    cast truncating towards zero as C's does.  ValueError unless the coordinates are an even number
+    of finite values with ``|5 c| < 2^30``."""
+    a = np.asarray(ring, dtype=np.float64).reshape(-1)
+    if a.size % 2:
+        raise ValueError('polygon ring: the number of coordinates must be even, got %d' % a.size)
+    if not np.isfinite(a).all():
+        raise ValueError('polygon ring: every coordinate must be finite')
+    if (np.abs(POLYGON_SCALE * a) >= 2.0 ** 30).any():
+        raise ValueError('polygon ring: |5 * coordinate| must be below 2^30')
+    return np.trunc(POLYGON_SCALE * a + .5).astype(np.int64).reshape(-1, 2)
+
+
+def ring_crossings(xy5, h, w):
+    """The crossings ``(x, y)`` (two int64 arrays) of one upsampled ring on an ``h x w`` image, in
+    no particular order: ``0 <= x < w``, ``0 <= y <= h`` (``y == h`` touches no pixel).  One
+    vectorised walk per edge; a ring of fewer than 3 vertices has none."""
+    xs_out, ys_out = [], []
+    k = len(xy5)
+    for j in range(k if k >= 3 else 0):
+        (xs, ys), (xe, ye) = (int(c) for c in xy5[j]), (int(c) for c in xy5[(j + 1) % k])
+        dx, dy = abs(xe - xs), abs(ye - ys)
+        if (dx >= dy and xs > xe) or (dx < dy and ys > ye):     # flip: the same points, met in
+            xs, xe, ys, ye = xe, xs, ye, ys                     # the other order
+            flip = True
+        else:
+            flip = False
+        n = max(dx, dy)
+        if n == 0:
+            continue
+        s = (ye - ys) / dx if dx >= dy else (xe - xs) / dy
+        for a in range(0, n, _WALK_CHUNK):
+            ti = np.arange(a, min(a + _WALK_CHUNK, n) + 1, dtype=np.int64)
+            t = ti.astype(np.float64)
+            if dx >= dy:
+                u, v = ti + xs, np.trunc(ys + s * t + .5).astype(np.int64)
+            else:
+                v, u = ti + ys, np.trunc(xs + s * t + .5).astype(np.int64)
+            if flip:
+                u, v = u[::-1], v[::-1]
+            ch = np.flatnonzero(u[1:] != u[:-1]) + 1
+            if not ch.size:
+                continue
+            xd = np.where(u[ch] < u[ch - 1], u[ch], u[ch] - 1).astype(np.float64)
+            xd = (xd + .5) / POLYGON_SCALE - .5
+            keep = (np.floor(xd) == xd) & (xd >= 0) & (xd <= w - 1)
+            yd = np.minimum(v[ch], v[ch - 1]).astype(np.float64)
+            yd = np.ceil(np.clip((yd + .5) / POLYGON_SCALE - .5, 0., float(h)))
+            xs_out.append(xd[keep].astype(np.int64))
+            ys_out.append(yd[keep].astype(np.int64))
+    if not xs_out:
+        return np.zeros((0,), np.int64), np.zeros((0,), np.int64)
+    return np.concatenate(xs_out), np.concatenate(ys_out)
+
+
+def _fill_ring(xy5, h, w):
+    """Even-odd fill of one ring: pixel (y, x) is set iff an odd number of its crossings (x, y')
+    have y' <= y."""
+    x, y = ring_crossings(xy5, h, w)
+    inside = y < h
+    toggles = np.bincount(y[inside] * w + x[inside], minlength=h * w).reshape(h, w) & 1
+    return np.bitwise_xor.accumulate(toggles.astype(np.uint8), axis=0).astype(bool)
+
+
+def polygon_to_mask_coco(rings, h, w):
+    """COCO's own polygon rule (``pycocotools.mask.frPyObjects`` + ``merge`` + ``decode``): a list
+    of rings ``[x0, y0, x1, y1, ...]`` -> (h, w) bool mask, the UNION of the rings, each ring
+    filled even-odd.  Not PIL's rule: the square [1,1, 4,1, 4,4, 1,4] is pixels 1..3 here and
+    1..4 under ``PIL.ImageDraw.polygon(outline=1, fill=1)``."""
+    h, w = int(h), int(w)
+    mask = np.zeros((h, w), bool)
+    for ring in rings:
+        mask |= _fill_ring(upsample_ring(ring), h, w)
+    return mask
+
+
+def _ring_box(xy5, h, w):
+    """Tight (y1, x1, y2, x2) of one ring's fill from its crossings alone, or None when the ring
+    sets nothing.  Equal crossings cancel; in a column the rest, sorted, open and close runs in
+    turn (a run left open ends at h)."""
+    x, y = ring_crossings(xy5, h, w)
+    key, count = np.unique(x * (h + 1) + y, return_counts=True)
+    key = key[(count & 1) == 1]
+    if not key.size:
+        return None
+    cx, cy = key // (h + 1), key % (h + 1)
+    cols, start, per = np.unique(cx, return_index=True, return_counts=True)
+    first, last = cy[start], np.where(per & 1, h, cy[start + per - 1])
+    ok = first < last
+    if not ok.any():
+        return None
+    return (int(first[ok].min()), int(cols[ok].min()), int(last[ok].max()), int(cols[ok].max()) + 1)
+
+
+def polygon_box_coco(rings, h, w):
+    """Tight (y1, x1, y2, x2) of ``polygon_to_mask_coco(rings, h, w)`` without filling it — the
+    hull of the non-empty rings' boxes — or (0, 0, 0, 0) when no pixel is set (the device's
+    convention; ``mask_to_bbox`` raises there)."""
+    boxes = [b for b in (_ring_box(upsample_ring(r), int(h), int(w)) for r in rings) if b is not None]
+    if not boxes:
+        return 0, 0, 0, 0
+    b = np.asarray(boxes)
+    return int(b[:, 0].min()), int(b[:, 1].min()), int(b[:, 2].max()), int(b[:, 3].max())
+
+
 class COCOInstanceSegmentationDataset(object):
 
     class_names = None  # initialized by __init__
     root_dir = osp.expanduser('~/data/datasets/COCO')
 
     def __init__(self, split, use_crowd=False, return_crowd=False, return_area=False,
-                 root_dir=None, packed_masks=False):
+                 root_dir=None, packed_masks=False, polygon_rule='pil', device_polygons=False):
+        if polygon_rule not in ('pil', 'coco'):
+            raise ValueError("polygon_rule must be 'pil' or 'coco', got %r" % (polygon_rule,))
+        if device_polygons and polygon_rule != 'coco':
+            raise ValueError("device_polygons=True requires polygon_rule='coco' (the device draws "
+                             "COCO's rule only)")
         if root_dir is not None:
             self.root_dir = root_dir
         test_dev = split == 'test-dev'
@@ -104,6 +225,8 @@ class COCOInstanceSegmentationDataset(object):
         self._return_crowd = return_crowd
         self._return_area = return_area
         self._packed_masks = packed_masks
+        self._polygon_rule = polygon_rule
+        self._device_polygons = bool(device_polygons)
 
         with open(ann_file) as f:
             data = json.load(f)
@@ -187,18 +310,38 @@ class COCOInstanceSegmentationDataset(object):
         for ann in anns:
             if 'segmentation' not in ann or (ann['iscrowd'] == 1 and not self._use_crowd):
                 continue
-            inst = self._rasterise(ann['segmentation'], height, width)
+            seg = ann['segmentation']
+            if isinstance(seg, list) and self._polygon_rule == 'coco':
+                # device_polygons: the rings travel on as they are (a list), nothing is drawn here
+                inst = seg if self._device_polygons else polygon_to_mask_coco(seg, height, width)
+            else:
+                inst = self._rasterise(seg, height, width)
             if inst is not None:
                 yield ann, inst
+
+    def _box(self, inst, height, width):
+        """The tight box of one kept instance: ``mask_to_bbox`` as ever under the PIL rule; under
+        COCO's rule a polygon may set no pixel at all, and its box is then zeros."""
+        if self._polygon_rule == 'pil':
+            return mask_to_bbox(inst)
+        if isinstance(inst, list):
+            return polygon_box_coco(inst, height, width)
+        return mask_to_bbox(inst) if inst.any() else (0, 0, 0, 0)
 
     def _annotations_to_example(self, anns, height, width):
         kept = list(self._kept_instances(anns, height, width))
         col = lambda fn, dt: np.asarray([fn(a, m) for a, m in kept], dtype=dt)
+        if self._device_polygons:
+            from .polygon_masks import PolygonMasks
+            masks = PolygonMasks.from_instances([m for _, m in kept], height, width)
+        elif self._packed_masks:
+            masks = PackedMasks.from_instances([m for _, m in kept], height, width)
+        else:
+            masks = col(lambda a, m: m, np.int32).reshape((-1, height, width))
         example = [
-            col(lambda a, m: mask_to_bbox(m), np.float32).reshape((-1, 4)),       # y1, x1, y2, x2
+            col(lambda a, m: self._box(m, height, width), np.float32).reshape((-1, 4)),   # y1, x1, y2, x2
             col(lambda a, m: self.cat_id_to_class_id[a['category_id']], np.int32),
-            PackedMasks.from_instances([m for _, m in kept], height, width) if self._packed_masks
-            else col(lambda a, m: m, np.int32).reshape((-1, height, width)),
+            masks,
         ]
         if self._return_crowd:
             example.append(col(lambda a, m: a['iscrowd'], np.int32))

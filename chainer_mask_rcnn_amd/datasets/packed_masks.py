@@ -19,6 +19,25 @@ def _pack_into(words, rows):
     words.view(np.uint8)[..., :bits.shape[-1]] = bits
 
 
+def packed_metadata(words, width):
+    """What the device entries return beside packed words, from host words (G, H, Wq): exact
+    ``area`` (G,), tight ``extent`` (G, 4) (y_lo, y_hi, wq_lo, wq_hi) and tight ``box`` (G, 4)
+    (y1, x1, y2, x2), all int32; an empty mask has area 0, a box of zeros and the empty extent
+    (H, 0, Wq, 0), as ``mrcnn_mask_pack`` leaves it."""
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    G, H, Wq = words.shape
+    area, extent, box = (np.zeros(s, np.int32) for s in ((G,), (G, 4), (G, 4)))
+    extent[:] = H, 0, Wq, 0
+    for g in range(G):
+        bits = np.unpackbits(words[g].view(np.uint8), axis=-1, bitorder='little')   # (H, 64 Wq)
+        rows, cols = np.flatnonzero(bits.any(axis=1)), np.flatnonzero(bits.any(axis=0))
+        if rows.size:
+            area[g] = int(bits.sum())
+            box[g] = rows[0], cols[0], rows[-1] + 1, cols[-1] + 1
+            extent[g] = rows[0], rows[-1] + 1, cols[0] >> 6, (cols[-1] >> 6) + 1
+    return area, extent, box
+
+
 class PackedMasks(object):
     """``words`` uint64 (G, H, Wq) + ``height`` + ``width``; behaves like the (G, H, W) stack
     where the input pipeline looks at it (``len``, ``shape``, ``ndim``, subsetting)."""

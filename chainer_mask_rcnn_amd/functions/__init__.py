@@ -26,3 +26,4 @@ from .gt_masks import resize_masks_nearest, upload_packed_masks
 from .scale_jitter import prepare_image_crop, resize_crop_masks
 from .copy_paste import copy_paste, copy_paste_meta
 from .ignore_regions import union_plane, box_coverage, ignored_from_counts
+from .polygons import rasterize_polygons, upsample_vertices

@@ -10,7 +10,15 @@ from .. import _lib
 def upload_packed_masks(packed, device):
     """``datasets.PackedMasks`` -> ``(words, width)``: the words as an int64 device tensor
     (G, H, Wq) (torch has no arithmetic on uint64; the bits are what matters) and the mask width
-    in pixels, which the word count alone does not give.  Only the bits cross PCIe."""
+    in pixels, which the word count alone does not give.  Only the bits cross PCIe.
+
+    A ``datasets.PolygonMasks`` crosses as its vertices instead: its polygons are drawn on the
+    device by one ``functions.rasterize_polygons`` call, the packed rows of its run-length
+    instances are copied in beside them, and the words never exist on the host."""
+    from ..datasets.polygon_masks import PolygonMasks
+    if isinstance(packed, PolygonMasks):
+        from .polygons import rasterize_polygons
+        return rasterize_polygons(packed, device)[0], packed.width
     words = torch.from_numpy(packed.words.view(np.int64)).to(device)
     return words, packed.width
 

@@ -43,7 +43,21 @@ def packed_words(W):
 
 def pack_masks(masks, device=None):
     """(N, H, W) uint8 / bool / int32 masks (host array or device tensor) -> (packed (N,H,Wq)
-    int64 bit pattern, area (N,) int32, extent (N,4) int32) device tensors."""
+    int64 bit pattern, area (N,) int32, extent (N,4) int32) device tensors.
+
+    Ground truth that never was a dense stack is taken as it is: a ``datasets.PolygonMasks`` is
+    drawn on the device from its vertices (``functions.rasterize_polygons``), a host
+    ``datasets.PackedMasks`` is uploaded as its words, with areas and extents counted on the host."""
+    from ...datasets.packed_masks import PackedMasks, packed_metadata
+    from ...datasets.polygon_masks import PolygonMasks
+    if isinstance(masks, PolygonMasks):
+        from ...functions.polygons import rasterize_polygons
+        return rasterize_polygons(masks, device=device if device is not None else _device())[:3]
+    if isinstance(masks, PackedMasks):
+        dev = torch.device(device) if device is not None else _device()
+        area, extent, _ = packed_metadata(masks.words, masks.width)
+        return (torch.from_numpy(masks.words.view(np.int64)).to(dev), torch.from_numpy(area).to(dev),
+                torch.from_numpy(extent).to(dev))
     dev = torch.device(device) if device is not None else (
         masks.device if isinstance(masks, torch.Tensor) and masks.is_cuda else _device())
     m = _as_device_masks(masks, dev)

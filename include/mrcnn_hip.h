@@ -1012,6 +1012,35 @@ int mrcnn_mask_union_pack(const uint8_t *masks, int G, int H, int W, const uint6
 int mrcnn_box_coverage(const uint64_t *plane, int H, int W, const float *boxes, int n,
                        int32_t *out, void *stream);
 
+/* ---- COCO polygons -> packed masks (csrc/polygon_raster.hip) ----------
+ * Ground-truth polygons drawn by COCO's own rule — pycocotools maskApi.c rleFrPoly: vertices
+ * upsampled by 5, a dense walk of each edge, crossings of pixel-column centres, an even-odd fill
+ * down each column — straight into the "Packed masks" format above, so that a polygon crosses
+ * PCIe as its vertices and the mask never exists on the host.  The reference draws polygons with
+ * PIL.ImageDraw (chainer_mask_rcnn/datasets/coco.py:136-143), which is a different rule. */
+/* Scratch of mrcnn_polygon_rasterize for G instances of an H x W image (one record per instance
+ * and 64-column strip), in bytes; 0 when G, H or W is not positive. */
+int64_t mrcnn_polygon_rasterize_workspace_bytes(int G, int H, int W);
+/* G instances, each the UNION of its rings (a ring by itself is filled even-odd).  xy5 (V,2)
+ * int32: the rings' vertices (x, y) one ring after another, already upsampled as maskApi.c does,
+ * X = (int)(5.0 * x + .5) in doubles, |X| < 2^30; ring_off (R+1) int32: ring r owns vertices
+ * ring_off[r] .. ring_off[r+1]; inst_off (G+1) int32: instance g owns rings inst_off[g] ..
+ * inst_off[g+1].  Both offset arrays are taken on trust (non-decreasing, from 0, ending at R and
+ * V): they bound reads only; every write is bounded by G, H and W.  A ring of fewer than 3
+ * vertices sets nothing; an instance may have no rings.  All arrays are device pointers; xy5 may
+ * be null when V = 0.
+ * Outputs: packed (G,H,Wq) — every word is written, pad bits are zero; area (G) exact; extent
+ * (G,4) tight (y_lo, y_hi, wq_lo, wq_hi), (H, 0, Wq, 0) for an empty mask as mrcnn_mask_pack
+ * leaves it; box (G,4) int32 the tight (y1, x1, y2, x2), half-open, zeros for an empty mask
+ * (mrcnn_mask_resize_crop's convention, the dataset's mask_to_bbox).  ws: mrcnn_polygon_rasterize_workspace_bytes(G, H, W) bytes, 4-byte
+ * aligned.  Two launches on the stream; LDS atomics and integer reductions only: the outputs are
+ * exact and identical run to run.  Replaces pycocotools.mask.frPyObjects + merge + decode (packed),
+ * area (area) and toBbox (box).  G == 0 returns without a launch.  H <= 4000 (a strip keeps two
+ * H-word arrays in LDS), H * W < 2^31, G * Wq < 2^31; R and V are bounded by int32 only. */
+int mrcnn_polygon_rasterize(const int32_t *xy5, const int32_t *ring_off, const int32_t *inst_off,
+                            int G, int H, int W, uint64_t *packed, int32_t *area, int32_t *extent,
+                            int32_t *box, void *ws, void *stream);
+
 /* ---- Gradient exchange over RCCL / xGMI ---------------------------------------------- */
 /* Replaces ChainerMN's communicator as the reference uses it
  * (examples/train_common.py:97-103 `chainermn.create_communicator('hierarchical')`, :178

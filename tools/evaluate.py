@@ -253,6 +253,10 @@ def main():
                          'any of them together; with --results, each type is scored from the file')
     ap.add_argument('--boundary-dilation-ratio', type=float, default=0.02, metavar='R',
                     help='Boundary AP: the boundary width as a fraction of the image diagonal')
+    ap.add_argument('--polygon-rule', choices=['pil', 'coco'], default='pil',
+                    help="how COCO polygon annotations become ground-truth masks: pil (PIL.ImageDraw, "
+                         "the reference's; about one pixel fatter) or coco (COCO's own rule, what "
+                         "pycocotools scores against; DESIGN.md section 25).  Also with --results")
     ap.add_argument('--arithmetic', default=None, choices=['fp32', 'split_bf16x3', 'split_bf16x2', 'bf16x1'],
                     help='arithmetic of the convolution GEMMs (functions.conv.set_gemm_arithmetic; default '
                          'split_bf16x3: fp32-accurate; split_bf16x2: 16-bit-class operands; bf16x1: bf16 '
@@ -299,7 +303,7 @@ def main():
             ap.error('--coco-root or --synthetic is required')
         data = cmr.datasets.COCOInstanceSegmentationDataset(
             args.split, root_dir=args.coco_root, use_crowd=True, return_crowd=True,
-            return_area=True)
+            return_area=True, polygon_rule=args.polygon_rule)
         class_names = [str(n) for n in data.class_names]
     if args.split == 'test-dev' and not args.save_results:
         ap.error('--split test-dev has no annotations to score: use --save-results FILE')
@@ -413,7 +417,8 @@ def score_results(args):
         raise SystemExit('test-dev has no public annotations: its results are scored by the '
                          'COCO evaluation server')
     data = cmr.datasets.COCOInstanceSegmentationDataset(
-        split, root_dir=args.coco_root, use_crowd=True, return_crowd=True, return_area=True)
+        split, root_dir=args.coco_root, use_crowd=True, return_crowd=True, return_area=True,
+        polygon_rule=getattr(args, 'polygon_rule', 'pil'))
     torch.cuda.set_device(0)
     t0 = time.perf_counter()
     result = {}

@@ -85,6 +85,13 @@ def parse_args(argv=None):
                          "proposal or an anchor more than THRESH of which a crowd mask covers is not "
                          "sampled (Detectron's TRAIN.CROWD_FILTER_THRESH, 0.7; DESIGN.md section 24).  "
                          "Needs --device-masks and --dataset coco.  Recorded in params.yaml when given")
+    ap.add_argument('--polygon-rule', choices=['pil', 'coco'], default=argparse.SUPPRESS,
+                    help="how COCO polygon annotations become masks, in training and evaluation: pil "
+                         "(PIL.ImageDraw, the reference's; the default) or coco (COCO's own rule, "
+                         "pycocotools' rleFrPoly; DESIGN.md section 25).  Recorded in params.yaml when given")
+    ap.add_argument('--device-polygons', action='store_true', default=argparse.SUPPRESS,
+                    help='COCO polygons cross PCIe as vertices and are drawn by a HIP kernel: no '
+                         'ground-truth mask exists on the host.  Needs --device-masks --polygon-rule coco')
     ap.add_argument('--eval-bbox', action='store_true',
                     help='the evaluator also scores the boxes: validation/main/bbox/map joins the '
                          'log and the printed report (the best snapshot stays on the mask map)')
@@ -120,6 +127,9 @@ def parse_args(argv=None):
             ap.error('--crowd-ignore needs --dataset coco (crowd regions are COCO annotations)')
         if not 0 <= args.crowd_ignore <= 1:
             ap.error('--crowd-ignore THRESH must lie in [0, 1], got %r' % (args.crowd_ignore,))
+    if getattr(args, 'device_polygons', False) and not (
+            args.device_masks and getattr(args, 'polygon_rule', 'pil') == 'coco'):
+        ap.error('--device-polygons needs --device-masks --polygon-rule coco')
     return args
 
 
@@ -210,7 +220,7 @@ def test_dataset(args):
     if args.dataset == 'coco':                       # examples/coco/train.py
         return cmr.datasets.COCOInstanceSegmentationDataset(
             'minival', root_dir=args.coco_root, use_crowd=True, return_crowd=True,
-            return_area=True), 'coco'
+            return_area=True, polygon_rule=getattr(args, 'polygon_rule', 'pil')), 'coco'
     if args.dataset == 'voc':                        # examples/voc/train.py
         return cmr.datasets.SBDInstanceSegmentationDataset('val', root_dir=args.sbd_root), 'voc'
     if args.dataset == 'custom':                     # examples/custom_dataset/train.py
@@ -229,6 +239,8 @@ def datasets(args):
         # --crowd-ignore: the crowd regions come along, flagged, and leave the transform as a plane
         crowds = dict(use_crowd=True, return_crowd=True) \
             if getattr(args, 'crowd_ignore', None) is not None else {}
+        crowds.update(polygon_rule=getattr(args, 'polygon_rule', 'pil'),
+                      device_polygons=getattr(args, 'device_polygons', False))
         train_data = T.ConcatenatedDataset(
             cmr.datasets.COCOInstanceSegmentationDataset('train', root_dir=args.coco_root,
                                                          packed_masks=packed, **crowds),

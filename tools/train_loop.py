@@ -457,6 +457,12 @@ def main():
     ap.add_argument('--device-masks', action='store_true',
                     help='ground-truth masks cross PCIe as bits and are resized / flipped by a HIP '
                          'kernel (COCO: the dataset also keeps them packed on the host)')
+    ap.add_argument('--polygon-rule', choices=['pil', 'coco'], default='pil',
+                    help="how COCO polygon annotations become masks: pil (PIL.ImageDraw, the "
+                         "reference's) or coco (COCO's own rule; DESIGN.md section 25)")
+    ap.add_argument('--device-polygons', action='store_true',
+                    help='COCO polygons cross PCIe as vertices and are drawn by a HIP kernel '
+                         '(needs --device-masks --polygon-rule coco)')
     add_scale_jitter_arguments(ap)
     add_copy_paste_argument(ap)
     ap.add_argument('--defer', type=int, default=5,
@@ -468,6 +474,8 @@ def main():
     args = ap.parse_args()
     scale_jitter, crop_size = scale_jitter_options(ap, args)
     copy_paste = copy_paste_option(ap, args)
+    if args.device_polygons and not (args.device_masks and args.polygon_rule == 'coco'):
+        ap.error('--device-polygons needs --device-masks --polygon-rule coco')
     import chainer_mask_rcnn_amd as cmr
     if os.environ.get('TORCH_THREADS'):
         torch.set_num_threads(int(os.environ['TORCH_THREADS']))
@@ -484,7 +492,9 @@ def main():
     else:
         data = cmr.datasets.COCOInstanceSegmentationDataset(args.split or 'minival',
                                                             root_dir=args.coco_root,
-                                                            packed_masks=args.device_masks)
+                                                            packed_masks=args.device_masks,
+                                                            polygon_rule=args.polygon_rule,
+                                                            device_polygons=args.device_polygons)
     loop, model, chain, opt = build(data, args.layers, 'cuda:0', args.batch, args.seed,
                                     defer=args.defer, prefetch=not args.no_prefetch,
                                     pooling_func=args.pooling_func, model_settings=settings,
