@@ -57,6 +57,7 @@ SIGNATURES = {
     'mrcnn_sparse3x3_scatter': (c_int, [c_vp, c_vp] + [c_int] * 4 + [c_vp, c_vp]),
     'mrcnn_roi_align_bwd_ex': (c_int, [c_vp, c_vp, c_vp] + [c_int] * 8 + [c_f32, c_int, c_vp, c_vp]),
     'mrcnn_roi_align_bwd_ws': (c_int, [c_vp, c_vp, c_vp] + [c_int] * 8 + [c_f32, c_int, c_vp, c_i64, c_vp]),
+    'mrcnn_roi_align_bwd_form': (c_int, [c_int] * 9),
     'mrcnn_roi_pool_fwd': (c_int, [c_vp] * 4 + [c_int] * 8 + [c_f32, c_vp, c_vp]),
     'mrcnn_roi_pool_bwd_workspace_bytes': (c_i64, [c_int] * 7),
     'mrcnn_roi_pool_bwd_ws': (c_int, [c_vp] * 4 + [c_int] * 8 + [c_f32, c_vp, c_i64, c_vp]),

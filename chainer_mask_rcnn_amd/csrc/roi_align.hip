@@ -577,7 +577,11 @@ __device__ __forceinline__ float4 fma_vec(float4 acc, float w, float4 v)
 
 // acc[x] += w[x] * v for the tile's 8 pixels.  Pixels the bin does not touch carry w = 0 and take
 // the FMA as well (adds 0 for finite gy): per-pixel tests cost four selects per FMA pair here
-// and made this loop, not the loads, the bound of the kernel.
+// and made this loop, not the loads, the bound of the kernel.  A non-finite gy element therefore
+// turns the zero-weight pixels of the tiles its bin touches into NaN (0 * inf) — in its own channel
+// only, and never in a tile row the bin has no weight on (no list entry there): the gradient stays
+// non-finite wherever the exact one is, which is what the trainer's non-finite step guard needs
+// (tests/test_gpu_roi_exact.py::test_owner_nonfinite_gy_stays_in_its_channel_and_tiles).
 template <typename V>
 __device__ __forceinline__ void owner_consume(V (&acc)[kOwnXT], const V v, const float *w)
 {
@@ -877,6 +881,37 @@ extern "C" int64_t mrcnn_roi_align_bwd_workspace_bytes(int N, int H, int W, int 
     return owner_ws(H, W, R, out_bins(PH, bin_stride), out_bins(PW, bin_stride)).total;
 }
 
+namespace {
+enum BwdForm { kBwdOwner = 0, kBwdGather = 1, kBwdScatter = 2 };
+
+// dynamic LDS of the gather form: Ay[PH], Bx[W + 4][PW], pwlo / pwhi[W + 4]
+inline size_t gather_lds_bytes(int W, int PH, int PW)
+{
+    return sizeof(float) * ((size_t)PH + (size_t)(W + 4) * PW) + sizeof(int) * 2 * (W + 4);
+}
+
+// Which backward kernel mrcnn_roi_align_bwd_ws launches (behind mrcnn_roi_align_bwd_form): the
+// pixel-owner form needs an aligned workspace, 16-bit patch extents and an int tile id; the gather
+// form its LDS tables within 48 KB, the feature row and the RoI in grid.x / grid.y; else scatter.
+inline int bwd_form(int N, int H, int W, int R, int PH, int PW, int bin_stride, bool has_ws,
+                    bool ws_aligned)
+{
+    (void)bin_stride;
+    const int64_t tiles = (int64_t)((W + kOwnXT - 1) / kOwnXT) * H * N;
+    if (has_ws && R > 0 && H <= 65535 && W <= 65535 && tiles + 8 < (int64_t)INT32_MAX && ws_aligned)
+        return kBwdOwner;
+    if (gather_lds_bytes(W, PH, PW) <= 48 * 1024 && H <= 65535 && R <= 65535) return kBwdGather;
+    return kBwdScatter;
+}
+}  // namespace
+
+extern "C" int mrcnn_roi_align_bwd_form(int N, int H, int W, int R, int PH, int PW, int bin_stride,
+                                        int has_ws, int ws_aligned)
+{
+    if (N <= 0 || H <= 0 || W <= 0 || R < 0 || PH <= 0 || PW <= 0 || bin_stride < 1) return -1;
+    return bwd_form(N, H, W, R, PH, PW, bin_stride, has_ws != 0, ws_aligned != 0);
+}
+
 extern "C" int mrcnn_roi_align_bwd_ex(const float *gy, const float *rois, float *gx, int N, int H,
                                       int W, int C, int R, int PH, int PW, int bin_stride,
                                       float spatial_scale, int sampling_ratio, void *ws,
@@ -902,8 +937,8 @@ extern "C" int mrcnn_roi_align_bwd_ws(const float *gy, const float *rois, float 
     const bool vec = C % 4 == 0 && ((uintptr_t)gx % 16 == 0) && ((uintptr_t)gy % 16 == 0);
     const int cv = vec ? C / 4 : C;
     const int64_t tiles = (int64_t)((W + kOwnXT - 1) / kOwnXT) * H * N;
-    if (ws && R > 0 && H <= 65535 && W <= 65535 && tiles + 8 < (int64_t)INT32_MAX &&
-        (uintptr_t)ws % 16 == 0) {
+    const int form = bwd_form(N, H, W, R, PH, PW, bin_stride, ws != nullptr, (uintptr_t)ws % 16 == 0);
+    if (form == kBwdOwner) {
         // pixel-owner form: every gx element is written exactly once, no zero-fill.
         // algorithmic bytes: read R*OH*OW*C, write the feature-map gradient
         hipEvent_t ev0, ev1;  // start of the table kernel .. end of the owner kernel, dispatch timestamps
@@ -931,8 +966,8 @@ extern "C" int mrcnn_roi_align_bwd_ws(const float *gy, const float *rois, float 
     // algorithmic bytes: read R*OH*OW*C, read-modify-write the feature-map gradient
     mrcnn::ProfScope prof(mrcnn::PROF_ROI_ALIGN_BWD, 0.,
                           4.0 * ((double)bins * C + 2.0 * (double)N * H * W * C), s);
-    const size_t lds = sizeof(float) * ((size_t)PH + (size_t)(W + 4) * PW) + sizeof(int) * 2 * (W + 4);
-    if (lds <= 48 * 1024 && H <= 65535 && R <= 65535) {
+    const size_t lds = gather_lds_bytes(W, PH, PW);
+    if (form == kBwdGather) {
         // gather form: one workgroup per (roi, feature row), one atomic per (pixel, channel)
         dispatch_vec(vec, [&](auto tag) {
             typedef decltype(tag) V;

@@ -118,6 +118,13 @@ int mrcnn_roi_align_bwd_ws(const float *gy, const float *rois, float *gx,
                            int N, int H, int W, int C, int R, int PH, int PW, int bin_stride,
                            float spatial_scale, int sampling_ratio, void *ws, int64_t ws_bytes,
                            void *stream);
+/* Which kernel mrcnn_roi_align_bwd_ws launches for this problem: 0 = pixel-owner, 1 = gather (one
+ * atomic add per RoI patch pixel and channel), 2 = scatter (the reference's four atomic adds per
+ * sample; taken when the gather form's tables of 4 (PH + (W + 4) PW) + 8 (W + 4) bytes exceed
+ * 48 KB of LDS or R > 65535).  has_ws: a workspace is passed; ws_aligned: it is 16-byte aligned.
+ * The function the launch itself consults; host only, needs no device.  -1 for a bad shape. */
+int mrcnn_roi_align_bwd_form(int N, int H, int W, int R, int PH, int PW, int bin_stride,
+                             int has_ws, int ws_aligned);
 
 /* ---- RoI max pooling and crop-and-resize --------------------------------------------------
  * The two other RoI feature extractors the reference's head accepts as pooling_func
