@@ -15,7 +15,8 @@ from .roi_pooling_2d import ROIPooling2D
 from .crop_and_resize import crop_and_resize
 from .crop_and_resize import CropAndResize
 
-from .conv import conv2d, deconv2x2s2, linear, stem_conv, building_block
+from .conv import conv2d, deconv2x2s2, linear, stem_conv
+from .stage import building_block
 from .pooling import max_pooling_2d, average_pooling_2d
 from .loss import (sigmoid_cross_entropy, softmax_cross_entropy, fast_rcnn_loc_loss,
                    mask_sigmoid_cross_entropy, softmax)

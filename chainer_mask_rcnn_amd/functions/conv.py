@@ -3,108 +3,40 @@
 Host-side mirror of chainer's ``L.Convolution2D`` (+ the ``AffineChannel2D``,
 residual add and ReLU that follow it inside chainer's Bottleneck blocks),
 ``L.Deconvolution2D(k=2, s=2)`` and ``L.Linear`` as the reference uses them
-(/root/reference/chainer_mask_rcnn/models/region_proposal_network.py:75-80,
+(the reference's models/region_proposal_network.py:75-80,
 models/mask_rcnn_resnet.py:131-143).  Tensors carry the
 reference's logical shapes — x (N,C,H,W), conv W (out,in,kh,kw), deconv W
 (in,out,kh,kw), linear W (out,in) — stored channels-last, which is exactly the
 NHWC / KRSC layout the HIP kernels consume.
+
+This module decides WHICH ROUTE a layer takes — the knobs below, ``uses_winograd``, the caches
+derived from weights with ``weights_changed`` — and holds the autograd nodes of the single layers.
+The launches are functions/_conv_launch.py, gradient ownership is functions/_wgrad.py (both
+re-exported here), the fused stage node is functions/stage.py, which reads the knobs from here.
+Every knob is read at call time as an attribute of THIS module: tests, tools and the benchmark
+assign them (``conv.WINOGRAD_MIN_WORK = ...``).
 """
-import collections
-import ctypes
 import os as _os
 
 import torch
 
 from .. import _lib
-from .._lib import ConvDesc, EPI_BIAS, EPI_AFFINE, EPI_RESIDUAL, EPI_RELU, EPI_ACCUM, EPI_EXACT_SIGNS
-from ..streams import join_wgrad_stream, wgrad_stream
-from ._layout import nhwc, empty_nhwc
-from ._roi_extractor import out_size
-from .roi_align_2d import roi_align_backward
+from .._lib import ConvDesc
+# (some of these names are not used below: tests, tools, the benchmark and the rest of the package
+# reach them through this module)
+from ._layout import nhwc, empty_nhwc                                           # noqa: F401
+from ._conv_launch import (                                                     # noqa: F401
+    make_desc, ctx_desc, split_ws, epilogue_bwd, _fwd_raw, _flip_transpose, _dgrad_raw,
+    _launch_wgrad, _sparse3x3_gather, _sparse3x3_scatter, _stem_fwd, _deconv_fwd, _deconv_dgrad,
+    _deconv_wgrad_into, _wino_ws, _wino_filter, _wino_fwd_raw, wino_dgrad, wino_wgrad_into,
+    RoiSpec, _roi_pool_affine, _roi_pool_bwd)
+from ._wgrad import _grad_target, _bias_grad, _wgrad, DeferQueue, run_deferred_wgrads   # noqa: F401
 
 
-def _direct_grad(p):
-    """Claim the right to WRITE ``p``'s gradient in place: true for an arena-backed parameter
-    (optimizers.ParamArena) whose arena view is intact and that has not received a gradient yet
-    in this step.  Otherwise the caller returns a fresh tensor and autograd accumulates it."""
-    arena = getattr(p, '_arena', None)
-    if arena is None:
-        return False
-    if arena.claim(p):
-        return True
-    join_wgrad_stream(p.device)      # an earlier in-place write may still be queued there
-    return False
-
-
-def _grad_target(p):
-    """The gradient-ownership rule in one place: ``(buffer, result)`` for parameter ``p`` — the
-    buffer the producing kernel writes (not adds) p's gradient into and what the autograd node
-    returns for p: ``(p.grad, None)`` when the arena slot could be claimed, else the same fresh
-    tensor twice (autograd accumulates it)."""
-    if _direct_grad(p):
-        return p.grad, None
-    g = empty_nhwc(tuple(p.shape), p.device) if p.dim() == 4 else \
-        torch.empty(tuple(p.shape), dtype=torch.float32, device=p.device)
-    return g, g
-
-
-def _bias_grad(b, g, M):
-    """Bias gradient = column sum of the (M, len(b)) gradient ``g``; returns what autograd gets."""
-    gb, result = _grad_target(b)
-    _colsum(_lib.ptr(g), M, b.shape[0], gb, g.device)
-    return result
-
-
-def conv_out_size(size, k, s, p):
-    return (size + 2 * p - k) // s + 1
-
-
-def make_desc(x_shape, w_shape, stride, pad):
-    N, C, H, W = x_shape
-    if len(w_shape) == 2:            # L.Linear weight (out, in) == 1x1 filter
-        w_shape = (w_shape[0], w_shape[1], 1, 1)
-    K, Cw, R, S = w_shape
-    if Cw != C:
-        raise ValueError('conv: input has %d channels, filter expects %d' % (C, Cw))
-    return ConvDesc(N, H, W, C, K, R, S, stride, pad,
-                    conv_out_size(H, R, stride, pad), conv_out_size(W, S, stride, pad))
-
-
-def ctx_desc(d):
-    return ctypes.byref(d)
-
-
-def _colsum(g2d_ptr, M, C, out, device):
-    ws = _lib.workspace(_lib.load().mrcnn_colsum_workspace_bytes(C), device, 'colsum')
-    _lib.call('mrcnn_colsum', g2d_ptr, _lib.ptr(out), M, C, _lib.ptr(ws), _lib.stream_ptr())
-
-
-def split_ws(device):
-    """Scratch for the split-K leftover launches of small-M forward / dgrad GEMMs (cached per
-    device and stream-ordered: safe because every user runs on the compute stream)."""
-    return _lib.workspace(_lib.load().mrcnn_conv2d_split_workspace_bytes(), device, 'conv-split')
-
-
-def epilogue_bwd(gy, y=None, scale=None):
-    """g = gy * (y > 0) * scale[c] on NHWC tensors (any of y/scale may be None)."""
-    _lib.require_device(gy, y, scale)
-    gy = nhwc(gy, torch.float32, 'epilogue_bwd', 'gy')
-    if y is not None:
-        y = nhwc(y, torch.float32, 'epilogue_bwd', 'y')
-    if scale is not None:
-        scale = _lib.dense(scale, torch.float32, 'epilogue_bwd', 'scale', align=True)
-    N, C = gy.shape[0], gy.shape[1]
-    M = gy.numel() // C
-    g = empty_nhwc(tuple(gy.shape), gy.device)
-    _lib.call('mrcnn_epilogue_bwd', _lib.ptr(gy), _lib.ptr(y), _lib.ptr(scale), _lib.ptr(g),
-              M, C, _lib.stream_ptr())
-    return g
-
-
-# Test hook: when set to a list, every ReLU output this module produces (fused conv epilogues, the
-# three activations of each bottleneck of a fused stage, the deconvolution) is appended as
-# (kind, tensor) in call order — tests/test_gpu_model.py reads the ReLU DECISIONS of the HIP path
-# from it.  None (default): nothing is recorded or kept alive.
+# Test hook: when set to a list, every ReLU output this module and functions/stage.py produce (fused
+# conv epilogues, the three activations of each bottleneck of a fused stage, the deconvolution) is
+# appended as (kind, tensor) in call order — tests/test_gpu_model.py reads the ReLU DECISIONS of
+# the HIP path from it.  None (default): nothing is recorded or kept alive.
 RELU_TAP = None
 
 
@@ -176,20 +108,15 @@ def _check_grad_rows(d, stride, pad, scale, residual):
 def _sparse3x3_backward(ctx, d, x, Wc, g, hint, need_x, need_w, need_b):
     """Backward of a 3x3 / stride 1 / pad 1 convolution whose output gradient ``g`` (already through
     ReLU) is zero outside ``hint.rows``: the 1x1 problem (N = rows, C = 9 C_in) on gathered patches."""
-    dev, n = g.device, hint.n
-    patches = torch.empty((n, 9 * d.C), dtype=torch.float32, device=dev)
-    g_rows = torch.empty((n, d.K), dtype=torch.float32, device=dev)
-    _lib.call('mrcnn_sparse3x3_gather', _lib.ptr(x), _lib.ptr(g), _lib.ptr(hint.rows), n,
-              d.N, d.H, d.W, d.C, d.K, _lib.ptr(patches), _lib.ptr(g_rows), _lib.stream_ptr())
+    n = hint.n
+    patches, g_rows = _sparse3x3_gather(d, x, g, hint.rows, n)
     d1 = ConvDesc(n, 1, 1, 9 * d.C, d.K, 1, 1, 1, 0, 1, 1)
     gx = gW = gb = None
     if need_w:
         gW = _wgrad(d1, patches, g_rows, ctx.W_param)
     if need_x:
         gp = _dgrad_raw(d1, g_rows, Wc)          # (rows, 3, 3, C) patch gradients
-        gx = empty_nhwc((d.N, d.C, d.H, d.W), dev)
-        _lib.call('mrcnn_sparse3x3_scatter', _lib.ptr(gp), _lib.ptr(hint.lookup), d.N, d.H, d.W,
-                  d.C, _lib.ptr(gx), _lib.stream_ptr())
+        gx = _sparse3x3_scatter(d, gp, hint.lookup)
     if need_b:
         gb = _bias_grad(ctx.b_param, g_rows, n)
     return gx, gW, gb
@@ -212,26 +139,15 @@ class _Conv2dFn(torch.autograd.Function):
         d = make_desc(x.shape, W.shape, stride, pad)
         if grad_rows is not None:
             _check_grad_rows(d, stride, pad, scale, residual)
-        flags = 0
-        if b is not None:
-            flags |= EPI_BIAS
-        if scale is not None:
-            flags |= EPI_AFFINE
         if residual is not None:
             residual = nhwc(residual, torch.float32, 'conv2d', 'residual')
-            flags |= EPI_RESIDUAL
-        if relu:
-            flags |= EPI_RELU
         ctx.wino = uses_winograd(d) and residual is None and (b is None or scale is None)
         if ctx.wino and _wino_forward('conv2d', records_graph and any(ctx.needs_input_grad)):
             y, _ = wino_fwd(x, Wc, d, scale, shift if scale is not None else b, relu,
                             cache_for=None if records_graph else W,
                             exact_signs=relu and records_graph)
         else:
-            y = empty_nhwc((d.N, d.K, d.P, d.Q), x.device)
-            _lib.call('mrcnn_conv2d_fwd', ctx_desc(d), _lib.ptr(x), _lib.ptr(Wc), _lib.ptr(b),
-                      _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual), _lib.ptr(y), flags,
-                      _lib.ptr(split_ws(x.device)), _lib.stream_ptr())
+            y = _fwd_raw(x, Wc, d, scale, shift, residual, relu, bias=b)
         ctx.d = d
         ctx.relu = relu
         ctx.has_bias = b is not None
@@ -300,17 +216,7 @@ class _StemFn(torch.autograd.Function):
         w784 = _lib.dense(w784, torch.float32, 'stem_conv', 'w784', align=True)
         b, scale, shift = (v if v is None else _lib.dense(v, torch.float32, 'stem_conv', name, align=True)
                            for name, v in (('b', b), ('scale', scale), ('shift', shift)))
-        N, H, W_, four = x4.shape
-        assert four == 4
-        K = w784.shape[0]
-        P, Q = conv_out_size(H, 7, 2, 3), conv_out_size(W_, 7, 2, 3)
-        y = empty_nhwc((N, K, P, Q), x4.device)
-        flags = EPI_RELU | (EPI_BIAS if b is not None else 0) | \
-            (EPI_AFFINE if scale is not None else 0)
-        _lib.call('mrcnn_conv_stem_fwd', _lib.ptr(x4), _lib.ptr(w784), _lib.ptr(b),
-                  _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y), N, H, W_, K, flags,
-                  _lib.stream_ptr())
-        return y
+        return _stem_fwd(x4, w784, b, scale, shift)
 
     @staticmethod
     def backward(ctx, gy):
@@ -343,20 +249,9 @@ class _Deconv2x2Fn(torch.autograd.Function):
         K = W.shape[1]
         if tuple(W.shape) != (C, K, 2, 2):
             raise ValueError('deconv: filter must be (in, out, 2, 2), got %s' % (tuple(W.shape),))
-        y = empty_nhwc((N, K, 2 * H, 2 * Wd), x.device)
-        flags = (EPI_BIAS if b is not None else 0) | (EPI_RELU if relu else 0)
-        if DECONV_FORWARD_FORM and GEMM_ARITHMETIC in SPLIT_GEMM_ARITHMETICS:
-            # forward form on the transposed filter (4K, C): both operands K-contiguous -> the
-            # split-operand kernels; the K-strided form below runs on fp32 MFMA
-            wT = _lib.workspace(4 * C * 4 * K, x.device, 'deconv-wT').view(torch.float32)
-            _lib.call('mrcnn_filter_flip_transpose', _lib.ptr(Wc), _lib.ptr(wT), C, 1, 1, 4 * K, None,
-                      _lib.stream_ptr())
-            _lib.call('mrcnn_deconv2x2s2_fwd_wt', _lib.ptr(x), _lib.ptr(wT), _lib.ptr(b), _lib.ptr(y),
-                      N, H, Wd, C, K, flags, _lib.stream_ptr())
-        else:
-            _lib.call('mrcnn_deconv2x2s2_fwd', _lib.ptr(x), _lib.ptr(Wc), _lib.ptr(b), _lib.ptr(y),
-                      N, H, Wd, C, K, flags, _lib.stream_ptr())
         ctx.dims = (N, H, Wd, C, K)
+        y = _deconv_fwd(x, Wc, b, ctx.dims, relu,
+                        forward_form=DECONV_FORWARD_FORM and GEMM_ARITHMETIC in SPLIT_GEMM_ARITHMETICS)
         ctx.relu = relu
         ctx.W_param, ctx.b_param = W, b_param
         ctx.save_for_backward(x, Wc, y if relu else None)
@@ -372,16 +267,10 @@ class _Deconv2x2Fn(torch.autograd.Function):
         g = epilogue_bwd(gy, y, None) if ctx.relu else gy
         gx = gW = gb = None
         if ctx.needs_input_grad[0]:
-            gx = empty_nhwc((N, C, H, Wd), gy.device)
-            _lib.call('mrcnn_deconv2x2s2_dgrad', _lib.ptr(g), _lib.ptr(Wc), _lib.ptr(gx),
-                      N, H, Wd, C, K, _lib.stream_ptr())
+            gx = _deconv_dgrad(g, Wc, ctx.dims)
         if ctx.needs_input_grad[1]:
             gWt, gW = _grad_target(ctx.W_param)
-            ws = _lib.workspace(
-                _lib.load().mrcnn_deconv2x2s2_wgrad_workspace_bytes(N, H, Wd, C, K),
-                gy.device, 'wgrad')
-            _lib.call('mrcnn_deconv2x2s2_wgrad', _lib.ptr(x), _lib.ptr(g), _lib.ptr(gWt),
-                      N, H, Wd, C, K, _lib.ptr(ws), _lib.stream_ptr())
+            _deconv_wgrad_into(x, g, gWt, ctx.dims)
         if ctx.b_param is not None and ctx.needs_input_grad[2]:
             gb = _bias_grad(ctx.b_param, g, N * 4 * H * Wd)
         return gx, gW, gb, None
@@ -397,93 +286,6 @@ def linear(x, W, b=None):
     x4 = x.reshape(n, -1, 1, 1)
     y = conv2d(x4, W, b)
     return y.reshape(n, W.shape[0])
-
-
-# ---- raw GEMM launches of the fused stage (_StageFn below) -------------------------------------
-
-def _fwd_raw(x, Wc, d, scale, shift, residual, relu):
-    flags = (EPI_AFFINE if scale is not None else 0) | (EPI_RESIDUAL if residual is not None else 0) \
-        | (EPI_RELU if relu else 0)
-    y = empty_nhwc((d.N, d.K, d.P, d.Q), x.device)
-    _lib.call('mrcnn_conv2d_fwd', ctx_desc(d), _lib.ptr(x), _lib.ptr(Wc), None, _lib.ptr(scale),
-              _lib.ptr(shift), _lib.ptr(residual), _lib.ptr(y), flags, _lib.ptr(split_ws(x.device)),
-              _lib.stream_ptr())
-    return y
-
-
-def _flip_transpose(Wc, d, row_scale, out):
-    _lib.call('mrcnn_filter_flip_transpose', _lib.ptr(Wc), _lib.ptr(out), d.K, d.R, d.S, d.C,
-              _lib.ptr(row_scale), _lib.stream_ptr())
-    return out
-
-
-def _stage_transposes(blocks, device):
-    """Flipped / transposed filters of every stride-1 convolution of a stage, built by ONE
-    launch into one buffer.  ``blocks``: one ``_StageBlock`` per bottleneck (the affine scales
-    s3 / s4 are folded into conv3 / conv4).  Returns a dict {'1','2','3','4'} -> flat tensor
-    per block."""
-    jobs = []
-    for bi, b in enumerate(blocks):
-        for key, W, d, sc in (('1', b.W1, b.d1, None), ('2', b.W2, b.d2, None),
-                              ('3', b.W3, b.d3, b.s3), ('4', b.W4, b.d4, b.s4)):
-            if W is not None and _uses_transposed_dgrad(d) and not uses_winograd(d):
-                jobs.append((bi, key, nhwc(W), d, sc))
-    out = [dict() for _ in blocks]
-    if not jobs:
-        return out
-    total = sum(j[2].numel() for j in jobs)
-    buf = torch.empty((total,), dtype=torch.float32, device=device)
-    n = len(jobs)
-    vp, ci = ctypes.c_void_p * n, ctypes.c_int * n
-    w, wT, sc = vp(), vp(), vp()
-    K, R, S, C = ci(), ci(), ci(), ci()
-    off = 0
-    for i, (bi, key, Wc, d, scale) in enumerate(jobs):
-        t = buf[off:off + Wc.numel()]
-        off += Wc.numel()
-        out[bi][key] = t
-        w[i], wT[i] = _lib.addr(Wc, 'w'), _lib.addr(t, 'wT')
-        sc[i] = _lib.addr(scale, 'row_scale')
-        K[i], R[i], S[i], C[i] = d.K, d.R, d.S, d.C
-    _lib.call('mrcnn_filter_flip_transpose_batched', n, w, wT, K, R, S, C, sc, _lib.stream_ptr())
-    return out
-
-
-# Data gradients in forward form on the flipped, transposed filter: stride-1 square filters, and
-# the strided 1x1 / pad 0 ones (res3.a / res4.a conv1 and conv4: dense gather of gy, rows scattered
-# to the strided pixels of a zero-filled gx).  Split-operand kernels; the K-strided form that the
-# other filters take runs on fp32 MFMA.
-def _uses_transposed_dgrad(d):
-    if d.stride == 1:
-        return d.R == d.S
-    return d.R == 1 and d.S == 1 and d.pad == 0
-
-
-def _dgrad_raw(d, g, Wc, res_g=None, res_y=None, out=None, accum=False,
-               out_mask_y=None, out_scale=None, fold_scale=None, wT=None):
-    """gx = dgrad(g) with the fused pieces of include/mrcnn_hip.h "Extended backward entry
-    points": producer-side ``out_mask_y`` / ``out_scale``, shortcut gradient ``res_g`` (masked
-    by ``res_y`` if given).  ``fold_scale`` is a per-output-channel scale of the incoming
-    gradient folded into the transposed filter (forward form only)."""
-    gx = out if out is not None else empty_nhwc((d.N, d.C, d.H, d.W), g.device)
-    if _uses_transposed_dgrad(d):
-        # forward-form dgrad on the flipped, transposed filter; ``wT`` = already built (with
-        # fold_scale applied), else rebuilt here (it moves 2 x the filter bytes)
-        if wT is None:
-            wT = _flip_transpose(Wc, d, fold_scale,
-                                 _lib.workspace(4 * d.K * d.R * d.S * d.C, g.device,
-                                                'wT').view(torch.float32))
-        _lib.call('mrcnn_conv2d_dgrad_wt', ctx_desc(d), _lib.ptr(g), _lib.ptr(wT), _lib.ptr(gx),
-                  EPI_ACCUM if accum else 0, _lib.ptr(res_g), _lib.ptr(res_y), _lib.ptr(out_mask_y),
-                  _lib.ptr(out_scale), _lib.ptr(split_ws(g.device)), _lib.stream_ptr())
-        return gx
-    if fold_scale is not None:
-        raise ValueError('dgrad: fold_scale needs the forward form (stride-1 square filters or '
-                         '1x1 / pad 0), got %dx%d / stride %d / pad %d' % (d.R, d.S, d.stride, d.pad))
-    _lib.call('mrcnn_conv2d_dgrad_ex', ctx_desc(d), _lib.ptr(g), _lib.ptr(Wc), _lib.ptr(gx),
-              EPI_ACCUM if accum else 0, _lib.ptr(res_g), _lib.ptr(res_y), _lib.ptr(out_mask_y),
-              _lib.ptr(out_scale), _lib.ptr(split_ws(g.device)), _lib.stream_ptr())
-    return gx
 
 
 # ---- Winograd F(4x4,3x3) path (csrc/conv_winograd.h) ------------------------------------------
@@ -544,10 +346,6 @@ def _wino_forward(kind, training):
     'conv2d' (F.conv2d) or 'stage' (a fused stage's conv2); ``training``: the call records a graph
     (see WINOGRAD_TRAIN_FORWARD above; without one every routed forward takes it)."""
     return WINOGRAD_TRAIN_FORWARD in (True, kind) or not training
-
-
-def _wino_ws(d, device):
-    return _lib.workspace(_lib.load().mrcnn_conv3x3_wino_workspace_bytes(ctx_desc(d)), device, 'wino')
 
 
 # Transformed filters of inference calls, keyed by the filter tensor: valid while the tensor has
@@ -661,195 +459,30 @@ def _cached_filter_transform(W, Wc, d):
     if hit is not None and hit[0] is W and hit[1] == W._version and hit[3] == W.data_ptr() \
             and hit[2].device == Wc.device:
         return hit[2]
-    u = torch.empty((_lib.load().mrcnn_conv3x3_wino_u_bytes(ctx_desc(d)) // 4,),
-                    dtype=torch.float32, device=Wc.device)
-    _lib.call('mrcnn_conv3x3_wino_filter', ctx_desc(d), _lib.ptr(Wc), _lib.ptr(u), _lib.stream_ptr())
+    u = _wino_filter(d, Wc)
     _wino_u_cache[key] = (W, W._version, u, W.data_ptr())
     return u
 
 
 def wino_fwd(x, Wc, d, scale, shift, relu, keep_v=False, cache_for=None, exact_signs=False):
-    """y = relu?(affine?(conv3x3(x))) — ``scale`` None with a ``shift``: plain bias — and, with
-    ``keep_v``, the transformed input (36, tiles, C) for the weight gradient.  ``cache_for``: the
+    """``_conv_launch._wino_fwd_raw`` (which see) behind the filter cache.  ``cache_for``: the
     parameter tensor ``Wc`` was taken from; its transformed filter is then built once and reused
-    until the parameter is written (inference).  ``exact_signs``: outputs within the Winograd
-    rounding bound of zero are recomputed directly (MRCNN_EPI_EXACT_SIGNS)."""
-    flags = (EPI_AFFINE if scale is not None else (EPI_BIAS if shift is not None else 0)) \
-        | (EPI_RELU if relu else 0) | (EPI_EXACT_SIGNS if exact_signs else 0)
-    y = empty_nhwc((d.N, d.K, d.P, d.Q), x.device)
-    v = None
-    if keep_v:
-        v = torch.empty((_lib.load().mrcnn_conv3x3_wino_v_bytes(ctx_desc(d)) // 4,),
-                        dtype=torch.float32, device=x.device)
+    until the parameter is written (inference)."""
     u = _cached_filter_transform(cache_for, Wc, d) \
         if cache_for is not None and not _WINO_CACHE_BYPASS else None
-    _lib.call('mrcnn_conv3x3_wino_fwd', ctx_desc(d), _lib.ptr(x), _lib.ptr(Wc), _lib.ptr(u),
-              _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y), flags, _lib.ptr(v),
-              _lib.ptr(_wino_ws(d, x.device)), _lib.stream_ptr())
-    return y, v
+    return _wino_fwd_raw(x, Wc, d, scale, shift, relu, keep_v=keep_v, u=u, exact_signs=exact_signs)
 
 
-def wino_dgrad(d, g, Wc, fold_scale=None, out_scale=None, out_mask_y=None):
-    gx = empty_nhwc((d.N, d.C, d.H, d.W), g.device)
-    _lib.call('mrcnn_conv3x3_wino_dgrad', ctx_desc(d), _lib.ptr(g), _lib.ptr(Wc),
-              _lib.ptr(fold_scale), _lib.ptr(gx), _lib.ptr(out_scale), _lib.ptr(out_mask_y),
-              _lib.ptr(_wino_ws(d, g.device)), _lib.stream_ptr())
-    return gx
-
-
-def wino_wgrad_into(d, x, v, g, gW, row_scale=None):
-    """gW = backward-filter from ``g`` and exactly one of ``x`` (raw input) / ``v`` (the
-    transformed input a forward with ``keep_v`` returned)."""
-    _lib.call('mrcnn_conv3x3_wino_wgrad', ctx_desc(d), _lib.ptr(x), _lib.ptr(v), _lib.ptr(g),
-              _lib.ptr(gW), _lib.ptr(row_scale), _lib.ptr(_wino_ws(d, g.device)),
-              _lib.stream_ptr())
-
-
-# ---- weight-gradient side stream -----------------------------------------------------------
-# dgrad and wgrad of a convolution are independent given the incoming gradient.  The wgrad
-# launches of a bottleneck go to a second HIP stream so that their workgroups fill the CUs
-# that the tail round of the concurrently running dgrad leaves idle (and vice versa): with
-# 128x128 tiles and 512 resident workgroups a single kernel wastes up to a round at its end.
-# (The stream itself: streams.wgrad_stream.)
-
-
-# ---- weight gradients deferred into the next step's proposal window --------------------------
-# Between the RPN convolution and the RoI head of a train step the GPU is nearly idle: the
-# proposal kernels (top-k, NMS scan: two workgroups) run, then the host samples the RoIs
-# (~2 ms together).  The RoI head's weights are not read before that window has passed, so the
-# weight gradients of some head layers — and the SGD update of exactly those parameters — can be
-# held back at the end of a step and run INSIDE the next step's window on a second stream, where
-# they cost nothing (optimizers.MomentumSGD.defer_weight_gradients; same gradients, same update,
-# applied before the parameter is read again: results are bit-identical).
-class WgradJob(object):
-    """One weight gradient: ``gW`` = backward-filter of descriptor ``d`` from the input ``x`` and
-    the output gradient ``g`` (rows scaled by ``row_scale`` if given).  ``wino``: on the Winograd
-    route, from the raw input ``x`` or the forward's kept transform ``v`` (the other is None)."""
-
-    def __init__(self, d, x, g, gW, row_scale=None, wino=False, v=None):
-        self.d, self.x, self.g, self.gW = d, x, g, gW
-        self.row_scale, self.wino, self.v = row_scale, wino, v
-
-    def launch(self):
-        """On the current stream (``_lib.workspace`` keys the scratch on it: two streams never
-        share a buffer)."""
-        if self.wino:
-            wino_wgrad_into(self.d, self.x, self.v, self.g, self.gW, self.row_scale)
-        else:
-            _launch_wgrad(self.d, self.x, self.g, self.gW, self.row_scale)
-
-    def tensors(self):
-        """The operands a held-back job keeps alive."""
-        return [t for t in (self.x, self.g, self.gW, self.row_scale, self.v) if t is not None]
-
-
-class DeferQueue(object):
-    """``jobs``: one ``WgradJob`` per held-back weight gradient of the parameters ``params``.
-    MomentumSGD.update hangs one on the parameter arena (``ParamArena.defer``) around backward."""
-
-    def __init__(self, params):
-        self.ids = set(id(p) for p in params)
-        self.jobs = []
-
-    def grad_ptrs(self):
-        """Addresses of the gradient buffers the held-back jobs will write."""
-        return set(j.gW.data_ptr() for j in self.jobs)
-
-
-def run_deferred_wgrads(jobs):
-    """Launch the held-back weight gradients on the current stream (the caller selects it)."""
-    for job in jobs:
-        job.launch()
-
-
-def _launch_wgrad(d, x, g, gW, row_scale=None, ex=True):
-    """The implicit-GEMM weight gradient into the buffer ``gW``, on the current stream.  ``ex``
-    False: the plain entry point (no ``row_scale``)."""
-    ws = _lib.workspace(_lib.load().mrcnn_conv2d_wgrad_workspace_bytes(ctx_desc(d)), g.device, 'wgrad')
-    tail = (_lib.ptr(row_scale), _lib.stream_ptr()) if ex else (_lib.stream_ptr(),)
-    _lib.call('mrcnn_conv2d_wgrad_ex' if ex else 'mrcnn_conv2d_wgrad', ctx_desc(d), _lib.ptr(x),
-              _lib.ptr(g), _lib.ptr(gW), _lib.ptr(ws), *tail)
-
-
-def _wgrad(d, x, g, W, side=None, row_scale=None, wino=False, v=None):
-    """Weight gradient of parameter ``W``; returns the tensor autograd should see for W (None when
-    written in place or held back in the defer queue).  ``wino`` / ``v``: see ``WgradJob``.  With
-    ``side`` (a stream) the launch is queued there, ordered after everything queued so far on the
-    current stream; only arena-backed (direct) gradients may use it."""
-    gW, result = _grad_target(W)
-    job = WgradJob(d, x, g, gW, row_scale, wino, v)
-    direct = result is None
-    # (direct: the arena slot was claimed, so the arena exists and answers the rest of the question)
-    defer = W._arena.defer if direct else None
-    if defer is not None and id(W) in defer.ids:
-        defer.jobs.append(job)
-    elif direct and side is not None:
-        side.wait_stream(torch.cuda.current_stream(g.device))
-        for t in (x, g):
-            t.record_stream(side)
-        with torch.cuda.stream(side):
-            job.launch()
-    else:
-        job.launch()
-    return result
-
-
-# ---------------------------------------------------------------------------------------
-# Whole-stage op: chainer BuildingBlock (BottleneckA + n x BottleneckB) as ONE autograd node.
-# Forward = 3 (4) fused implicit-GEMM launches per block; backward = 3 (4) dgrad + 3 (4) wgrad
-# launches per block and nothing else: every gradient tensor inside the stage is written ALREADY
-# multiplied by the ReLU mask (and affine scale) of the conv that consumes it — in the epilogue
-# of the dgrad that produces it — and the identity-shortcut gradient is added there too, so none
-# of the stage's backward GEMMs stages a mask: they all run the 168-register kernels, three
-# workgroups per CU.  Only the gradient entering the stage from autograd takes one elementwise
-# masking pass.
-# ---------------------------------------------------------------------------------------
+# ---- knobs of the fused stage (functions/stage.py reads them from here) --------------------------
 # Weight gradients of the backbone's small-M layers (<= 40 000 output pixels: res3 / res4) are
 # queued on a second HIP stream: such a launch has only 2-4 workgroups per CU, so the wgrad and
 # the next dgrad share the GPU (same-box A/B: 54.4 -> 54.0 ms per step).  For the large res5
 # launches the same trick measured no overlap (round 1: 68.9 vs 68.1 ms per step).
 SMALL_WGRAD_MAX_PIXELS = int(_os.environ.get('MRCNN_SIDE_WGRAD_MAX_PIXELS', 40000))
 
-
-# ---- pooling AFTER res5.a's 1x1 projections ("projected pooling") --------------------------------
-# The RoI head applies ROIAlign to the C4 feature map and then res5 (models/mask_rcnn_resnet.py:
-# 168-176), whose first block reads the pooled map only through two 1x1 convolutions (conv1 and the
-# shortcut conv4, each followed by AffineChannel2D).  ROIAlign is linear over positions per channel
-# with no constant term, a bias-free 1x1 convolution is linear over channels per position: they
-# commute exactly,
-#     bn(conv1x1(roi_align(x))) == bn(roi_align(conv1x1(x))),
-# so both projections run on the N*H*W map pixels (2 x 51 x 84 = 8 568 at the C2 shape) instead of
-# the R*7*7 pooled ones (50 176), and ROIAlign pools their 512- / 2048-channel outputs with the
-# affine (+ ReLU) in its epilogue.  Backward likewise: ROIAlign's adjoint first, then data and
-# weight gradient of the projections on the map.  Same sums in a different order (fp32 rounding
-# only); PROJECTED_POOLING = False restores the reference order.
+# Pooling AFTER res5.a's 1x1 projections ("projected pooling", described in functions/stage.py);
+# False restores the reference order.
 PROJECTED_POOLING = _os.environ.get('MRCNN_PROJECTED_POOLING', '1') != '0'
-
-
-class RoiSpec(object):
-    """What ``building_block(..., roi=)`` needs to pool inside the stage node: ``rois`` (R, 5) float32
-    device rows (batch, x1, y1, x2, y2), the pooled size ``outh`` x ``outw`` of the FULL bin grid,
-    ``bin_stride`` (the stride of block a's 1x1 convolutions: only those bins are produced) and the
-    optional processing ``order`` (functions.roi_align_2d.spatial_order)."""
-
-    def __init__(self, rois, outh, outw, spatial_scale, bin_stride=1, order=None, sampling_ratio=0,
-                 proj=None):
-        # ``proj`` (inference only): the two projections of the map, ``projected_map(...)``, when the
-        # caller pools several RoI sets from one map (MaskRCNN.predict_prepared: one head call per image)
-        self.proj = proj
-        _lib.require_device(rois, order)
-        self.rois = _lib.dense(rois, torch.float32, 'RoiSpec', 'rois')
-        if order is not None:
-            order = _lib.dense(order, torch.int32, 'RoiSpec', 'order')
-        self.outh, self.outw = int(outh), int(outw)
-        self.spatial_scale = float(spatial_scale)
-        self.bin_stride = int(bin_stride)
-        self.order = order
-        self.sampling_ratio = int(sampling_ratio)
-
-    @property
-    def out_hw(self):
-        return out_size(self.outh, self.bin_stride), out_size(self.outw, self.bin_stride)
 
 
 # The projections of one feature map, kept while the SAME map is pooled again without a graph
@@ -870,306 +503,8 @@ def projected_map(x, W1, W4):
         return hit[2], hit[3]
     d1 = make_desc(x.shape, W1.shape, 1, 0)
     d4 = make_desc(x.shape, W4.shape, 1, 0)
-    z1 = _fwd_raw(x, nhwc(W1, torch.float32, 'projected_map', 'W1'), d1, None, None, None, False)
-    z4 = _fwd_raw(x, nhwc(W4, torch.float32, 'projected_map', 'W4'), d4, None, None, None, False)
+    z1 = _fwd_raw(x, nhwc(W1, torch.float32, 'projected_map', 'W1'), d1)
+    z4 = _fwd_raw(x, nhwc(W4, torch.float32, 'projected_map', 'W4'), d4)
     _proj_cache['entry'] = (key, x, z1, z4)
     return z1, z4
 
-
-def _roi_pool_affine(z, roi, scale, shift, relu):
-    """relu?(roi_align(z) * scale + shift) for an NHWC map ``z`` (N, C, H, W logical)."""
-    N, C, H, W = z.shape
-    R = roi.rois.shape[0]
-    oh, ow = roi.out_hw
-    y = empty_nhwc((R, C, oh, ow), z.device)
-    order = roi.order if R > 0 else None
-    _lib.call('mrcnn_roi_align_fwd_affine', _lib.ptr(z), _lib.ptr(roi.rois), _lib.ptr(y), N, H, W, C, R,
-              roi.outh, roi.outw, roi.bin_stride, roi.spatial_scale, roi.sampling_ratio,
-              _lib.ptr(order) if order is not None else None, _lib.ptr(scale), _lib.ptr(shift),
-              1 if relu else 0, _lib.stream_ptr())
-    return y
-
-
-def _roi_pool_bwd(g, roi, map_shape):
-    """ROIAlign's adjoint: g (R, C, oh, ow) -> (N, C, H, W), pixel-owner form (no atomics)."""
-    return roi_align_backward(g, roi.rois, map_shape, roi.outh, roi.outw, roi.bin_stride,
-                              roi.spatial_scale, roi.sampling_ratio)
-
-
-def _pool_bwd_alone(side, device):
-    """The compute stream waits for the weight-gradient side stream before a pixel-owner ROIAlign
-    backward inside a stage.  Round 6 finding (tests/test_gpu_model.py::test_training_is_bit_
-    reproducible_run_to_run on the small test model, whose RoI head is small enough to use the side
-    stream): with the weight-gradient GEMM of the SAME block running on the side stream — it reads the
-    gradient tensor the ROIAlign backward reads, written by the data-gradient GEMM just before — a
-    launch now and then lost ONE list entry's contribution in ONE component of 16 lanes (a handful
-    of gx elements, different from run to run; captured and analysed on the host: inputs and tables
-    identical, the sum short of exactly one term).  The same two kernels side by side in isolation
-    (900 launches, the captured tensors included) never did; neither kernel uses scratch; four
-    plain v_fma_f32 instead of the packed FMAs change nothing.  Two measures, either of which removes
-    it on its own (each 8 of 8 runs clean): the pooled backward of a block is queued BEFORE that
-    block's weight gradients go to the side stream (no second reader of its input is in flight), and
-    the streams are serialised here.  Costs nothing at full size (the head's weight gradients do not
-    use the side stream there), ~20 us in the small configurations that do.  Root cause not found."""
-    if side is not None:
-        torch.cuda.current_stream(device).wait_stream(side)
-
-
-class _StageBlock(object):
-    """One bottleneck of a stage node, built once by ``_StageFn.forward``: the filters W1..W4 with
-    their affine vectors s* / b* (conv4's are None without a projection shortcut), the
-    descriptors d1..d4 (d4 None likewise) and ``i1..i4``, the index of each filter among
-    ``forward``'s inputs — that of its flag in ``needs_input_grad`` and of its gradient in what
-    ``backward`` returns."""
-
-    def __init__(self, params, at, has_proj):
-        """From forward's flat ``params``, this block's starting at ``params[at]``."""
-        self.n_params = 12 if has_proj else 9
-        (self.W1, self.s1, self.b1, self.W2, self.s2, self.b2,
-         self.W3, self.s3, self.b3) = params[at:at + 9]
-        self.W4, self.s4, self.b4 = params[at + 9:at + 12] if has_proj else (None, None, None)
-        for name in ('W1', 'W2', 'W3', 'W4', 's1', 'b1', 's2', 'b2', 's3', 'b3', 's4', 'b4'):
-            t = getattr(self, name)
-            if t is None:
-                continue
-            if t.dtype != torch.float32:
-                raise TypeError('building_block: %s must be %s, got %s' % (name, torch.float32, t.dtype))
-            if name[0] != 'W':      # (the filters go through nhwc() where they are read)
-                setattr(self, name, _lib.dense(t, torch.float32, 'building_block', name, align=True))
-        w1 = _StageFn.FIXED_INPUTS + at
-        self.i1, self.i2, self.i3, self.i4 = w1, w1 + 3, w1 + 6, w1 + 9
-        self.d1 = self.d2 = self.d3 = self.d4 = None
-
-
-# The activations of one bottleneck that backward reads: its input and its three ReLU outputs.
-_StageActs = collections.namedtuple('_StageActs', 'x h1 h2 y')
-
-
-def _save_stage(ctx, x, acts, wino_v):
-    """Saved tensors of a stage node: the input, (h1, h2, y) per block, then the kept Winograd
-    input transforms (``wino_v[i]`` of block i, or None)."""
-    ctx.wino_slots = [i for i, v in enumerate(wino_v) if v is not None]
-    ctx.save_for_backward(x, *([t for a in acts for t in a] + [wino_v[i] for i in ctx.wino_slots]))
-
-
-def _saved_stage(ctx):
-    """Inverse of ``_save_stage``: ([_StageActs per block], {block index: kept transform})."""
-    saved = ctx.saved_tensors
-    acts, xin = [], saved[0]
-    for i in range(len(ctx.blocks)):
-        acts.append(_StageActs(xin, *saved[1 + 3 * i:4 + 3 * i]))
-        xin = acts[-1].y
-    return acts, dict(zip(ctx.wino_slots, saved[1 + 3 * len(acts):]))
-
-
-class _StageFn(torch.autograd.Function):
-
-    # inputs of forward in front of *params (x .. records_graph): a change of the signature below
-    # changes this number, and nothing else
-    FIXED_INPUTS = 8
-
-    @staticmethod
-    def forward(ctx, x, strides, proj, poll, tail_rows, tail_slot, roi, records_graph, *params):
-        """``roi`` (a ``RoiSpec`` or None): with it ``x`` is the FEATURE MAP and block 0 (which must
-        have a projection shortcut) runs its two 1x1 convolutions on the map and pools their outputs
-        (projected pooling, see above) — the stage then equals ``stage(roi_align(x, roi))``.
-        ``strides[i]`` / ``proj[i]``: conv1(/conv4) stride and has-projection flag of block
-        i; ``poll``: optional callable invoked during backward at the stage's entry and after
-        every block's weight gradients have been queued (parallel.DataParallelGradSync launches
-        the gradient buckets that are complete); ``tail_rows``: None, or an int64 index tensor —
-        the node then returns ``(average_pooling(y) (N,C,1,1), y[tail_rows])`` instead of the
-        stage output y (the RoI head's two consumers of res5, models/mask_rcnn_resnet.py:186-195),
-        and its backward forms the gradient entering the last block from both in ONE pass,
-        ReLU mask included (``mrcnn_head_tail_bwd``); ``tail_slot``: the int32 table row -> position
-        among ``tail_rows`` (-1 elsewhere), None = built here; ``records_graph``: torch.is_grad_enabled()
-        at the call (in here grad mode is always off and ctx.needs_input_grad reports the inputs'
-        requires_grad flags even under torch.no_grad()); ``params``: per block
-        W1,s1,b1,W2,s2,b2,W3,s3,b3 (+ W4,s4,b4 when proj[i])."""
-        assert len(ctx.needs_input_grad) == _StageFn.FIXED_INPUTS + len(params)
-        _lib.require_device(x, tail_rows, tail_slot, *params)
-        x = nhwc(x, torch.float32, 'building_block')
-        if tail_rows is not None and tail_rows.dtype != torch.int64:
-            raise TypeError('building_block: tail_rows must be %s, got %s' % (torch.int64, tail_rows.dtype))
-        if tail_slot is not None:
-            tail_slot = _lib.dense(tail_slot, torch.int32, 'building_block', 'tail_slot')
-        ng = ctx.needs_input_grad
-        training = records_graph and any(ng)
-        blocks, at = [], 0
-        for pj in proj:
-            blocks.append(_StageBlock(params, at, pj))
-            at += blocks[-1].n_params
-        if roi is not None:
-            if roi.proj is not None and training:
-                raise ValueError('RoiSpec(proj=) is for graph-free calls (the projections would be '
-                                 'outside the recorded graph)')
-            a = blocks[0]
-            if not (a.W4 is not None and strides[0] == 1 and a.W1.shape[2] == 1 and a.W4.shape[2] == 1):
-                raise ValueError('projected pooling needs a first block with 1x1 conv1 / conv4 at stride 1 '
-                                 '(the RoI bins of the stride are selected by RoiSpec.bin_stride)')
-        acts, wino_v = [], []
-        h = x
-        for b, stride in zip(blocks, strides):
-            pooled_here = roi is not None and b is blocks[0]
-            b.d1 = make_desc(h.shape, b.W1.shape, stride, 0)
-            if pooled_here:
-                # conv1 on the map, then pooled with bn1 + ReLU in ROIAlign's epilogue
-                z1 = roi.proj[0] if roi.proj is not None else _fwd_raw(h, nhwc(b.W1), b.d1, None, None, None, False)
-                h1 = _roi_pool_affine(z1, roi, b.s1, b.b1, True)
-                del z1
-            else:
-                h1 = _fwd_raw(h, nhwc(b.W1), b.d1, b.s1, b.b1, None, True)
-            b.d2 = make_desc(h1.shape, b.W2.shape, 1, 1)
-            v2 = None
-            if uses_winograd(b.d2) and _wino_forward('stage', training):
-                # (with a weight gradient to come, the transformed input is kept for it)
-                h2, v2 = wino_fwd(h1, nhwc(b.W2), b.d2, b.s2, b.b2, True,
-                                  keep_v=training and bool(ng[b.i2]),
-                                  cache_for=None if training else b.W2,
-                                  exact_signs=training)
-            else:
-                h2 = _fwd_raw(h1, nhwc(b.W2), b.d2, b.s2, b.b2, None, True)
-            if b.W4 is None:
-                shortcut = h
-            else:
-                b.d4 = make_desc(h.shape, b.W4.shape, stride, 0)
-                if pooled_here:
-                    z4 = roi.proj[1] if roi.proj is not None else _fwd_raw(h, nhwc(b.W4), b.d4, None, None, None, False)
-                    shortcut = _roi_pool_affine(z4, roi, b.s4, b.b4, False)
-                    del z4
-                else:
-                    shortcut = _fwd_raw(h, nhwc(b.W4), b.d4, b.s4, b.b4, None, False)
-            b.d3 = make_desc(h2.shape, b.W3.shape, 1, 0)
-            y = _fwd_raw(h2, nhwc(b.W3), b.d3, b.s3, b.b3, shortcut, True)
-            if RELU_TAP is not None:
-                RELU_TAP.append(('block', (h1, h2, y)))
-            acts.append((h1, h2, y))
-            wino_v.append(v2)
-            h = y
-        ctx.blocks = blocks
-        ctx.poll = poll
-        ctx.roi = roi
-        _save_stage(ctx, x, acts, wino_v)
-        ctx.tail = tail_rows is not None
-        if ctx.tail:
-            # the two consumers of the stage output, produced here so that backward receives
-            # their gradients separately (h itself is not an output of the node)
-            R_, C_ = h.shape[0], h.shape[1]
-            pooled = torch.empty((R_, C_), dtype=torch.float32, device=h.device)
-            _lib.call('mrcnn_avgpool_fwd', _lib.ptr(h), _lib.ptr(pooled), R_, h.shape[2] * h.shape[3],
-                      C_, _lib.stream_ptr())
-            sub = h.permute(0, 2, 3, 1).index_select(0, tail_rows).permute(0, 3, 1, 2)
-            if tail_slot is None:
-                tail_slot = torch.full((R_,), -1, dtype=torch.int32, device=h.device)
-                tail_slot[tail_rows] = torch.arange(tail_rows.numel(), dtype=torch.int32, device=h.device)
-            ctx.tail_slot = tail_slot
-        if ctx.tail:
-            return pooled.reshape(R_, C_, 1, 1), sub
-        return h
-
-    @staticmethod
-    def backward(ctx, gy, g_rows=None):
-        acts, wino_v = _saved_stage(ctx)
-        blocks = ctx.blocks
-        ng = ctx.needs_input_grad
-        grads = [None] * len(ng)
-        poll = ctx.poll
-        if poll is not None:
-            poll()                 # everything upstream of this stage has queued its gradients
-        if not ctx.tail:
-            gy = nhwc(gy)
-        # small-M layers (backbone stages) leave CUs idle: their weight gradients go to a
-        # second stream so that they can share the GPU with the next dgrad
-        d_top = blocks[-1].d3
-        dev_ = gy.device if gy is not None else g_rows.device
-        side = wgrad_stream(dev_) if d_top.N * d_top.P * d_top.Q <= SMALL_WGRAD_MAX_PIXELS else None
-        # all the stage's filter transposes in one launch (built during the forward on the side
-        # stream instead, they measured no faster: 53.2 vs 53.0 ms per step)
-        stage_wT = _stage_transposes(blocks, dev_)
-        # gm: gradient w.r.t. the block output, already through that output's ReLU
-        y_top = acts[-1].y
-        if ctx.tail:
-            R_, C_, Hh, Ww = y_top.shape
-            if gy is None:
-                gy = torch.zeros((R_, C_), dtype=torch.float32, device=dev_)
-            gp = _lib.dense(gy.reshape(R_, C_), torch.float32, 'building_block', 'the pooled gradient',
-                            align=True)
-            gr = nhwc(g_rows) if g_rows is not None else None
-            gm = empty_nhwc((R_, C_, Hh, Ww), dev_)
-            _lib.call('mrcnn_head_tail_bwd', _lib.ptr(gp), _lib.ptr(gr),
-                      _lib.ptr(ctx.tail_slot) if gr is not None else None, _lib.ptr(y_top),
-                      _lib.ptr(gm), R_, Hh * Ww, C_, _lib.stream_ptr())
-        else:
-            gm = epilogue_bwd(gy, y_top, None)
-        for i in range(len(blocks) - 1, -1, -1):
-            b, wT = blocks[i], stage_wT[i]
-            x, h1, h2, _ = acts[i]
-            first = i == 0
-            pooled_here = first and ctx.roi is not None
-            need_w4 = b.W4 is not None and ng[b.i4]
-            # what the gradient leaving this block must be masked with: the previous block's
-            # output ReLU (= this block's input); the stage input belongs to someone else
-            xm = None if first else x
-            # the gradient the shortcut's conv4 reads: the block output's, or with pooling ...
-            g4 = gm
-            if pooled_here and (need_w4 or ng[0]):
-                # ... that gradient back on the map (ROIAlign's adjoint commutes with the
-                # per-channel scale s4, which stays folded into conv4's filter / gradient rows).
-                # Queued BEFORE this block's weight gradients go to the side stream, and with the side
-                # stream drained: see _pool_bwd_alone.
-                _pool_bwd_alone(side, dev_)
-                g4 = _roi_pool_bwd(gm, ctx.roi, (x.shape[0], b.d4.K, x.shape[2], x.shape[3]))
-            if ng[b.i3]:
-                grads[b.i3] = _wgrad(b.d3, h2, gm, b.W3, side, row_scale=b.s3)
-            if need_w4:
-                grads[b.i4] = _wgrad(b.d4, x, g4, b.W4, side, row_scale=b.s4)
-            gh2 = _dgrad_raw(b.d3, gm, nhwc(b.W3), fold_scale=b.s3, out_mask_y=h2, out_scale=b.s2,
-                             wT=wT.get('3'))
-            if uses_winograd(b.d2):
-                if ng[b.i2]:
-                    v2 = wino_v.get(i)
-                    grads[b.i2] = _wgrad(b.d2, h1 if v2 is None else None, gh2, b.W2, wino=True, v=v2)
-                gh1 = wino_dgrad(b.d2, gh2, nhwc(b.W2), out_scale=b.s1, out_mask_y=h1)
-            else:
-                if ng[b.i2]:
-                    grads[b.i2] = _wgrad(b.d2, h1, gh2, b.W2, side)
-                gh1 = _dgrad_raw(b.d2, gh2, nhwc(b.W2), out_mask_y=h1, out_scale=b.s1, wT=wT.get('2'))
-            if pooled_here and (ng[b.i1] or ng[0]):
-                _pool_bwd_alone(side, dev_)
-                gh1 = _roi_pool_bwd(gh1, ctx.roi, (x.shape[0], b.d1.K, x.shape[2], x.shape[3]))
-            if ng[b.i1]:
-                grads[b.i1] = _wgrad(b.d1, x, gh1, b.W1, side)
-            if poll is not None:
-                poll()             # this block's weight gradients are queued
-            if first and not ng[0]:
-                break
-            if b.W4 is None:
-                gm = _dgrad_raw(b.d1, gh1, nhwc(b.W1), res_g=gm, out_mask_y=xm, wT=wT.get('1'))
-                continue
-            # projection shortcut: both data gradients into one buffer; the input's ReLU mask is
-            # fused into the second where conv1 has stride 1, else applied by a pass of its own
-            fused = b.d1.stride == 1
-            gx = _dgrad_raw(b.d1, gh1, nhwc(b.W1), wT=wT.get('1'))
-            gm = _dgrad_raw(b.d4, g4, nhwc(b.W4), fold_scale=b.s4, out=gx, accum=True,
-                            out_mask_y=xm if fused else None, wT=wT.get('4'))
-            if xm is not None and not fused:
-                gm = epilogue_bwd(gm, xm, None)
-        if ng[0]:
-            grads[0] = gm
-        return tuple(grads)
-
-
-def building_block(x, blocks, first_stride=None, poll=None, tail_rows=None, roi=None, tail_slot=None):
-    """A chain of Bottleneck links (chainer BuildingBlock) as one fused autograd node.  With
-    ``tail_rows`` (int64 row indices) it returns ``(average_pooling_2d(y, map size), y[tail_rows])``
-    instead of y (``tail_slot``: their optional slot table) — see _StageFn.forward.  With ``roi``
-    (a ``RoiSpec``) ``x`` is the feature map and the result is ``building_block(roi_align(x, roi), ...)`` (projected pooling)."""
-    strides, proj, params = [], [], []
-    for i, b in enumerate(blocks):
-        strides.append(b.conv1.stride if not (i == 0 and first_stride is not None) else first_stride)
-        proj.append(bool(b.projection))
-        params += [b.conv1.W, b.bn1.W, b.bn1.b, b.conv2.W, b.bn2.W, b.bn2.b,
-                   b.conv3.W, b.bn3.W, b.bn3.b]
-        if b.projection:
-            params += [b.conv4.W, b.bn4.W, b.bn4.b]
-    return _StageFn.apply(x, tuple(strides), tuple(proj), poll, tail_rows, tail_slot, roi,
-                          torch.is_grad_enabled(), *params)

@@ -103,7 +103,7 @@ class ResNetRoIHead(torch.nn.Module):
         self.roi_size = roi_size
         self.spatial_scale = spatial_scale
         self.pooling_func = pooling_func
-        # Pool BEHIND res5.a's 1x1 projections instead of in front of them (functions/conv.py
+        # Pool BEHIND res5.a's 1x1 projections instead of in front of them (functions/stage.py
         # "projected pooling": the same values up to fp32 rounding, the two projections on the map's
         # pixels instead of the pooled ones).  None = follow functions.conv.PROJECTED_POOLING.
         self.projected_pooling = None

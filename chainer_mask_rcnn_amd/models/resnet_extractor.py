@@ -65,7 +65,7 @@ class Bottleneck(torch.nn.Module):
             self.bn4 = AffineChannel2D(out_ch)
 
     def forward(self, x, stride=None):
-        """The block as a one-block fused stage (functions/conv.py:_StageFn)."""
+        """The block as a one-block fused stage (functions/stage.py:_StageFn)."""
         return F.building_block(x, [self], first_stride=stride)
 
     def forward_unfused(self, x):
@@ -79,7 +79,7 @@ class Bottleneck(torch.nn.Module):
 
 class BuildingBlock(torch.nn.Module):
     """chainer BuildingBlock(n_layer, in, mid, out, stride): children a, b1 .. b{n-1}, run as
-    one autograd node whose backward GEMMs need no mask staging (functions/conv.py:_StageFn)."""
+    one autograd node whose backward GEMMs need no mask staging (functions/stage.py:_StageFn)."""
 
     def __init__(self, n_layer, in_ch, mid_ch, out_ch, stride):
         super(BuildingBlock, self).__init__()
@@ -98,7 +98,7 @@ class BuildingBlock(torch.nn.Module):
         stride-2 subsampling has already been done by the pooling op).  ``tail_rows``: return
         ``(average_pooling_2d(y), y[tail_rows])`` instead of y (``tail_slot``: see
         ``F.building_block``).  ``roi`` (a ``functions.conv.RoiSpec``): ``x`` is the feature map and the
-        stage pools inside block ``a``, behind its 1x1 projections (functions/conv.py "projected pooling")."""
+        stage pools inside block ``a``, behind its 1x1 projections (functions/stage.py "projected pooling")."""
         return F.building_block(x, [getattr(self, n) for n in self._names], first_stride, poll=self.grad_poll,
                                 tail_rows=tail_rows, roi=roi, tail_slot=tail_slot)
 

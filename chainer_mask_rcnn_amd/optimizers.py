@@ -111,7 +111,8 @@ class ParamArena(object):
         self.momenta = torch.zeros(total, dtype=torch.float32, device=dev)
         self.epoch = 1            # bumped by every optimizer step
         # None, or the conv.DeferQueue of the backward in progress: a weight gradient that claimed
-        # its slot and whose parameter the queue names is held back instead of launched (conv._wgrad)
+        # its slot and whose parameter the queue names is held back instead of launched
+        # (functions/_wgrad.py: _wgrad)
         self.defer = None
         with torch.no_grad():
             for i, (p, off) in enumerate(zip(self.params, offs)):
@@ -359,8 +360,8 @@ class MomentumSGD(object):
             # Data parallel: a deferred parameter is in NO in-backward bucket (the bucket plan
             # leaves it to reduce_deferred).  If its weight gradient was not actually held back
             # this step (the in-place claim failed: gradient view dropped, parameter used twice,
-            # a route that bypasses conv._wgrad), nothing would all-reduce it and the ranks would
-            # drift apart silently — fail loudly instead.
+            # a route that bypasses functions/_wgrad.py: _wgrad), nothing would all-reduce it and the
+            # ranks would drift apart silently — fail loudly instead.
             queued = deferred.grad_ptrs()
             missing = [i for i, p in enumerate(a.params)
                        if id(p) in deferred.ids and p._grad_epoch == a.epoch

@@ -712,7 +712,7 @@ def policy_cases():
 
 # ---- every GEMM call of the lists -------------------------------------------------------------------
 def uses_transposed_dgrad(d):
-    """functions/conv.py:_uses_transposed_dgrad."""
+    """functions/_conv_launch.py:_uses_transposed_dgrad."""
     if d.stride == 1:
         return d.R == d.S
     return d.R == 1 and d.S == 1 and d.pad == 0

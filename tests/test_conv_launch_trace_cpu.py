@@ -1,4 +1,5 @@
-"""Launch trace of functions/conv.py without a device.
+"""Launch trace of the convolution host code (functions/conv.py, functions/stage.py and the two
+modules below them) without a device.
 
 The host side of the convolutions decides WHICH entry point of libmrcnn_hip.so runs with WHICH
 arguments: the routes (implicit GEMM / Winograd / row-sparse / transposed-filter data gradient),
@@ -199,6 +200,22 @@ def _head_no_grad(rec, mp):
         F.building_block(x, blocks, first_stride=1, tail_rows=tail, roi=spec)
 
 
+def _head_pooled_first(rec, mp, tail):
+    """The same stage with ``roi=None``: its input is the already pooled map (the reference order)."""
+    blocks, _, _, tail_rows = _head_pieces(rec, mp)
+    x = _input(rec, (5, 32, 3, 3), True)
+    if tail:
+        pooled, sub = F.building_block(x, blocks, first_stride=1, tail_rows=tail_rows)
+        assert tuple(pooled.shape) == (5, 64, 1, 1) and tuple(sub.shape) == (3, 64, 3, 3)
+        out = pooled.sum() + sub.sum()
+    else:
+        y = F.building_block(x, blocks, first_stride=1)
+        assert tuple(y.shape) == (5, 64, 3, 3)
+        out = y.sum()
+    rec.mark('backward')
+    out.backward()
+
+
 def _head_arena(rec, mp):
     """Arena-backed parameters: gradients written in place; some held back in a DeferQueue."""
     blocks, rois, order, tail = _head_pieces(rec, mp)
@@ -225,19 +242,34 @@ def _conv_layer(rec, in_ch, out_ch, k):
     return W, b
 
 
-def _conv2d_sparse(rec, mp, filled):
+def _stem(rec, mp):
+    """The frozen stem: forward only, bias + affine + ReLU."""
+    torch.manual_seed(0)
+    x4 = rec.name('x4', torch.randn(2, 6, 8, 4))
+    w784 = rec.name('w784', torch.randn(8, 7, 8, 4))
+    b, scale, shift = (rec.name(n, torch.randn(8)) for n in ('b', 'scale', 'shift'))
+    y = F.stem_conv(x4, w784, b, scale, shift)
+    assert tuple(y.shape) == (2, 8, 3, 4)
+    rec.mark('no affine')
+    F.stem_conv(x4, w784, b, None, None)
+
+
+def _conv2d_sparse(rec, mp, filled, knob=True, map_size=2 * 5 * 6):
+    """``map_size``: what the hint's tables describe (the node's own map has 2 x 5 x 6 positions)."""
+    mp.setattr(C, 'SPARSE_CONV_BACKWARD', knob)
     W, b = _conv_layer(rec, 8, 16, 3)
     x = _input(rec, (2, 8, 5, 6), True)
     hint = C.SparseRows()
     y = F.conv2d(x, W, b, stride=1, pad=1, relu=True, grad_rows=hint)
     if filled:
         import numpy as np
-        rows, lookup = C.SparseRows.host_tables([3, 17, 40, 41], 2 * 5 * 6)
+        rows, lookup = C.SparseRows.host_tables([3, 17, 40, 41], map_size)
         hint.set(rec.name('rows', torch.from_numpy(np.ascontiguousarray(rows))),
                  rec.name('lookup', torch.from_numpy(np.ascontiguousarray(lookup))), len(rows))
     rec.mark('backward')
     y.backward(torch.ones_like(y))
-    assert hint.n == 0 or not filled
+    # (a hint the backward did not use, for either reason, is left as it was)
+    assert hint.n == (0 if knob and map_size == 2 * 5 * 6 else 4) or not filled
 
 
 def _conv2d_affine_residual(rec, mp):
@@ -263,6 +295,39 @@ def _conv2d_winograd(rec, mp, train_forward):
     rec.mark('no_grad')
     with torch.no_grad():
         F.conv2d(x, W, b, stride=1, pad=1, relu=True)
+        F.conv2d(x, W, b, stride=1, pad=1, relu=True)
+
+
+def _conv2d_winograd_no_filter_cache(rec, mp):
+    """Graph-free calls inside ``no_filter_cache()``: the filter is transformed per call, by the
+    forward launch itself, and nothing is cached."""
+    mp.setattr(C, 'WINOGRAD_MIN_CHANNELS', 8)
+    mp.setattr(C, 'WINOGRAD_MIN_WORK', 0)
+    W, b = _conv_layer(rec, 8, 16, 3)
+    x = _input(rec, (2, 8, 5, 6), False)
+    with torch.no_grad():
+        with C.no_filter_cache():
+            F.conv2d(x, W, b, stride=1, pad=1, relu=True)
+            F.conv2d(x, W, b, stride=1, pad=1, relu=True)
+            assert not C._wino_u_cache
+        rec.mark('outside: cached')
+        F.conv2d(x, W, b, stride=1, pad=1, relu=True)
+        assert len(C._wino_u_cache) == 1
+
+
+def _conv2d_winograd_bf16x1(rec, mp):
+    """A Winograd-sized layer under 'bf16x1' takes the direct kernel, forward and backward."""
+    mp.setattr(C, 'WINOGRAD_MIN_CHANNELS', 8)
+    mp.setattr(C, 'WINOGRAD_MIN_WORK', 0)
+    mp.setattr(C, 'GEMM_ARITHMETIC', 'bf16x1')
+    W, b = _conv_layer(rec, 8, 16, 3)
+    x = _input(rec, (2, 8, 5, 6), True)
+    assert not C.uses_winograd(C.make_desc(x.shape, W.shape, 1, 1))
+    y = F.conv2d(x, W, b, stride=1, pad=1, relu=True)
+    rec.mark('backward')
+    y.backward(torch.ones_like(y))
+    rec.mark('no_grad')
+    with torch.no_grad():
         F.conv2d(x, W, b, stride=1, pad=1, relu=True)
 
 
@@ -329,6 +394,14 @@ CASES = [
     ('deconv2x2s2 fp32', lambda r, m: _deconv(r, m, 'fp32')),
     ('deconv2x2s2 arena', lambda r, m: _deconv(r, m, 'split_bf16x3', arena=True)),
     ('linear', _linear),
+    ('stem_conv', _stem),
+    ('head stage, roi=None, tail_rows', lambda r, m: _head_pooled_first(r, m, True)),
+    ('head stage, roi=None', lambda r, m: _head_pooled_first(r, m, False)),
+    ('conv2d winograd, no_filter_cache', _conv2d_winograd_no_filter_cache),
+    ('conv2d winograd-sized, bf16x1: direct kernel', _conv2d_winograd_bf16x1),
+    ('conv2d bias relu, sparse hint filled, SPARSE_CONV_BACKWARD=False',
+     lambda r, m: _conv2d_sparse(r, m, True, knob=False)),
+    ('conv2d bias relu, sparse hint for another map size', lambda r, m: _conv2d_sparse(r, m, True, map_size=2 * 5 * 7)),
 ]
 
 

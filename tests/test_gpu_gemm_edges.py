@@ -7,10 +7,13 @@ launch_ref.LaunchChecker under the suite's convolution bound |got - ref| <= 1e-4
 tail mask does not fault: it reads a neighbour row or drops a term, and only a value comparison
 finds it.  Two more things are held:
 
-* what is never written.  Outputs that functions/conv.py allocates are prefilled with a NaN (an
-  element the kernel skips would otherwise show the allocator's previous, identical result); outputs
-  of the direct C-ABI calls live inside a larger NaN-prefilled buffer whose 256-byte guard bands
-  must come back bit-identical (gemm_edge_cases.Guarded).
+* what is never written.  Outputs that the host code allocates (functions/_conv_launch.py, and the
+  fresh gradient tensors of functions/_wgrad.py) are prefilled with a NaN (an element the kernel
+  skips would otherwise show the allocator's previous, identical result); outputs of the direct
+  C-ABI calls live inside a larger NaN-prefilled buffer whose 256-byte guard bands must come back
+  bit-identical (gemm_edge_cases.Guarded).  The harness proves that the prefill is live: a ``case``
+  during which the NaN allocator was never called fails, unless it declares that all its outputs
+  are buffers of its own (``own_outputs=True``) — and then the allocator must not have been called.
 * the launch policy.  Around every case the profiler counts launches per kind; the GEMM counts must
   equal what gemm_edge_cases.route() predicts for the calls the case made.  That holds the Python
   restatement of the launch policy (csrc/conv_gemm_plan.h: plan_gemm / plan_wgrad) to what the
@@ -35,6 +38,7 @@ import launch_ref as L
 from chainer_mask_rcnn_amd import _lib
 from chainer_mask_rcnn_amd import functions as F
 from chainer_mask_rcnn_amd.functions import conv as C
+from chainer_mask_rcnn_amd.functions import _conv_launch, _wgrad, stage
 from chainer_mask_rcnn_amd.functions._layout import nhwc
 from chainer_mask_rcnn_amd._lib import EPI_BIAS, EPI_RELU
 
@@ -53,6 +57,11 @@ def _t(a, dev, grad=False):
 def _nan_empty_nhwc(shape, device, dtype=torch.float32):
     n, c, h, w = shape
     return torch.full((n, h, w, c), NAN, dtype=dtype, device=device).permute(0, 3, 1, 2)
+
+
+# The host modules of the convolution family (functions/conv.py's layering): the NaN allocator
+# replaces ``empty_nhwc`` in every one of them that allocates with it.
+_HOST_MODULES = (_conv_launch, _wgrad, C, stage)
 
 
 def _gemm_kinds():
@@ -94,8 +103,8 @@ _DECODE = {
 
 class Session(object):
     """One test's harness: the knobs (restored to the library defaults on exit), a LaunchChecker under
-    every ``_lib.call``, NaN-prefilled outputs in functions/conv.py, and per ``case`` the profiler's
-    GEMM launch counts against route()'s prediction for the calls made."""
+    every ``_lib.call``, NaN-prefilled outputs of the host code (``nan_allocs`` counts them), and per
+    ``case`` the profiler's GEMM launch counts against route()'s prediction for the calls made."""
 
     def __init__(self, monkeypatch, family, knobs=None, predict=True):
         self.mp, self.family, self.predict = monkeypatch, family, predict
@@ -104,6 +113,7 @@ class Session(object):
         self.chk = L.LaunchChecker()
         self.predicted = collections.Counter()
         self.labels = []
+        self.nan_allocs = 0
         self.lib = _lib.load()
 
     def set(self, **knobs):
@@ -126,7 +136,14 @@ class Session(object):
                 self.labels.append((name, r.label))
         self._call = call
         self.mp.setattr(_lib, 'call', call)
-        self.mp.setattr(C, 'empty_nhwc', _nan_empty_nhwc)
+
+        def nan_alloc(*args, **kwargs):
+            self.nan_allocs += 1
+            return _nan_empty_nhwc(*args, **kwargs)
+        allocating = [m for m in _HOST_MODULES if hasattr(m, 'empty_nhwc')]
+        assert _conv_launch in allocating
+        for m in allocating:
+            self.mp.setattr(m, 'empty_nhwc', nan_alloc)
         return self
 
     def __exit__(self, *exc):
@@ -145,22 +162,25 @@ class Session(object):
         finally:
             _lib.call = self._call
 
-    def case(self, cid):
-        return _Case(self, cid)
+    def case(self, cid, own_outputs=False):
+        """``own_outputs``: every output of the case is a buffer of the test's own (guarded or
+        NaN-filled), none comes from the host code's allocator."""
+        return _Case(self, cid, own_outputs)
 
     def assert_clean(self):
         self.chk.assert_clean()
 
 
 class _Case(object):
-    def __init__(self, sess, cid):
-        self.s, self.cid = sess, cid
+    def __init__(self, sess, cid, own_outputs):
+        self.s, self.cid, self.own_outputs = sess, cid, own_outputs
 
     def __enter__(self):
         s = self.s
         s.predicted.clear()
         del s.labels[:]
         self.fails = len(s.chk.fails)
+        self.allocs = s.nan_allocs
         _lib.check(s.lib.mrcnn_profile_enable(3), 'profile_enable')
         return self
 
@@ -180,6 +200,12 @@ class _Case(object):
         if s.predict:
             assert kinds == dict(s.predicted), '[%s] GEMM launches %s, route() predicted %s via %s' % (
                 self.cid, kinds, dict(s.predicted), s.labels)
+        allocs = s.nan_allocs - self.allocs
+        if self.own_outputs:
+            assert allocs == 0, '[%s] declares its own outputs, but the host code allocated %d' % (self.cid, allocs)
+        else:
+            assert allocs > 0, '[%s] the NaN-prefilling allocator was never called: nothing would show ' \
+                'an output element that a kernel leaves unwritten' % self.cid
         return False
 
 
@@ -334,14 +360,14 @@ def test_k_strided_dgrad_entry_points(dev, monkeypatch, variant):
     with Session(monkeypatch, 'K-strided dgrad, direct') as s:
         for cid, d in G.DGRAD_DIRECT:
             for ws in (True, False):
-                with s.case('%s %s ws=%d' % (cid, variant, ws)):
+                with s.case('%s %s ws=%d' % (cid, variant, ws), own_outputs=True):
                     _dgrad_direct(dev, cid, d, 'conv2d_dgrad_ex', variant, ws)
             if variant in ('plain', 'accum'):
-                with s.case('%s %s plain entry' % (cid, variant)):
+                with s.case('%s %s plain entry' % (cid, variant), own_outputs=True):
                     _dgrad_direct(dev, cid, d, 'conv2d_dgrad', variant, False)
         cid, d = G.DGRAD_TINY_SPLIT
         for ws, label in ((True, 'small/tiny_split'), (False, 'small/plain')):
-            with s.case('%s %s ws=%d' % (cid, variant, ws)):
+            with s.case('%s %s ws=%d' % (cid, variant, ws), own_outputs=True):
                 _dgrad_direct(dev, cid, d, 'conv2d_dgrad_ex', variant, ws)
                 assert s.labels == [('mrcnn_conv2d_dgrad_ex', label)], s.labels
         s.assert_clean()
@@ -355,7 +381,7 @@ def test_strided_1x1(dev, monkeypatch):
     with Session(monkeypatch, 'strided 1x1') as s:
         for cid, d in G.STRIDED:
             x, w, gy = G.operands(d)
-            with s.case(cid + ' forward'):
+            with s.case(cid + ' forward', own_outputs=True):
                 y = G.Guarded(d.N * d.P * d.Q * d.K, dev)
                 xt, wt = _dev_nhwc(x, dev), _krsc(w, dev)
                 _lib.call('mrcnn_conv2d_fwd', C.ctx_desc(_cdesc(d)), _lib.ptr(xt), _lib.ptr(wt), None, None, None,
@@ -366,7 +392,7 @@ def test_strided_1x1(dev, monkeypatch):
             between[:, ::2, ::2] = False
             for entry in ('conv2d_dgrad_wt', 'conv2d_dgrad_ex'):
                 for variant in ('plain', 'accum'):
-                    with s.case('%s %s %s' % (cid, entry, variant)):
+                    with s.case('%s %s %s' % (cid, entry, variant), own_outputs=True):
                         gx = _dgrad_direct(dev, cid, d, entry, variant, True)
                         if variant == 'plain':
                             assert bool((gx[between] == 0).all()), '[%s] %s: not exact zeros between the ' \
@@ -388,7 +414,7 @@ def test_wgrad_by_pixel_count(dev, monkeypatch, pixels):
             ws = _lib.workspace(_lib.load().mrcnn_conv2d_wgrad_workspace_bytes(C.ctx_desc(_cdesc(d))), dev, 'wgrad')
             for has_ws in (True, False):
                 for scale in (None, rs):
-                    with s.case('%s ws=%d scale=%d' % (cid, has_ws, scale is not None)):
+                    with s.case('%s ws=%d scale=%d' % (cid, has_ws, scale is not None), own_outputs=True):
                         g = G.Guarded(d.K * d.C, dev)
                         args = (C.ctx_desc(_cdesc(d)), _lib.ptr(xt), _lib.ptr(gyt), _lib.ptr(g.out),
                                 _lib.ptr(ws) if has_ws else None)
@@ -413,7 +439,7 @@ def test_wgrad_wperm_gates(dev, monkeypatch):
             x, w, gy = G.operands(d)
             xt, gyt = _dev_nhwc(x, dev), _dev_nhwc(gy, dev)
             ws = _lib.workspace(_lib.load().mrcnn_conv2d_wgrad_workspace_bytes(C.ctx_desc(_cdesc(d))), dev, 'wgrad')
-            with s.case(cid):
+            with s.case(cid, own_outputs=True):
                 g = G.Guarded(d.K * 9 * d.C, dev)
                 _lib.call('mrcnn_conv2d_wgrad_ex', C.ctx_desc(_cdesc(d)), _lib.ptr(xt), _lib.ptr(gyt), _lib.ptr(g.out),
                           _lib.ptr(ws), None, _lib.stream_ptr())
@@ -500,7 +526,7 @@ def test_policy_branch_with_ragged_tiles(dev, monkeypatch, entry, d, knobs, labe
     cid = request.node.callspec.id
     with Session(monkeypatch, 'policy branches', knobs) as s:
         x, w, gy = G.operands(d, seed=G.seed_of(d.W, d.C, d.K))
-        with s.case(cid):
+        with s.case(cid, own_outputs=True):
             if entry == 'conv2d_fwd':
                 rng = np.random.RandomState(1)
                 b = torch.tensor(rng.standard_normal(d.K).astype(np.float32), device=dev)

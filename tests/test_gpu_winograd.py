@@ -152,6 +152,7 @@ def test_conv2d_winograd_route_bias_relu(dev, train_forward):
     input / filter / bias gradients against the float64 oracle.  In a train step only the
     backward takes the Winograd route (WINOGRAD_TRAIN_FORWARD); under no_grad the forward does."""
     from chainer_mask_rcnn_amd import functions as F
+    from chainer_mask_rcnn_amd.functions import _wgrad as WG      # (where the weight-gradient job launches)
     N, Cc, H, W, K = 2, 256, 19, 30, 256
     rng = np.random.RandomState(5)
     x = np.maximum(rng.standard_normal((N, Cc, H, W)), 0).astype(np.float32)
@@ -160,14 +161,14 @@ def test_conv2d_winograd_route_bias_relu(dev, train_forward):
     saved = (C.WINOGRAD_MIN_WORK, C.WINOGRAD_TRAIN_FORWARD)
     C.WINOGRAD_MIN_WORK, C.WINOGRAD_TRAIN_FORWARD = 0, train_forward
     calls = {'fwd': 0, 'dgrad': 0, 'wgrad': 0}
-    orig = (C.wino_fwd, C.wino_dgrad, C.wino_wgrad_into)
+    orig = (C.wino_fwd, C.wino_dgrad, WG.wino_wgrad_into)
 
     def spy(name, fn):
         def wrapped(*a, **k):
             calls[name] += 1
             return fn(*a, **k)
         return wrapped
-    C.wino_fwd, C.wino_dgrad, C.wino_wgrad_into = (spy(n, f) for n, f in zip(calls, orig))
+    C.wino_fwd, C.wino_dgrad, WG.wino_wgrad_into = (spy(n, f) for n, f in zip(calls, orig))
     try:
         xt, wt, bt = _t(x, dev, True), _t(Wt, dev, True), _t(b, dev, True)
         y = F.conv2d(xt, wt, bt, stride=1, pad=1, relu=True)
@@ -186,7 +187,7 @@ def test_conv2d_winograd_route_bias_relu(dev, train_forward):
         assert calls['fwd'] == int(train_forward) + 1
         _close(y2.cpu().numpy(), np.maximum(pre, 0))
     finally:
-        C.wino_fwd, C.wino_dgrad, C.wino_wgrad_into = orig
+        C.wino_fwd, C.wino_dgrad, WG.wino_wgrad_into = orig
         C.WINOGRAD_MIN_WORK, C.WINOGRAD_TRAIN_FORWARD = saved
 
 

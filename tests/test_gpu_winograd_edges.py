@@ -3,7 +3,7 @@ epilogue and the sign fix-up: the Winograd lists of tests/gemm_edge_cases.py on 
 
 The harness is tests/test_gpu_gemm_edges.py's Session: launch_ref.LaunchChecker compares every
 mrcnn_conv3x3_wino_* call with its float64 restatement under the suite's convolution bound
-|got - ref| <= 1e-4 |ref| + 1e-5 max|ref|, outputs that functions/conv.py allocates are NaN-prefilled,
+|got - ref| <= 1e-4 |ref| + 1e-5 max|ref|, outputs that the host code allocates are NaN-prefilled,
 and the profiler's GEMM launch counts per kind (the W8 kernel included) must equal what
 gemm_edge_cases.route() predicts from plan_wino_gemm / plan_wino_wgrad.  The GEMMs read and write
 through buffer descriptors, so a wrong row range, m_lo or tail mask does not fault: it drops a term or
@@ -162,7 +162,7 @@ def test_epilogues_on_ragged_and_one_tile_maps(dev, monkeypatch, c):
                 assert bool(torch.isfinite(gx).all()), sorted(kw)
                 if 'out_mask_y' in kw:
                     assert bool((gx[mask <= 0] == 0).all()), 'masked elements are not exact zeros'
-        with s.case('%s weight gradient' % (c,)):
+        with s.case('%s weight gradient' % (c,), own_outputs=True):
             for row_scale in (None, rs):
                 gW = torch.full_like(wt, NAN)
                 C.wino_wgrad_into(dd, xt, None, gt, gW, row_scale=row_scale)
@@ -203,7 +203,7 @@ def _guarded_passes(dev, s, cid, d, exact_signs_flags=EPI_RELU):
         for g in defined:
             _guard_ok(g, '%s after %s' % (cid, what))
 
-    with s.case(cid):
+    with s.case(cid, own_outputs=True):
         _lib.call('mrcnn_conv3x3_wino_fwd', dp, _lib.ptr(xt), _lib.ptr(wt), None, None, None, _lib.ptr(y.out), 0,
                   _lib.ptr(v.out), _lib.ptr(ws.out), _lib.stream_ptr())
         after('fwd', y, v)
@@ -292,7 +292,7 @@ def test_fix_list_overflow(dev, monkeypatch):
             # (the data gradient and the weight gradient ran on the workspace since: once more for the count)
             x, w, _ = G.operands(d)
             y = G.Guarded(d.N * d.H * d.W * d.K, dev)
-            with s.case('fix-list overflow: the count'):
+            with s.case('fix-list overflow: the count', own_outputs=True):
                 _lib.call('mrcnn_conv3x3_wino_fwd', C.ctx_desc(dd), _lib.ptr(_dev_nhwc(x, dev)), _lib.ptr(_krsc(w, dev)),
                           None, None, None, _lib.ptr(y.out), EPI_EXACT_SIGNS, None, _lib.ptr(ws.out), _lib.stream_ptr())
                 assert _fixup_count(dd, _lib.ptr(ws.out)) == d.N * d.H * d.W * d.K == 73800

@@ -5,18 +5,18 @@ import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 from test_gpu_model import _build
-from chainer_mask_rcnn_amd.functions import conv as C
+from chainer_mask_rcnn_amd.functions import conv as C, stage as S
 C.WINOGRAD_MIN_WORK = 0
 dev = torch.device('cuda:0')
-orig = C._fwd_raw
+orig = S._fwd_raw                 # (the stage node calls its direct forwards through functions.stage)
 
 
-def spy(x, Wc, d, scale, shift, residual, relu):
+def spy(x, Wc, d, scale=None, shift=None, residual=None, relu=False):
     y = orig(x, Wc, d, scale, shift, residual, relu)
     if d.R == 3 and d.N >= 32 and d.H == 7:
         yw, _ = C.wino_fwd(x, Wc, d, scale, shift, relu)
         xa = x.abs()
-        pre = orig(x, Wc, d, None, None, None, False)
+        pre = orig(x, Wc, d)
         diff = (yw - y).abs()
         print('  conv2 N=%d: input max %.3g rms %.3g (max/rms %.0f)  |pre| max %.3g rms %.3g   wino-direct: max %.2e rms %.2e of output max %.3g (rel-to-rms %.2e)' % (
             d.N, xa.max().item(), x.pow(2).mean().sqrt().item(), xa.max().item() / x.pow(2).mean().sqrt().item(),
@@ -25,7 +25,7 @@ def spy(x, Wc, d, scale, shift, residual, relu):
     return y
 
 
-C._fwd_raw = spy
+S._fwd_raw = spy
 for n in (50, 101):
     print('R-%d' % n)
     model, chain, imgs, bboxes, labels, masks = _build(dev, n)
